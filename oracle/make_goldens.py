@@ -456,8 +456,9 @@ def gen_ncsnpp(ref):
 def gen_sr3_160_long(ref):
     """Full-size SR3-160 (BASELINE configs[1] network: nf = 96, ch_mult (1,1,2,2,3,3), attention at 20/10/5, 160 x 160), the REAL
     1000-step PC schedule (sampling/conditional.py:180-226), B = 2, noise from a seeded tape, run by the imported reference
-    on the CPU -> tests/golden/sr3_160_long.npz: x after every 50th PC step on a stride-4 pixel grid, the full final x_mean,
-    and one B = 1 network evaluation.  ~35 min on 8 cores."""
+    on the CPU -> tests/golden/sr3_160_long.npz: x after every 50th PC step on a stride-4 pixel grid, sr3_160_final.npz: the full
+    final x_mean, sr3_160_forward.npz: one B = 1 network evaluation (three files, each under 1 MiB).  ~35 min
+    on 8 cores."""
     import time
     cfg = cases.make_config(**cases.SR3_160)
     model, _ = build_ref_model(ref, cfg)
@@ -489,7 +490,10 @@ def gen_sr3_160_long(ref):
     out['evo_rms'] = ev[every - 1::every].double().pow(2).mean(dim=(1, 2, 3, 4)).sqrt().numpy()
     out['final'] = res.numpy()
     print('sr3_160_long: %.0f s; |x| max per snapshot' % (time.time() - t0), out['evo_absmax'], 'final absmax', float(res.abs().max()))
-    np.savez_compressed(os.path.join(OUT, 'sr3_160_long.npz'), **out)
+    parts = {'sr3_160_long': ('steps', 'evo', 'evo_absmax', 'evo_rms'), 'sr3_160_final': ('final',),
+             'sr3_160_forward': ('fwd_x', 'fwd_label', 'fwd_net')}
+    for name, keys in parts.items():
+        np.savez_compressed(os.path.join(OUT, name + '.npz'), **{k: out[k] for k in keys})
 
 
 def _ref_pc_conditional(ref, cfg, model, sde, y, tape, p_steps, show_evolution=False):

@@ -1,7 +1,7 @@
 """-m gpu: parity at the BENCHMARKED shapes.
 
 * the full-size SR3-160 network (BASELINE configs[1]) over the REAL 1000-step PC schedule against a run of the imported
-  reference itself (tests/golden/sr3_160_long.npz, oracle/make_goldens.py:gen_sr3_160_long) - in every precision mode,
+  reference itself (tests/golden/sr3_160_{long,final,forward}.npz, oracle/make_goldens.py:gen_sr3_160_long) - in every precision mode,
   at the north-star tolerance 1e-3, norm-wise AND element-wise;
 * batch 64 (the bench batch): sample 17 of a B = 64 evaluation equals the B = 1 evaluation bit for bit, and matches the oracle;
 * BASELINE configs[4]'s network (NCSN++ 256 x 256, nf = 128, seven levels, attention at 16) against the oracle.
@@ -69,6 +69,7 @@ def test_long_schedule_vs_reference(golden_dir, precision, tol_n, tol_e):
     from conditional_score_diffusion_amd import sde_lib
     from conditional_score_diffusion_amd.sampling import fused
     g = np.load(os.path.join(golden_dir, 'sr3_160_long.npz'))
+    final = np.load(os.path.join(golden_dir, 'sr3_160_final.npz'))['final']
     cfg, nc, p, model = build_sr3_160(precision)
     sde = sde_lib.cVESDE(cfg.model.sigma_min_x, cfg.model.sigma_max_x, cfg.model.num_scales)
     tape, y = long_inputs()
@@ -79,7 +80,7 @@ def test_long_schedule_vs_reference(golden_dir, precision, tol_n, tol_e):
         got = rec[int(step)][:, :, ::st, ::st].cpu().numpy()
         worst_n = max(worst_n, normwise(got, g['evo'][j]))
         worst_e = max(worst_e, elementwise(got, g['evo'][j]))
-    fin_n, fin_e = normwise(x.cpu().numpy(), g['final']), elementwise(x.cpu().numpy(), g['final'])
+    fin_n, fin_e = normwise(x.cpu().numpy(), final), elementwise(x.cpu().numpy(), final)
     print('long schedule %s: snapshots norm-wise %.3e element-wise %.3e; final %.3e / %.3e'
           % (precision, worst_n, worst_e, fin_n, fin_e))
     assert max(worst_n, fin_n) < tol_n and max(worst_e, fin_e) < tol_e
@@ -88,7 +89,7 @@ def test_long_schedule_vs_reference(golden_dir, precision, tol_n, tol_e):
 @pytest.mark.parametrize('precision,tol_n,tol_e', MODES)
 def test_full_size_forward_vs_reference(golden_dir, precision, tol_n, tol_e):
     """one evaluation of the full-size network against the reference's own output"""
-    g = np.load(os.path.join(golden_dir, 'sr3_160_long.npz'))
+    g = np.load(os.path.join(golden_dir, 'sr3_160_forward.npz'))
     cfg, nc, p, model = build_sr3_160(precision)
     y = cases.sr3_160_y(cases.LONG_B)[:1]
     with torch.no_grad():

@@ -43,11 +43,11 @@ def main(tag, outpath):
             cls['launches'] += n
             cls['fetch'] += fetch * n
             cls['write'] += write * n
-    res = {'source': 'rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) of `bench.py --steps 1 --warmup 0`, '
+    res = {'source': 'rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) of `bench.py --full --steps 1 --warmup 0`, '
                      'tools/pmc_hbm.sh; fetch = 2 x FETCH_SIZE KiB, write = WRITE_SIZE KiB (calibrated on the sampler '
                      'update kernels of the same run)',
            'class_definition': 'conv_xk_kernel launches (profiler class conv3x3)' if any_xk else 'every 3x3 stride-1 kernel of the mode',
-           'conv3x3_class': {'launches_in_run': cls['launches'], 'run': 'bench.py --steps 1 --warmup 0 = 1 timed + 1 profiled PC step',
+           'conv3x3_class': {'launches_in_run': cls['launches'], 'run': 'bench.py --full --steps 1 --warmup 0 = 1 timed + 1 profiled PC step',
                              'hbm_bytes_per_launch': (cls['fetch'] + cls['write']) / max(cls['launches'], 1),
                              'fetch_bytes_per_launch': cls['fetch'] / max(cls['launches'], 1),
                              'write_bytes_per_launch': cls['write'] / max(cls['launches'], 1)},

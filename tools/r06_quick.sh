@@ -10,7 +10,7 @@ if [ -n "$T" ]; then
   cat $O/tests.txt
 fi
 for b in ${BATCHES:-64}; do
-  python bench.py --steps 20 --warmup 5 --no-alt --no-cpu-baseline --batch $b > $O/bench_b$b.json 2> $O/bench_b$b.err
+  python bench.py --full --steps 20 --warmup 5 --no-alt --no-cpu-baseline --batch $b > $O/bench_b$b.json 2> $O/bench_b$b.err
   python - <<P
 import json
 try:
