@@ -89,6 +89,7 @@ SIGNATURES = {
     'csd_unet_train_workspace_bytes': (_sz, [_vp, _i, _f]),
     'csd_unet_train_forward': (_i, [_vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _i, _f, ctypes.c_uint64, ctypes.c_uint64, _vp]),
     'csd_unet_backward': (_i, [_vp, _vp, _vp, _vp, _sz, _vp, _i, ctypes.c_uint64, _vp]),
+    'csd_unet_backward_ex': (_i, [_vp, _vp, _vp, _vp, _vp, _sz, _vp, _i, ctypes.c_uint64, _vp]),
     'csd_unet_train_release': (_i, [_vp, _vp]),
     'csd_unet_train_release_call': (_i, [_vp, _vp, ctypes.c_uint64]),
     'csd_unet_backward_marks': (_i, [_vp, _vp, _vp, _i]),
@@ -148,6 +149,9 @@ SIGNATURES = {
     'csd_global_norm': (_i, [_vp, _vp, _i64, _vp, _vp]),
     'csd_ema_update': (_i, [_vp, _vp, _i64, _f, _vp]),
     'csd_dropout': (_i, [_vp, _vp, _vp, _f, _u64, _u64, _i64, _vp]),
+    'csd_pf_ode_state': (_i, [_vp, _vp, _vp, _vp, _i, _i64, _vp]),
+    'csd_pf_ode_scratch_bytes': (_sz, [_i, _i64]),
+    'csd_pf_ode_rhs': (_i, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i, _i64, _vp, _vp]),
 }
 
 

@@ -116,6 +116,17 @@ __global__ void copy2d_kernel(const float* __restrict__ src, int spitch, float* 
   }
 }
 
+// rows of `width` floats, scaled: dst[r*dpitch + j] = scale * src[r*spitch + j]   (the x-channel slice of an input-layer weight for the
+// data gradient of the network input; scale 2 = the 2x - 1 input map of non-centred data)
+__global__ void wslice_kernel(const float* __restrict__ src, int spitch, float* __restrict__ dst, int dpitch, int width, int rows, float scale) {
+  const size_t n = (size_t)width * rows;
+  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+    const size_t r = i / width;
+    const int j = (int)(i - r * width);
+    dst[r * dpitch + j] = scale * src[r * spitch + j];
+  }
+}
+
 struct TG {
   Net& n;
   TrainState& st;
@@ -132,6 +143,10 @@ struct TG {
   int drop_count = 0;
   GradMarks* gm = nullptr;      // backward only
   size_t gm_next = 0;
+  bool pg = true;               // backward: parameter gradients wanted (false: csd_unet_backward_ex with grads == NULL)
+  bool want_dx = false;         // backward: d loss / d x wanted (d_x = the caller's [B, x_channels, S, S] NCHW buffer)
+  float* d_x = nullptr;
+  float* dpyr = nullptr;        // NCSN++ input pyramid: x-channel gradient [B, cx, side, side] NCHW of the finest level combined so far
   // every gradient of the modules with index >= `from` has been enqueued: record the marks that this completes
   int marks_reached(int from) {
     if (!gm || dry) return CSD_OK;
@@ -157,7 +172,8 @@ struct TG {
   float skip_scale() const { return (n.cfg.arch == 1 && n.cfg.skip_rescale) ? 0.70710678118654752440f : 1.f; }
   size_t act_n(int H, int C) const { return (size_t)B * H * H * C; }
   const float* W(int mod, const char* sub) const { const int i = n.P(mname(mod, sub)); return (dry || i < 0) ? nullptr : P[i]; }
-  float* DW(int mod, const char* sub) const { const int i = n.P(mname(mod, sub)); return (dry || i < 0) ? nullptr : G[i]; }
+  // (G == NULL: csd_unet_backward_ex without parameter gradients - every consumer of DW() is skipped then, but its arguments are evaluated)
+  float* DW(int mod, const char* sub) const { const int i = n.P(mname(mod, sub)); return (dry || i < 0 || !G) ? nullptr : G[i]; }
 
 #define TG_RUN(expr)                       \
   do {                                     \
@@ -177,6 +193,7 @@ struct TG {
     return CSD_OK;
   }
   int wgrad(const float* x, const float* dy, float* dw, int Cin, int Cout, int H, int k, int stride, int dpad, int up2, int layout) {
+    if (!pg) return CSD_OK;
     const size_t m = top;
     float* sc = alloc_bytes(csd_conv_wgrad_scratch_bytes(B, Cin, Cout, H, H, k, stride, up2));
     TG_RUN(csd_conv2d_wgrad_ex(x, dy, dw, B, Cin, Cout, H, H, k, stride, dpad, up2, layout | (prec == CSD_PREC_F32 ? 0 : 4), sc, s));
@@ -202,7 +219,7 @@ struct TG {
     float* brow = alloc((size_t)B * C);
     float* sc = alloc_bytes(csd_groupnorm_nhwc_scratch_bytes(B, C, H * H));
     TG_RUN(groupnorm_act_backward_nhwc_add(x, gamma, beta, rs, ms, dy, add, dx, grow, brow, C, B, C, H * H, G_of(C), a, sc, s));
-    TG_RUN(sum_rows2(grow, dgamma, brow, dbeta, B, C, s));
+    if (pg) TG_RUN(sum_rows2(grow, dgamma, brow, dbeta, B, C, s));
     top = m;
     return CSD_OK;
   }
@@ -219,6 +236,7 @@ struct TG {
     return CSD_OK;
   }
   int bias_grad(const float* dy, float* db, int C, int H) {          // conv bias: batch + pixel sum of an NHWC gradient
+    if (!pg) return CSD_OK;
     const size_t m = top;
     float* bc = alloc((size_t)B * C);
     int rc = sum_pixels(dy, bc, C, H);
@@ -728,7 +746,7 @@ struct TG {
     if (rc) return rc;
     d1 = d1b;
     // Conv_0 bias and the time-embedding row share the per-(sample, channel) pixel sums of d1
-    {
+    if (pg) {
       float* dd = alloc((size_t)B * cout);
       rc = sum_pixels(d1, dd, cout, H); if (rc) return rc;
       TG_RUN(csd_sum_rows(dd, DW(m.idx, "Conv_0.bias"), B, cout, s));
@@ -791,7 +809,7 @@ struct TG {
                 DW(m.idx, "GroupNorm_1.bias"), cout, Ho, act);
     if (rc) return rc;
     d1 = d1b;
-    {
+    if (pg) {
       float* dd = alloc((size_t)B * cout);
       rc = sum_pixels(d1, dd, cout, Ho); if (rc) return rc;
       TG_RUN(csd_sum_rows(dd, DW(m.idx, "Conv_0.bias"), B, cout, s));
@@ -866,6 +884,7 @@ struct TG {
       snprintf(wn, sizeof(wn), "NIN_%d.W", j); snprintf(bn, sizeof(bn), "NIN_%d.b", j);
       hipLaunchKernelGGL(copy2d_kernel, dim3(launch_blocks((size_t)C * C)), dim3(256), 0, s, W(m.idx, wn), C, wc + j * C, 3 * C, C, C);
       CSD_LAUNCH_CHECK();
+      if (!pg) continue;
       hipLaunchKernelGGL(copy2d_kernel, dim3(launch_blocks((size_t)C * C)), dim3(256), 0, s, dwc + j * C, 3 * C, DW(m.idx, wn), C, C, C);
       CSD_LAUNCH_CHECK();
       TG_RUN(copy(dbc + j * C, DW(m.idx, bn), C));
@@ -878,13 +897,64 @@ struct TG {
     return contribute(sp.in0, dh);
   }
 
+  // ---- d loss / d x: the network input is cat(x, y) NCHW (2h - 1 when not centred); only its x channels take a gradient ------------
+  float in_scale() const { return n.cfg.centered ? 1.f : 2.f; }
+  // the x-channel columns [rows, cx * k2] of an input-layer weight [rows, cio * k2], times in_scale(): the transposed-weight
+  // convolution (layout bit 2) with this slice writes the x channels only, the 2x - 1 map folded in (a power of two: exact)
+  int x_weight_slice(const float* w, int rows, int k2, float** out) {
+    const int cx = n.cfg.x_channels, cio = cx + n.cfg.y_channels;
+    float* ws = alloc((size_t)rows * cx * k2);
+    *out = ws;
+    if (!dry) {
+      hipLaunchKernelGGL(wslice_kernel, dim3(launch_blocks((size_t)rows * cx * k2)), dim3(256), 0, s, w, cio * k2, ws, cx * k2, cx * k2, rows,
+                         in_scale());
+      CSD_LAUNCH_CHECK();
+    }
+    return CSD_OK;
+  }
+  // d pyramid_l = Conv_0^T(dh_l) + FIR-down^T(d pyramid_{l+1})  (input_skip: pyramid_l = FIR-down(pyramid_{l-1}), pyramid_0 = the input)
+  int pyramid_dx(const Module& m, const TT& to) {
+    const int cx = n.cfg.x_channels, side = to.H;
+    const size_t np = (size_t)B * cx * side * side;
+    float* g = alloc(np);                            // kept until the next finer level (or the stem) has read it
+    const size_t mk = top;
+    float* w = nullptr;
+    int rc = x_weight_slice(W(m.idx, "Conv_0.weight"), m.cout, 1, &w); if (rc) return rc;
+    rc = conv(to.g, w, nullptr, g, m.cout, cx, side, 1, 1, 0, 0, 1 | 4); if (rc) return rc;
+    if (dpyr) {
+      float* u = alloc(np);
+      rc = fir(dpyr, u, B * cx, side / 2, 1, true, true); if (rc) return rc;
+      rc = add_into(g, u, np); if (rc) return rc;
+    }
+    top = mk;
+    dpyr = g;
+    return CSD_OK;
+  }
+  // the first 3x3 conv's data gradient, NHWC nf channels -> NCHW x channels, + FIR-down^T of the input pyramid's gradient
+  int stem_dx(const Module& m, const TT& to) {
+    const int cx = n.cfg.x_channels, S = to.H;
+    const size_t np = (size_t)B * cx * S * S;
+    const size_t mk = top;
+    float* w = nullptr;
+    int rc = x_weight_slice(W(m.idx, "weight"), n.cfg.nf, 9, &w); if (rc) return rc;
+    rc = conv(to.g, w, nullptr, d_x, n.cfg.nf, cx, S, 3, 1, 0, 0, 1 | 4); if (rc) return rc;
+    if (dpyr) {
+      float* u = alloc(np);
+      rc = fir(dpyr, u, B * cx, S / 2, 1, true, true); if (rc) return rc;
+      rc = add_into(d_x, u, np); if (rc) return rc;
+    }
+    top = mk;
+    return CSD_OK;
+  }
+
   int backward(const float* d_out) {
     const csd_unet_config& c = n.cfg;
     const int nf = c.nf;
     top = st.fwd_top;
     int rc;
     float* dtemb_act = nullptr;                      // sum over the blocks of dDense . W: gradient w.r.t. act(temb2)
-    if (c.conditional) {
+    dpyr = nullptr;
+    if (c.conditional && pg) {
       dtemb_act = alloc((size_t)B * 4 * nf);
       if (!dry) CSD_CHECK_HIP(hipMemsetAsync(dtemb_act, 0, (size_t)B * 4 * nf * sizeof(float), s));
     }
@@ -914,7 +984,7 @@ struct TG {
           float* dh = alloc(act_n(H, C));
           const size_t mk = top;
           rc = wgrad(sp.sv[0], d_out, DW(mc.idx, "weight"), C, Co, H, 3, 1, 0, 0, 1); if (rc) return rc;
-          {                                          // bias: NCHW gradient -> per-(sample, channel) sums -> batch sum
+          if (pg) {                                  // bias: NCHW gradient -> per-(sample, channel) sums -> batch sum
             float* bc = alloc((size_t)B * Co);
             TG_RUN(csd_sum_inner(d_out, bc, (int64_t)B * Co, (int64_t)H * H, s));
             TG_RUN(csd_sum_rows(bc, DW(mc.idx, "bias"), B, Co, s));
@@ -929,12 +999,13 @@ struct TG {
           break;
         }
         case TS_RES: rc = (c.arch == 1 ? respp_bwd(sp, dtemb_act) : res_bwd(sp, dtemb_act)); if (rc) return rc; break;
-        case TS_COMBINE: {                           // out = Conv_0(pyramid) + h: the pyramid is data (no gradient), h's gradient is dout
+        case TS_COMBINE: {                           // out = Conv_0(pyramid) + h: h's gradient is dout; the pyramid's only when d_x is wanted
           const Module& m = n.mods[sp.mod];
           const TT& to = st.t[sp.out];
           const int cio = c.x_channels + c.y_channels;
           rc = wgrad(sp.sv[0], to.g, DW(m.idx, "Conv_0.weight"), cio, m.cout, to.H, 1, 1, 0, 0, 2); if (rc) return rc;
           rc = bias_grad(to.g, DW(m.idx, "Conv_0.bias"), m.cout, to.H); if (rc) return rc;
+          if (want_dx) { rc = pyramid_dx(m, to); if (rc) return rc; }
           rc = contribute(sp.in0, to.g); if (rc) return rc;
           break;
         }
@@ -948,7 +1019,7 @@ struct TG {
           float* dprev = (sp.flag & 1) ? alloc((size_t)B * Co * (H / 2) * (H / 2)) : nullptr;
           const size_t mk = top;
           rc = wgrad(sp.sv[0], dP, DW(mc.idx, "weight"), C, Co, H, 3, 1, 0, 0, 1); if (rc) return rc;
-          {
+          if (pg) {
             float* bc = alloc((size_t)B * Co);
             TG_RUN(csd_sum_inner(dP, bc, (int64_t)B * Co, (int64_t)H * H, s));
             TG_RUN(csd_sum_rows(bc, DW(mc.idx, "bias"), B, Co, s));
@@ -1019,11 +1090,12 @@ struct TG {
           const int cio = c.x_channels + c.y_channels;
           rc = wgrad(st.xin, to.g, DW(m.idx, "weight"), cio, nf, to.H, 3, 1, 0, 0, 2); if (rc) return rc;
           rc = bias_grad(to.g, DW(m.idx, "bias"), nf, to.H); if (rc) return rc;
+          if (want_dx) { rc = stem_dx(m, to); if (rc) return rc; }
           break;
         }
       }
     }
-    if (c.conditional) {                             // temb MLP (models/ddpm.py:153-160)
+    if (c.conditional && pg) {                       // temb MLP (models/ddpm.py:153-160)
       const size_t mk = top;
       float* d2 = alloc((size_t)B * 4 * nf);         // gradient w.r.t. temb2 = act'(temb2) * dtemb_act
       TG_RUN(csd_act(st.temb2, dtemb_act, d2, act, (int64_t)B * 4 * nf, s));
@@ -1059,6 +1131,7 @@ extern "C" size_t csd_unet_train_workspace_bytes(csd_unet* net, int B, float dro
   TrainState st;
   TG g(net->net, st, B, nullptr, true, nullptr, nullptr, reinterpret_cast<float*>(uintptr_t(256)));
   g.p_drop = dropout_p;
+  g.want_dx = true;                                  // (sized for the largest backward: every parameter gradient and d_x)
   if (g.forward(nullptr, nullptr, nullptr, nullptr)) return 0;
   if (g.backward(nullptr)) return 0;
   return g.peak * sizeof(float) + 256;
@@ -1108,9 +1181,22 @@ extern "C" int csd_unet_train_release_call(csd_unet* net, const void* workspace,
 
 extern "C" int csd_unet_backward(csd_unet* net, const float* const* params, float* const* grads, void* workspace,
                                  size_t workspace_bytes, const float* d_out, int B, uint64_t call_index, void* stream) {
+  CSD_REQUIRE(grads, "backward: null argument");
+  return csd_unet_backward_ex(net, params, grads, nullptr, workspace, workspace_bytes, d_out, B, call_index, stream);
+}
+
+extern "C" int csd_unet_backward_ex(csd_unet* net, const float* const* params, float* const* grads, float* d_x, void* workspace,
+                                    size_t workspace_bytes, const float* d_out, int B, uint64_t call_index, void* stream) {
   int rc = train_check(net);
   if (rc) return rc;
-  CSD_REQUIRE(params && grads && workspace && d_out, "backward: null argument");
+  CSD_REQUIRE(params && workspace && d_out, "backward: null argument");
+  CSD_REQUIRE(grads || d_x, "backward_ex: neither parameter gradients (grads) nor the input gradient (d_x) requested");
+  if (d_x) {
+    const csd_unet_config& c = net->net.cfg;
+    CSD_REQUIRE(c.x_channels >= 1, "backward_ex: d_x needs x_channels >= 1");
+    CSD_REQUIRE(c.arch == 0 || c.progressive_input == 0 || c.progressive_input == 1,
+                "backward_ex: d_x is not provided for progressive_input id %d (only 'none' and 'input_skip')", c.progressive_input);
+  }
   TrainState* sp = train_state_find(&net->net, workspace);
   if (!sp || !sp->valid || sp->B != B || sp->ws != workspace) {
     set_error("backward: no matching csd_unet_train_forward (same handle, workspace and batch) precedes this call");
@@ -1128,10 +1214,13 @@ extern "C" int csd_unet_backward(csd_unet* net, const float* const* params, floa
     return CSD_ERR_WORKSPACE;
   }
   for (size_t i = 0; i < net->net.params.size(); ++i)
-    CSD_REQUIRE(params[i] && grads[i], "backward: parameter / gradient pointer %zu (%s) is null", i, net->net.params[i].name.c_str());
+    CSD_REQUIRE(params[i] && (!grads || grads[i]), "backward: parameter / gradient pointer %zu (%s) is null", i, net->net.params[i].name.c_str());
   for (auto& t : st.t) t.g = nullptr;
   TG g(net->net, st, B, (hipStream_t)stream, false, params, grads, static_cast<float*>(workspace));
-  {
+  g.pg = grads != nullptr;
+  g.want_dx = d_x != nullptr;
+  g.d_x = d_x;
+  if (g.pg) {                                        // (the gradient-ready marks describe parameter gradients: none without them)
     std::lock_guard<std::mutex> lk(g_train_mu);
     auto it = g_marks.find(&net->net);
     g.gm = it == g_marks.end() ? nullptr : &it->second;

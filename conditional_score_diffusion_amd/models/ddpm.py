@@ -211,6 +211,10 @@ class HipUNet(nn.Module):
             if y_noise is not None:
                 raise RuntimeError('the fused y-perturbation is a sampling feature; perturb y before a training step')
             return self._train_forward(x, y, labels)
+        if torch.is_grad_enabled() and x.requires_grad:
+            if y_noise is not None:
+                raise RuntimeError('the fused y-perturbation is a sampling feature; it has no input gradient')
+            return self._input_grad_forward(x, y, labels)
         B = x.shape[0]
         S = self.image_size
         if tuple(x.shape) != (B, self.x_channels, S, S):
@@ -232,6 +236,33 @@ class HipUNet(nn.Module):
                                      current_stream(x.device)), 'unet_forward')
         return out
 
+
+    # -- eval-mode autograd with respect to x: the planned training graph without dropout, an input-only backward ------------------
+    def _check_io(self, x, y, labels):
+        B, S = x.shape[0], self.image_size
+        if tuple(x.shape) != (B, self.x_channels, S, S):
+            raise RuntimeError('x has shape %s, expected %s' % (tuple(x.shape), (B, self.x_channels, S, S)))
+        if self.y_channels:
+            require_gpu_tensor(y, 'y')
+            if tuple(y.shape) != (B, self.y_channels, S, S):
+                raise RuntimeError('y has shape %s, expected %s' % (tuple(y.shape), (B, self.y_channels, S, S)))
+        labels = labels.to(device=x.device, dtype=torch.float32).contiguous()
+        if labels.shape != (B,):
+            raise RuntimeError('labels must have shape [%d]' % B)
+        return labels
+
+    def _input_grad_forward(self, x, y, labels):
+        """``model.eval()`` with ``x.requires_grad`` under autograd: ONE node whose forward is csd_unet_train_forward with dropout 0
+        (the activations stay in a private workspace) and whose backward is csd_unet_backward_ex(grads = NULL, d_x): the data gradient
+        only, no parameter gradient.  Only x is differentiated (y is the condition)."""
+        if y is not None and y.requires_grad:
+            raise NotImplementedError('the HIP score network differentiates its input x only; y takes no gradient')
+        if self.arch == 0 and not self._cfg.resamp_with_conv:
+            raise NotImplementedError('input gradients with resamp_with_conv=False are not provided')
+        labels = self._check_io(x, y, labels)
+        self._xgrad_calls = getattr(self, '_xgrad_calls', 0) + 1
+        return _InputGradNet.apply(self, x.contiguous(), y.detach().contiguous() if self.y_channels else None, labels.detach(),
+                                   self._xgrad_calls)
 
     # -- training-mode evaluation: ONE planned graph behind the C ABI (csd_unet_train_forward / csd_unet_backward) -------------------
     def _train_workspace(self, B):
@@ -440,14 +471,52 @@ class _PlannedNet(torch.autograd.Function):
             flat = torch.empty(offs[-1], dtype=torch.float32, device=dout.device)
             grads = [flat[o:o + n].view(shape) for o, (shape, n) in zip(offs, ctx.shapes)]
         gtable = (ctypes.c_void_p * len(grads))(*[g.data_ptr() for g in grads])
-        check(lib().csd_unet_backward(model._h, ctx.table, gtable, ptr(ctx.ws), ctx.ws.numel(), ptr(dout), B, ctx.call,
-                                      current_stream(dout.device)), 'unet_backward')
+        # d loss / d x from the same call when autograd asks for it (csd_unet_backward_ex: the parameter gradients are unchanged)
+        dx = torch.empty(B, model.x_channels, model.image_size, model.image_size, dtype=torch.float32, device=dout.device) \
+            if ctx.needs_input_grad[1] else None
+        check(lib().csd_unet_backward_ex(model._h, ctx.table, gtable, ptr(dx), ptr(ctx.ws), ctx.ws.numel(), ptr(dout), B, ctx.call,
+                                         current_stream(dout.device)), 'unet_backward')
         if ctx.fin is not None:          # (the backward releases the workspace itself; the finalizer of this context must not fire later)
             ctx.fin.detach()
             _release_shared_ws(lambda: model, ctx.call)
         if direct:
-            return (None, None, None, None) + (None,) * len(grads)
-        return (None, None, None, None) + tuple(g if need else None for g, need in zip(grads, ctx.needs_input_grad[4:]))
+            return (None, dx, None, None) + (None,) * len(grads)
+        return (None, dx, None, None) + tuple(g if need else None for g, need in zip(grads, ctx.needs_input_grad[4:]))
+
+
+class _InputGradNet(torch.autograd.Function):
+    """The eval-mode network as one autograd node with respect to x: csd_unet_train_forward (dropout 0) / csd_unet_backward_ex with
+    grads = NULL.  Each forward owns a workspace; its record in the library is dropped after the backward (or with the context)."""
+
+    @staticmethod
+    def forward(ctx, model, x, y, labels, call):
+        B = x.shape[0]
+        params = model._train_params()
+        for name, p in zip(model._param_names, params):
+            if p.dtype != torch.float32 or not p.is_contiguous() or p.device != x.device:
+                raise RuntimeError('parameter %s must be contiguous float32 on %s' % (name, x.device))
+        need = lib().csd_unet_train_workspace_bytes(model._h, B, 0.0)
+        if need == 0:
+            raise RuntimeError('libcsd_hip: cannot plan the input-gradient graph at batch %d: %s' % (B, lib().csd_last_error().decode()))
+        ws = torch.empty(need, dtype=torch.uint8, device=x.device)
+        table = (ctypes.c_void_p * len(params))(*[p.data_ptr() for p in params])
+        out = torch.empty(B, model.out_channels, model.image_size, model.image_size, dtype=torch.float32, device=x.device)
+        check(lib().csd_unet_train_forward(model._h, table, ptr(ws), ws.numel(), ptr(x), ptr(y), ptr(labels), ptr(out), B, 0.0,
+                                           model.dropout_seed, call, current_stream(x.device)), 'unet_train_forward')
+        import weakref
+        ctx.model, ctx.params, ctx.table, ctx.ws, ctx.B, ctx.call = model, params, table, ws, B, call
+        ctx.fin = weakref.finalize(ctx, _release_private_ws, weakref.ref(model), model._h, ws.data_ptr(), call)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        model, B = ctx.model, ctx.B
+        dout = dout.contiguous()
+        dx = torch.empty(B, model.x_channels, model.image_size, model.image_size, dtype=torch.float32, device=dout.device)
+        check(lib().csd_unet_backward_ex(model._h, ctx.table, None, ptr(dx), ptr(ctx.ws), ctx.ws.numel(), ptr(dout), B, ctx.call,
+                                         current_stream(dout.device)), 'unet_backward_ex')
+        ctx.fin()
+        return None, dx, None, None, None
 
 
 @utils.register_model(name='ddpm')

@@ -301,6 +301,9 @@ class NCSNpp(nn.Module):
     def forward(self, x, time_cond):
         require_gpu_tensor(x, 'x')
         require_gpu_tensor(time_cond, 'time_cond')
+        if not self.training and torch.is_grad_enabled() and x.requires_grad:
+            raise NotImplementedError("input gradients are provided by the planned NCSN++ graph only; this operator-granular class "
+                                      "(progressive_input='residual') has none")
         x = x.contiguous().float()
         time_cond = time_cond.contiguous().float()
         mods, nodes = self._mods, self.all_modules

@@ -413,6 +413,14 @@ int csd_unet_train_forward(csd_unet* net, const float* const* params, void* work
                            uint64_t call_index, void* stream);
 int csd_unet_backward(csd_unet* net, const float* const* params, float* const* grads, void* workspace, size_t workspace_bytes,
                       const float* d_out, int B, uint64_t call_index, void* stream);
+/* csd_unet_backward_ex: csd_unet_backward with optional outputs.
+ *   grads == NULL: no parameter gradient is formed (no wgrad, no bias sums, no temb-MLP backward, no gradient-ready marks).
+ *   d_x != NULL:   d loss / d x, [B, x_channels, S, S] NCHW fp32 (the x channels of the input only; y takes no gradient).
+ * csd_unet_backward(...) is csd_unet_backward_ex(..., grads, NULL).  The data-gradient kernels are the same with or without grads,
+ * so d_x does not depend on whether parameter gradients are formed.  Both architectures; NCSN++ with progressive_input 'none' or
+ * 'input_skip' (the input pyramid's gradient chain: d pyr_l = Conv_0^T(dh_l) + FIR-down^T(d pyr_l+1), d x += FIR-down^T(d pyr_1)). */
+int csd_unet_backward_ex(csd_unet* net, const float* const* params, float* const* grads, float* d_x, void* workspace,
+                         size_t workspace_bytes, const float* d_out, int B, uint64_t call_index, void* stream);
 /* The library keeps one recorded training graph per (handle, workspace).  A caller that frees a workspace (a monitoring forward's
  * private one) tells the library so: the record is dropped (no error if there is none).  csd_unet_destroy drops all of a handle's. */
 int csd_unet_train_release(csd_unet* net, const void* workspace);
@@ -433,6 +441,24 @@ void* csd_event_create(void);                         /* hipEventDisableTiming; 
 int csd_event_destroy(void* event);
 int csd_stream_wait_event(void* stream, void* event);
 int csd_event_query(void* event);                     /* 1: complete, 0: not yet, < 0: error */
+
+/* ------------------------------------------------------------------------------------------
+ * Probability-flow ODE right-hand side of the likelihood (csrc/likelihood.hip; reference likelihood.py:53-103 get_likelihood_fn
+ * with the Hutchinson-Skilling divergence of get_div_fn).  Rows b < B of D = x_channels * S * S values; the state is scipy's
+ * flattened float64 vector: y = [x (B * D) | log p (B)].
+ *   csd_pf_ode_state: x32 [B, D] = float(y_x), labels32 [B] = float(labels)   (the network's fp32 operands; labels may be NULL)
+ *   csd_pf_ode_rhs:   out [B * D + B] float64:
+ *       out[b*D + i] = a[b] * y[b*D + i] + c[b] * h[b*net_stride + i]                     (drift = f + c * h, f = a * x)
+ *       out[B*D + b] = a[b] * sum_i eps_i^2 + c[b] * sum_i v[b*D + i] * eps_i               (eps_i = eps[b*net_stride + i])
+ *     h = the raw network output, eps = the Hutchinson noise as the backward's d_out, both [B, net_stride] with the x channels
+ *     first (net_stride = out_channels * S * S); v = d (h . eps) / d x [B, D] (csd_unet_backward_ex's d_x).  The row sums are
+ *     fp64, deterministic: fixed-order partials of several workgroups per row, then a fixed-order finalize.
+ *     scratch: csd_pf_ode_scratch_bytes(B, D).
+ * ---------------------------------------------------------------------------------------- */
+int csd_pf_ode_state(const double* y, const double* labels, float* x32, float* labels32, int B, int64_t D, void* stream);
+size_t csd_pf_ode_scratch_bytes(int B, int64_t D);
+int csd_pf_ode_rhs(const double* y, const float* h, const float* v, const float* eps, int64_t net_stride, const double* a,
+                   const double* c, double* out, int B, int64_t D, void* scratch, void* stream);
 
 #ifdef __cplusplus
 }
