@@ -115,6 +115,8 @@ SIGNATURES = {
     'csd_conv2d': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     'csd_attention_scratch_bytes': (_sz, [_i, _i, _i, _i]),
     'csd_attention': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    'csd_fir_pyr_conv_scratch_bytes': (_sz, [_i, _i]),
+    'csd_fir_pyr_conv': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _f, _vp, _vp]),
     'csd_upfirdn2d': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     'csd_fused_bias_act': (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i64, _i, _i, _f, _f, _vp]),
     'csd_nearest_up2': (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),

@@ -286,6 +286,17 @@ int fir_resample_nhwc_launch(const float* in, float* out, int B, int H, int W, i
 // out_x = FIR(in), out_h = FIR(act(in * nscale + nshift)) in one pass (the up / down BigGAN block's two resampled tensors)
 int fir_resample2_nhwc_launch(const float* in, const float* nscale, const float* nshift, float* out_x, float* out_h, int B, int H, int W,
                               int C, const float* taps4, int up, int act, hipStream_t s);
+// NCSN++ residual input pyramid (fir_pyramid.hip): the FIR + stride-2 3x3 conv as one folded 6x6 stride-2 conv.  taps4 == NULL: fir = False
+// (F.pad(0, 1, 0, 1) + stride-2 conv).  Sources / data gradients are addressed as b * sb + (Y * H + X) * sp + c * sc (NHWC or NCHW).
+int fir_pyr_fold_launch(const float* w, int Cin, int Cout, const float* taps4, float* gf, float* gt, hipStream_t s);
+int fir_pyr_conv_launch(const float* x, int64_t sb, int sp, int64_t sc, int B, int H, int Cin, const float* gf, const float* bias,
+                        const float* res, float* out, int Cout, bool fir, float scale, hipStream_t s);
+int fir_pyr_dgrad_launch(const float* dy, const float* gt, float* dx, int64_t db, int dp, int64_t dc, int B, int H, int Cin, int nc, int Cout,
+                         bool fir, float scale, hipStream_t s);
+int fir_pyr_wgrad_slices(int B, int Cin, int Cout);
+size_t fir_pyr_wgrad_scratch_floats(int B, int Cin, int Cout);
+int fir_pyr_wgrad_launch(const float* x, int64_t sb, int sp, int64_t sc, int B, int H, int Cin, const float* dy, int Cout, const float* taps4,
+                         bool fir, float* dw, float* scratch, hipStream_t s);
 int fourier_embedding_launch(const float* t, const float* W, float* out, int B, int E, hipStream_t s);
 // per-operator convolution of the C ABI (ops_api.hip) with an optional NHWC residual added in the epilogue; GroupNorm backward with
 // an optional addend (train_nhwc.hip): the fused forms the planned training graph (train_graph.h) uses

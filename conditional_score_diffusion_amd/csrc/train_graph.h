@@ -2,8 +2,8 @@
 // ABI: csd_unet_train_forward / csd_unet_backward.  Included at the end of unet.hip (shares Net /
 // Module / Param).  NCSN++ (models/ncsnpp.py:238-388, models/layerspp.py:44-91,212-274): BigGAN blocks with FIR up / down sampling of
 // both branches (backward = the transposed FIR: the other direction's geometry with the flipped taps, op/upfirdn2d.py:20-87), the
-// Conv_2 shortcut, (x + h) / sqrt(2), AttnBlockpp, Combine 'sum' of the input pyramid, the output pyramid, Fourier or positional
-// embedding, GroupNorm(min(C / 4, 32)).
+// Conv_2 shortcut, (x + h) / sqrt(2), AttnBlockpp, Combine 'sum' of the input pyramid, the 'residual' input pyramid (fir_pyramid.hip),
+// the output pyramid, Fourier or positional embedding, GroupNorm(min(C / 4, 32)).
 //
 // What it replaces: torch autograd over models/ddpm.py:149-213 + models/layers.py:524-675 in training mode (run_lib.py:55-73).
 // The forward runs the reference's layer sequence on the NHWC operators of this library with nn.Dropout active and keeps
@@ -20,13 +20,14 @@
 namespace csd {
 
 struct TT { float* p = nullptr; int H = 0, C = 0; float* g = nullptr; };          // tensor [B, H, H, C]: data, gradient
-enum TSKind { TS_STEM, TS_RES, TS_ATTN, TS_DOWN, TS_UP, TS_CAT, TS_HEAD, TS_COMBINE, TS_PYR };
+enum TSKind { TS_STEM, TS_RES, TS_ATTN, TS_DOWN, TS_UP, TS_CAT, TS_HEAD, TS_COMBINE, TS_PYR, TS_RPYR };
 struct TStep {
   TSKind kind;
   int mod = -1, in0 = -1, in1 = -1, out = -1;
   float* sv[10] = {};
   uint64_t drop_id = 0;
   int flag = 0;                 // TS_PYR: 1 = the pyramid level above adds FIR-up of the previous level (in1)
+                                // (TS_RPYR: in0 = the down block's h, in1 = the pyramid source tensor, -1 = the network input)
 };
 
 struct TrainState {
@@ -147,6 +148,7 @@ struct TG {
   bool want_dx = false;         // backward: d loss / d x wanted (d_x = the caller's [B, x_channels, S, S] NCHW buffer)
   float* d_x = nullptr;
   float* dpyr = nullptr;        // NCSN++ input pyramid: x-channel gradient [B, cx, side, side] NCHW of the finest level combined so far
+  float* dres0 = nullptr;       // NCSN++ 'residual' pyramid: its level-0 convolution's x-channel data gradient [B, cx, S, S] NCHW (stem_dx adds it)
   // every gradient of the modules with index >= `from` has been enqueued: record the marks that this completes
   int marks_reached(int from) {
     if (!gm || dry) return CSD_OK;
@@ -270,6 +272,14 @@ struct TG {
     st.t.push_back(t);
     return (int)st.t.size() - 1;
   }
+
+  // the 'residual' pyramid's source: level 0 = the NCHW network input st.xin, later levels = the previous combined h (NHWC)
+  struct PyrSrc { const float* p; int64_t sb; int sp; int64_t sc; };
+  PyrSrc pyr_src(int tid, int H, int C) const {
+    if (tid < 0) return PyrSrc{st.xin, (int64_t)C * H * H, 1, (int64_t)H * H};
+    return PyrSrc{st.t[tid].p, (int64_t)H * H * C, C, 1};
+  }
+  const float* pyr_taps() const { return n.cfg.progressive_input == 2 ? n.cfg.fir_kernel : nullptr; }
 
   // =====================================================================================================================
   // forward (models/ddpm.py:149-213 with model.train())
@@ -614,6 +624,7 @@ struct TG {
     };
     const float* pyr_in = st.xin;                    // input pyramid (NCHW = [B * cio] single-channel images for the FIR pass)
     int pyr_side = S;
+    int pyr_tid = -1;                                // 'residual': the pyramid source tensor (-1: the network input st.xin)
     int h = -1;
     for (int l = 0; l < c.n_levels; ++l) {
       for (int b = 0; b < c.num_res_blocks; ++b) {
@@ -636,6 +647,24 @@ struct TG {
           sp.kind = TS_COMBINE; sp.mod = cm.idx; sp.in0 = h; sp.out = o; sp.sv[0] = pn;
           st.steps.push_back(sp);
           h = o;
+        } else if (c.progressive_input >= 2) {       // 'residual' (ncsnpp.py:300-307): h = (Downsample(pyramid) + h) * skip scale; pyramid = h
+          const Module& pm = n.mods[mi++];
+          const int side = st.t[h].H, C = pm.cout;
+          const int o = new_tensor(side, C);
+          {
+            const size_t mk = top;
+            float* gf = alloc((size_t)36 * pm.cin * C);
+            const PyrSrc ps = pyr_src(pyr_tid, 2 * side, pm.cin);
+            TG_RUN(fir_pyr_fold_launch(W(pm.idx, pyr_sub(c, false)), pm.cin, C, pyr_taps(), gf, nullptr, s));
+            TG_RUN(fir_pyr_conv_launch(ps.p, ps.sb, ps.sp, ps.sc, B, 2 * side, pm.cin, gf, W(pm.idx, pyr_sub(c, true)), st.t[h].p, st.t[o].p, C,
+                                       c.progressive_input == 2, skip_scale(), s));
+            top = mk;
+          }
+          TStep sp;
+          sp.kind = TS_RPYR; sp.mod = pm.idx; sp.in0 = h; sp.in1 = pyr_tid; sp.out = o;
+          st.steps.push_back(sp);
+          h = o;
+          pyr_tid = o;
         }
         hs.push_back(h);
       }
@@ -943,6 +972,7 @@ struct TG {
       rc = fir(dpyr, u, B * cx, S / 2, 1, true, true); if (rc) return rc;
       rc = add_into(d_x, u, np); if (rc) return rc;
     }
+    if (dres0) { rc = add_into(d_x, dres0, np); if (rc) return rc; }
     top = mk;
     return CSD_OK;
   }
@@ -954,6 +984,7 @@ struct TG {
     int rc;
     float* dtemb_act = nullptr;                      // sum over the blocks of dDense . W: gradient w.r.t. act(temb2)
     dpyr = nullptr;
+    dres0 = nullptr;
     if (c.conditional && pg) {
       dtemb_act = alloc((size_t)B * 4 * nf);
       if (!dry) CSD_CHECK_HIP(hipMemsetAsync(dtemb_act, 0, (size_t)B * 4 * nf * sizeof(float), s));
@@ -1007,6 +1038,35 @@ struct TG {
           rc = bias_grad(to.g, DW(m.idx, "Conv_0.bias"), m.cout, to.H); if (rc) return rc;
           if (want_dx) { rc = pyramid_dx(m, to); if (rc) return rc; }
           rc = contribute(sp.in0, to.g); if (rc) return rc;
+          break;
+        }
+        case TS_RPYR: {                              // out = (Downsample(src) + h) * k: d h = d Downsample = k dout
+          const Module& m = n.mods[sp.mod];
+          const TT& to = st.t[sp.out];
+          const int side = to.H, Hs = 2 * side, Cin = m.cin, C = m.cout, cx = c.x_channels;
+          const bool fir = c.progressive_input == 2;
+          float* dh = to.g;
+          if (skip_scale() != 1.f) { dh = alloc(act_n(side, C)); rc = scale_into(to.g, dh, skip_scale(), act_n(side, C)); if (rc) return rc; }
+          // the source's gradient: always into the previous level's combined h (the parameter gradients upstream depend on it); at level 0
+          // into d_x only when it is wanted (the x channels, times the 2x - 1 input map's 2 when not centred)
+          float* dsrc = sp.in1 >= 0 ? alloc(act_n(Hs, Cin)) : nullptr;
+          if (sp.in1 < 0 && want_dx) dres0 = alloc((size_t)B * cx * Hs * Hs);
+          const size_t mk = top;
+          const PyrSrc ps = pyr_src(sp.in1, Hs, Cin);
+          rc = bias_grad(dh, DW(m.idx, pyr_sub(c, true)), C, side); if (rc) return rc;
+          if (pg) {
+            float* part = alloc(fir_pyr_wgrad_scratch_floats(B, Cin, C));
+            TG_RUN(fir_pyr_wgrad_launch(ps.p, ps.sb, ps.sp, ps.sc, B, Hs, Cin, dh, C, pyr_taps(), fir, DW(m.idx, pyr_sub(c, false)), part, s));
+          }
+          if (dsrc || (sp.in1 < 0 && want_dx)) {
+            float* gt = alloc((size_t)36 * Cin * C);
+            TG_RUN(fir_pyr_fold_launch(W(m.idx, pyr_sub(c, false)), Cin, C, pyr_taps(), nullptr, gt, s));
+            if (dsrc) TG_RUN(fir_pyr_dgrad_launch(dh, gt, dsrc, (int64_t)Hs * Hs * Cin, Cin, 1, B, Hs, Cin, Cin, C, fir, 1.f, s));
+            else TG_RUN(fir_pyr_dgrad_launch(dh, gt, dres0, (int64_t)cx * Hs * Hs, 1, (int64_t)Hs * Hs, B, Hs, Cin, cx, C, fir, in_scale(), s));
+          }
+          top = mk;
+          rc = contribute(sp.in0, dh); if (rc) return rc;
+          if (dsrc) { rc = contribute(sp.in1, dsrc); if (rc) return rc; }
           break;
         }
         case TS_PYR: {                               // pyramid level: Conv(act(GroupNorm(h))) (+ FIR-up of the coarser level), NCHW
@@ -1194,8 +1254,8 @@ extern "C" int csd_unet_backward_ex(csd_unet* net, const float* const* params, f
   if (d_x) {
     const csd_unet_config& c = net->net.cfg;
     CSD_REQUIRE(c.x_channels >= 1, "backward_ex: d_x needs x_channels >= 1");
-    CSD_REQUIRE(c.arch == 0 || c.progressive_input == 0 || c.progressive_input == 1,
-                "backward_ex: d_x is not provided for progressive_input id %d (only 'none' and 'input_skip')", c.progressive_input);
+    CSD_REQUIRE(c.arch == 0 || (c.progressive_input >= 0 && c.progressive_input <= 3),
+                "backward_ex: d_x is not provided for progressive_input id %d", c.progressive_input);
   }
   TrainState* sp = train_state_find(&net->net, workspace);
   if (!sp || !sp->valid || sp->B != B || sp->ws != workspace) {

@@ -77,7 +77,7 @@ struct Param {
   const float* ptr = nullptr;
 };
 
-enum ModKind { M_LINEAR, M_CONV3, M_RES, M_ATTN, M_DOWN, M_UP, M_GN, M_FOURIER, M_COMBINE };
+enum ModKind { M_LINEAR, M_CONV3, M_RES, M_ATTN, M_DOWN, M_UP, M_GN, M_FOURIER, M_COMBINE, M_PYR };      // M_PYR: the 'residual' input pyramid's Downsample
 struct Module {
   ModKind kind;
   int idx;
@@ -107,7 +107,7 @@ struct Net;
 // execution plan for one batch size
 // ---------------------------------------------------------------------------------------------
 enum OpKind { OP_ASSEMBLE, OP_STEM, OP_TEMB, OP_FOURIER, OP_FIR, OP_FIR2, OP_GN_APPLY32, OP_LINEAR, OP_GN_STATS, OP_GN_FINAL, OP_GN_FINAL_TILES, OP_GN_APPLY16, OP_GN_FUSED16, OP_GN_STATFIN, OP_CONV, OP_ATTN, OP_AVGPOOL,
-              OP_UPNEAR, OP_TO_NCHW, OP_TAPSUM,
+              OP_UPNEAR, OP_TO_NCHW, OP_TAPSUM, OP_PYRCONV,
               OP_FORK, OP_JOIN };     // batch-chunk region (build_plan): the chunk streams start behind / the main stream resumes behind them
 
 static const size_t NONE = (size_t)-1;
@@ -208,6 +208,7 @@ struct Net {
   struct Copy { int param; size_t off; };            // raw fp32 copies (linear, GN affine, dense)
   std::vector<Copy> copies;
   std::map<std::string, size_t> copy_off;
+  std::map<int, size_t> pyr_fold_off;               // M_PYR module idx -> its folded 6x6 stride-2 weight (fir_pyramid.hip layout)
   size_t packed_floats = 0;
   size_t dense_all_off = 0, dense_all_bias_off = 0;  // concatenated Dense_0 of every res block
   int dense_total = 0;
@@ -399,7 +400,10 @@ static int build_modules(Net& n) {
 }
 
 // ---- NCSN++ module list: mirrors NCSNpp.__init__ (models/ncsnpp.py:44-236) for resblock_type 'biggan', fir = True,
-// progressive in {none, output_skip}, progressive_input in {none, input_skip}, progressive_combine 'sum' ----
+// progressive in {none, output_skip}, progressive_input in {none, input_skip, residual}, progressive_combine 'sum' ----
+static const char* pyr_sub(const csd_unet_config& c, bool bias) {      // layerspp.Downsample: Conv2d_0 (fir) or Conv_0 (fir = False)
+  return c.progressive_input == 2 ? (bias ? "Conv2d_0.bias" : "Conv2d_0.weight") : (bias ? "Conv_0.bias" : "Conv_0.weight");
+}
 static int ncsnpp_groups(int c) { return std::min(c / 4, 32); }     // layerspp.py:67,219,231; ncsnpp.py:200-233
 
 static int build_modules_ncsnpp(Net& n) {
@@ -414,8 +418,9 @@ static int build_modules_ncsnpp(Net& n) {
   CSD_REQUIRE(c.act >= CSD_ACT_SWISH && c.act <= CSD_ACT_ELU, "ncsnpp: bad activation id %d", c.act);
   CSD_REQUIRE(c.precision >= CSD_PREC_F32 && c.precision <= CSD_PREC_F16F8, "ncsnpp: bad precision id %d", c.precision);
   CSD_REQUIRE(c.conditional, "ncsnpp: only time-conditional networks are supported");
-  CSD_REQUIRE(c.progressive >= 0 && c.progressive <= 1 && c.progressive_input >= 0 && c.progressive_input <= 1,
-              "ncsnpp: 'residual' progressive growing is not supported");
+  CSD_REQUIRE(c.progressive >= 0 && c.progressive <= 1, "ncsnpp: progressive id %d is not supported (output 'residual' is not)",
+              c.progressive);
+  CSD_REQUIRE(c.progressive_input >= 0 && c.progressive_input <= 3, "ncsnpp: bad progressive_input id %d", c.progressive_input);
   CSD_REQUIRE(c.n_fir == 4, "ncsnpp: a 4-tap FIR kernel is required (got %d taps)", c.n_fir);
   auto add = [&](ModKind k, int cin, int cout, int up = 0, int down = 0) {
     Module m;
@@ -433,7 +438,7 @@ static int build_modules_ncsnpp(Net& n) {
   add(M_LINEAR, 4 * nf, 4 * nf);
   add(M_CONV3, channels, nf);
   std::vector<int> hs_c{nf};
-  int in_ch = nf;
+  int in_ch = nf, pyr_ch = channels;
   for (int l = 0; l < c.n_levels; ++l) {
     const int res = c.image_size >> l;
     for (int b = 0; b < c.num_res_blocks; ++b) {
@@ -446,6 +451,7 @@ static int build_modules_ncsnpp(Net& n) {
     if (l != c.n_levels - 1) {
       add(M_RES, in_ch, in_ch, 0, 1);
       if (c.progressive_input == 1) add(M_COMBINE, channels, in_ch);
+      if (c.progressive_input >= 2) { add(M_PYR, pyr_ch, in_ch); pyr_ch = in_ch; }      // ncsnpp.py:171-173
       hs_c.push_back(in_ch);
     }
   }
@@ -487,6 +493,10 @@ static int build_modules_ncsnpp(Net& n) {
       case M_COMBINE:
         n.add_param(mname(m.idx, "Conv_0.weight"), {m.cout, m.cin, 1, 1});
         n.add_param(mname(m.idx, "Conv_0.bias"), {m.cout});
+        break;
+      case M_PYR:
+        n.add_param(mname(m.idx, pyr_sub(c, false)), {m.cout, m.cin, 3, 3});
+        n.add_param(mname(m.idx, pyr_sub(c, true)), {m.cout});
         break;
       case M_ATTN:
         n.add_param(mname(m.idx, "GroupNorm_0.weight"), {m.cin});
@@ -777,6 +787,11 @@ static int build_packed_layout(Net& n) {
           rc = add_conv(std::to_string(m.idx) + ".Conv_0", n.in_cpad, 0, m.cout, 1,
                         {{n.P(mname(m.idx, "Conv_0.weight")), n.P(mname(m.idx, "Conv_0.bias")), 0, m.cout, 0, m.cin}});
           if (rc) return rc;
+        }
+        if (c.progressive_input >= 2) {
+          Module& m = nextm();      // 'residual' pyramid: the FIR-folded 6x6 stride-2 weight (pack_all folds it) + the raw bias
+          n.pyr_fold_off[m.idx] = take((size_t)36 * m.cin * m.cout);
+          add_copy(mname(m.idx, pyr_sub(c, true)));
         }
         hc.push_back(ich);
       }
@@ -1167,6 +1182,26 @@ struct Builder {
     return o.out;
   }
 
+  // 'residual' input pyramid (ncsnpp.py:300-307): (Downsample(src) + h) * skip scale in ONE launch (fir_pyramid.hip); src NHWC with
+  // `pix` floats per pixel.  (The next GroupNorm takes its statistics from a streaming pass: this kernel leaves no tile partials.)
+  size_t pyr_conv(const Module& m, size_t src, int pix, int side, size_t h) {
+    const csd_unet_config& c = n.cfg;
+    Op o;
+    o.kind = OP_PYRCONV;
+    o.a = src; o.c = h;
+    o.pk0 = n.pyr_fold_off.at(m.idx); o.pk1 = n.copy_off.at(mname(m.idx, pyr_sub(c, true)));
+    o.i0 = side; o.i1 = m.cin; o.i2 = m.cout; o.i3 = pix; o.i4 = c.progressive_input == 2 ? 1 : 0;
+    o.fscale = c.skip_rescale ? 0.70710678118654752440f : 1.f;
+    const size_t out_elems = (size_t)B * (side / 2) * (side / 2) * m.cout;
+    o.out = alloc_(out_elems);
+    o.cls = CSD_PROF_CONV3X3_RESAMPLE;
+    pl.ops.push_back(o);
+    // algorithmic flops: FIR + VALID stride-2 3x3 (fir) or the stride-2 3x3 (fir = False), as the reference computes them
+    count(2.0 * out_elems * m.cin * 9 + (o.i4 ? 2.0 * B * (side + 1) * (side + 1) * m.cin * 16 : 0.0),
+          ((double)B * side * side * m.cin + 2.0 * out_elems) * 4);
+    return o.out;
+  }
+
   // act(GroupNorm(x)) materialised in fp32 (the up/down blocks resample it before Conv_0)
   size_t gn_apply32(size_t src, int C, int hw, int act) {
     Op o;
@@ -1340,7 +1375,7 @@ static int build_plan(Net& n, int B, Plan** out) {
     Op as;
     as.kind = OP_ASSEMBLE;
     as.out = NONE;
-    if (!stem_pc.stem || c.progressive_input == 1) {      // (the input pyramid reads the assembled tensor)
+    if (!stem_pc.stem || c.progressive_input != 0) {      // (the input pyramid reads the assembled tensor)
       as.out = bd.alloc_((size_t)B * S * S * n.in_cpad);
       pl.ops.push_back(as);
       pl.launches += 1;
@@ -1395,8 +1430,8 @@ static int build_plan(Net& n, int B, Plan** out) {
     }
     struct Skip { size_t off; int ch; };
     std::vector<Skip> hs;
-    size_t pyr_in = c.progressive_input == 1 ? as.out : NONE;     // input pyramid (8-channel padded NHWC)
-    int pyr_side = S;
+    size_t pyr_in = c.progressive_input != 0 ? as.out : NONE;     // input pyramid (8-channel padded NHWC)
+    int pyr_side = S, pyr_pix = n.in_cpad;
     {
       const Module& m = next_mod();
       const size_t h0 = stem_pc.stem ? bd.stem(stem_pc, m, S)
@@ -1432,11 +1467,19 @@ static int build_plan(Net& n, int B, Plan** out) {
                                      NONE, false, channels);
           bd.ar.release(h);
           h = hc2;
+        } else if (c.progressive_input >= 2) {
+          // 'residual': input_pyramid = Downsample(input_pyramid); h = (input_pyramid + h) * skip scale; input_pyramid = h.  From level 1
+          // on the source is the previous level's combined h, a live skip-stack entry: the up path releases it, never this one
+          const Module& pm = next_mod();
+          const size_t hc2 = bd.pyr_conv(pm, pyr_in, pyr_pix, side, h);
+          bd.ar.release(h);
+          h = hc2;
+          pyr_in = h; pyr_pix = in_ch; pyr_side = side / 2;
         }
         hs.push_back({h, in_ch});
       }
     }
-    if (pyr_in != NONE && pyr_in != as.out) bd.ar.release(pyr_in);
+    if (c.progressive_input == 1 && pyr_in != NONE && pyr_in != as.out) bd.ar.release(pyr_in);
     bd.ar.release(as.out);
     size_t h = hs.back().off;
     {
@@ -1935,6 +1978,10 @@ static int run_plan(Net& n, const Plan& pl, const float* pk, float* ws, const fl
       case OP_UPNEAR:
         rc = nearest_up2_nhwc_launch(W(o.a), W(o.out), Bo, o.i0, o.i0, o.i1, so);
         break;
+      case OP_PYRCONV:
+        rc = fir_pyr_conv_launch(W(o.a), (int64_t)o.i0 * o.i0 * o.i3, o.i3, 1, Bo, o.i0, o.i1, pk + o.pk0, pk + o.pk1, W(o.c), W(o.out), o.i2,
+                                 o.i4 != 0, o.fscale, so);
+        break;
       case OP_TAPSUM:
         rc = tapsum_launch(W(o.a), pk + o.pk1, W(o.c), o.out_external ? out : W(o.out), Bo, o.i0, o.i1, o.i2, o.out_external, o.fscale, so);
         break;
@@ -2015,6 +2062,12 @@ static int pack_all(Net& n, float* pk, hipStream_t s) {
       if (rc) return rc;
       batch.add(n.params[src.param_b].ptr, pk + pc.b_off + src.cout_off, (size_t)src.cout_src);      // (behind the fill above: same stream)
     }
+  }
+  for (auto& m : n.mods) {
+    if (m.kind != M_PYR) continue;
+    rc = fir_pyr_fold_launch(n.params[n.P(mname(m.idx, pyr_sub(n.cfg, false)))].ptr, m.cin, m.cout,
+                             n.cfg.progressive_input == 2 ? n.cfg.fir_kernel : nullptr, pk + n.pyr_fold_off.at(m.idx), nullptr, s);
+    if (rc) return rc;
   }
   if (n.cfg.conditional) {
     const int K = 4 * n.cfg.nf;

@@ -8,8 +8,9 @@ resampling, Linear, Fourier / positional embedding, axpby, bias add) - torch onl
 skip connections (a copy) and slices views.  There is no PyTorch fallback.
 
 This first NCSN++ executor is *operator-granular* (one C-ABI call per layer, NCHW at the boundary, weights packed
-per call): it establishes parity for the family the north star names; the planned NHWC graph executor that the
-DDPM family already has (csrc/unet.hip) is the next step for it.
+per call).  The registry hands out the planned NHWC graph executor (``NCSNppPlanned`` below, csrc/unet.hip arch 1) for
+every option; the operator-granular classes stay registered as ``ncsnpp_ops`` / ``ncsnpp_paired_ops``, the A/B
+yardstick of the planned graph.
 
 Covered options - every NCSN++ / DDPM++ config of the reference (configs/{ve,vp,subvp}/*ncsnpp*, *ddpmpp*) falls in this set:
 ``resblock_type='biggan'``, ``fir`` True (any FIR kernel) or False (naive nearest / 2x2-mean resampling), ``progressive`` in
@@ -412,14 +413,14 @@ class HipNCSNpp(HipUNet):
         m = config.model
         if m.resblock_type.lower() != 'biggan':
             raise NotImplementedError("ncsnpp on the HIP path: resblock_type 'biggan' only (got %r)" % m.resblock_type)
-        if m.progressive.lower() == 'residual' or m.progressive_input.lower() == 'residual':
-            raise NotImplementedError("the planned NCSN++ graph does not cover 'residual' progressive growing (the registry hands "
-                                      "out the operator-granular class for progressive_input='residual')")
+        if m.progressive.lower() == 'residual':
+            # (its pyramid_upsample is up_or_down_sampling.Conv2d(up=True) = upsample_conv_2d, which fails upstream; no config uses it)
+            raise NotImplementedError("ncsnpp on the HIP path: progressive='residual' is not provided")
         if m.progressive_combine.lower() != 'sum':
             raise NotImplementedError("ncsnpp on the HIP path: progressive_combine 'sum' only")
         if not m.conditional:
             raise NotImplementedError('ncsnpp on the HIP path: time-conditional networks only')
-        assert m.progressive.lower() in ['none', 'output_skip'] and m.progressive_input.lower() in ['none', 'input_skip']
+        assert m.progressive.lower() in ['none', 'output_skip'] and m.progressive_input.lower() in ['none', 'input_skip', 'residual']
         assert m.embedding_type.lower() in ['fourier', 'positional']
         if m.embedding_type.lower() == 'fourier':
             assert config.training.continuous, "Fourier features are only used for continuous training."
@@ -438,7 +439,8 @@ class HipNCSNpp(HipUNet):
         m = config.model
         cfg.skip_rescale = int(bool(m.skip_rescale))
         cfg.progressive = 1 if m.progressive.lower() == 'output_skip' else 0
-        cfg.progressive_input = 1 if m.progressive_input.lower() == 'input_skip' else 0
+        # 'residual': 2 = layerspp.Downsample with fir (Conv2d_0: FIR + VALID stride-2 conv), 3 = without (Conv_0: pad + stride-2 conv)
+        cfg.progressive_input = {'none': 0, 'input_skip': 1, 'residual': 2 if m.fir else 3}[m.progressive_input.lower()]
         cfg.embedding_type = 1 if m.embedding_type.lower() == 'fourier' else 0
         # fir = False (naive nearest / 2x2-mean resampling, up_or_down_sampling.py:59-69) IS the 4-tap FIR (0, 1, 1, 0): the
         # normalised kernel is a 2x2 box, with the same pads
@@ -514,17 +516,13 @@ class NCSNppPairedPlanned(HipNCSNpp):
         return {'x': out[:, :c], 'y': out[:, c:]}
 
 
-def _needs_operator_granular(config):
-    return config.model.progressive_input.lower() == 'residual'
-
-
 def create_ncsnpp(config, **kw):
-    """``ncsnpp``: the planned graph executor, or the operator-granular class for the options only it covers"""
-    return (NCSNpp if _needs_operator_granular(config) else NCSNppPlanned)(config, **kw)
+    """``ncsnpp``: the planned graph executor (every option the HIP path covers runs on it)"""
+    return NCSNppPlanned(config, **kw)
 
 
 def create_ncsnpp_paired(config, **kw):
-    return (NCSNpp_paired if _needs_operator_granular(config) else NCSNppPairedPlanned)(config, **kw)
+    return NCSNppPairedPlanned(config, **kw)
 
 
 utils.register_model(create_ncsnpp, name='ncsnpp')

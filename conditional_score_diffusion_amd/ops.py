@@ -51,6 +51,40 @@ def conv2d(x, weight, bias=None, stride=1, downsample_pad=False, up2=False, prec
     return y
 
 
+def fir_pyr_conv(x, weight, bias=None, res=None, fir_kernel=(1, 3, 3, 1), out_scale=1.0):
+    """The 'residual' input pyramid of NCSN++ (layerspp.Downsample(with_conv=True), layerspp.py:129-163) on NHWC fp32 tensors:
+    ``(Downsample(x) + res) * out_scale``.  x [B, H, H, Cin], weight [Cout, Cin, 3, 3] OIHW, res [B, H/2, H/2, Cout] or None.
+    ``fir_kernel`` (4 taps): conv_downsample_2d (FIR with pads (2, 2), then a VALID stride-2 conv); None: fir = False
+    (F.pad(0, 1, 0, 1) + stride-2 conv).  csd_fir_pyr_conv.  Returns [B, H/2, H/2, Cout]."""
+    import ctypes
+    x, weight = _c(x, 'x'), _c(weight, 'weight')
+    B, H, W, Cin = x.shape
+    Cout = weight.shape[0]
+    if H != W or H % 2 or tuple(weight.shape[1:]) != (Cin, 3, 3):
+        raise RuntimeError('fir_pyr_conv: x %s / weight %s do not match' % (tuple(x.shape), tuple(weight.shape)))
+    if bias is not None:
+        bias = _c(bias, 'bias')
+        if tuple(bias.shape) != (Cout,):
+            raise RuntimeError('fir_pyr_conv: bias %s is not [Cout] = [%d]' % (tuple(bias.shape), Cout))
+    if res is not None:
+        res = _c(res, 'res')
+        if tuple(res.shape) != (B, H // 2, H // 2, Cout):
+            raise RuntimeError('fir_pyr_conv: res %s is not [B, H/2, H/2, Cout]' % (tuple(res.shape),))
+    if any(t is not None and t.device != x.device for t in (weight, bias, res)):
+        raise RuntimeError('fir_pyr_conv: x, weight, bias and res must be on one device')
+    taps = None
+    if fir_kernel is not None:
+        if len(fir_kernel) != 4:
+            raise NotImplementedError('fir_pyr_conv: 4-tap FIR kernels only')
+        taps = (ctypes.c_float * 4)(*[float(v) for v in fir_kernel])
+    y = torch.empty(B, H // 2, H // 2, Cout, dtype=torch.float32, device=x.device)
+    sc = _scratch(lib().csd_fir_pyr_conv_scratch_bytes(Cin, Cout), x.device)
+    check(lib().csd_fir_pyr_conv(ptr(x), ptr(weight), ptr(bias), ptr(res), ptr(y), B, Cin, Cout, H, Cin,
+                                 ctypes.cast(taps, ctypes.c_void_p) if taps is not None else None, float(out_scale), ptr(sc),
+                                 current_stream(x.device)), 'fir_pyr_conv')
+    return y
+
+
 def conv3x3_block(x0, weight, bias=None, x1=None, nscale=None, nshift=None, temb=None, res=None, out_scale=1.0,
                   precision='fp16x3', want_stats=False):
     """The ResnetBlock convolution with its prologue fused (models/layers.py:632-675): y = Conv3x3(SiLU(x*nscale + nshift))

@@ -109,7 +109,8 @@ typedef struct csd_unet_config {
   /* ---- arch 1 (NCSN++, models/ncsnpp.py:44-236) only; resblock_type 'biggan', fir = True, combine 'sum' ---- */
   int32_t skip_rescale;         /* config.model.skip_rescale: (x + h)/sqrt(2)                */
   int32_t progressive;          /* 0 'none', 1 'output_skip'                                 */
-  int32_t progressive_input;    /* 0 'none', 1 'input_skip'                                  */
+  int32_t progressive_input;    /* 0 'none', 1 'input_skip', 2 'residual' with fir = True (Downsample Conv2d_0: FIR + VALID
+                                   stride-2 conv), 3 'residual' with fir = False (Downsample Conv_0: pad (0,1,0,1) + stride-2 conv) */
   int32_t embedding_type;       /* 0 'positional', 1 'fourier' (W [nf] is parameter all_modules.0.W) */
   int32_t n_fir;                /* taps of config.model.fir_kernel (<= 8)                    */
   float fir_kernel[8];
@@ -265,6 +266,16 @@ int csd_upfirdn2d(const float* x, const float* kernel, float* out, int N, int C,
                   int pad_y1, void* stream);
 /* fused_bias_act (op/fused_bias_act_kernel.cu:18-49): out = lrelu(x + b[c], alpha) * scale,
  * act: 1 linear, 3 lrelu; grad 0 forward, 1 backward w.r.t. x using `ref` = forward output. */
+/* NCSN++ residual input pyramid (layerspp.Downsample(with_conv=True), layerspp.py:129-163; fir_pyramid.hip):
+ *   out = (Downsample(x) + res) * out_scale     (res == NULL: Downsample(x) * out_scale)
+ * x NHWC [B, H, H, Cin] with x_pixel_stride (>= Cin) floats per pixel; w [Cout, Cin, 3, 3] OIHW, bias [Cout] (may be NULL);
+ * res / out NHWC [B, H/2, H/2, Cout].  fir_kernel (host, 4 taps): conv_downsample_2d = upfirdn2d with the normalised FIR, pads
+ * (2, 2), then a VALID stride-2 conv (up_or_down_sampling.py:144-178); fir_kernel == NULL: F.pad(0,1,0,1) + stride-2 conv (fir = False).
+ * Computed as one 6x6 stride-2 convolution with the FIR folded into the weight (fp64 fold), fp32 arithmetic, deterministic.
+ * scratch: csd_fir_pyr_conv_scratch_bytes(Cin, Cout). */
+size_t csd_fir_pyr_conv_scratch_bytes(int Cin, int Cout);
+int csd_fir_pyr_conv(const float* x, const float* w, const float* bias, const float* res, float* out, int B, int Cin, int Cout, int H,
+                     int x_pixel_stride, const float* fir_kernel, float out_scale, void* scratch, void* stream);
 int csd_fused_bias_act(const float* x, const float* bias, const float* ref, float* out, int64_t numel,
                        int C, int64_t inner, int act, int grad, float alpha, float scale, void* stream);
 /* nearest-neighbour x2 upsample (F.interpolate in models/layers.py:601) */
@@ -417,8 +428,10 @@ int csd_unet_backward(csd_unet* net, const float* const* params, float* const* g
  *   grads == NULL: no parameter gradient is formed (no wgrad, no bias sums, no temb-MLP backward, no gradient-ready marks).
  *   d_x != NULL:   d loss / d x, [B, x_channels, S, S] NCHW fp32 (the x channels of the input only; y takes no gradient).
  * csd_unet_backward(...) is csd_unet_backward_ex(..., grads, NULL).  The data-gradient kernels are the same with or without grads,
- * so d_x does not depend on whether parameter gradients are formed.  Both architectures; NCSN++ with progressive_input 'none' or
- * 'input_skip' (the input pyramid's gradient chain: d pyr_l = Conv_0^T(dh_l) + FIR-down^T(d pyr_l+1), d x += FIR-down^T(d pyr_1)). */
+ * so d_x does not depend on whether parameter gradients are formed.  Both architectures; NCSN++ with every progressive_input:
+ * 'input_skip' (the input pyramid's gradient chain: d pyr_l = Conv_0^T(dh_l) + FIR-down^T(d pyr_l+1), d x += FIR-down^T(d pyr_1)),
+ * 'residual' (the pyramid convolution's data gradient flows into the previous level's combined h - always, the parameter gradients
+ * depend on it - and, at level 0, into d_x). */
 int csd_unet_backward_ex(csd_unet* net, const float* const* params, float* const* grads, float* d_x, void* workspace,
                          size_t workspace_bytes, const float* d_out, int B, uint64_t call_index, void* stream);
 /* The library keeps one recorded training graph per (handle, workspace).  A caller that frees a workspace (a monitoring forward's
