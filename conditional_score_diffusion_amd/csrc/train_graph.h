@@ -379,7 +379,7 @@ struct TG {
         rc = fir(a0, hr, B, H, cin, m.up != 0, false); if (rc) return rc;
         rc = fir(h, xr, B, H, cin, m.up != 0, false); if (rc) return rc;
       }
-      float* d = alloc((size_t)B * cout);            // (time-conditional networks only: build_modules_ncsnpp)
+      float* d = alloc((size_t)B * cout);            // (time-conditional networks only: build_modules)
       TG_RUN(csd_linear(st.temb2_act, W(m.idx, "Dense_0.weight"), W(m.idx, "Dense_0.bias"), d, B, 4 * c.nf, cout, CSD_ACT_NONE, s));
       rc = conv(hr, W(m.idx, "Conv_0.weight"), W(m.idx, "Conv_0.bias"), c0, cin, cout, Ho, 3, 1, 0, 0, 3, nullptr, d, pl0);
       if (rc) return rc;
@@ -466,14 +466,45 @@ struct TG {
     return CSD_OK;
   }
 
+  // act(GroupNorm(h)) + conv, NHWC in, NCHW out: the head (pyr == null) or one level of the NCSN++ output pyramid - pyramid =
+  // Conv(act(GroupNorm(h))) + pyramid_upsample(pyramid) (ncsnpp.py:340-352; *pyr: tensor id of the coarser level, NCHW data; level 0 writes `out`)
+  int out_fwd(const Module& mg, int h, float* out, int* pyr) {
+    const Module& mc = n.mods[mg.idx + 1];
+    const int H = st.t[h].H, C = mg.cin, co = n.cfg.out_channels;
+    float* g = alloc(act_n(H, C));
+    float* rs = alloc((size_t)B * C); float* ms = alloc((size_t)B * C);
+    int rc = gn(st.t[h].p, W(mg.idx, "weight"), W(mg.idx, "bias"), g, rs, ms, C, H, act); if (rc) return rc;
+    TStep sp;
+    sp.kind = pyr ? TS_PYR : TS_HEAD; sp.mod = mg.idx; sp.in0 = h;
+    sp.sv[0] = g; sp.sv[1] = rs; sp.sv[2] = ms;
+    if (pyr) {
+      sp.out = new_tensor(H, co, false);
+      st.t[sp.out].p = out = mg.level == 0 ? out : alloc((size_t)B * co * H * H);
+      sp.in1 = *pyr;
+      sp.flag = (*pyr >= 0 ? 1 : 0) | (mg.level == 0 ? 2 : 0);
+    }
+    rc = conv(g, W(mc.idx, "weight"), W(mc.idx, "bias"), out, C, co, H, 3, 1, 0, 0, 1); if (rc) return rc;
+    if (pyr && *pyr >= 0) {
+      const size_t mk = top;
+      float* up = alloc((size_t)B * co * H * H);
+      rc = fir(st.t[*pyr].p, up, B * co, H / 2, 1, true, false); if (rc) return rc;
+      rc = add_into(out, up, (size_t)B * co * H * H); if (rc) return rc;
+      top = mk;
+    }
+    st.steps.push_back(sp);
+    if (pyr) *pyr = sp.out;
+    return CSD_OK;
+  }
+
+  // one walk over Net::mods for both families (models/ddpm.py:149-213, models/ncsnpp.py:238-388 with model.train())
   int forward(const float* x, const float* y, const float* labels, float* out) {
     const csd_unet_config& c = n.cfg;
-    if (c.arch == 1) return forward_ncsnpp(x, y, labels, out);
+    const bool pp = c.arch == 1;
     const int S = c.image_size, cx = c.x_channels, cy = c.y_channels, cio = cx + cy, nf = c.nf;
     st.t.clear(); st.steps.clear();
     drop_count = 0;
     st.lin0 = 0; st.emb_dim = nf; st.fourier_mod = -1;
-    // network input: cat(x, y) NCHW (models/ddpm.py:275-298 wrappers), 2h - 1 for data in [0, 1] (:163-168)
+    // network input: cat(x, y) NCHW (models/ddpm.py:275-298 wrappers), 2h - 1 for data in [0, 1] (:163-168; ncsnpp.py:266-268)
     const size_t hw = (size_t)S * S;
     st.xin = alloc((size_t)B * cio * hw);
     if (!dry) {
@@ -481,248 +512,113 @@ struct TG {
       if (cy) CSD_CHECK_HIP(hipMemcpy2DAsync(st.xin + cx * hw, cio * hw * 4, y, cy * hw * 4, cy * hw * 4, B, hipMemcpyDeviceToDevice, s));
       if (!c.centered) TG_RUN(csd_axpby(st.xin, nullptr, st.xin, 2.f, 0.f, -1.f, 1.f, (int64_t)((size_t)B * cio * hw), s));
     }
-    size_t mi = 0;
-    if (c.conditional) {                             // timestep embedding + 2-layer MLP (models/ddpm.py:153-160)
-      st.emb = alloc((size_t)B * nf); st.temb1 = alloc((size_t)B * 4 * nf); st.temb2 = alloc((size_t)B * 4 * nf);
-      TG_RUN(csd_timestep_embedding(labels, st.emb, B, nf, s));
-      TG_RUN(csd_linear(st.emb, W(0, "weight"), W(0, "bias"), st.temb1, B, nf, 4 * nf, CSD_ACT_NONE, s));
-      TG_RUN(csd_linear(st.temb1, W(1, "weight"), W(1, "bias"), st.temb2, B, 4 * nf, 4 * nf, act, s));
-      st.temb2_act = alloc((size_t)B * 4 * nf);
-      TG_RUN(csd_act(st.temb2, nullptr, st.temb2_act, act, (int64_t)B * 4 * nf, s));
-      mi = 2;
-    }
-    int rc;
-    std::vector<int> hs;
-    {                                                // stem conv: NCHW in, NHWC out
-      const Module& m = n.mods[mi++];
-      const int t0 = new_tensor(S, nf);
-      rc = conv(st.xin, W(m.idx, "weight"), W(m.idx, "bias"), st.t[t0].p, cio, nf, S, 3, 1, 0, 0, 2);
-      if (rc) return rc;
-      TStep sp;
-      sp.kind = TS_STEM; sp.mod = m.idx; sp.out = t0;
-      st.steps.push_back(sp);
-      hs.push_back(t0);
-    }
-    auto is_attn = [&](int res) {
-      for (int i = 0; i < c.n_attn; ++i) if (c.attn_resolutions[i] == res) return true;
-      return false;
-    };
-    int h = -1;
-    for (int l = 0; l < c.n_levels; ++l) {
-      for (int b = 0; b < c.num_res_blocks; ++b) {
-        rc = res_fwd(n.mods[mi++], hs.back(), &h);
-        if (rc) return rc;
-        if (is_attn(st.t[h].H)) { rc = attn_fwd(n.mods[mi++], h, &h); if (rc) return rc; }
-        hs.push_back(h);
-      }
-      if (l != c.n_levels - 1) {                     // Downsample: pad (0,1,0,1) + stride-2 conv (models/layers.py:619-625)
-        const Module& m = n.mods[mi++];
-        const int in = hs.back(), H = st.t[in].H, C = m.cin;
-        const int o = new_tensor(H / 2, C);
-        rc = conv(st.t[in].p, W(m.idx, "Conv_0.weight"), W(m.idx, "Conv_0.bias"), st.t[o].p, C, C, H, 3, 2, 1, 0, 3);
-        if (rc) return rc;
-        TStep sp;
-        sp.kind = TS_DOWN; sp.mod = m.idx; sp.in0 = in; sp.out = o;
-        st.steps.push_back(sp);
-        hs.push_back(o);
-      }
-    }
-    h = hs.back();
-    rc = res_fwd(n.mods[mi++], h, &h); if (rc) return rc;
-    rc = attn_fwd(n.mods[mi++], h, &h); if (rc) return rc;
-    rc = res_fwd(n.mods[mi++], h, &h); if (rc) return rc;
-    for (int l = c.n_levels - 1; l >= 0; --l) {
-      for (int b = 0; b < c.num_res_blocks + 1; ++b) {
-        int cat;
-        rc = cat_fwd(h, hs.back(), &cat); if (rc) return rc;
-        hs.pop_back();
-        rc = res_fwd(n.mods[mi++], cat, &h); if (rc) return rc;
-      }
-      if (is_attn(st.t[h].H)) { rc = attn_fwd(n.mods[mi++], h, &h); if (rc) return rc; }
-      if (l != 0) {                                  // Upsample: nearest x2 + conv (models/layers.py:600-604)
-        const Module& m = n.mods[mi++];
-        const int H = st.t[h].H, C = m.cin;
-        const int o = new_tensor(2 * H, C);
-        rc = conv(st.t[h].p, W(m.idx, "Conv_0.weight"), W(m.idx, "Conv_0.bias"), st.t[o].p, C, C, H, 3, 1, 0, 1, 3);
-        if (rc) return rc;
-        TStep sp;
-        sp.kind = TS_UP; sp.mod = m.idx; sp.in0 = h; sp.out = o;
-        st.steps.push_back(sp);
-        h = o;
-      }
-    }
-    CSD_REQUIRE(hs.empty() && mi + 2 == n.mods.size(), "train_forward: module walk out of step (%zu of %zu)", mi, n.mods.size());
-    {                                                // head: act(GroupNorm) + conv, NHWC in, NCHW out
-      const Module& mg = n.mods[mi];
-      const Module& mc = n.mods[mi + 1];
-      const int H = st.t[h].H, C = mg.cin;
-      float* g = alloc(act_n(H, C));
-      float* rs = alloc((size_t)B * C); float* ms = alloc((size_t)B * C);
-      rc = gn(st.t[h].p, W(mg.idx, "weight"), W(mg.idx, "bias"), g, rs, ms, C, H, act);
-      if (rc) return rc;
-      rc = conv(g, W(mc.idx, "weight"), W(mc.idx, "bias"), out, C, c.out_channels, H, 3, 1, 0, 0, 1);
-      if (rc) return rc;
-      TStep sp;
-      sp.kind = TS_HEAD; sp.mod = mg.idx; sp.in0 = h;
-      sp.sv[0] = g; sp.sv[1] = rs; sp.sv[2] = ms;
-      st.steps.push_back(sp);
-    }
-    st.fwd_top = top;
-    return CSD_OK;
-  }
-
-  // =====================================================================================================================
-  // forward, NCSN++ (models/ncsnpp.py:238-388 with model.train(); the module walk of build_modules_ncsnpp)
-  // =====================================================================================================================
-  int forward_ncsnpp(const float* x, const float* y, const float* labels, float* out) {
-    const csd_unet_config& c = n.cfg;
-    const int S = c.image_size, cx = c.x_channels, cy = c.y_channels, cio = cx + cy, nf = c.nf;
-    st.t.clear(); st.steps.clear();
-    drop_count = 0;
-    const size_t hw = (size_t)S * S;
-    st.xin = alloc((size_t)B * cio * hw);            // cat(x, y) NCHW, 2h - 1 for data in [0, 1] (ncsnpp.py:266-268)
-    if (!dry) {
-      CSD_CHECK_HIP(hipMemcpy2DAsync(st.xin, cio * hw * 4, x, cx * hw * 4, cx * hw * 4, B, hipMemcpyDeviceToDevice, s));
-      if (cy) CSD_CHECK_HIP(hipMemcpy2DAsync(st.xin + cx * hw, cio * hw * 4, y, cy * hw * 4, cy * hw * 4, B, hipMemcpyDeviceToDevice, s));
-      if (!c.centered) TG_RUN(csd_axpby(st.xin, nullptr, st.xin, 2.f, 0.f, -1.f, 1.f, (int64_t)((size_t)B * cio * hw), s));
-    }
-    size_t mi = 0;
-    st.fourier_mod = -1;
-    st.emb_dim = nf;
-    if (c.embedding_type == 1) {                     // Gaussian Fourier features of the label (layerspp.py:32-41; W is a fixed buffer)
-      const Module& fm = n.mods[mi++];
-      st.fourier_mod = fm.idx;
-      st.emb_dim = 2 * nf;
-      st.emb = alloc((size_t)B * 2 * nf);
-      TG_RUN(csd_fourier_embedding(labels, W(fm.idx, "W"), st.emb, B, nf, s));
-    } else {
-      st.emb = alloc((size_t)B * nf);
-      TG_RUN(csd_timestep_embedding(labels, st.emb, B, nf, s));
-    }
-    st.lin0 = (int)mi;
-    st.temb1 = alloc((size_t)B * 4 * nf); st.temb2 = alloc((size_t)B * 4 * nf);
-    TG_RUN(csd_linear(st.emb, W((int)mi, "weight"), W((int)mi, "bias"), st.temb1, B, st.emb_dim, 4 * nf, CSD_ACT_NONE, s));
-    TG_RUN(csd_linear(st.temb1, W((int)mi + 1, "weight"), W((int)mi + 1, "bias"), st.temb2, B, 4 * nf, 4 * nf, act, s));
-    st.temb2_act = alloc((size_t)B * 4 * nf);
-    TG_RUN(csd_act(st.temb2, nullptr, st.temb2_act, act, (int64_t)B * 4 * nf, s));
-    mi += 2;
-    int rc;
-    std::vector<int> hs;
-    {                                                // first conv: NCHW in, NHWC out
-      const Module& m = n.mods[mi++];
-      const int t0 = new_tensor(S, nf);
-      rc = conv(st.xin, W(m.idx, "weight"), W(m.idx, "bias"), st.t[t0].p, cio, nf, S, 3, 1, 0, 0, 2);
-      if (rc) return rc;
-      TStep sp;
-      sp.kind = TS_STEM; sp.mod = m.idx; sp.out = t0;
-      st.steps.push_back(sp);
-      hs.push_back(t0);
-    }
-    auto is_attn = [&](int res) {
-      for (int i = 0; i < c.n_attn; ++i) if (c.attn_resolutions[i] == res) return true;
-      return false;
-    };
+    std::vector<int> hs;                             // skip stack (tensor ids)
+    int h = -1;                                      // the current tensor
     const float* pyr_in = st.xin;                    // input pyramid (NCHW = [B * cio] single-channel images for the FIR pass)
     int pyr_side = S;
     int pyr_tid = -1;                                // 'residual': the pyramid source tensor (-1: the network input st.xin)
-    int h = -1;
-    for (int l = 0; l < c.n_levels; ++l) {
-      for (int b = 0; b < c.num_res_blocks; ++b) {
-        rc = respp_fwd(n.mods[mi++], hs.back(), &h); if (rc) return rc;
-        if (is_attn(st.t[h].H)) { rc = attn_fwd(n.mods[mi++], h, &h); if (rc) return rc; }
-        hs.push_back(h);
-      }
-      if (l != c.n_levels - 1) {
-        rc = respp_fwd(n.mods[mi++], hs.back(), &h); if (rc) return rc;      // the down block
-        if (c.progressive_input == 1) {              // pyramid_downsample + Combine 'sum': Conv_0(pyramid) + h (layerspp.py:44-59)
-          const Module& cm = n.mods[mi++];
-          const int side = st.t[h].H, C = cm.cout;
+    int pyr = -1;                                    // output pyramid: tensor id of the previous (coarser) level, NCHW data
+    for (const Module& m : n.mods) {
+      int rc = CSD_OK;
+      switch (m.role) {
+        case R_EMB_FOURIER:                          // Gaussian Fourier features of the label (layerspp.py:32-41; W is a fixed buffer)
+          st.fourier_mod = m.idx;
+          st.emb_dim = 2 * nf;
+          st.emb = alloc((size_t)B * 2 * nf);
+          TG_RUN(csd_fourier_embedding(labels, W(m.idx, "W"), st.emb, B, nf, s));
+          break;
+        case R_EMB_LINEAR0:                          // (timestep embedding +) 2-layer MLP (models/ddpm.py:153-160)
+          st.lin0 = m.idx;
+          if (st.fourier_mod < 0) {
+            st.emb = alloc((size_t)B * nf);
+            TG_RUN(csd_timestep_embedding(labels, st.emb, B, nf, s));
+          }
+          st.temb1 = alloc((size_t)B * 4 * nf); st.temb2 = alloc((size_t)B * 4 * nf);
+          TG_RUN(csd_linear(st.emb, W(m.idx, "weight"), W(m.idx, "bias"), st.temb1, B, st.emb_dim, 4 * nf, CSD_ACT_NONE, s));
+          break;
+        case R_EMB_LINEAR1:
+          TG_RUN(csd_linear(st.temb1, W(m.idx, "weight"), W(m.idx, "bias"), st.temb2, B, 4 * nf, 4 * nf, act, s));
+          st.temb2_act = alloc((size_t)B * 4 * nf);
+          TG_RUN(csd_act(st.temb2, nullptr, st.temb2_act, act, (int64_t)B * 4 * nf, s));
+          break;
+        case R_STEM: {                               // NCHW in, NHWC out
+          h = new_tensor(S, nf);
+          rc = conv(st.xin, W(m.idx, "weight"), W(m.idx, "bias"), st.t[h].p, cio, nf, S, 3, 1, 0, 0, 2);
+          if (rc) return rc;
+          TStep sp;
+          sp.kind = TS_STEM; sp.mod = m.idx; sp.out = h;
+          st.steps.push_back(sp);
+          break;
+        }
+        case R_UP_BLOCK:
+          rc = cat_fwd(h, hs.back(), &h); if (rc) return rc;
+          hs.pop_back();
+          [[fallthrough]];
+        case R_DOWN_BLOCK: case R_MID_RES_IN: case R_MID_RES_OUT:
+          rc = pp ? respp_fwd(m, h, &h) : res_fwd(m, h, &h);
+          break;
+        case R_ATTN: case R_MID_ATTN:
+          rc = attn_fwd(m, h, &h);
+          break;
+        case R_DOWNSAMPLE: case R_UPSAMPLE: {
+          if (pp) { rc = respp_fwd(m, h, &h); break; }      // the BigGAN down / up block
+          // Downsample: pad (0,1,0,1) + stride-2 conv (models/layers.py:619-625); Upsample: nearest x2 + conv (:600-604)
+          const bool down = m.role == R_DOWNSAMPLE;
+          const int H = st.t[h].H, C = m.cin;
+          const int o = new_tensor(m.out_side, C);
+          rc = conv(st.t[h].p, W(m.idx, "Conv_0.weight"), W(m.idx, "Conv_0.bias"), st.t[o].p, C, C, H, 3, down ? 2 : 1, down ? 1 : 0, down ? 0 : 1, 3);
+          if (rc) return rc;
+          TStep sp;
+          sp.kind = down ? TS_DOWN : TS_UP; sp.mod = m.idx; sp.in0 = h; sp.out = o;
+          st.steps.push_back(sp);
+          h = o;
+          break;
+        }
+        case R_COMBINE: {                            // pyramid_downsample + Combine 'sum': Conv_0(pyramid) + h (layerspp.py:44-59)
+          const int side = st.t[h].H, C = m.cout;
           float* pn = alloc((size_t)B * cio * side * side);
           rc = fir(pyr_in, pn, B * cio, pyr_side, 1, false, false); if (rc) return rc;
           pyr_in = pn; pyr_side = side;
           const int o = new_tensor(side, C);
-          rc = conv(pn, W(cm.idx, "Conv_0.weight"), W(cm.idx, "Conv_0.bias"), st.t[o].p, cio, C, side, 1, 1, 0, 0, 2); if (rc) return rc;
+          rc = conv(pn, W(m.idx, "Conv_0.weight"), W(m.idx, "Conv_0.bias"), st.t[o].p, cio, C, side, 1, 1, 0, 0, 2); if (rc) return rc;
           rc = add_into(st.t[o].p, st.t[h].p, act_n(side, C)); if (rc) return rc;
           TStep sp;
-          sp.kind = TS_COMBINE; sp.mod = cm.idx; sp.in0 = h; sp.out = o; sp.sv[0] = pn;
+          sp.kind = TS_COMBINE; sp.mod = m.idx; sp.in0 = h; sp.out = o; sp.sv[0] = pn;
           st.steps.push_back(sp);
           h = o;
-        } else if (c.progressive_input >= 2) {       // 'residual' (ncsnpp.py:300-307): h = (Downsample(pyramid) + h) * skip scale; pyramid = h
-          const Module& pm = n.mods[mi++];
-          const int side = st.t[h].H, C = pm.cout;
+          break;
+        }
+        case R_PYR_DOWN: {                           // 'residual' (ncsnpp.py:300-307): h = (Downsample(pyramid) + h) * skip scale; pyramid = h
+          const int side = st.t[h].H, C = m.cout;
           const int o = new_tensor(side, C);
           {
             const size_t mk = top;
-            float* gf = alloc((size_t)36 * pm.cin * C);
-            const PyrSrc ps = pyr_src(pyr_tid, 2 * side, pm.cin);
-            TG_RUN(fir_pyr_fold_launch(W(pm.idx, pyr_sub(c, false)), pm.cin, C, pyr_taps(), gf, nullptr, s));
-            TG_RUN(fir_pyr_conv_launch(ps.p, ps.sb, ps.sp, ps.sc, B, 2 * side, pm.cin, gf, W(pm.idx, pyr_sub(c, true)), st.t[h].p, st.t[o].p, C,
+            float* gf = alloc((size_t)36 * m.cin * C);
+            const PyrSrc ps = pyr_src(pyr_tid, 2 * side, m.cin);
+            TG_RUN(fir_pyr_fold_launch(W(m.idx, pyr_sub(c, false)), m.cin, C, pyr_taps(), gf, nullptr, s));
+            TG_RUN(fir_pyr_conv_launch(ps.p, ps.sb, ps.sp, ps.sc, B, 2 * side, m.cin, gf, W(m.idx, pyr_sub(c, true)), st.t[h].p, st.t[o].p, C,
                                        c.progressive_input == 2, skip_scale(), s));
             top = mk;
           }
           TStep sp;
-          sp.kind = TS_RPYR; sp.mod = pm.idx; sp.in0 = h; sp.in1 = pyr_tid; sp.out = o;
+          sp.kind = TS_RPYR; sp.mod = m.idx; sp.in0 = h; sp.in1 = pyr_tid; sp.out = o;
           st.steps.push_back(sp);
-          h = o;
-          pyr_tid = o;
+          h = pyr_tid = o;
+          break;
         }
-        hs.push_back(h);
+        case R_PYR_GN:
+          rc = out_fwd(m, h, out, &pyr);
+          break;
+        case R_HEAD_GN:
+          rc = out_fwd(m, h, out, nullptr);
+          break;
+        case R_PYR_CONV: case R_HEAD_CONV:
+          break;                                     // (with its GroupNorm)
       }
+      if (rc) return rc;
+      if (m.push) hs.push_back(h);
     }
-    h = hs.back();
-    rc = respp_fwd(n.mods[mi++], h, &h); if (rc) return rc;
-    rc = attn_fwd(n.mods[mi++], h, &h); if (rc) return rc;
-    rc = respp_fwd(n.mods[mi++], h, &h); if (rc) return rc;
-    int pyr = -1;                                    // output pyramid: tensor id of the previous (coarser) level, NCHW data
-    for (int l = c.n_levels - 1; l >= 0; --l) {
-      for (int b = 0; b < c.num_res_blocks + 1; ++b) {
-        int cat;
-        rc = cat_fwd(h, hs.back(), &cat); if (rc) return rc;
-        hs.pop_back();
-        rc = respp_fwd(n.mods[mi++], cat, &h); if (rc) return rc;
-      }
-      if (is_attn(st.t[h].H)) { rc = attn_fwd(n.mods[mi++], h, &h); if (rc) return rc; }
-      if (c.progressive == 1) {                      // output_skip: pyramid = Conv(act(GroupNorm(h))) + pyramid_upsample(pyramid) (ncsnpp.py:340-352)
-        const Module& mg = n.mods[mi++];
-        const Module& mc = n.mods[mi++];
-        const int H = st.t[h].H, C = mg.cin;
-        float* g = alloc(act_n(H, C));
-        float* rs = alloc((size_t)B * C); float* ms = alloc((size_t)B * C);
-        rc = gn(st.t[h].p, W(mg.idx, "weight"), W(mg.idx, "bias"), g, rs, ms, C, H, act); if (rc) return rc;
-        const int pt = new_tensor(H, cio, false);
-        st.t[pt].p = l == 0 ? out : alloc((size_t)B * cio * H * H);
-        rc = conv(g, W(mc.idx, "weight"), W(mc.idx, "bias"), st.t[pt].p, C, cio, H, 3, 1, 0, 0, 1); if (rc) return rc;
-        TStep sp;
-        sp.kind = TS_PYR; sp.mod = mg.idx; sp.in0 = h; sp.in1 = pyr; sp.out = pt;
-        sp.sv[0] = g; sp.sv[1] = rs; sp.sv[2] = ms;
-        sp.flag = (pyr >= 0 ? 1 : 0) | (l == 0 ? 2 : 0);
-        if (pyr >= 0) {
-          const size_t mk = top;
-          float* up = alloc((size_t)B * cio * H * H);
-          rc = fir(st.t[pyr].p, up, B * cio, H / 2, 1, true, false); if (rc) return rc;
-          rc = add_into(st.t[pt].p, up, (size_t)B * cio * H * H); if (rc) return rc;
-          top = mk;
-        }
-        st.steps.push_back(sp);
-        pyr = pt;
-      }
-      if (l != 0) { rc = respp_fwd(n.mods[mi++], h, &h); if (rc) return rc; }      // the up block
-    }
-    if (c.progressive != 1) {                        // act(GroupNorm) + conv, NHWC in, NCHW out
-      const Module& mg = n.mods[mi];
-      const Module& mc = n.mods[mi + 1];
-      mi += 2;
-      const int H = st.t[h].H, C = mg.cin;
-      float* g = alloc(act_n(H, C));
-      float* rs = alloc((size_t)B * C); float* ms = alloc((size_t)B * C);
-      rc = gn(st.t[h].p, W(mg.idx, "weight"), W(mg.idx, "bias"), g, rs, ms, C, H, act); if (rc) return rc;
-      rc = conv(g, W(mc.idx, "weight"), W(mc.idx, "bias"), out, C, c.out_channels, H, 3, 1, 0, 0, 1); if (rc) return rc;
-      TStep sp;
-      sp.kind = TS_HEAD; sp.mod = mg.idx; sp.in0 = h;
-      sp.sv[0] = g; sp.sv[1] = rs; sp.sv[2] = ms;
-      st.steps.push_back(sp);
-    }
-    CSD_REQUIRE(hs.empty() && mi == n.mods.size(), "train_forward (ncsnpp): module walk out of step (%zu of %zu)", mi, n.mods.size());
+    CSD_REQUIRE(hs.empty(), "train_forward: the skip stack is not empty behind the last module");
     st.fwd_top = top;
     return CSD_OK;
   }

@@ -1,0 +1,143 @@
+// unet_run.h - run_plan: enqueue the launches of a plan.  No allocation, no synchronisation, no decision that the plan has not already
+// taken.  Included by unet.hip.
+#pragma once
+
+namespace csd {
+
+static int run_plan(Net& n, const Plan& pl, const float* pk, float* ws, const float* x, const float* y,
+                    const float* labels, float* out, const float* y_noise, float y_sigma, hipStream_t s) {
+  const csd_unet_config& c = n.cfg;
+  const int B = pl.B, S = c.image_size;
+  auto W = [&](size_t off) -> float* { return off == NONE ? nullptr : ws + off; };
+  bool side_pending = false;
+  for (const Op& o : pl.ops) {
+    int rc = CSD_OK;
+    // batch-chunk region: the chunk streams start behind everything enqueued so far; the caller's stream resumes behind all of them
+    if (o.kind == OP_FORK) {
+      if (!n.chunks_ready(o.i0 - 1)) { set_error("unet: cannot create the chunk streams"); return CSD_ERR_HIP; }
+      CSD_CHECK_HIP(hipEventRecord(n.ev_cfork, s));
+      for (int k = 0; k + 1 < o.i0; ++k) CSD_CHECK_HIP(hipStreamWaitEvent(n.cstream[k], n.ev_cfork, 0));
+      continue;
+    }
+    if (o.kind == OP_JOIN) {
+      for (int k = 0; k + 1 < o.i0; ++k) {
+        CSD_CHECK_HIP(hipEventRecord(n.ev_cjoin[k], n.cstream[k]));
+        CSD_CHECK_HIP(hipStreamWaitEvent(s, n.ev_cjoin[k], 0));
+      }
+      continue;
+    }
+    const int Bo = o.nb ? o.nb : B;
+    // side-stream ops: fork after everything enqueued so far, join before the op that consumes the result
+    hipStream_t so = o.stream ? n.cstream[o.stream - 1] : s;
+    if (o.side == 1 && n.side_ready()) {
+      CSD_CHECK_HIP(hipEventRecord(n.ev_fork, s));
+      CSD_CHECK_HIP(hipStreamWaitEvent(n.side, n.ev_fork, 0));
+      so = n.side;
+    } else if (o.side == 2 && side_pending) {
+      CSD_CHECK_HIP(hipStreamWaitEvent(s, n.ev_join, 0));
+      side_pending = false;
+    }
+    ProfScope prof(o.cls, o.flops, o.bytes, so, o.abytes);
+    switch (o.kind) {
+      case OP_ASSEMBLE:
+        rc = assemble_input_launch(x, y, y_noise, y_sigma, W(o.out), Bo, c.x_channels, c.y_channels, S * S,
+                                   n.in_cpad, c.centered, so);
+        break;
+      case OP_STEM:
+        rc = stem_launch(x, y, y_noise, y_sigma, pk + o.pk0, pk + o.pk1, W(o.out), reinterpret_cast<double*>(W(o.stats)), Bo,
+                         c.x_channels, c.y_channels, o.i0, S, c.centered, o.i4, so);
+        break;
+      case OP_TEMB:
+        rc = timestep_embedding_launch(labels, W(o.out), Bo, o.i0, so);
+        break;
+      case OP_FOURIER:
+        rc = fourier_embedding_launch(labels, pk + o.pk0, W(o.out), Bo, o.i0, so);
+        break;
+      case OP_FIR:
+        rc = fir_resample_nhwc_launch(W(o.a), W(o.out), Bo, o.i0, o.i0, o.i1, c.fir_kernel, o.i2, so);
+        break;
+      case OP_FIR2:
+        rc = fir_resample2_nhwc_launch(W(o.a), W(o.d), W(o.e), W(o.c), W(o.out), Bo, o.i0, o.i0, o.i1, c.fir_kernel, o.i2, o.act, so);
+        break;
+      case OP_GN_APPLY32:
+        rc = gn_apply_launch(W(o.a), W(o.d), W(o.e), W(o.out), Bo, o.i1, o.i0, o.act, so);
+        break;
+      case OP_LINEAR:
+        rc = linear_launch(W(o.a), pk + o.pk0, pk + o.pk1, W(o.out), Bo, o.i0, o.i1, o.act, so, o.i2);
+        break;
+      case OP_GN_STATS:
+        rc = gn_stats_launch(o.gp, W(o.a), W(o.b), reinterpret_cast<double*>(W(o.out)), so, o.i0);
+        break;
+      case OP_GN_FINAL:
+        rc = gn_finalize_launch(o.gp, reinterpret_cast<const double*>(W(o.a)), pk + o.pk0, pk + o.pk1, 1e-6f,
+                                W(o.out), W(o.b), so);
+        break;
+      case OP_GN_FINAL_TILES:
+        rc = gn_finalize_tiles_launch(reinterpret_cast<const double*>(W(o.a)), o.i0, o.i1,
+                                      reinterpret_cast<const double*>(W(o.b)), o.i2, o.i3, Bo, o.i4, o.gp.G, pk + o.pk0,
+                                      pk + o.pk1, 1e-6f, W(o.out), W(o.c), so);
+        break;
+      case OP_GN_STATFIN:
+        rc = gn_fused16_launch(W(o.a), W(o.b), o.gp.C0, o.gp.C1, pk + o.pk0, pk + o.pk1, 1e-6f, nullptr, nullptr, Bo, o.gp.HW, o.gp.G,
+                               CSD_ACT_NONE, so, 0, W(o.out), W(o.c));
+        break;
+      case OP_GN_FUSED16:
+        rc = gn_fused16_launch(W(o.a), W(o.b), o.i0, o.i1, pk + o.pk0, pk + o.pk1, 1e-6f, W(o.out), W(o.c), Bo, o.i2, o.gp.G, o.act, so, o.i3);
+        break;
+      case OP_GN_APPLY16:
+        rc = gn_apply16_launch(W(o.a), W(o.b), o.i0, o.i1, W(o.d), W(o.e), W(o.out), W(o.c), Bo, o.i2, o.act, so, o.i3);
+        break;
+      case OP_CONV: {
+        ConvArgs a;
+        a.src0 = W(o.a); a.src1 = W(o.b);
+        a.wpack = pk + o.pk0; a.bias = o.pk1 == NONE ? nullptr : pk + o.pk1;
+        a.temb = o.temb_col == NONE ? nullptr : ws + o.temb_base + o.temb_col;
+        a.res = W(o.c);
+        a.nscale = W(o.d);
+        a.nshift = W(o.e);
+        a.out = o.out_external ? out : W(o.out);
+        a.temb_stride = o.temb_stride;
+        a.out_stride = o.cp.Cout; a.out_coff = 0;
+        a.out_nchw = o.out_external;
+        a.act = o.act;
+        a.out_scale = o.fscale;
+        a.dbg = nullptr;
+        a.stats = reinterpret_cast<double*>(W(o.stats));
+        rc = o.i2 == 3 ? convff_launch(o.cp, o.i4, a, so)
+           : o.i2 == 2 ? conv16q_launch(o.cp, o.i4, a, so, o.i3 == 2)
+           : o.i2 ? pw16_launch(o.cp, o.i4, a, so) : (o.i4 ? conv16_launch(o.cp, o.i4, a, so, o.i3 != 0) : conv_launch(o.cp, a, so));
+        if (so == n.side && n.side != nullptr && rc == CSD_OK) {
+          CSD_CHECK_HIP(hipEventRecord(n.ev_join, n.side));
+          side_pending = true;
+        }
+        break;
+      }
+      case OP_ATTN:
+        // fp16 arithmetic modes: the split-operand kernel on the fp16 matrix cores (fp32-class in the split modes); fp32 mode: the fp32 MFMA one
+        rc = (precision_ns(c.precision) && !CSD_TUNE_ENV("CSD_ATTN_F32"))
+                 ? attention16_launch(W(o.a), 3 * o.i1, W(o.out), Bo, o.i0, o.i1, precision_ns(c.precision) >= 2 ? 2 : 1, so)
+                 : attention_launch(W(o.a), 3 * o.i1, W(o.out), Bo, o.i0, o.i1, so);
+        break;
+      case OP_AVGPOOL:
+        rc = avgpool2_launch(W(o.a), W(o.out), Bo, o.i0, o.i0, o.i1, so);
+        break;
+      case OP_UPNEAR:
+        rc = nearest_up2_nhwc_launch(W(o.a), W(o.out), Bo, o.i0, o.i0, o.i1, so);
+        break;
+      case OP_PYRCONV:
+        rc = fir_pyr_conv_launch(W(o.a), (int64_t)o.i0 * o.i0 * o.i3, o.i3, 1, Bo, o.i0, o.i1, pk + o.pk0, pk + o.pk1, W(o.c), W(o.out), o.i2,
+                                 o.i4 != 0, o.fscale, so);
+        break;
+      case OP_TAPSUM:
+        rc = tapsum_launch(W(o.a), pk + o.pk1, W(o.c), o.out_external ? out : W(o.out), Bo, o.i0, o.i1, o.i2, o.out_external, o.fscale, so);
+        break;
+      default:
+        set_error("unet: unknown op");
+        rc = CSD_ERR_STATE;
+    }
+    if (rc) return rc;
+  }
+  return CSD_OK;
+}
+
+}  // namespace csd

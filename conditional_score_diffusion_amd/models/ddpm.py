@@ -215,18 +215,10 @@ class HipUNet(nn.Module):
             if y_noise is not None:
                 raise RuntimeError('the fused y-perturbation is a sampling feature; it has no input gradient')
             return self._input_grad_forward(x, y, labels)
-        B = x.shape[0]
-        S = self.image_size
-        if tuple(x.shape) != (B, self.x_channels, S, S):
-            raise RuntimeError('x has shape %s, expected %s' % (tuple(x.shape), (B, self.x_channels, S, S)))
+        labels = self._check_io(x, y, labels)
+        B, S = x.shape[0], self.image_size
         if self.y_channels:
-            require_gpu_tensor(y, 'y')
-            if tuple(y.shape) != (B, self.y_channels, S, S):
-                raise RuntimeError('y has shape %s, expected %s' % (tuple(y.shape), (B, self.y_channels, S, S)))
             y = y.contiguous()
-        labels = labels.to(device=x.device, dtype=torch.float32).contiguous()
-        if labels.shape != (B,):
-            raise RuntimeError('labels must have shape [%d]' % B)
         self._ensure_packed()
         ws = self._workspace(B)
         out = torch.empty(B, self.out_channels, S, S, dtype=torch.float32, device=x.device)
@@ -237,8 +229,8 @@ class HipUNet(nn.Module):
         return out
 
 
-    # -- eval-mode autograd with respect to x: the planned training graph without dropout, an input-only backward ------------------
     def _check_io(self, x, y, labels):
+        """shapes of one call's x, y, labels; returns the labels as a contiguous float32 tensor on x's device"""
         B, S = x.shape[0], self.image_size
         if tuple(x.shape) != (B, self.x_channels, S, S):
             raise RuntimeError('x has shape %s, expected %s' % (tuple(x.shape), (B, self.x_channels, S, S)))
@@ -251,6 +243,7 @@ class HipUNet(nn.Module):
             raise RuntimeError('labels must have shape [%d]' % B)
         return labels
 
+    # -- eval-mode autograd with respect to x: the planned training graph without dropout, an input-only backward ------------------
     def _input_grad_forward(self, x, y, labels):
         """``model.eval()`` with ``x.requires_grad`` under autograd: ONE node whose forward is csd_unet_train_forward with dropout 0
         (the activations stay in a private workspace) and whose backward is csd_unet_backward_ex(grads = NULL, d_x): the data gradient
@@ -283,16 +276,7 @@ class HipUNet(nn.Module):
         models/ddpm.py:149-213, dropout on, activations kept in a library workspace), the backward csd_unet_backward (every
         parameter gradient from one call).  ``self.grad_sink``: when a Trainer owns the flat gradient buffer the gradients are
         written straight into ``p.grad`` (which it zeroed) and autograd is handed nothing to accumulate."""
-        B, S = x.shape[0], self.image_size
-        if tuple(x.shape) != (B, self.x_channels, S, S):
-            raise RuntimeError('x has shape %s, expected %s' % (tuple(x.shape), (B, self.x_channels, S, S)))
-        if self.y_channels:
-            require_gpu_tensor(y, 'y')
-            if tuple(y.shape) != (B, self.y_channels, S, S):
-                raise RuntimeError('y has shape %s, expected %s' % (tuple(y.shape), (B, self.y_channels, S, S)))
-        labels = labels.to(device=x.device, dtype=torch.float32).contiguous()
-        if labels.shape != (B,):
-            raise RuntimeError('labels must have shape [%d]' % B)
+        labels = self._check_io(x, y, labels)
         self._train_calls += 1
         return _PlannedNet.apply(self, x.contiguous(), y.contiguous() if self.y_channels else None, labels, *self._train_params())
 
@@ -315,10 +299,7 @@ class HipUNet(nn.Module):
         else:
             from .. import grad_ops as G
         m, prec, act = self.all_modules, self.precision, self._act_name
-        B, S = x.shape[0], self.image_size
-        if tuple(x.shape) != (B, self.x_channels, S, S):
-            raise RuntimeError('x has shape %s, expected %s' % (tuple(x.shape), (B, self.x_channels, S, S)))
-        labels = labels.to(device=x.device, dtype=torch.float32).contiguous()
+        labels = self._check_io(x, y, labels)
         self._train_calls += 1
         drop = [0]
         cdim = 3 if nhwc else 1            # channel axis of an activation

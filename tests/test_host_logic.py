@@ -380,3 +380,86 @@ def test_bucket_first_modules_follow_the_module_list():
     assert bucket_first_modules(names, [[0, 1, 2], [3, 4], [5, 6]]) == [0, 3, 10]
     assert bucket_first_modules(names, [[0, 1, 2, 3], [4, 5, 6]]) == [0, 3]      # a module split over two buckets completes both
     assert bucket_first_modules(names + ['head.weight'], [[0], [7]]) is None      # not the reference's naming: no events, no overlap
+
+
+# ---- plan digests: everything the host side derives from a configuration, pinned bit for bit --------------------------------------
+_DIGEST_BATCHES = (1, 7, 32, 64, 65)        # 64 / 65: two batch chunks, equal and ragged
+
+
+def _digest_configs():
+    """name -> reference-style config.  The GPU tools are not imported: the values of tools/bench_other.py (cmde128_config,
+    ncsnpp_config), tests/test_gpu_fullsize.py (build_ncsnpp_256), tools/bench_train.py (the two training shapes) and
+    tools/bench_ncsnpp_cifar.py (cifar_config) are restated."""
+    import itertools
+    import bench
+    out = {}
+    for case in cases.CASES:
+        out[case] = cases.case_config(case)[0]
+    for case, (kw, _) in cases.NCSNPP_CASES.items():
+        out[case] = cases.make_ncsnpp_config(**kw)
+    out['sr3_160'] = bench.sr3_160_config()
+    out['cmde_128'] = cases.make_config(name='ddpm_paired', nf=96, ch_mult=(1, 1, 2, 2, 3, 3), attn_resolutions=(16, 8, 4), image_size=128)
+    big = dict(channels=6, nf=96, ch_mult=(1, 1, 2, 2, 3, 3), num_res_blocks=2, attn_resolutions=(20, 10, 5), image_size=160,
+               embedding_type='positional')
+    for name in ('ncsnpp', 'ncsnpp_paired'):
+        out[name + '_160'] = cases.make_ncsnpp_config(name=name, **big)
+    out['ncsnpp_256'] = cases.make_ncsnpp_config(name='ncsnpp', channels=3, nf=128, ch_mult=(1, 1, 2, 2, 2, 2, 2), num_res_blocks=2,
+                                                 attn_resolutions=(16,), image_size=256, embedding_type='fourier')
+    out['train_ddpm_paired_64'] = cases.make_config(name='ddpm_paired', nf=128, ch_mult=(1, 1, 2, 2), attn_resolutions=(16, 8), image_size=64)
+    out['train_ncsnpp_paired_64'] = cases.make_ncsnpp_config(name='ncsnpp_paired', channels=6, nf=128, ch_mult=(1, 1, 2, 2), num_res_blocks=2,
+                                                             attn_resolutions=(16,), image_size=64, embedding_type='positional')
+    for pin, fir, emb, prog in itertools.product(('none', 'input_skip', 'residual'), (True, False), ('positional', 'fourier'),
+                                                 ('none', 'output_skip')):
+        out['cifar_%s_%s_%s_%s' % (pin, 'fir' if fir else 'nofir', emb, prog)] = cases.make_ncsnpp_config(
+            nf=128, ch_mult=(1, 2, 2, 2), num_res_blocks=4, attn_resolutions=(16,), image_size=32, channels=3, embedding_type=emb,
+            progressive=prog, progressive_input=pin, fir=fir)
+    out['ddpm_no_resamp_conv'] = cases.make_config(nf=32, ch_mult=(1, 2, 2, 2), attn_resolutions=(20,), image_size=80)
+    out['ddpm_no_resamp_conv'].model.csd_digest_no_resamp_conv = True       # (see _plan_digests)
+    out['ddpm_unconditional'] = cases.make_config(name='ddpm', nf=32, ch_mult=(1, 2, 2, 2), attn_resolutions=(10,), image_size=80)
+    out['ddpm_unconditional'].model.conditional = False
+    return out
+
+
+def _plan_digests():
+    """{'config/precision': {'B': [params, layout, plan, training dry run]}} from csd_unet_debug_digest (csrc/plan_digest.h)"""
+    from conditional_score_diffusion_amd import _lib
+    from conditional_score_diffusion_amd.models import utils as mutils
+    import conditional_score_diffusion_amd.models.ncsnpp      # noqa: F401  (registers the model names)
+    fn = ctypes.CDLL(_lib.LIB_PATH).csd_unet_debug_digest
+    fn.restype, fn.argtypes = ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.POINTER(ctypes.c_uint64)]
+    out = {}
+    for name, cfg in _digest_configs().items():
+        for prec in ('fp32', 'fp16x3', 'fp16', 'fp16f8'):
+            cfg.model.csd_precision = prec
+            with torch.device('meta'):                      # (the digests need the handle only: no parameter values)
+                model = mutils.create_model(cfg)
+            h = model._h
+            if getattr(cfg.model, 'csd_digest_no_resamp_conv', False):
+                # resamp_with_conv = False: the Python adapter cannot hold a module list with parameter-less entries; the library plans it
+                c = model._cfg
+                c.resamp_with_conv = 0
+                h = ctypes.c_void_p()
+                assert _lib.lib().csd_unet_create(ctypes.byref(c), ctypes.byref(h)) == 0
+            per_b = out['%s/%s' % (name, prec)] = {}
+            for B in _DIGEST_BATCHES:
+                d = (ctypes.c_uint64 * 4)()
+                assert fn(h, B, float(cfg.model.dropout), d) == 0, (name, prec, B, _lib.lib().csd_last_error())
+                per_b[str(B)] = ['%016x' % v for v in d]
+            if h is not model._h:
+                _lib.lib().csd_unet_destroy(h)
+    return out
+
+
+def test_plan_digests_equal_the_pinned_ones(golden_dir):
+    """The parameter table, the packed-weight layout, the inference plan (every launch with its offsets, geometry and tiles) and the
+    training graph's dry run (recorded steps, saved-tensor offsets, workspace size) of every configuration the project tests or
+    benchmarks, in the four precision modes and at five batch sizes, hash to the values in tests/golden/plan_digests.json.  That file
+    was recorded with this same code on the commit it names.  A pull request that MEANS to change a plan, a layout or the training
+    graph regenerates the file (json.dump of _plan_digests() plus its own parent's hash) and says so; one that does not must leave
+    every digest equal."""
+    import json
+    want = json.load(open(os.path.join(golden_dir, 'plan_digests.json')))['digests']
+    got = _plan_digests()
+    assert sorted(got) == sorted(want)
+    diff = ['%s B=%s' % (k, b) for k in want for b in want[k] if got[k].get(b) != want[k][b]]
+    assert not diff, '%d of %d digests differ, first: %s' % (len(diff), sum(len(v) for v in want.values()), diff[:8])
