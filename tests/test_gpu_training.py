@@ -37,14 +37,14 @@ def test_conv2d_backward_vs_torch(B, Cin, Cout, H, k, stride, up2):
     from conditional_score_diffusion_amd import grad_ops as G
     rs = np.random.RandomState(5)
     x, w, b = rnd(rs, B, Cin, H, H), rnd(rs, Cout, Cin, k, k) * 0.1, rnd(rs, Cout)
-    xr, wr, br = (t.clone().requires_grad_(True) for t in (x, w, b))
+    xr, wr, br = (t.double().requires_grad_(True) for t in (x, w, b))          # float64 reference
     u = F.interpolate(xr, scale_factor=2, mode='nearest') if up2 else xr
     if stride == 2:
         ref = F.conv2d(F.pad(u, (0, 1, 0, 1)), wr, br, stride=2)
     else:
         ref = F.conv2d(u, wr, br, padding=k // 2)
     dy = rnd(rs, *ref.shape)
-    ref.backward(dy)
+    ref.backward(dy.double())
     xd, wd, bd = (t.to(dev()).requires_grad_(True) for t in (x, w, b))
     out = G.conv2d(xd, wd, bd, stride=stride, downsample_pad=stride == 2, up2=up2)
     assert rel(out, ref) < 1e-5
@@ -77,11 +77,11 @@ def test_groupnorm_act_backward_vs_torch(B, C, H, groups, act):
     from conditional_score_diffusion_amd import grad_ops as G
     rs = np.random.RandomState(7)
     x, ga, be = rnd(rs, B, C, H, H) * 2 + 0.3, rnd(rs, C) * 0.5 + 1, rnd(rs, C) * 0.2
-    xr, gr, br = (t.clone().requires_grad_(True) for t in (x, ga, be))
+    xr, gr, br = (t.double().requires_grad_(True) for t in (x, ga, be))          # float64 reference
     ref = F.group_norm(xr, groups, gr, br, eps=1e-6)
     ref = F.silu(ref) if act == 'swish' else ref
     dy = rnd(rs, *ref.shape)
-    ref.backward(dy)
+    ref.backward(dy.double())
     xd, gd, bd = (t.to(dev()).requires_grad_(True) for t in (x, ga, be))
     out = G.groupnorm_act(xd, gd, bd, groups, 1e-6, act)
     assert rel(out, ref) < 1e-5
@@ -96,12 +96,12 @@ def test_attention_backward_vs_torch(B, C, H):
     from conditional_score_diffusion_amd import grad_ops as G
     rs = np.random.RandomState(8)
     q, k, v = rnd(rs, B, C, H, H), rnd(rs, B, C, H, H), rnd(rs, B, C, H, H)
-    qr, kr, vr = (t.clone().requires_grad_(True) for t in (q, k, v))
+    qr, kr, vr = (t.double().requires_grad_(True) for t in (q, k, v))          # float64 reference
     w = torch.einsum('bchw,bcij->bhwij', qr, kr) * (int(C) ** (-0.5))        # models/layers.py:584-588
     w = F.softmax(w.reshape(B, H, H, H * H), dim=-1).reshape(B, H, H, H, H)
     ref = torch.einsum('bhwij,bcij->bchw', w, vr)
     do = rnd(rs, *ref.shape)
-    ref.backward(do)
+    ref.backward(do.double())
     qd, kd, vd = (t.to(dev()).requires_grad_(True) for t in (q, k, v))
     out = G.attention(qd, kd, vd)
     assert rel(out, ref) < 1e-5
@@ -116,10 +116,10 @@ def test_linear_backward_vs_torch(B, K, N, act):
     from conditional_score_diffusion_amd import grad_ops as G
     rs = np.random.RandomState(9)
     x, w, b = rnd(rs, B, K), rnd(rs, N, K) * 0.1, rnd(rs, N)
-    xr, wr, br = (t.clone().requires_grad_(True) for t in (x, w, b))
+    xr, wr, br = (t.double().requires_grad_(True) for t in (x, w, b))          # float64 reference
     ref = F.linear(F.silu(xr) if act == 'swish' else xr, wr, br)
     dy = rnd(rs, B, N)
-    ref.backward(dy)
+    ref.backward(dy.double())
     xd, wd, bd = (t.to(dev()).requires_grad_(True) for t in (x, w, b))
     out = G.linear(xd, wd, bd, act_in=act)
     out.backward(dy.to(dev()))
