@@ -41,7 +41,8 @@ class PCParams(ctypes.Structure):
                 ('record', ctypes.c_void_p), ('predictor', ctypes.c_int32), ('corrector', ctypes.c_int32),
                 ('pred_coef', ctypes.POINTER(ctypes.c_float)), ('corr_coef', ctypes.POINTER(ctypes.c_float)),
                 ('path_coef', ctypes.POINTER(ctypes.c_float)), ('path_std0', ctypes.c_float),
-                ('corr_alpha', ctypes.POINTER(ctypes.c_float))]
+                ('corr_alpha', ctypes.POINTER(ctypes.c_float)), ('rd_drift', ctypes.POINTER(ctypes.c_float)),
+                ('rd_sub_x', ctypes.c_int32), ('probability_flow', ctypes.c_int32)]
 
 
 def build(verbose=False):
@@ -101,6 +102,7 @@ SIGNATURES = {
     'csd_update_scratch_bytes': (_sz, [_i]),
     'csd_langevin_step': (_i, [_vp, _vp, _vp, _vp, _f, _f, _f, _i, _i64, _vp, _vp]),
     'csd_reverse_diffusion_step': (_i, [_vp, _vp, _vp, _vp, _f, _f, _i, _i64, _vp]),
+    'csd_reverse_diffusion_step_ex': (_i, [_vp, _vp, _vp, _vp, _f, _f, _f, _f, _i, _f, _f, _i, _i64, _vp]),
     'csd_row_norms': (_i, [_vp, _vp, _i, _i64, _vp]),
     'csd_affine_noise_step': (_i, [_vp, _vp, _vp, _vp, _f, _f, _f, _i64, _vp]),
     'csd_linear': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),

@@ -337,6 +337,9 @@ int affine_net_update_launch(float* x, float* x_mean, const float* net, int64_t 
                              float a, float c, int B, int64_t per, hipStream_t s);
 int reverse_diffusion_update_launch(float* x, float* x_mean, const float* net, int64_t net_stride,
                                     const float* z, float std, float G, int B, int64_t per, hipStream_t s);
+int reverse_diffusion_drift_update_launch(float* x, float* x_mean, const float* net, int64_t net_stride, const float* z, float std,
+                                          float G, float a, float b, int drift, int sub_x, float kappa, float g_noise, int B,
+                                          int64_t per, hipStream_t s);
 int randn_launch(float* out, int64_t n, uint64_t seed, uint64_t stream_id, hipStream_t s);
 int scale_rows_launch(float* out, const float* in, const float* scale, int divide, int B, int64_t per,
                       hipStream_t s);

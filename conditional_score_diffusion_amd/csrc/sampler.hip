@@ -8,6 +8,9 @@
 //     fp64 partial sums, the update kernel folds them (deterministic order) in its prologue.
 //   reverse diffusion (sampling/predictors.py:84-89,97-102 with sde_lib.py:135-140,410-418):
 //       x_mean = x + G^2*score ; x = x_mean + G*z
+//   reverse diffusion with a forward drift / as the probability flow (the same lines with sde_lib.py:65-102,186-195,49-63):
+//       f = sqrt(alpha_i)*x - x (VP) | (phi*x)*dt (sub-VP) | 0 (VE) ; rev_f = f - G^2*score*kappa ; x_mean = x - rev_f ;
+//       x = x_mean + G_noise*z, kappa = 1/2 and G_noise = 0 for the probability flow
 // fp contraction is disabled so that mul/add round exactly like the reference's separate torch ops.
 #include <algorithm>
 
@@ -168,6 +171,31 @@ __global__ __launch_bounds__(256) void reverse_diffusion_update_kernel(float* __
   }
 }
 
+// the reverse-diffusion update of an SDE with a linear forward drift, and of the probability flow of any SDE, in the reference's order
+// of operations: f = (a*x)*b, minus x when sub_x (VP discretize: a = sqrt(alpha_i), b = 1; Euler default of sub-VP: a = phi(t),
+// b = dt, sub_x = 0; drift == 0: f = 0, the VE SDEs); rev_f = f - G^2*score*kappa; x_mean = x - rev_f; x = x_mean + g_noise*z
+__global__ __launch_bounds__(256) void reverse_diffusion_drift_update_kernel(float* __restrict__ x, float* __restrict__ x_mean,
+                                                                             const float* __restrict__ net, int64_t net_stride,
+                                                                             const float* __restrict__ z, float std, float G,
+                                                                             float a, float b, int drift, int sub_x, float kappa,
+                                                                             float g_noise, int64_t per, size_t total) {
+  const float G2 = G * G;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    const size_t bi = i / (size_t)per;
+    const float score = net[bi * net_stride + (i - bi * per)] / std;
+    const float xi = x[i];
+    float f = 0.f;
+    if (drift) {
+      f = (a * xi) * b;
+      if (sub_x) f = f - xi;
+    }
+    const float rev_f = f - (G2 * score) * kappa;
+    const float xm = xi - rev_f;
+    x_mean[i] = xm;
+    x[i] = xm + g_noise * z[i];
+  }
+}
+
 // out[b] = ||a_b||_2 (fp64 sum of squares, one workgroup per sample): the per-sample norms of the Langevin step size
 // (sampling/correctors.py:102-103) for callers that combine them across ranks before the update
 __global__ __launch_bounds__(256) void row_norms_kernel(const float* __restrict__ a, float* __restrict__ out, int64_t per) {
@@ -307,6 +335,16 @@ int reverse_diffusion_update_launch(float* x, float* x_mean, const float* net, i
   return CSD_OK;
 }
 
+int reverse_diffusion_drift_update_launch(float* x, float* x_mean, const float* net, int64_t net_stride, const float* z, float std,
+                                          float G, float a, float b, int drift, int sub_x, float kappa, float g_noise, int B,
+                                          int64_t per, hipStream_t s) {
+  const size_t total = (size_t)B * per;
+  hipLaunchKernelGGL(reverse_diffusion_drift_update_kernel, dim3(ew_grid(total)), dim3(256), 0, s, x, x_mean, net, net_stride, z,
+                     std, G, a, b, drift, sub_x, kappa, g_noise, per, total);
+  CSD_LAUNCH_CHECK();
+  return CSD_OK;
+}
+
 // x_mean = p*x + (a/std)*net, x = x_mean + c*z on the network's (row-strided) output: the affine update rules inside the fused loop
 __global__ __launch_bounds__(256) void affine_net_update_kernel(float* __restrict__ x, float* __restrict__ x_mean,
                                                                 const float* __restrict__ net, int64_t net_stride,
@@ -394,6 +432,15 @@ extern "C" int csd_reverse_diffusion_step(float* x, float* x_mean, const float* 
                                           float G, int B, int64_t per_sample, void* stream) {
   CSD_REQUIRE(B > 0 && per_sample > 0, "reverse_diffusion_step: bad arguments");
   return reverse_diffusion_update_launch(x, x_mean, net, per_sample, z, std, G, B, per_sample, (hipStream_t)stream);
+}
+
+extern "C" int csd_reverse_diffusion_step_ex(float* x, float* x_mean, const float* net, const float* z, float std, float G,
+                                             float drift_a, float drift_b, int drift_form, float kappa, float g_noise, int B,
+                                             int64_t per_sample, void* stream) {
+  CSD_REQUIRE(x && x_mean && net && z && B > 0 && per_sample > 0, "reverse_diffusion_step_ex: bad arguments");
+  CSD_REQUIRE(drift_form >= 0 && drift_form <= 2, "reverse_diffusion_step_ex: drift_form is 0 (none), 1 ((a*x)*b) or 2 ((a*x)*b - x)");
+  return reverse_diffusion_drift_update_launch(x, x_mean, net, per_sample, z, std, G, drift_a, drift_b, drift_form != 0,
+                                               drift_form == 2, kappa, g_noise, B, per_sample, (hipStream_t)stream);
 }
 
 extern "C" int csd_row_norms(const float* a, float* out, int B, int64_t per_sample, void* stream) {

@@ -716,6 +716,10 @@ static int pc_setup(PCCtx* c, csd_unet* net, const void* packed, void* workspace
   CSD_REQUIRE(p->predictor != 1 || p->pred_coef, "pc_sample: predictor table missing");
   CSD_REQUIRE(p->corrector != 1 || p->corr_coef, "pc_sample: corrector table missing");
   CSD_REQUIRE(p->predictor != 2 || p->corrector != 2, "pc_sample: predictor and corrector are both 'none'");
+  CSD_REQUIRE(p->predictor == 0 || (!p->rd_drift && !p->probability_flow),
+              "pc_sample: rd_drift / probability_flow belong to the reverse-diffusion predictor (an affine table carries its own)");
+  CSD_REQUIRE((p->rd_sub_x == 0 || p->rd_sub_x == 1) && (p->probability_flow == 0 || p->probability_flow == 1) &&
+              (p->rd_sub_x == 0 || p->rd_drift), "pc_sample: bad rd_sub_x / probability_flow");
   const csd_unet_config& cf = net->net.cfg;
   CSD_REQUIRE((cf.y_channels == 0) == (y == nullptr), "pc_sample: y must be given iff y_channels > 0");
   CSD_REQUIRE(!(p->std_y && cf.y_channels == 0), "pc_sample: std_y given for an unconditional network");
@@ -791,6 +795,12 @@ static int pc_phase(const PCCtx& c, int i, int phase, int part, float* sums_out,
                                                    alpha, c.B, c.per, c.s, c.nonfinite)
                    : langevin_update_launch(c.x, c.x_mean, c.net_out, c.net_stride, zp, c.partial, c.nchunk, p->std_x[i],
                                             p->snr, alpha, c.B, c.per, c.s, c.nonfinite);
+    } else if (p->rd_drift || p->probability_flow) {      // a forward drift (VP / sub-VP) and / or the probability flow
+      const float* d = p->rd_drift ? p->rd_drift + (size_t)i * 2 : nullptr;
+      const bool pf = p->probability_flow != 0;
+      rc = reverse_diffusion_drift_update_launch(c.x, c.x_mean, c.net_out, c.net_stride, zp, p->std_x[i], p->G[i], d ? d[0] : 0.f,
+                                                 d ? d[1] : 0.f, d != nullptr, p->rd_sub_x, pf ? 0.5f : 1.f, pf ? 0.f : p->G[i],
+                                                 c.B, c.per, c.s);
     } else {
       rc = reverse_diffusion_update_launch(c.x, c.x_mean, c.net_out, c.net_stride, zp, p->std_x[i], p->G[i], c.B, c.per, c.s);
     }

@@ -308,11 +308,22 @@ def affine_noise_step(x, score, z, p, a, c):
     return x, x_mean
 
 
-def reverse_diffusion_step(x, net, z, std, G):
-    """In-place reverse-diffusion predictor update (sampling/predictors.py:97-102)."""
+def reverse_diffusion_step(x, net, z, std, G, drift=None, probability_flow=False):
+    """In-place reverse-diffusion predictor update (sampling/predictors.py:84-89,97-102).
+
+    ``drift``: None for an SDE without forward drift (VE), else ``(a, b, sub_x)`` with the discretised forward drift
+    f = (a*x)*b, minus x when ``sub_x`` (VP: (sqrt(alpha_i), 1, True); sub-VP: (phi(t), dt, False)).  ``probability_flow``: the
+    reverse ODE (half the score term, no noise; ``z`` is still read).  Without either, the VE kernel runs as before."""
     x, net, z = _c(x, 'x'), _c(net, 'net'), _c(z, 'z')
     B = x.shape[0]
     x_mean = torch.empty_like(x)
-    check(lib().csd_reverse_diffusion_step(ptr(x), ptr(x_mean), ptr(net), ptr(z), float(std), float(G), B,
-                                           x.numel() // B, current_stream(x.device)), 'reverse_diffusion_step')
+    if drift is None and not probability_flow:
+        check(lib().csd_reverse_diffusion_step(ptr(x), ptr(x_mean), ptr(net), ptr(z), float(std), float(G), B,
+                                               x.numel() // B, current_stream(x.device)), 'reverse_diffusion_step')
+        return x, x_mean
+    a, b, sub_x = drift if drift is not None else (0.0, 0.0, False)
+    form = 0 if drift is None else (2 if sub_x else 1)
+    check(lib().csd_reverse_diffusion_step_ex(ptr(x), ptr(x_mean), ptr(net), ptr(z), float(std), float(G), float(a), float(b), form,
+                                              0.5 if probability_flow else 1.0, 0.0 if probability_flow else float(G), B,
+                                              x.numel() // B, current_stream(x.device)), 'reverse_diffusion_step_ex')
     return x, x_mean

@@ -4,9 +4,9 @@ Mirrors sampling/conditional.py of the reference: ``get_conditional_sampling_fn`
 the same ``'default'`` sentinels, and ``get_pc_conditional_sampler`` (:47-228) returning
 ``pc_conditional_sampler(model, y, show_evolution=False) -> (x, info)``.
 
-Fast path: for the (conditional_reverse_diffusion, conditional_langevin, VE) pair - what every
-BASELINE config selects - the whole loop runs on the device through csd_pc_sample
-(sampling/fused.py).  Any other registered predictor/corrector pair runs the reference's
+Fast path: for every registered predictor / corrector pair on a VE SDE, the two-SDE VE pair or a cVPSDE
+(``fused.fusable``) the whole loop runs on the device through csd_pc_sample
+(sampling/fused.py).  Anything else (c_steps != 1, a model that is not a HipUNet) runs the reference's
 per-step protocol (corrector then predictor, sampling/conditional.py:208-211) by calling the
 objects' ``update_fn``; ``use_path=True`` runs the bridge sampler of :124-178.  Extra keyword arguments (not in the reference): ``noise_tape`` (list of
 standard-normal tensors in the reference's draw order, SURVEY.md 3.1 - parity mode) and ``seed``
@@ -139,14 +139,14 @@ def get_pc_conditional_sampler(sde, shape, predictor, corrector, snr, p_steps, c
         if fused.fusable(model, sde, predictor, corrector, c_steps, probability_flow, continuous):
             x, rec, _ = fused.run(model, sde, shape, y, p_steps, snr, eps, denoise, noise_tape=noise_tape,
                                   seed=seed, record=show_evolution, global_norm=global_norm, predictor=predictor, corrector=corrector,
-                                  probability_flow=probability_flow)
+                                  probability_flow=probability_flow, continuous=continuous)
             if show_evolution:
                 return x, {'evolution': {'x': rec.cpu(), 'y': None}}
             return x, {}
         if noise_tape is not None:
             raise NotImplementedError('noise_tape is only available on the fused path')
         if global_norm is not None:
-            # the step-by-step fallback (c_steps != 1, a VP SDE, a model that is not a HipUNet) computes per-shard norms: refusing is
+            # the step-by-step fallback (c_steps != 1, a model that is not a HipUNet) computes per-shard norms: refusing is
             # better than silently not delivering "identical to one process"; use the 'conditional_langevin_global' corrector there
             raise NotImplementedError('global-norm sharded sampling runs on the fused device loop only; this (model, sde, predictor, '
                                       'corrector, c_steps) combination falls back to the step-by-step loop')

@@ -1,8 +1,9 @@
 """Host driver of the fused device-resident PC loop (csd_pc_sample).
 
 Computes the per-step scalars on the CPU in fp32 with the SAME torch expressions the reference
-evaluates per step (timesteps: sampling/conditional.py:202; labels: models/utils.py:213; sigma(t):
-sde_lib.py:390-395; G_i: sde_lib.py:410-418), then launches ONE library call that runs the whole
+evaluates per step (timesteps: sampling/conditional.py:202; labels: models/utils.py:198,213,234; sigma(t):
+sde_lib.py:390-395; G_i: sde_lib.py:410-418; the VP / sub-VP std, drift and G: sde_lib.py:49-63,170-195,268-287),
+then launches ONE library call that runs the whole
 loop on the device: 2 network evaluations + 2 update kernels per step, no per-step Python objects,
 no host synchronisation.
 """
@@ -38,23 +39,40 @@ def _rule_ids(predictor, corrector):
     return pid, cid
 
 
+_VE = (sde_lib.VESDE, sde_lib.cVESDE)
+_VP = (sde_lib.VPSDE, sde_lib.cVPSDE)             # (the classes with the DDPM tables: discrete_betas, alphas, ...)
+_VP_FAMILY = _VP + (sde_lib.subVPSDE,)
+
+
 def fusable(model, sde, predictor, corrector, c_steps, probability_flow, continuous, use_path=False):
-    """True when (model, sde, predictor, corrector) runs on the fused device loop: a VE SDE with any registered predictor
-    (reverse diffusion, Euler-Maruyama, ancestral sampling, none) and corrector (Langevin, annealed Langevin dynamics, none)."""
+    """True when (model, sde, predictor, corrector) runs on the fused device loop: a VE SDE (or the two-SDE VE pair), a VPSDE, cVPSDE
+    or subVPSDE with any registered predictor (reverse diffusion, Euler-Maruyama, ancestral sampling, none) and corrector (Langevin,
+    annealed Langevin dynamics, none) that the SDE's class supports in the step-by-step classes."""
     from ..models.ddpm import HipUNet
     from . import predictors as P
     c_sde = sde['x'] if isinstance(sde, dict) else sde
-    ok_sde = isinstance(c_sde, (sde_lib.VESDE, sde_lib.cVESDE))
-    if isinstance(sde, dict):
-        ok_sde = ok_sde and isinstance(sde.get('y'), sde_lib.VESDE) and len(sde) == 2
+    if isinstance(sde, dict):                   # the two-SDE setting: VE members only (models/utils.py:171-188 refuses the others)
+        ok_sde = isinstance(c_sde, _VE) and isinstance(sde.get('y'), sde_lib.VESDE) and len(sde) == 2
+    else:
+        ok_sde = isinstance(c_sde, _VE + _VP_FAMILY)
     ids = _rule_ids(predictor, corrector)
     if ids is None or ids == (2, 2):
         return False
-    # the probability-flow drift exists for Euler-Maruyama only (the reverse-diffusion step kernel and ancestral sampling refuse it)
-    ok_pf = (not probability_flow) or predictor in (P.EulerMaruyamaPredictor, P.conditionalEulerMaruyamaPredictor)
+    ancestral = predictor in (P.AncestralSamplingPredictor, P.conditionalAncestralSamplingPredictor)
+    # the probability flow: reverse diffusion and Euler-Maruyama (ancestral sampling refuses it)
+    ok_pf = (not probability_flow) or (ids[0] != 2 and not ancestral)
+    if isinstance(c_sde, sde_lib.subVPSDE):
+        # no DDPM tables: the Langevin / ALD step size (alphas[timestep]) and ancestral sampling (discrete_betas) raise for it
+        ok_sde = ok_sde and ids[1] == 2 and not ancestral
+    # discrete-time score functions: the VP classes index sqrt_1m_alphas_cumprod with the truncated label; the VE ones are not provided
+    ok_time = continuous or isinstance(c_sde, _VP_FAMILY)
     # use_path (the bridge for y_t): two-SDE setting only
     ok_path = (not use_path) or isinstance(sde, dict)
-    return (isinstance(model, HipUNet) and ok_sde and c_steps == 1 and ok_pf and continuous and ok_path)
+    return (isinstance(model, HipUNet) and ok_sde and c_steps == 1 and ok_pf and ok_time and ok_path)
+
+
+def _index(c_sde, t1):
+    return int((t1 * (c_sde.N - 1) / c_sde.T).long()[0])
 
 
 def rule_tables(c_sde, ts, predictor, corrector, snr, probability_flow):
@@ -75,6 +93,10 @@ def rule_tables(c_sde, ts, predictor, corrector, snr, probability_flow):
                 dt = -1.0 / c_sde.N
                 kappa = 0.5 if probability_flow else 1.0
                 co = (1.0 + phi * dt, -kappa * g * g * dt, 0.0 if probability_flow else g * (-dt) ** 0.5)
+            elif isinstance(c_sde, _VP):
+                beta = float(c_sde.discrete_betas.to(torch.float32)[_index(c_sde, t1)])
+                r = (1.0 - beta) ** 0.5
+                co = (1.0 / r, beta / r, beta ** 0.5)
             else:
                 k = int((t1 * (c_sde.N - 1) / c_sde.T).long()[0])
                 sig = c_sde.discrete_sigmas.to(torch.float32)
@@ -87,15 +109,48 @@ def rule_tables(c_sde, ts, predictor, corrector, snr, probability_flow):
         for i in range(n):
             t1 = ts[i:i + 1].to(torch.float32)
             std = float(c_sde.marginal_prob(torch.zeros(1, 1, 1, 1), t1)[1].flatten()[0])
-            step = (snr * std) ** 2 * 2 * 1.0          # alpha = 1 for the VE SDEs
+            alpha = float(c_sde.alphas.to(torch.float32)[_index(c_sde, t1)]) if isinstance(c_sde, _VP_FAMILY) else 1.0
+            step = (snr * std) ** 2 * 2 * alpha
             corr[i] = torch.tensor((1.0, step, (2 * step) ** 0.5), dtype=torch.float64).to(torch.float32)
     return pid, cid, pred, corr
 
 
-def step_scalars(sde, p_steps, eps, unconditional_label=None):
+def reverse_diffusion_table(c_sde, ts):
+    """(rd_drift [n][2] fp32 or None, rd_sub_x) of csd_pc_params: the reverse-diffusion predictor's forward drift per step, from the
+    same host evaluation the per-step class makes (sampling/predictors.py:reverse_diffusion_drift); None for the VE SDEs (f = 0)."""
+    from .predictors import reverse_diffusion_drift
+    rows = [reverse_diffusion_drift(c_sde, ts[i:i + 1].to(torch.float32)) for i in range(ts.numel())]
+    if rows[0] is None:
+        return None, 0
+    tab = torch.tensor([r[:2] for r in rows], dtype=torch.float64).to(torch.float32).contiguous()
+    return tab, int(rows[0][2])
+
+
+def langevin_alphas(c_sde, ts):
+    """corr_alpha of csd_pc_params: alphas[timestep_i] (sampling/correctors.py:63-65,94-96) for the VP classes, None (= 1) for VE;
+    subVPSDE has no ``alphas`` and raises AttributeError as the per-step corrector (and the reference) does."""
+    if not isinstance(c_sde, _VP_FAMILY):
+        return None
+    return torch.stack([c_sde.alphas[_index(c_sde, ts[i:i + 1])] for i in range(ts.numel())]).to(torch.float32).contiguous()
+
+
+def step_scalars(sde, p_steps, eps, unconditional_label=None, continuous=True):
     """fp32 per-step arrays (labels, std_x, G, std_y|None) + the timesteps tensor."""
     c_sde = sde['x'] if isinstance(sde, dict) else sde
     ts = torch.linspace(c_sde.T, eps, p_steps)
+    if isinstance(c_sde, _VP_FAMILY):
+        # one evaluation per step at a one-element time, like the per-step classes (models/utils.py:get_score_fn, predictors.py);
+        # the label is t*(N-1), unrounded, for the conditional and the unconditional score function alike
+        labels = (ts * (c_sde.N - 1)).float()
+        std_x, G = torch.empty(p_steps), torch.empty(p_steps)
+        for i in range(p_steps):
+            t1 = ts[i:i + 1]
+            if continuous or isinstance(c_sde, sde_lib.subVPSDE):
+                std_x[i] = c_sde.marginal_prob(torch.zeros(1, 1), t1)[1][0]        # (sub-VP: 1 - exp(2*lmc), no square root)
+            else:
+                std_x[i] = c_sde.sqrt_1m_alphas_cumprod.type_as(labels)[labels[i:i + 1].long()][0]
+            G[i] = c_sde.discretize(torch.zeros(1, 1), t1)[1][0]
+        return ts, labels.contiguous(), std_x, G, None
     dummy = torch.zeros(p_steps, 1)
     std_x = c_sde.marginal_prob(dummy, ts)[1].float()
     G = c_sde.discretize(dummy, ts)[1].float()
@@ -134,13 +189,18 @@ def path_tables(sy, ts):
 
 def run(model, sde, shape, y, p_steps, snr, eps, denoise, noise_tape=None, seed=None, record=False,
         unconditional_label=None, global_norm=None, predictor=None, corrector=None, probability_flow=False, use_path=False,
-        corr_alpha=None):
+        corr_alpha=None, continuous=True):
     """Run the fused loop; returns (samples, record_or_None, timesteps).  ``seed=None``: a fresh key per call (fresh_seed).
 
     ``predictor`` / ``corrector``: the registered classes (default: the reverse-diffusion / Langevin pair); see ``fusable``.
 
-    ``corr_alpha``: optional [p_steps] fp32 factors of the Langevin step size (csd_pc_params.corr_alpha: alphas[timestep] of the VP
-    SDEs, sampling/correctors.py:63-65,94-96); None = 1 (the VE SDEs - the only ones ``fusable`` admits today).
+    ``corr_alpha``: optional [p_steps] fp32 factors of the Langevin step size (csd_pc_params.corr_alpha); None = alphas[timestep] for
+    the VP classes (sampling/correctors.py:63-65,94-96) and 1 for the VE SDEs.
+
+    ``continuous``: False selects the discrete-time std of the VP classes (sqrt_1m_alphas_cumprod at the truncated label,
+    models/utils.py:201-205,237-241); the VE SDEs run continuous only.
+
+    Prior: N(0, sigma_max^2) (+ data mean) for the VE SDEs, N(0, I) for VP / sub-VP; ``noise_tape[0]`` is the standard-normal draw.
 
     ``global_norm``: None = the Langevin step size uses the batch means of THIS call's batch (the reference run on this batch;
     one library call enqueues the whole loop).  Otherwise ``(reduce_fn, global_batch)``: the batch is one shard of a larger one
@@ -155,7 +215,12 @@ def run(model, sde, shape, y, p_steps, snr, eps, denoise, noise_tape=None, seed=
     if dev.type != 'cuda':
         raise RuntimeError('the fused PC sampler runs on the MI355X only (model is on %s)' % dev)
     B = shape[0]
-    ts, labels, std_x, G, std_y = step_scalars(sde, p_steps, eps, unconditional_label)
+    ve = isinstance(c_sde, _VE)
+    if not ve and isinstance(sde, dict):
+        raise NotImplementedError('This combination of SDEs is not supported for conditional SDEs yet.')
+    if ve and not continuous:
+        raise NotImplementedError('the fused loop runs the VE SDEs in continuous time only')
+    ts, labels, std_x, G, std_y = step_scalars(sde, p_steps, eps, unconditional_label, continuous)
     pid = cid = 0
     pred_tab = corr_tab = None
     if predictor is not None or corrector is not None:
@@ -163,6 +228,9 @@ def run(model, sde, shape, y, p_steps, snr, eps, denoise, noise_tape=None, seed=
         predictor = predictor or P_.ReverseDiffusionPredictor
         corrector = corrector or C_.LangevinCorrector
         pid, cid, pred_tab, corr_tab = rule_tables(c_sde, ts, predictor, corrector, float(snr), probability_flow)
+    rd_tab, rd_sub_x = reverse_diffusion_table(c_sde, ts) if pid == 0 else (None, 0)
+    if cid == 0 and corr_alpha is None:
+        corr_alpha = langevin_alphas(c_sde, ts)
     n_phases = (pid != 2) + (cid != 2)
     path_tab, path_std0 = None, 0.0
     if use_path:
@@ -172,11 +240,11 @@ def run(model, sde, shape, y, p_steps, snr, eps, denoise, noise_tape=None, seed=
             raise NotImplementedError('use_path is not provided in the global-norm sharded mode')
         path_tab, path_std0 = path_tables(sde['y'], ts)
         std_y = None                            # y_t comes from the bridge, not from the marginal
-    # prior: N(0, sigma_max^2) (+ data mean) - drawn on the host like the reference (sde_lib.py:397-403)
+    # prior: VE N(0, sigma_max^2) (+ data mean) - drawn on the host like the reference (sde_lib.py:397-403); VP / sub-VP N(0, I) (:177-178)
     if noise_tape is not None:
         tape = [t.float() for t in noise_tape]
-        x = (tape[0] * c_sde.sigma_max)
-        if c_sde.diffused_mean is not None:
+        x = (tape[0] * c_sde.sigma_max) if ve else tape[0]
+        if ve and c_sde.diffused_mean is not None:
             x = x + c_sde.diffused_mean.unsqueeze(0)
         x = x.to(dev).contiguous()
         flat = torch.cat([t.reshape(-1) for t in tape[1:]]).to(dev).contiguous() if len(tape) > 1 else None
@@ -187,8 +255,9 @@ def run(model, sde, shape, y, p_steps, snr, eps, denoise, noise_tape=None, seed=
             raise RuntimeError('noise tape holds %d draws after the prior, the loop needs %d' % (len(tape) - 1, expected))
     else:
         x = ops.randn(tuple(shape), seed, 0, dev)
-        x = ops.scale_rows(x, torch.full((B,), float(c_sde.sigma_max), device=dev))
-        if c_sde.diffused_mean is not None:
+        if ve:
+            x = ops.scale_rows(x, torch.full((B,), float(c_sde.sigma_max), device=dev))
+        if ve and c_sde.diffused_mean is not None:
             raise NotImplementedError('data-mean prior with on-device noise is not provided yet')
         flat = None
     model.eval()
@@ -215,6 +284,9 @@ def run(model, sde, shape, y, p_steps, snr, eps, denoise, noise_tape=None, seed=
         if corr_alpha.numel() != p_steps:
             raise ValueError('corr_alpha needs one factor per step (%d), got %d' % (p_steps, corr_alpha.numel()))
     p.corr_alpha = _fp(corr_alpha) if corr_alpha is not None else None
+    p.rd_drift = _fp(rd_tab) if rd_tab is not None else None
+    p.rd_sub_x = rd_sub_x
+    p.probability_flow = int(bool(probability_flow)) if pid == 0 else 0      # (an affine table carries the flow in its coefficients)
     if global_norm is not None and cid != 0:
         global_norm = None                      # only the Langevin corrector couples the samples of a batch
     yy = y.contiguous() if y is not None else None
@@ -232,5 +304,5 @@ def run(model, sde, shape, y, p_steps, snr, eps, denoise, noise_tape=None, seed=
             reduce_fn(sums)
             check(lib().csd_pc_step_end(*args, i, ptr(sums), int(global_batch), current_stream(dev)), 'pc_step_end')
     # keep the host arrays alive until the enqueue returned (they are read at enqueue time only)
-    del labels, std_x, G, std_y, pred_tab, corr_tab, path_tab, corr_alpha
+    del labels, std_x, G, std_y, pred_tab, corr_tab, path_tab, corr_alpha, rd_tab
     return x, rec, ts

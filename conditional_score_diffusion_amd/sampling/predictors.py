@@ -1,4 +1,5 @@
-"""Predictor registry + the reverse-diffusion predictor on the HIP update kernel.
+"""Predictor registry + the reverse-diffusion predictor on the HIP update kernels (VE, VP and sub-VP SDEs, reverse SDE and
+probability flow).
 
 Mirrors sampling/predictors.py of the reference: ``register_predictor`` / ``get_predictor``
 (:6-28), the ``Predictor`` base (:30-50) and the classes registered under
@@ -56,28 +57,43 @@ def _uniform_scalar(v, what):
     return v0
 
 
-def _ve_reverse_diffusion(sde, score, x, t, probability_flow):
-    """x_mean = x + G^2*score (f = 0 for VE); x = x_mean + G*z  (sde_lib.py:135-140,353-362)."""
+def reverse_diffusion_drift(sde, t1):
+    """(a, b, sub_x) of the discretised forward drift f = (a*x)*b [- x] at the one-element fp32 host time ``t1``, or None where
+    f = 0 (the VE SDEs).  VP (sde_lib.py:186-195): f = sqrt(alpha_i)*x - x; one evaluation of ``discretize`` at x = 1 gives
+    sqrt(alpha_i) - 1, an exact fp32 difference (both operands lie within a factor 2), so adding 1 returns sqrt(alpha_i) itself.
+    sub-VP inherits the Euler default (:49-63), f = (phi*x)*dt: phi from ``sde`` at x = 1 as in ``_linear_sde_coeffs``."""
+    if isinstance(sde, (sde_lib.VESDE, sde_lib.cVESDE)):
+        return None
+    if isinstance(sde, (sde_lib.VPSDE, sde_lib.cVPSDE)):
+        f1 = sde.discretize(torch.ones(1, 1, 1, 1), t1)[0]
+        return 1.0 + float(f1.flatten()[0]), 1.0, True
+    if isinstance(sde, sde_lib.subVPSDE):
+        return _linear_sde_coeffs(sde, t1)[0], 1.0 / sde.N, False
+    raise NotImplementedError('the HIP reverse-diffusion step covers the VE, VP and sub-VP SDEs; got %s' % sde.__class__.__name__)
+
+
+def _reverse_diffusion(sde, score, x, t, probability_flow):
+    """rev_f = f - G^2*score*(1/2 if ode else 1); x_mean = x - rev_f; x = x_mean + (0 if ode else G)*z
+    (sampling/predictors.py:79-102; sde_lib.py:65-102 with the forward ``discretize`` of the SDE's class)."""
+    tc = t.detach().cpu()
+    G = _uniform_scalar(sde.discretize(torch.zeros(t.shape[0], 1), tc)[1], 'G')
     if not isinstance(sde, (sde_lib.VESDE, sde_lib.cVESDE)):
-        raise NotImplementedError('the HIP reverse-diffusion step covers the VE SDEs; got %s'
-                                  % sde.__class__.__name__)
-    if probability_flow:
-        raise NotImplementedError('probability-flow predictor is not provided by the HIP step kernel yet')
-    G = _uniform_scalar(sde.discretize(torch.zeros(t.shape[0], 1), t.detach().cpu())[1], 'G')
+        _uniform_scalar(tc, 't')                # (the drift coefficient is one scalar per call as well)
     z = torch.randn_like(x)
-    return ops.reverse_diffusion_step(x.clone(), score, z, 1.0, G)
+    drift = reverse_diffusion_drift(sde, tc.flatten()[:1].to(torch.float32))
+    return ops.reverse_diffusion_step(x.clone(), score, z, 1.0, G, drift, probability_flow)
 
 
 @register_predictor(name='reverse_diffusion')
 class ReverseDiffusionPredictor(Predictor):
     def update_fn(self, x, t):
-        return _ve_reverse_diffusion(self.sde, self.score_fn(x, t), x, t, self.probability_flow)
+        return _reverse_diffusion(self.sde, self.score_fn(x, t), x, t, self.probability_flow)
 
 
 @register_predictor(name='conditional_reverse_diffusion')
 class conditionalReverseDiffusionPredictor(Predictor):
     def update_fn(self, x, y, t):
-        return _ve_reverse_diffusion(self.sde, self.score_fn(x, y, t), x, t, self.probability_flow)
+        return _reverse_diffusion(self.sde, self.score_fn(x, y, t), x, t, self.probability_flow)
 
 
 @register_predictor(name='none')

@@ -156,10 +156,12 @@ def get_pc_sampler(sde, shape, predictor, corrector, snr, p_steps, c_steps, prob
     def pc_sampler(model, show_evolution=False, noise_tape=None, seed=None, global_norm=None):
         steps = p_steps * (c_steps + 1)
         if fused.fusable(model, sde, predictor, corrector, c_steps, probability_flow, continuous):
+            # the network's label: sigma(t) or log sigma(t) for the VE SDEs; VP / sub-VP take t*(N-1) whatever is passed here
             label = 'fourier' if getattr(model, 'embedding_type', 'positional') == 'fourier' else 'sigma'
             x, rec, ts = fused.run(model, sde, shape, None, p_steps, snr, eps, denoise, noise_tape=noise_tape,
                                    seed=seed, record=show_evolution, unconditional_label=label, global_norm=global_norm,
-                                   predictor=predictor, corrector=corrector, probability_flow=probability_flow)
+                                   predictor=predictor, corrector=corrector, probability_flow=probability_flow,
+                                   continuous=continuous)
             info = {'times': ts, 'steps': steps}
             if show_evolution:
                 info['evolution'] = rec.cpu()

@@ -150,8 +150,9 @@ int csd_unet_stats(csd_unet* net, int B, int64_t* launches, double* flops, doubl
 
 /* ------------------------------------------------------------------------------------------
  * Fused predictor-corrector sampler - replaces the loop of sampling/conditional.py:180-226 and
- * sampling/unconditional.py:194-226 for the (reverse_diffusion, langevin) VE pair
- * (sampling/predictors.py:79-102, sampling/correctors.py:51-108, sde_lib.py:353-362,410-418).
+ * sampling/unconditional.py:194-226 for the registered predictors and correctors on a single VE, VP or sub-VP SDE and on
+ * the two-SDE VE pair (sampling/predictors.py:52-200, sampling/correctors.py:51-163, sde_lib.py:49-63,186-195,353-362,410-418).
+ * A zero-initialised struct with the first block of fields set is the (reverse_diffusion, langevin) VE pair.
  * Per-step scalars are computed by the host mirror in fp32 exactly as the reference does and
  * handed over as arrays of length n_steps.
  * ---------------------------------------------------------------------------------------- */
@@ -182,9 +183,15 @@ typedef struct csd_pc_params {
   float path_std0;              /* sigma_y(T + tau)                                                                    */
   /* Langevin corrector of the VP / subVP SDEs (sampling/correctors.py:63-65,94-96): step size times alphas[timestep_i]     */
   const float* corr_alpha;      /* [n_steps] or NULL (= 1: the VE SDEs)                                                */
+  /* predictor == 0 on an SDE with a forward drift, or as the probability flow (sde_lib.py:65-102): f = (a*x)*b, minus x when
+   * rd_sub_x (VP discretize, :186-195: a = sqrt(alpha_i), b = 1; the Euler default sub-VP inherits, :49-63: a = phi(t), b = dt);
+   * rev_f = f - G^2*score*kappa, x_mean = x - rev_f, x = x_mean + G_noise*z.  All three zero = the VE update above, same kernel. */
+  const float* rd_drift;        /* [n_steps][2] = (a, b), or NULL (f = 0: the VE SDEs)                                 */
+  int32_t rd_sub_x;             /* 1: f = (a*x)*b - x; needs rd_drift                                                  */
+  int32_t probability_flow;     /* 1: kappa = 1/2 and G_noise = 0 (the draw is still consumed); 0: kappa = 1, G_noise = G */
 } csd_pc_params;
 
-/* x: [B, x_channels, S, S] in: prior sample (already scaled by sigma_max); out: result.
+/* x: [B, x_channels, S, S] in: prior sample (VE: already scaled by sigma_max); out: result.
  * y: [B, y_channels, S, S] or NULL.  scratch: csd_pc_scratch_bytes() device bytes.
  * Finiteness contract: the Langevin corrector's norms (which see every element of the score and of the noise) and one pass over the
  * returned state set a device flag; csd_pc_sample reads it back behind the stream before it returns - its ONE synchronisation - and
@@ -213,6 +220,9 @@ int csd_pc_step_end(csd_unet* net, const void* packed, void* workspace, size_t w
  *   csd_langevin_step: sampling/correctors.py:51-78,88-108: step = (snr * mean||z|| / mean||score||)^2 * 2 * alpha with
  *                      alpha = sde.alphas[timestep] for the VP / subVP SDEs (:63-65,94-96) and 1 for the VE SDEs
  *   csd_reverse_diffusion_step: sampling/predictors.py:84-89,97-102 with f = 0
+ *   csd_reverse_diffusion_step_ex: the same lines for every SDE and for the probability flow: drift_form 0: f = 0; 1: f =
+ *                      (drift_a*x)*drift_b (Euler default, sub-VP); 2: that minus x (VP discretize); rev_f = f - G^2*score*kappa,
+ *                      x_mean = x - rev_f, x = x_mean + g_noise*z (reverse SDE: kappa = 1, g_noise = G; flow: 1/2 and 0)
  * net: raw network output; score = net / std.  x is updated in place, x_mean written.
  * scratch: >= csd_update_scratch_bytes(B) bytes. */
 size_t csd_update_scratch_bytes(int B);
@@ -220,6 +230,9 @@ int csd_langevin_step(float* x, float* x_mean, const float* net, const float* z,
                       float snr, float alpha, int B, int64_t per_sample, void* scratch, void* stream);
 int csd_reverse_diffusion_step(float* x, float* x_mean, const float* net, const float* z, float std,
                                float G, int B, int64_t per_sample, void* stream);
+int csd_reverse_diffusion_step_ex(float* x, float* x_mean, const float* net, const float* z, float std, float G,
+                                  float drift_a, float drift_b, int drift_form, float kappa, float g_noise, int B,
+                                  int64_t per_sample, void* stream);
 /* General one-step update  x_mean = p*x + a*score,  x = x_mean + c*z  (n elements, scalars per call): the
  * Euler-Maruyama and ancestral-sampling predictors (sampling/predictors.py:52-76,105-179) and the annealed
  * Langevin corrector (sampling/correctors.py:111-142); `score` is the score itself (already divided by std). */
