@@ -45,6 +45,12 @@ class PCParams(ctypes.Structure):
                 ('rd_sub_x', ctypes.c_int32), ('probability_flow', ctypes.c_int32)]
 
 
+class PCInpaintParams(ctypes.Structure):
+    """csd_pc_inpaint_params: data / mask are device addresses, mean_scale / std host arrays of n_steps floats"""
+    _fields_ = [('data', ctypes.c_void_p), ('mask', ctypes.c_void_p),
+                ('mean_scale', ctypes.POINTER(ctypes.c_float)), ('std', ctypes.POINTER(ctypes.c_float))]
+
+
 def build(verbose=False):
     """Compile libcsd_hip.so for gfx950 (hipcc cross-compiles without a GPU)."""
     cmd = ['make', '-C', CSRC, '-j', str(min(8, os.cpu_count() or 1))]
@@ -87,6 +93,14 @@ SIGNATURES = {
     'csd_pc_sample': (_i, [_vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _i, ctypes.POINTER(PCParams), _vp]),
     'csd_pc_step_begin': (_i, [_vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _i, ctypes.POINTER(PCParams), _i, _vp, _vp]),
     'csd_pc_step_end': (_i, [_vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _i, ctypes.POINTER(PCParams), _i, _vp, _i, _vp]),
+    'csd_pc_inpaint_scratch_bytes': (_sz, [_vp, _i]),
+    'csd_pc_inpaint_sample': (_i, [_vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _i, ctypes.POINTER(PCParams),
+                                   ctypes.POINTER(PCInpaintParams), _vp]),
+    'csd_pc_inpaint_step_begin': (_i, [_vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _i, ctypes.POINTER(PCParams),
+                                       ctypes.POINTER(PCInpaintParams), _i, _vp, _vp]),
+    'csd_pc_inpaint_step_end': (_i, [_vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _i, ctypes.POINTER(PCParams),
+                                     ctypes.POINTER(PCInpaintParams), _i, _vp, _i, _vp]),
+    'csd_inpaint_blend': (_i, [_vp, _vp, _vp, _vp, _vp, _f, _f, _i64, _u64, _u64, _vp]),
     'csd_unet_train_workspace_bytes': (_sz, [_vp, _i, _f]),
     'csd_unet_train_forward': (_i, [_vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _i, _f, ctypes.c_uint64, ctypes.c_uint64, _vp]),
     'csd_unet_backward': (_i, [_vp, _vp, _vp, _vp, _sz, _vp, _i, ctypes.c_uint64, _vp]),

@@ -341,6 +341,9 @@ int reverse_diffusion_drift_update_launch(float* x, float* x_mean, const float* 
                                           float G, float a, float b, int drift, int sub_x, float kappa, float g_noise, int B,
                                           int64_t per, hipStream_t s);
 int randn_launch(float* out, int64_t n, uint64_t seed, uint64_t stream_id, hipStream_t s);
+// z == nullptr: the normals of (seed, stream_id) in registers (std == 0: no draw); x_mean may be nullptr
+int inpaint_blend_launch(float* x, float* x_mean, const float* data, const float* mask, const float* z, float m, float std, size_t n,
+                         uint64_t seed, uint64_t stream_id, hipStream_t s);
 int scale_rows_launch(float* out, const float* in, const float* scale, int divide, int B, int64_t per,
                       hipStream_t s);
 int sumsq_nchunk(int64_t per);

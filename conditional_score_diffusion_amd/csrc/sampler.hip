@@ -237,33 +237,84 @@ __device__ __forceinline__ void philox_round(uint32_t& c0, uint32_t& c1, uint32_
   c0 = n0; c1 = n1; c2 = n2; c3 = n3;
 }
 
+// the four standard normals of Philox counter i: key = seed, (c2, c3) = stream_id; lane j is element 4*i + j of the stream
+__device__ __forceinline__ void philox_normal4(size_t i, uint64_t seed, uint64_t stream_id, float v[4]) {
+  uint32_t c0 = (uint32_t)i, c1 = (uint32_t)(i >> 32), c2 = (uint32_t)stream_id, c3 = (uint32_t)(stream_id >> 32);
+  uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    philox_round(c0, c1, c2, c3, k0, k1);
+    k0 += 0x9E3779B9u;
+    k1 += 0xBB67AE85u;
+  }
+  // uniforms in (0,1]: (u32 + 1) * 2^-32 computed via the top 24 bits to stay exact in fp32
+  const float u0 = ((float)(c0 >> 8) + 1.0f) * (1.0f / 16777216.0f);
+  const float u1 = ((float)(c1 >> 8) + 0.5f) * (1.0f / 16777216.0f);
+  const float u2 = ((float)(c2 >> 8) + 1.0f) * (1.0f / 16777216.0f);
+  const float u3 = ((float)(c3 >> 8) + 0.5f) * (1.0f / 16777216.0f);
+  const float r0 = sqrtf(-2.0f * logf(u0)), r1 = sqrtf(-2.0f * logf(u2));
+  float s0, cs0, s1, cs1;
+  sincosf(6.283185307179586f * u1, &s0, &cs0);
+  sincosf(6.283185307179586f * u3, &s1, &cs1);
+  v[0] = r0 * cs0; v[1] = r0 * s0; v[2] = r1 * cs1; v[3] = r1 * s1;
+}
+
 __global__ void randn_kernel(float* __restrict__ out, size_t n, uint64_t seed, uint64_t stream_id) {
   const size_t n4 = (n + 3) / 4;
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4;
        i += (size_t)gridDim.x * blockDim.x) {
-    uint32_t c0 = (uint32_t)i, c1 = (uint32_t)(i >> 32), c2 = (uint32_t)stream_id, c3 = (uint32_t)(stream_id >> 32);
-    uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-      philox_round(c0, c1, c2, c3, k0, k1);
-      k0 += 0x9E3779B9u;
-      k1 += 0xBB67AE85u;
-    }
-    // uniforms in (0,1]: (u32 + 1) * 2^-32 computed via the top 24 bits to stay exact in fp32
-    const float u0 = ((float)(c0 >> 8) + 1.0f) * (1.0f / 16777216.0f);
-    const float u1 = ((float)(c1 >> 8) + 0.5f) * (1.0f / 16777216.0f);
-    const float u2 = ((float)(c2 >> 8) + 1.0f) * (1.0f / 16777216.0f);
-    const float u3 = ((float)(c3 >> 8) + 0.5f) * (1.0f / 16777216.0f);
-    const float r0 = sqrtf(-2.0f * logf(u0)), r1 = sqrtf(-2.0f * logf(u2));
-    float s0, cs0, s1, cs1;
-    sincosf(6.283185307179586f * u1, &s0, &cs0);
-    sincosf(6.283185307179586f * u3, &s1, &cs1);
-    const float v[4] = {r0 * cs0, r0 * s0, r1 * cs1, r1 * s1};
+    float v[4];
+    philox_normal4(i, seed, stream_id, v);
     const size_t base = i * 4;
     if (base + 3 < n) {
       *reinterpret_cast<float4*>(out + base) = make_float4(v[0], v[1], v[2], v[3]);
     } else {
       for (int j = 0; j < 4 && base + j < n; ++j) out[base + j] = v[j];
+    }
+  }
+}
+
+// inpainting: re-impose the known pixels after an update (sampling/unconditional.py:268-271), in the reference's order of operations:
+//   masked_mean = m*data ; masked = masked_mean + std*z ; x = x*(1 - mask) + masked*mask ; x_mean = x*(1 - mask) + masked_mean*mask
+// (x_mean from the NEW x).  m, std: per-call scalars (all samples share one time).  z: the tape, or - z == nullptr and draw - the
+// normals of (seed, stream_id) made in registers with randn_kernel's mapping (one thread = one Philox counter = 4 consecutive
+// elements), which saves the write and the read of a noise buffer; neither: masked = masked_mean (std == 0, the initial state).
+// vec: every pointer is 16-byte aligned - full groups move as float4, the last partial group and unaligned tensors element-wise.
+__global__ __launch_bounds__(256) void inpaint_blend_kernel(float* __restrict__ x, float* __restrict__ x_mean,
+                                                            const float* __restrict__ data, const float* __restrict__ mask,
+                                                            const float* __restrict__ z, float m, float std, size_t n, uint64_t seed,
+                                                            uint64_t stream_id, int draw, int vec) {
+  const size_t n4 = (n + 3) / 4;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (size_t)gridDim.x * blockDim.x) {
+    const size_t base = i * 4;
+    const bool full = vec && base + 3 < n;
+    const int cnt = base + 3 < n ? 4 : (int)(n - base);
+    float xv[4] = {0.f, 0.f, 0.f, 0.f}, dv[4] = {0.f, 0.f, 0.f, 0.f}, mk[4] = {0.f, 0.f, 0.f, 0.f}, zv[4] = {0.f, 0.f, 0.f, 0.f};
+    if (full) {
+      const float4 a = *reinterpret_cast<const float4*>(x + base), b = *reinterpret_cast<const float4*>(data + base),
+                   c = *reinterpret_cast<const float4*>(mask + base);
+      xv[0] = a.x; xv[1] = a.y; xv[2] = a.z; xv[3] = a.w;
+      dv[0] = b.x; dv[1] = b.y; dv[2] = b.z; dv[3] = b.w;
+      mk[0] = c.x; mk[1] = c.y; mk[2] = c.z; mk[3] = c.w;
+      if (z) { const float4 d = *reinterpret_cast<const float4*>(z + base); zv[0] = d.x; zv[1] = d.y; zv[2] = d.z; zv[3] = d.w; }
+    } else {
+      for (int j = 0; j < cnt; ++j) { xv[j] = x[base + j]; dv[j] = data[base + j]; mk[j] = mask[base + j]; if (z) zv[j] = z[base + j]; }
+    }
+    if (!z && draw) philox_normal4(i, seed, stream_id, zv);
+    float xn[4], xm[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const float masked_mean = m * dv[j];
+      const float masked = (z || draw) ? masked_mean + std * zv[j] : masked_mean;
+      const float keep = 1.f - mk[j];
+      xn[j] = xv[j] * keep + masked * mk[j];
+      xm[j] = xn[j] * keep + masked_mean * mk[j];
+    }
+    if (full) {
+      *reinterpret_cast<float4*>(x + base) = make_float4(xn[0], xn[1], xn[2], xn[3]);
+      if (x_mean) *reinterpret_cast<float4*>(x_mean + base) = make_float4(xm[0], xm[1], xm[2], xm[3]);
+    } else {
+      for (int j = 0; j < cnt; ++j) { x[base + j] = xn[j]; if (x_mean) x_mean[base + j] = xm[j]; }
     }
   }
 }
@@ -385,6 +436,18 @@ int randn_launch(float* out, int64_t n, uint64_t seed, uint64_t stream_id, hipSt
   return CSD_OK;
 }
 
+int inpaint_blend_launch(float* x, float* x_mean, const float* data, const float* mask, const float* z, float m, float std, size_t n,
+                         uint64_t seed, uint64_t stream_id, hipStream_t s) {
+  if (n == 0) return CSD_OK;
+  const uintptr_t bits = reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(x_mean) | reinterpret_cast<uintptr_t>(data) |
+                         reinterpret_cast<uintptr_t>(mask) | reinterpret_cast<uintptr_t>(z);
+  CSD_REQUIRE((bits & 3) == 0, "inpaint_blend: tensors must be 4-byte aligned");
+  hipLaunchKernelGGL(inpaint_blend_kernel, dim3(ew_grid((n + 3) / 4)), dim3(256), 0, s, x, x_mean, data, mask, z, m, std, n, seed,
+                     stream_id, (z == nullptr && std != 0.f) ? 1 : 0, (bits & 15) == 0 ? 1 : 0);
+  CSD_LAUNCH_CHECK();
+  return CSD_OK;
+}
+
 int scale_rows_launch(float* out, const float* in, const float* scale, int divide, int B, int64_t per,
                       hipStream_t s) {
   const size_t total = (size_t)B * per;
@@ -463,4 +526,10 @@ extern "C" int csd_randn(float* out, int64_t n, uint64_t seed, uint64_t stream_i
 extern "C" int csd_scale_rows(float* out, const float* in, const float* scale, int divide, int B,
                               int64_t per_sample, void* stream) {
   return scale_rows_launch(out, in, scale, divide, B, per_sample, (hipStream_t)stream);
+}
+
+extern "C" int csd_inpaint_blend(float* x, float* x_mean, const float* data, const float* mask, const float* z, float mean_scale,
+                                 float std, int64_t n, uint64_t seed, uint64_t stream_id, void* stream) {
+  CSD_REQUIRE(x && data && mask && n > 0, "inpaint_blend: bad arguments");
+  return inpaint_blend_launch(x, x_mean, data, mask, z, mean_scale, std, (size_t)n, seed, stream_id, (hipStream_t)stream);
 }

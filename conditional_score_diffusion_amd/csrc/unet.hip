@@ -666,6 +666,7 @@ struct PCCtx {
   int* nonfinite;                                    // device flag of the finiteness contract (behind the norm partials)
   bool path = false;                                 // use_path: y_t follows the bridge (csd_pc_params.path_coef)
   const csd_pc_params* p;
+  const csd_pc_inpaint_params* ip = nullptr;         // inpainting: the known pixels are re-imposed after every phase (csd_pc_inpaint_*)
   float* x; const float* y;
   int B, nchunk;
   size_t nx, ny;
@@ -675,7 +676,15 @@ struct PCCtx {
   // a phase whose rule is 'none' (csd_pc_params.corrector / .predictor == 2) evaluates nothing and draws nothing
   bool has_phase(int phase) const { return (phase == 0 ? p->corrector : p->predictor) != 2; }
   int draws_per_phase() const { return perturb_y ? 2 : 1; }
-  int draws_per_step() const { return draws_per_phase() * ((has_phase(0) ? 1 : 0) + (has_phase(1) ? 1 : 0)); }
+  int draws_per_step() const {
+    const int nph = (has_phase(0) ? 1 : 0) + (has_phase(1) ? 1 : 0);
+    return ip ? nph + 2 : draws_per_phase() * nph;   // inpainting: one blend draw behind every phase, a 'none' phase included
+  }
+  // index (within the step) of the first draw of a phase; inpainting: [z_corrector] z_blend [z_predictor] z_blend
+  int first_draw(int phase) const {
+    if (ip) return phase == 1 ? (has_phase(0) ? 2 : 1) : 0;
+    return (phase == 1 && has_phase(0) ? 1 : 0) * draws_per_phase();
+  }
   // draw k (0-based, in the order of the phases that exist) of step i: from the tape (reference order) or Philox stream
   // 1 + i*draws + k (stream 0 is the prior)
   // use_path draws: -1 = z_y0 (before the loop); step i: 0 = z_y, 1 .. = the existing phases in the order predictor, corrector
@@ -705,7 +714,8 @@ struct PCCtx {
 };
 
 static int pc_setup(PCCtx* c, csd_unet* net, const void* packed, void* workspace, size_t workspace_bytes, void* scratch,
-                    size_t scratch_bytes, float* x, const float* y, int B, const csd_pc_params* p, void* stream) {
+                    size_t scratch_bytes, float* x, const float* y, int B, const csd_pc_params* p, void* stream,
+                    const csd_pc_inpaint_params* ip = nullptr, bool inpaint = false) {
   Plan* pl = nullptr;
   int rc = check_forward_args(net, packed, workspace, workspace_bytes, B, &pl);
   if (rc) return rc;
@@ -731,6 +741,12 @@ static int pc_setup(PCCtx* c, csd_unet* net, const void* packed, void* workspace
   const size_t hw = (size_t)cf.image_size * cf.image_size;
   c->n = &net->net; c->pl = pl; c->pk = static_cast<const float*>(packed); c->ws = static_cast<float*>(workspace);
   c->p = p; c->x = x; c->y = y; c->B = B; c->s = (hipStream_t)stream;
+  if (inpaint) {
+    CSD_REQUIRE(ip && ip->data && ip->mask && ip->mean_scale && ip->std, "pc_inpaint: data, mask, mean_scale and std are required");
+    CSD_REQUIRE(cf.y_channels == 0 && !y, "pc_inpaint: inpainting runs unconditional networks only (y_channels = %d)", cf.y_channels);
+    CSD_REQUIRE(!p->std_y && !p->path_coef, "pc_inpaint: std_y / path_coef belong to the conditional samplers");
+    c->ip = ip;
+  }
   c->nx = (size_t)B * cf.x_channels * hw; c->ny = (size_t)B * cf.y_channels * hw;
   const size_t no = (size_t)B * cf.out_channels * hw;
   float* f = static_cast<float*>(scratch);
@@ -752,17 +768,31 @@ static int pc_setup(PCCtx* c, csd_unet* net, const void* packed, void* workspace
   return CSD_OK;
 }
 
+// inpainting: re-impose the known pixels behind the update of a phase (sampling/unconditional.py:268-271).  The blend's draw follows
+// the phase's own; without a tape the kernel makes it in registers.  x_mean is only ever read after the last predictor phase.
+static int pc_blend(const PCCtx& c, int i, int phase) {
+  const csd_pc_params* p = c.p;
+  const int k = c.first_draw(phase) + (c.has_phase(phase) ? 1 : 0);
+  const size_t draw = (size_t)i * c.draws_per_step() + k;
+  const bool want_mean = phase == 1 && i == p->n_steps - 1 && p->denoise;
+  ProfScope prof(CSD_PROF_SAMPLER, 0, (p->noise_tape ? 5.0 : 4.0) * c.nx * 4, c.s);
+  return inpaint_blend_launch(c.x, want_mean ? c.x_mean : nullptr, c.ip->data, c.ip->mask,
+                              p->noise_tape ? p->noise_tape + draw * c.nx : nullptr, c.ip->mean_scale[i], c.ip->std[i], c.nx, p->seed,
+                              (uint64_t)1 + draw, c.s);
+}
+
 // phase 0: corrector (sampling/conditional.py:208-209), phase 1: predictor (:211).  part bit 0: network + noise + (corrector:
 // norm partials); bit 1: the update.  norm_sums != null: the corrector's step size comes from those two (all-reduced) sums.
 static int pc_phase(const PCCtx& c, int i, int phase, int part, float* sums_out, const float* sums_in, int Bg) {
   int rc;
   const csd_pc_params* p = c.p;
   if (!c.has_phase(phase)) {                       // 'none': x stays, x_mean = x (sampling/predictors.py:182-200, correctors.py:145-163)
+    if (c.ip) return (part & 2) ? pc_blend(c, i, phase) : CSD_OK;      // (the reference wraps the 'none' update functions as well)
     if ((part & 2) && phase == (c.path ? 0 : 1) && i == p->n_steps - 1 && p->denoise)      // (the step's LAST phase)
       CSD_CHECK_HIP(hipMemcpyAsync(c.x_mean, c.x, c.nx * sizeof(float), hipMemcpyDeviceToDevice, c.s));
     return CSD_OK;
   }
-  const int k0 = (phase == 1 && c.has_phase(0) ? 1 : 0) * c.draws_per_phase();
+  const int k0 = c.first_draw(phase);
   const int kp = 1 + (phase == 0 && c.has_phase(1) ? 1 : 0);       // use_path: the predictor draws first
   const float* zp = c.p->noise_tape ? (c.path ? c.noise_path(i, kp, nullptr, c.nx) : c.noise(i, k0 + (c.perturb_y ? 1 : 0), nullptr, c.nx))
                                     : c.z;
@@ -805,6 +835,7 @@ static int pc_phase(const PCCtx& c, int i, int phase, int part, float* sums_out,
       rc = reverse_diffusion_update_launch(c.x, c.x_mean, c.net_out, c.net_stride, zp, p->std_x[i], p->G[i], c.B, c.per, c.s);
     }
     if (rc) return rc;
+    if (c.ip && (rc = pc_blend(c, i, phase))) return rc;
   }
   return CSD_OK;
 }
@@ -835,11 +866,11 @@ static int pc_finish(const PCCtx& c) {
   return CSD_OK;
 }
 
-extern "C" int csd_pc_sample(csd_unet* net, const void* packed, void* workspace, size_t workspace_bytes,
-                             void* scratch, size_t scratch_bytes, float* x, const float* y, int B,
-                             const csd_pc_params* p, void* stream) {
+static int pc_sample_run(csd_unet* net, const void* packed, void* workspace, size_t workspace_bytes, void* scratch,
+                         size_t scratch_bytes, float* x, const float* y, int B, const csd_pc_params* p,
+                         const csd_pc_inpaint_params* ip, bool inpaint, void* stream) {
   PCCtx c;
-  int rc = pc_setup(&c, net, packed, workspace, workspace_bytes, scratch, scratch_bytes, x, y, B, p, stream);
+  int rc = pc_setup(&c, net, packed, workspace, workspace_bytes, scratch, scratch_bytes, x, y, B, p, stream, ip, inpaint);
   if (rc) return rc;
   CSD_CHECK_HIP(hipMemsetAsync(c.nonfinite, 0, sizeof(int), c.s));
   if (c.path) {                                 // y_{T+tau} = y + sigma_y(T+tau) z (sampling/conditional.py:146-149)
@@ -866,11 +897,11 @@ extern "C" int csd_pc_sample(csd_unet* net, const void* packed, void* workspace,
   return pc_finish(c);
 }
 
-extern "C" int csd_pc_step_begin(csd_unet* net, const void* packed, void* workspace, size_t workspace_bytes, void* scratch,
-                                 size_t scratch_bytes, float* x, const float* y, int B, const csd_pc_params* p, int step,
-                                 float* norm_sums, void* stream) {
+static int pc_step_begin_run(csd_unet* net, const void* packed, void* workspace, size_t workspace_bytes, void* scratch,
+                             size_t scratch_bytes, float* x, const float* y, int B, const csd_pc_params* p,
+                             const csd_pc_inpaint_params* ip, bool inpaint, int step, float* norm_sums, void* stream) {
   PCCtx c;
-  int rc = pc_setup(&c, net, packed, workspace, workspace_bytes, scratch, scratch_bytes, x, y, B, p, stream);
+  int rc = pc_setup(&c, net, packed, workspace, workspace_bytes, scratch, scratch_bytes, x, y, B, p, stream, ip, inpaint);
   if (rc) return rc;
   CSD_REQUIRE(norm_sums && step >= 0 && step < p->n_steps, "pc_step_begin: bad step %d / null norm_sums", step);
   CSD_REQUIRE(!c.path, "pc_step_begin: use_path runs through csd_pc_sample only");
@@ -878,15 +909,59 @@ extern "C" int csd_pc_step_begin(csd_unet* net, const void* packed, void* worksp
   return pc_phase(c, step, 0, 1, norm_sums, nullptr, 0);
 }
 
-extern "C" int csd_pc_step_end(csd_unet* net, const void* packed, void* workspace, size_t workspace_bytes, void* scratch,
-                               size_t scratch_bytes, float* x, const float* y, int B, const csd_pc_params* p, int step,
-                               const float* norm_sums, int global_batch, void* stream) {
+static int pc_step_end_run(csd_unet* net, const void* packed, void* workspace, size_t workspace_bytes, void* scratch,
+                           size_t scratch_bytes, float* x, const float* y, int B, const csd_pc_params* p,
+                           const csd_pc_inpaint_params* ip, bool inpaint, int step, const float* norm_sums, int global_batch,
+                           void* stream) {
   PCCtx c;
-  int rc = pc_setup(&c, net, packed, workspace, workspace_bytes, scratch, scratch_bytes, x, y, B, p, stream);
+  int rc = pc_setup(&c, net, packed, workspace, workspace_bytes, scratch, scratch_bytes, x, y, B, p, stream, ip, inpaint);
   if (rc) return rc;
   CSD_REQUIRE(norm_sums && global_batch >= B && step >= 0 && step < p->n_steps, "pc_step_end: bad arguments");
   if ((rc = pc_phase(c, step, 0, 2, nullptr, norm_sums, global_batch))) return rc;
   if ((rc = pc_phase(c, step, 1, 3, nullptr, nullptr, 0))) return rc;
   if ((rc = pc_step_tail(c, step))) return rc;
   return step == p->n_steps - 1 ? pc_finish(c) : CSD_OK;
+}
+
+extern "C" int csd_pc_sample(csd_unet* net, const void* packed, void* workspace, size_t workspace_bytes,
+                             void* scratch, size_t scratch_bytes, float* x, const float* y, int B,
+                             const csd_pc_params* p, void* stream) {
+  return pc_sample_run(net, packed, workspace, workspace_bytes, scratch, scratch_bytes, x, y, B, p, nullptr, false, stream);
+}
+
+extern "C" int csd_pc_step_begin(csd_unet* net, const void* packed, void* workspace, size_t workspace_bytes, void* scratch,
+                                 size_t scratch_bytes, float* x, const float* y, int B, const csd_pc_params* p, int step,
+                                 float* norm_sums, void* stream) {
+  return pc_step_begin_run(net, packed, workspace, workspace_bytes, scratch, scratch_bytes, x, y, B, p, nullptr, false, step, norm_sums,
+                           stream);
+}
+
+extern "C" int csd_pc_step_end(csd_unet* net, const void* packed, void* workspace, size_t workspace_bytes, void* scratch,
+                               size_t scratch_bytes, float* x, const float* y, int B, const csd_pc_params* p, int step,
+                               const float* norm_sums, int global_batch, void* stream) {
+  return pc_step_end_run(net, packed, workspace, workspace_bytes, scratch, scratch_bytes, x, y, B, p, nullptr, false, step, norm_sums,
+                         global_batch, stream);
+}
+
+// ---- inpainting on the same loop (include/csd.h: csd_pc_inpaint_params) -------------------------------------------------------------
+extern "C" size_t csd_pc_inpaint_scratch_bytes(const csd_unet* net, int B) { return csd_pc_scratch_bytes(net, B); }      // (the blend needs no buffer)
+
+extern "C" int csd_pc_inpaint_sample(csd_unet* net, const void* packed, void* workspace, size_t workspace_bytes, void* scratch,
+                                     size_t scratch_bytes, float* x, const float* y, int B, const csd_pc_params* p,
+                                     const csd_pc_inpaint_params* ip, void* stream) {
+  return pc_sample_run(net, packed, workspace, workspace_bytes, scratch, scratch_bytes, x, y, B, p, ip, true, stream);
+}
+
+extern "C" int csd_pc_inpaint_step_begin(csd_unet* net, const void* packed, void* workspace, size_t workspace_bytes, void* scratch,
+                                         size_t scratch_bytes, float* x, const float* y, int B, const csd_pc_params* p,
+                                         const csd_pc_inpaint_params* ip, int step, float* norm_sums, void* stream) {
+  return pc_step_begin_run(net, packed, workspace, workspace_bytes, scratch, scratch_bytes, x, y, B, p, ip, true, step, norm_sums, stream);
+}
+
+extern "C" int csd_pc_inpaint_step_end(csd_unet* net, const void* packed, void* workspace, size_t workspace_bytes, void* scratch,
+                                       size_t scratch_bytes, float* x, const float* y, int B, const csd_pc_params* p,
+                                       const csd_pc_inpaint_params* ip, int step, const float* norm_sums, int global_batch,
+                                       void* stream) {
+  return pc_step_end_run(net, packed, workspace, workspace_bytes, scratch, scratch_bytes, x, y, B, p, ip, true, step, norm_sums,
+                         global_batch, stream);
 }

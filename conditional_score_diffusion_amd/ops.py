@@ -4,6 +4,8 @@ Tensors are containers only: every function checks that its operands are contigu
 tensors, allocates the output / scratch with torch, and enqueues the HIP kernels on the current
 stream.  No torch arithmetic happens here.
 """
+import ctypes
+
 import torch
 
 from . import _lib
@@ -266,6 +268,33 @@ def randn(shape, seed, stream_id, device):
     out = torch.empty(*shape, dtype=torch.float32, device=device)
     check(lib().csd_randn(ptr(out), out.numel(), int(seed), int(stream_id), current_stream(out.device)), 'randn')
     return out
+
+
+def _addr(t, name):
+    """device address of a float32 GPU tensor whose elements lie densely in memory (a view at any 4-byte offset is fine)"""
+    _lib.require_gpu_tensor(t, name)
+    if not t.is_contiguous():
+        raise RuntimeError('%s must be contiguous' % name)
+    return ctypes.c_void_p(t.data_ptr())
+
+
+def inpaint_blend(x, data, mask, z=None, mean_scale=1.0, std=0.0, seed=0, stream_id=0, x_mean=True):
+    """In-place re-imposition of the known pixels (sampling/unconditional.py:268-271), one kernel:
+    ``masked_mean = mean_scale*data; masked = masked_mean + std*z; x = x*(1 - mask) + masked*mask;
+    x_mean = x*(1 - mask) + masked_mean*mask`` (x_mean from the new x); returns ``(x, x_mean)``, ``x_mean=False``: ``(x, None)``.
+
+    ``z=None``: the normals of ``randn(shape, seed, stream_id)`` are made in registers (bit-identical to passing that tensor); with
+    ``std == 0`` nothing is drawn.  ``mask`` has ``x``'s shape and may hold any value in [0, 1].  The tensors may be views at any
+    element offset: 16-byte accesses are used when every address allows them."""
+    tensors = [('x', x), ('data', data), ('mask', mask)] + ([('z', z)] if z is not None else [])
+    for name, t in tensors[1:]:
+        if t.shape != x.shape:
+            raise RuntimeError('inpaint_blend: %s has shape %s, x has %s' % (name, tuple(t.shape), tuple(x.shape)))
+    xm = torch.empty_like(x) if x_mean else None
+    check(lib().csd_inpaint_blend(_addr(x, 'x'), ptr(xm), _addr(data, 'data'), _addr(mask, 'mask'),
+                                  _addr(z, 'z') if z is not None else None, float(mean_scale), float(std), x.numel(), int(seed),
+                                  int(stream_id), current_stream(x.device)), 'inpaint_blend')
+    return x, xm
 
 
 def scale_rows(x, scale, divide=False):

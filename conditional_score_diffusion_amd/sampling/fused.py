@@ -162,6 +162,26 @@ def step_scalars(sde, p_steps, eps, unconditional_label=None, continuous=True):
     return ts, labels.contiguous(), std_x.contiguous(), G.contiguous(), (std_y.contiguous() if std_y is not None else None)
 
 
+def inpaint_tables(sde, ts):
+    """(mean_scale, std) of csd_pc_inpaint_params, [n] fp32 each: p_t(x | data) = N(mean_scale*data, std^2) per step, from one
+    ``sde.marginal_prob`` evaluation at a one-element time like ``step_scalars`` (sampling/unconditional.py:268 evaluates it on the
+    data at the step's time).  The marginal std in discrete time as well: the inpainter perturbs the data with the SDE's marginal,
+    whatever std the score function divides by.  mean_scale is exactly 1 for the VE SDEs."""
+    n = ts.numel()
+    mean_scale, std = torch.empty(n, dtype=torch.float32), torch.empty(n, dtype=torch.float32)
+    one = torch.ones(1, 1, 1, 1)
+    for i in range(n):
+        m, sd = sde.marginal_prob(one, ts[i:i + 1].to(torch.float32))
+        mean_scale[i], std[i] = m.flatten()[0], sd.flatten()[0]
+    return mean_scale.contiguous(), std.contiguous()
+
+
+def inpaint_tape_length(p_steps, has_corrector, has_predictor):
+    """draws of an inpainting run in the order of the step-by-step inpainter's randn_like calls: the prior, then per step
+    [z_corrector] z_blend [z_predictor] z_blend - a 'none' phase draws no update noise but its blend does draw"""
+    return 1 + (int(bool(has_corrector)) + int(bool(has_predictor)) + 2) * p_steps
+
+
 def _fp(t):
     return t.data_ptr() and ctypes.cast(t.data_ptr(), ctypes.POINTER(ctypes.c_float))
 
@@ -189,7 +209,7 @@ def path_tables(sy, ts):
 
 def run(model, sde, shape, y, p_steps, snr, eps, denoise, noise_tape=None, seed=None, record=False,
         unconditional_label=None, global_norm=None, predictor=None, corrector=None, probability_flow=False, use_path=False,
-        corr_alpha=None, continuous=True):
+        corr_alpha=None, continuous=True, inpaint=None):
     """Run the fused loop; returns (samples, record_or_None, timesteps).  ``seed=None``: a fresh key per call (fresh_seed).
 
     ``predictor`` / ``corrector``: the registered classes (default: the reverse-diffusion / Langevin pair); see ``fusable``.
@@ -201,6 +221,13 @@ def run(model, sde, shape, y, p_steps, snr, eps, denoise, noise_tape=None, seed=
     models/utils.py:201-205,237-241); the VE SDEs run continuous only.
 
     Prior: N(0, sigma_max^2) (+ data mean) for the VE SDEs, N(0, I) for VP / sub-VP; ``noise_tape[0]`` is the standard-normal draw.
+
+    ``inpaint``: ``(data, mask)`` - inpainting with an unconditional network (csd_pc_inpaint_sample; sampling/unconditional.py:230-345):
+    the loop starts from prior*(1 - mask) + data*mask and re-imposes the known pixels (mask = 1) at every step's noise level after
+    each phase.  ``mask`` broadcasts to ``data`` (the Haar multi-scale model passes [1, C, 1, 1]).  Draw order / tape layout: prior,
+    then per step [z_corrector] z_blend [z_predictor] z_blend (``inpaint_tape_length``); without a tape the prior is ``ops.randn``
+    stream 0 and draw k of step i is Philox stream 1 + i*draws_per_step + k.  ``record`` then returns [p_steps + 1, ...]: the
+    initial state followed by every step.
 
     ``global_norm``: None = the Langevin step size uses the batch means of THIS call's batch (the reference run on this batch;
     one library call enqueues the whole loop).  Otherwise ``(reduce_fn, global_batch)``: the batch is one shard of a larger one
@@ -233,6 +260,15 @@ def run(model, sde, shape, y, p_steps, snr, eps, denoise, noise_tape=None, seed=
         corr_alpha = langevin_alphas(c_sde, ts)
     n_phases = (pid != 2) + (cid != 2)
     path_tab, path_std0 = None, 0.0
+    if inpaint is not None:
+        if y is not None or isinstance(sde, dict) or use_path:
+            raise NotImplementedError('inpainting on the device loop runs unconditional networks on a single SDE')
+        data, mask = inpaint
+        if tuple(data.shape) != tuple(shape):
+            raise ValueError('inpaint: data has shape %s, the sampler runs %s' % (tuple(data.shape), tuple(shape)))
+        data = data.to(dev, torch.float32).contiguous()
+        mask = mask.to(dev, torch.float32).expand_as(data).contiguous()
+        ip_mean, ip_std = inpaint_tables(c_sde, ts)
     if use_path:
         if not isinstance(sde, dict):
             raise NotImplementedError('use_path needs the two-SDE (CMDE / VS-CMDE) setting: sde = {"x": ..., "y": ...}')
@@ -251,6 +287,8 @@ def run(model, sde, shape, y, p_steps, snr, eps, denoise, noise_tape=None, seed=
         expected = n_phases * p_steps * (2 if std_y is not None else 1)
         if use_path:                            # z_y0 | per step: z_y, z_predictor, z_corrector
             expected = 1 + p_steps * (1 + n_phases)
+        if inpaint is not None:
+            expected = inpaint_tape_length(p_steps, cid != 2, pid != 2) - 1
         if len(tape) - 1 != expected:
             raise RuntimeError('noise tape holds %d draws after the prior, the loop needs %d' % (len(tape) - 1, expected))
     else:
@@ -264,7 +302,18 @@ def run(model, sde, shape, y, p_steps, snr, eps, denoise, noise_tape=None, seed=
     model._ensure_packed()
     ws = model._workspace(B)
     scratch = torch.empty(lib().csd_pc_scratch_bytes(model._h, B), dtype=torch.uint8, device=dev)
-    rec = torch.empty((p_steps,) + tuple(x.shape), dtype=torch.float32, device=dev) if record else None
+    n_rec = p_steps + (1 if inpaint is not None else 0)
+    rec = torch.empty((n_rec,) + tuple(x.shape), dtype=torch.float32, device=dev) if record else None
+    rec_steps = rec
+    ip = None
+    if inpaint is not None:
+        ops.inpaint_blend(x, data, mask, x_mean=False)                # prior*(1 - mask) + data*mask
+        if record:
+            rec[0].copy_(x)
+            rec_steps = rec[1:]
+        ip = _lib.PCInpaintParams()
+        ip.data, ip.mask = data.data_ptr(), mask.data_ptr()
+        ip.mean_scale, ip.std = _fp(ip_mean), _fp(ip_std)
     p = _lib.PCParams()
     p.n_steps = p_steps
     p.labels, p.std_x, p.G = _fp(labels), _fp(std_x), _fp(G)
@@ -273,7 +322,7 @@ def run(model, sde, shape, y, p_steps, snr, eps, denoise, noise_tape=None, seed=
     p.denoise = int(bool(denoise))
     p.noise_tape = flat.data_ptr() if flat is not None else None
     p.seed = int(seed)
-    p.record = rec.data_ptr() if rec is not None else None
+    p.record = rec_steps.data_ptr() if rec is not None else None
     p.predictor, p.corrector = pid, cid
     p.pred_coef = _fp(pred_tab) if pred_tab is not None else None
     p.corr_coef = _fp(corr_tab) if corr_tab is not None else None
@@ -290,7 +339,20 @@ def run(model, sde, shape, y, p_steps, snr, eps, denoise, noise_tape=None, seed=
     if global_norm is not None and cid != 0:
         global_norm = None                      # only the Langevin corrector couples the samples of a batch
     yy = y.contiguous() if y is not None else None
-    if global_norm is None:
+    if ip is not None:
+        args = (model._h, ptr(model._packed), ptr(ws), ws.numel(), ptr(scratch), scratch.numel(), ptr(x), None, B, ctypes.byref(p),
+                ctypes.byref(ip))
+        if global_norm is None:
+            check(lib().csd_pc_inpaint_sample(*args, current_stream(dev)), 'pc_inpaint_sample')
+        else:
+            reduce_fn, global_batch = global_norm
+            sums = torch.zeros(2, dtype=torch.float32, device=dev)
+            for i in range(p_steps):
+                check(lib().csd_pc_inpaint_step_begin(*args, i, ptr(sums), current_stream(dev)), 'pc_inpaint_step_begin')
+                reduce_fn(sums)
+                check(lib().csd_pc_inpaint_step_end(*args, i, ptr(sums), int(global_batch), current_stream(dev)), 'pc_inpaint_step_end')
+        del ip_mean, ip_std, data, mask         # (alive until the enqueue returned; the last call synchronised)
+    elif global_norm is None:
         check(lib().csd_pc_sample(model._h, ptr(model._packed), ptr(ws), ws.numel(), ptr(scratch), scratch.numel(),
                                   ptr(x), ptr(yy) if yy is not None else None, B, ctypes.byref(p),
                                   current_stream(dev)), 'pc_sample')

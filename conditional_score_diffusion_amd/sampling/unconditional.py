@@ -4,7 +4,8 @@ Mirrors ``get_sampling_fn`` (sampling/unconditional.py:13-75) and ``get_pc_sampl
 ``pc_sampler(model, show_evolution=False) -> (samples, {'times', 'steps'[, 'evolution']})``.
 ``sampling.method='ode'`` gives the probability-flow ODE sampler (:93-158): scipy's black-box RK45 on the host, every drift
 evaluation = one network evaluation + one HIP axpby.  ``get_inpainting_fn`` / ``get_pc_inpainter`` (:78-91, :230-345): the PC loop
-with the known pixels re-imposed after every update (masked blend on csd_axpby / csd_mul).
+with the known pixels re-imposed after every update (masked blend on csd_axpby / csd_mul), or - ``device_loop=True`` - the same
+sampler on the fused device loop (csd_pc_inpaint_sample: one library call, on-device noise, no host synchronisation).
 """
 import functools
 
@@ -85,13 +86,28 @@ def get_inpainting_fn(config, sde, eps, n_steps_each=1):
     return get_pc_inpainter(sde=sde, predictor=get_predictor(config.sampling.predictor.lower()),
                             corrector=get_corrector(config.sampling.corrector.lower()), snr=config.sampling.snr,
                             n_steps=n_steps_each, probability_flow=config.sampling.probability_flow,
-                            continuous=config.training.continuous, denoise=config.sampling.noise_removal, eps=eps)
+                            continuous=config.training.continuous, denoise=config.sampling.noise_removal, eps=eps,
+                            device_loop=config.sampling.get('csd_device_loop', False))
 
 
-def get_pc_inpainter(sde, predictor, corrector, snr, n_steps=1, probability_flow=False, continuous=False, denoise=True, eps=1e-5):
+def get_pc_inpainter(sde, predictor, corrector, snr, n_steps=1, probability_flow=False, continuous=False, denoise=True, eps=1e-5,
+                     device_loop=False):
     """Image inpainting with an unconditional model (sampling/unconditional.py:230-345):
-    ``pc_inpainter(model, data, mask, show_evolution=False) -> (x, info)``; ``mask`` is 1 on known pixels.  After every
-    corrector / predictor update the known region is replaced by the data perturbed to the current noise level."""
+    ``pc_inpainter(model, data, mask, show_evolution=False, noise_tape=None, seed=None, global_norm=None) -> (x, info)``; ``mask`` is
+    1 on known pixels.  After every corrector / predictor update the known region is replaced by the data perturbed to the current
+    noise level.
+
+    ``device_loop=False`` (the default) is the step-by-step loop, exactly as it has always run: two update objects per step, the
+    blend on csd_axpby / csd_mul, noise from torch's generator (``torch.randn`` / ``torch.randn_like``, which is what a caller who
+    patches or seeds them relies on).  That path is not touched by ``device_loop`` and takes none of the three keywords: it raises
+    NotImplementedError for them, like ``pc_sampler`` off the fused loop.
+
+    ``device_loop=True`` runs the whole sampler (``sde.N`` steps) as one call of the fused device loop (``fused.run(...,
+    inpaint=(data, mask))``) with the re-imposition as one kernel per phase: Philox noise on the device (``seed=``; None = a fresh
+    key), ``noise_tape=`` in the draw order prior | per step [z_corrector] z_blend [z_predictor] z_blend, ``global_norm=(reduce_fn,
+    global_batch)`` for a batch that is one shard of a larger one, NonFiniteError instead of NaN images.  ``mask`` may broadcast to
+    ``data``.  A (model, sde, predictor, corrector, n_steps) combination the loop does not cover raises NotImplementedError naming the
+    reason - there is no silent fall-back to the step-by-step loop."""
     from .. import ops
     from ..losses import _bstd
 
@@ -115,7 +131,44 @@ def get_pc_inpainter(sde, predictor, corrector, snr, n_steps=1, probability_flow
         x_mean = blend(x, mean, mask)
         return x, x_mean
 
-    def pc_inpainter(model, data, mask, show_evolution=False):
+    def why_not_fused(model):
+        """None when the device loop covers this sampler, else the reason"""
+        from ..models.ddpm import HipUNet
+        if not isinstance(model, HipUNet):
+            return 'the model is a %s, not a HipUNet' % type(model).__name__
+        if getattr(model, 'y_channels', 0) > 0:
+            return 'inpainting uses an unconditional network, this one takes a %d-channel condition' % model.y_channels
+        if n_steps != 1:
+            return 'n_steps = %d corrector steps per update (the device loop runs 1)' % n_steps
+        if isinstance(sde, dict):
+            return 'a single SDE is needed, not an {x, y} pair'
+        pred = NonePredictor if predictor is None else predictor
+        corr = NoneCorrector if corrector is None else corrector
+        if not fused.fusable(model, sde, pred, corr, n_steps, probability_flow, continuous):
+            return 'the device loop does not implement (%s, %s, %s, probability_flow=%s, continuous=%s)' % (
+                type(sde).__name__, pred.__name__, corr.__name__, probability_flow, continuous)
+        if model.device.type != 'cuda':
+            return 'the model is on %s, the device loop runs on the GPU' % model.device
+        return None
+
+    def fused_inpainter(model, data, mask, show_evolution, noise_tape, seed, global_norm):
+        why = why_not_fused(model)
+        if why is not None:
+            raise NotImplementedError('get_pc_inpainter(device_loop=True): ' + why)
+        label = 'fourier' if getattr(model, 'embedding_type', 'positional') == 'fourier' else 'sigma'
+        x, rec, _ = fused.run(model, sde, tuple(data.shape), None, sde.N, snr, eps, denoise, noise_tape=noise_tape, seed=seed,
+                              record=show_evolution, unconditional_label=label, global_norm=global_norm,
+                              predictor=NonePredictor if predictor is None else predictor,
+                              corrector=NoneCorrector if corrector is None else corrector, probability_flow=probability_flow,
+                              continuous=continuous, inpaint=(data, mask))
+        return x, ({'evolution': rec.cpu()} if show_evolution else {})
+
+    def pc_inpainter(model, data, mask, show_evolution=False, noise_tape=None, seed=None, global_norm=None):
+        if device_loop:
+            return fused_inpainter(model, data, mask, show_evolution, noise_tape, seed, global_norm)
+        for name, value in (('noise_tape', noise_tape), ('seed', seed), ('global_norm', global_norm)):
+            if value is not None:
+                raise NotImplementedError('%s is only available on the device loop: get_pc_inpainter(..., device_loop=True)' % name)
         with torch.no_grad():
             data, mask = data.contiguous().float(), mask.contiguous().float()
             x = blend(sde.prior_sampling(data.shape).to(data.device), data, mask)

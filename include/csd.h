@@ -216,6 +216,47 @@ int csd_pc_step_end(csd_unet* net, const void* packed, void* workspace, size_t w
                     size_t scratch_bytes, float* x, const float* y, int B, const csd_pc_params* p, int step,
                     const float* norm_sums, int global_batch, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Inpainting with an unconditional network on the same device loop (sampling/unconditional.py:230-345): after the update of
+ * EVERY phase - a phase whose rule is `none` included, the reference wraps every update function - the known pixels are re-imposed
+ * at the step's noise level (:268-271), in fp32 and in this order:
+ *     masked_mean = mean_scale[i]*data ; masked = masked_mean + std[i]*z ;
+ *     x = x*(1 - mask) + masked*mask ; x_mean = x*(1 - mask) + masked_mean*mask        (x_mean from the NEW x)
+ * x (in): the initial state prior*(1 - mask) + data*mask.  mask is 1 on known pixels; any value in [0, 1] is blended as written.
+ * Unconditional networks only: y_channels > 0, std_y or path_coef are refused with CSD_ERR_INVALID.
+ * Draw order = the order of the step-by-step inpainter's randn_like calls: prior | per step: z_corrector (if a corrector exists),
+ * z_blend, z_predictor (if a predictor exists; a probability-flow predictor still consumes it), z_blend.  A `none` phase evaluates
+ * no network and draws no update noise, but it does draw its blend noise.  p->noise_tape holds the draws after the prior in that
+ * layout, draws_per_step = 2 + (existing phases) tensors of x's size per step.  With p->noise_tape == NULL the Philox stream id of
+ * draw k of step i is 1 + i*draws_per_step + k in the same order (stream 0 is the caller's prior); the blend makes its normals in
+ * registers, bit-identical to a csd_randn fill of that stream id.
+ * denoise returns the re-imposed x_mean of the last predictor phase; record, the finiteness contract and the single final
+ * synchronisation are those of the loop above, and the two step calls with global_batch == B and no all-reduce reproduce the one
+ * call.  The entry points without an inpainting struct keep their noise numbering and results bit for bit.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct csd_pc_inpaint_params {
+  const float* data;            /* device [B, x_channels, S, S]: the image whose known pixels are imposed             */
+  const float* mask;            /* device, same shape: 1 = known pixel                                                */
+  const float* mean_scale;      /* host [n_steps]: mean of p_t(x | data) = mean_scale * data (1 for the VE SDEs)      */
+  const float* std;             /* host [n_steps]: std of p_t(x | data), the SDE's marginal std                       */
+} csd_pc_inpaint_params;
+
+size_t csd_pc_inpaint_scratch_bytes(const csd_unet* net, int B);
+int csd_pc_inpaint_sample(csd_unet* net, const void* packed, void* workspace, size_t workspace_bytes, void* scratch,
+                          size_t scratch_bytes, float* x, const float* y, int B, const csd_pc_params* p,
+                          const csd_pc_inpaint_params* ip, void* stream);
+int csd_pc_inpaint_step_begin(csd_unet* net, const void* packed, void* workspace, size_t workspace_bytes, void* scratch,
+                              size_t scratch_bytes, float* x, const float* y, int B, const csd_pc_params* p,
+                              const csd_pc_inpaint_params* ip, int step, float* norm_sums, void* stream);
+int csd_pc_inpaint_step_end(csd_unet* net, const void* packed, void* workspace, size_t workspace_bytes, void* scratch,
+                            size_t scratch_bytes, float* x, const float* y, int B, const csd_pc_params* p,
+                            const csd_pc_inpaint_params* ip, int step, const float* norm_sums, int global_batch, void* stream);
+/* The re-imposition alone, in place on x over n elements (x_mean may be NULL).  z: the normals to use, or NULL: Philox4x32-10 +
+ * Box-Muller of (seed, stream_id) in registers - element e is lane e % 4 of counter e / 4, exactly the fill of the randn operator
+ * below - and nothing is drawn when std == 0.  16-byte loads and stores when every pointer is 16-byte aligned. */
+int csd_inpaint_blend(float* x, float* x_mean, const float* data, const float* mask, const float* z, float mean_scale,
+                      float std, int64_t n, uint64_t seed, uint64_t stream_id, void* stream);
+
 /* Stand-alone update kernels (the "noise-add" steps), usable with any score source:
  *   csd_langevin_step: sampling/correctors.py:51-78,88-108: step = (snr * mean||z|| / mean||score||)^2 * 2 * alpha with
  *                      alpha = sde.alphas[timestep] for the VP / subVP SDEs (:63-65,94-96) and 1 for the VE SDEs
