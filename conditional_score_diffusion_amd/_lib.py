@@ -51,6 +51,11 @@ class PCInpaintParams(ctypes.Structure):
                 ('mean_scale', ctypes.POINTER(ctypes.c_float)), ('std', ctypes.POINTER(ctypes.c_float))]
 
 
+class OdeCoef(ctypes.Structure):
+    """csd_ode_coef: one Runge-Kutta tableau row, passed by value"""
+    _fields_ = [('c', ctypes.c_double * 7)]
+
+
 def build(verbose=False):
     """Compile libcsd_hip.so for gfx950 (hipcc cross-compiles without a GPU)."""
     cmd = ['make', '-C', CSRC, '-j', str(min(8, os.cpu_count() or 1))]
@@ -68,6 +73,7 @@ WEIGHT_EPOCH = [0]     # bumped by every raw-kernel write to model parameters (o
 # name -> (restype, argtypes); mirrors include/csd.h one to one
 _vp, _i, _i64, _f, _sz, _u64 = (ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float,
                                 ctypes.c_size_t, ctypes.c_uint64)
+_d = ctypes.c_double
 SIGNATURES = {
     'csd_version': (ctypes.c_char_p, []),
     'csd_last_error': (ctypes.c_char_p, []),
@@ -170,6 +176,11 @@ SIGNATURES = {
     'csd_pf_ode_state': (_i, [_vp, _vp, _vp, _vp, _i, _i64, _vp]),
     'csd_pf_ode_scratch_bytes': (_sz, [_i, _i64]),
     'csd_pf_ode_rhs': (_i, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i, _i64, _vp, _vp]),
+    'csd_ode_scratch_bytes': (_sz, [_i64]),
+    'csd_ode_combine': (_i, [_vp, _vp, _i64, _i, OdeCoef, _d, _vp, _vp, _i64, _i64, _vp]),
+    'csd_ode_error_sumsq': (_i, [_vp, _vp, _vp, _i64, OdeCoef, _d, _d, _d, _i64, _vp, _vp, _vp]),
+    'csd_ode_scaled_sumsq': (_i, [_vp, _vp, _d, _d, _vp, _d, _d, _i64, _vp, _vp, _vp]),
+    'csd_ode_drift': (_i, [_vp, _vp, _i64, _vp, _vp, _vp, _i, _i64, _vp]),
 }
 
 

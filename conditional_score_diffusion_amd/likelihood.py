@@ -20,6 +20,12 @@ Two paths compute the right-hand side:
 
 ``get_conditional_likelihood_fn`` gives the conditional NLL of x given a clean y under a single conditional SDE (cVESDE / cVPSDE: the
 CDE / SR3 estimator).  The CMDE / VS-CMDE pair diffuses y as well and is not provided.
+
+``device_loop=True`` (both getters; the default False is the path above, unchanged) keeps the fused right-hand side and replaces scipy by
+``ode_solver.solve``: the same RK45 controller with the float64 state and the stage derivatives in device memory.  The per-evaluation
+upload shrinks to the 20 B bytes of coefficients and labels, the download to one double per attempted step; the network's fp32 input is
+written by the stage combination itself (``csd_ode_combine``), so ``csd_pf_ode_state`` is not run.  A combination it does not cover
+raises NotImplementedError; it never falls back to the host loop.
 """
 import ctypes
 
@@ -108,7 +114,7 @@ def _fused_supported(model, sde, conditional):
 class _FusedRHS:
     """The probability-flow right-hand side of one likelihood call on the HIP network (buffers allocated once per call)."""
 
-    def __init__(self, model, sde, x, y, epsilon, conditional):
+    def __init__(self, model, sde, x, y, epsilon, conditional, host_state=True):
         self.model, self.sde, self.conditional = model, sde, conditional
         dev = x.device
         B, cx, S = x.shape[0], model.x_channels, model.image_size
@@ -127,11 +133,12 @@ class _FusedRHS:
         self.ws = torch.empty(need, dtype=torch.uint8, device=dev)
         n = B * self.D
         self.n = n
-        # upload: [x (B*D) | log p (B) | a (B) | c (B) | labels (B)] float64 - ONE copy per evaluation
-        self.host = torch.empty(n + 4 * B, dtype=torch.float64).pin_memory()
-        self.up = torch.empty(n + 4 * B, dtype=torch.float64, device=dev)
-        self.res = torch.empty(n + B, dtype=torch.float64, device=dev)
-        self.res_host = torch.empty(n + B, dtype=torch.float64).pin_memory()
+        if host_state:              # (the state lives with scipy; host_state=False: with ode_solver on the device, see device_rhs)
+            # upload: [x (B*D) | log p (B) | a (B) | c (B) | labels (B)] float64 - ONE copy per evaluation
+            self.host = torch.empty(n + 4 * B, dtype=torch.float64).pin_memory()
+            self.up = torch.empty(n + 4 * B, dtype=torch.float64, device=dev)
+            self.res = torch.empty(n + B, dtype=torch.float64, device=dev)
+            self.res_host = torch.empty(n + B, dtype=torch.float64).pin_memory()
         self.x32 = torch.empty(B, cx, S, S, dtype=torch.float32, device=dev)
         self.lab32 = torch.empty(B, dtype=torch.float32, device=dev)
         self.out = torch.empty(B, oc, S, S, dtype=torch.float32, device=dev)
@@ -141,11 +148,25 @@ class _FusedRHS:
         self.y = y.to(device=dev, dtype=torch.float32).contiguous() if model.y_channels else None
         self.scratch = torch.empty(lib().csd_pf_ode_scratch_bytes(B, self.D), dtype=torch.uint8, device=dev)
         self.stream = current_stream(dev)
-        base = self.up.data_ptr()
-        self.p_a, self.p_c, self.p_lab = (ctypes.c_void_p(base + 8 * (n + k * B)) for k in (1, 2, 3))
+        if host_state:
+            base = self.up.data_ptr()
+            self.p_a, self.p_c, self.p_lab = (ctypes.c_void_p(base + 8 * (n + k * B)) for k in (1, 2, 3))
+
+    def _evaluate(self, state, lab32, p_a, p_c, res):
+        """forward, input-only backward and csd_pf_ode_rhs at the fp32 operands self.x32 / lab32; state, res: float64 [n + B]"""
+        model, B = self.model, self.B
+        model._xgrad_calls = getattr(model, '_xgrad_calls', 0) + 1
+        call = model._xgrad_calls
+        check(lib().csd_unet_train_forward(model._h, self.table, ptr(self.ws), self.ws.numel(), ptr(self.x32), ptr(self.y),
+                                           ptr(lab32), ptr(self.out), B, 0.0, model.dropout_seed, call, self.stream),
+              'unet_train_forward')
+        check(lib().csd_unet_backward_ex(model._h, self.table, None, ptr(self.v), ptr(self.ws), self.ws.numel(), ptr(self.dout), B,
+                                         call, self.stream), 'unet_backward_ex')
+        check(lib().csd_pf_ode_rhs(ptr(state), ptr(self.out), ptr(self.v), ptr(self.dout), self.net_stride, p_a, p_c,
+                                   ptr(res), B, self.D, ptr(self.scratch), self.stream), 'pf_ode_rhs')
 
     def __call__(self, t, state):
-        model, B, n = self.model, self.B, self.n
+        B, n = self.B, self.n
         a, c, labels = _row_coefficients(self.sde, self.score, self.probe, t, B, self.conditional)
         h = self.host.numpy()
         h[:n + B] = state
@@ -154,18 +175,24 @@ class _FusedRHS:
         h[n + 3 * B:] = labels.numpy()
         self.up.copy_(self.host, non_blocking=True)
         check(lib().csd_pf_ode_state(ptr(self.up), self.p_lab, ptr(self.x32), ptr(self.lab32), B, self.D, self.stream), 'pf_ode_state')
-        model._xgrad_calls = getattr(model, '_xgrad_calls', 0) + 1
-        call = model._xgrad_calls
-        check(lib().csd_unet_train_forward(model._h, self.table, ptr(self.ws), self.ws.numel(), ptr(self.x32), ptr(self.y),
-                                           ptr(self.lab32), ptr(self.out), B, 0.0, model.dropout_seed, call, self.stream),
-              'unet_train_forward')
-        check(lib().csd_unet_backward_ex(model._h, self.table, None, ptr(self.v), ptr(self.ws), self.ws.numel(), ptr(self.dout), B,
-                                         call, self.stream), 'unet_backward_ex')
-        check(lib().csd_pf_ode_rhs(ptr(self.up), ptr(self.out), ptr(self.v), ptr(self.dout), self.net_stride, self.p_a, self.p_c,
-                                   ptr(self.res), B, self.D, ptr(self.scratch), self.stream), 'pf_ode_rhs')
+        self._evaluate(self.up, self.lab32, self.p_a, self.p_c, self.res)
         self.res_host.copy_(self.res, non_blocking=True)
         torch.cuda.current_stream(self.dev).synchronize()
         return self.res_host.numpy().copy()
+
+    def device_rhs(self):
+        """The same evaluation as an ``ode_solver`` right-hand side ``rhs(t, y, x32, k_out)``: the state ``y`` and the derivative
+        ``k_out`` (float64 [n + B]) stay on the device, ``x32`` is self.x32 (the solver's combine pass keeps it equal to float(y_x));
+        what is uploaded per evaluation is [a | c | labels] through a pinned ring."""
+        from .ode_solver import CoefficientRing
+        ring = CoefficientRing(self.B, self.dev)
+        p_a, p_c = ctypes.c_void_p(ring.a.data_ptr()), ctypes.c_void_p(ring.c.data_ptr())
+
+        def rhs(t, y, x32, k_out):
+            ring.upload(*_row_coefficients(self.sde, self.score, self.probe, t, self.B, self.conditional))
+            self._evaluate(y, ring.labels, p_a, p_c, k_out)
+
+        return rhs
 
     def close(self):
         lib().csd_unet_train_release(self.model._h, ptr(self.ws))
@@ -182,12 +209,51 @@ def _solve(ode_func, data, sde, rtol, atol, method, eps):
     return z, delta_logp, nfe
 
 
-def _run(model, sde, inverse_scaler, data, y, hutchinson_type, epsilon, rtol, atol, method, eps, conditional, drift_fn):
+def why_not_device_loop(model, sde, conditional, method):
+    """None when (model, sde, method) runs on the device-resident RK45 loop, else the reason as text."""
+    from .models.ddpm import HipUNet
+    if method != 'RK45':
+        return "the device loop integrates with RK45 only, not method = '%s'" % method
+    if not isinstance(model, HipUNet):
+        return 'the model is a %s, not a HipUNet' % type(model).__name__
+    if model.device.type != 'cuda':
+        return 'the model is on %s, the device loop runs on the GPU' % model.device
+    if not _fused_supported(model, sde, conditional):
+        want = 'cVESDE / cVPSDE with a network that takes a condition' if conditional else \
+            'VESDE / VPSDE / subVPSDE with an unconditional network'
+        return 'the fused right-hand side covers %s, not %s with a %d-channel condition' % (
+            want, type(sde).__name__, getattr(model, 'y_channels', 0))
+    return None
+
+
+def _solve_on_device(rhs, data, sde, rtol, atol, eps):
+    """_solve with the state [x | log p] and the stage derivatives in device memory (ode_solver.solve)"""
+    from . import ode_solver
+    B = data.shape[0]
+    init = torch.cat([data.reshape(-1).double(), torch.zeros(B, dtype=torch.float64, device=data.device)])
+    be = ode_solver.DeviceBackend(init, x32=rhs.x32)
+    res = ode_solver.solve(rhs.device_rhs(), be, eps, sde.T, rtol, atol)
+    z = res.y[:-B].reshape(data.shape).type(torch.float32)
+    delta_logp = res.y[-B:].type(torch.float32)
+    return z, delta_logp, res.nfev
+
+
+def _run(model, sde, inverse_scaler, data, y, hutchinson_type, epsilon, rtol, atol, method, eps, conditional, drift_fn,
+         device_loop=False):
     with torch.no_grad():
         shape = data.shape
         epsilon = _hutchinson_noise(hutchinson_type, data) if epsilon is None else \
             epsilon.to(device=data.device, dtype=torch.float32).reshape(shape)
-        if _fused_supported(model, sde, conditional):
+        if device_loop:
+            why = why_not_device_loop(model, sde, conditional, method)
+            if why is not None:
+                raise NotImplementedError('likelihood (device_loop=True): ' + why)
+            rhs = _FusedRHS(model, sde, data, y, epsilon, conditional, host_state=False)
+            try:
+                z, delta_logp, nfe = _solve_on_device(rhs, data, sde, rtol, atol, eps)
+            finally:
+                rhs.close()
+        elif _fused_supported(model, sde, conditional):
             rhs = _FusedRHS(model, sde, data, y, epsilon, conditional)
             try:
                 z, delta_logp, nfe = _solve(rhs, data, sde, rtol, atol, method, eps)
@@ -207,12 +273,14 @@ def _run(model, sde, inverse_scaler, data, y, hutchinson_type, epsilon, rtol, at
         return _bpd(sde, inverse_scaler, z, delta_logp, shape), z, nfe
 
 
-def get_likelihood_fn(sde, inverse_scaler, hutchinson_type='Rademacher', rtol=1e-5, atol=1e-5, method='RK45', eps=1e-5):
+def get_likelihood_fn(sde, inverse_scaler, hutchinson_type='Rademacher', rtol=1e-5, atol=1e-5, method='RK45', eps=1e-5,
+                      device_loop=False):
     """Create a function to compute the unbiased log-likelihood estimate of a given data point (reference likelihood.py:40-103).
 
     Returns ``likelihood_fn(model, data, epsilon=None) -> (bpd, z, nfe)``: bits/dim [B], the latent code, the number of function
     evaluations of the black-box solver.  ``epsilon`` (shape of ``data``) pins the Hutchinson noise; by default it is drawn once per
-    call as in the reference."""
+    call as in the reference.  ``device_loop=True``: the same fused right-hand side under the device-resident RK45 of ``ode_solver``
+    instead of scipy on the host (module docstring); NotImplementedError where it does not apply."""
 
     def likelihood_fn(model, data, epsilon=None):
         def drift_fn(x, t):
@@ -221,15 +289,17 @@ def get_likelihood_fn(sde, inverse_scaler, hutchinson_type='Rademacher', rtol=1e
             rsde = sde.reverse(score_fn, probability_flow=True)
             return rsde.sde(x, t)[0]
 
-        return _run(model, sde, inverse_scaler, data, None, hutchinson_type, epsilon, rtol, atol, method, eps, False, drift_fn)
+        return _run(model, sde, inverse_scaler, data, None, hutchinson_type, epsilon, rtol, atol, method, eps, False, drift_fn,
+                    device_loop)
 
     return likelihood_fn
 
 
-def get_conditional_likelihood_fn(sde, inverse_scaler, hutchinson_type='Rademacher', rtol=1e-5, atol=1e-5, method='RK45', eps=1e-5):
+def get_conditional_likelihood_fn(sde, inverse_scaler, hutchinson_type='Rademacher', rtol=1e-5, atol=1e-5, method='RK45', eps=1e-5,
+                                  device_loop=False):
     """Conditional NLL of x given y in bits/dim under the CDE / SR3 estimator: a single ``cVESDE`` / ``cVPSDE`` on x, the score network
     ``get_score_fn(..., conditional=True)`` sees the clean condition y.  Returns ``likelihood_fn(model, x, y, epsilon=None) ->
-    (bpd, z, nfe)``; bits/dim are per dimension of x."""
+    (bpd, z, nfe)``; bits/dim are per dimension of x.  ``device_loop`` as in ``get_likelihood_fn``."""
     if isinstance(sde, dict):
         raise NotImplementedError('the conditional likelihood is provided for a single conditional SDE (CDE / SR3); the CMDE / VS-CMDE '
                                   'pair diffuses y as well')
@@ -242,6 +312,6 @@ def get_conditional_likelihood_fn(sde, inverse_scaler, hutchinson_type='Rademach
             rsde = sde.reverse(mutils.get_conditional_score_fn(score_fn, 'x'), probability_flow=True)
             return rsde.sde(xx, y, t)[0]
 
-        return _run(model, sde, inverse_scaler, x, y, hutchinson_type, epsilon, rtol, atol, method, eps, True, drift_fn)
+        return _run(model, sde, inverse_scaler, x, y, hutchinson_type, epsilon, rtol, atol, method, eps, True, drift_fn, device_loop)
 
     return likelihood_fn

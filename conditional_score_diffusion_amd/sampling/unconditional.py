@@ -3,9 +3,11 @@
 Mirrors ``get_sampling_fn`` (sampling/unconditional.py:13-75) and ``get_pc_sampler`` (:161-228):
 ``pc_sampler(model, show_evolution=False) -> (samples, {'times', 'steps'[, 'evolution']})``.
 ``sampling.method='ode'`` gives the probability-flow ODE sampler (:93-158): scipy's black-box RK45 on the host, every drift
-evaluation = one network evaluation + one HIP axpby.  ``get_inpainting_fn`` / ``get_pc_inpainter`` (:78-91, :230-345): the PC loop
-with the known pixels re-imposed after every update (masked blend on csd_axpby / csd_mul), or - ``device_loop=True`` - the same
-sampler on the fused device loop (csd_pc_inpaint_sample: one library call, on-device noise, no host synchronisation).
+evaluation = one network evaluation + one HIP axpby; with ``device_loop=True`` (``config.sampling.csd_device_loop``) the same RK45
+with the float64 state in device memory (ode_solver.py, csrc/ode_rk45.hip) and one 8-byte read per step.  ``get_inpainting_fn`` /
+``get_pc_inpainter`` (:78-91, :230-345): the PC loop with the known pixels re-imposed after every update (masked blend on csd_axpby /
+csd_mul), or - ``device_loop=True`` - the same sampler on the fused device loop (csd_pc_inpaint_sample: one library call, on-device
+noise, no host synchronisation).
 """
 import functools
 
@@ -31,7 +33,8 @@ def get_sampling_fn(config, sde, shape, eps, predictor='default', corrector='def
         denoise = config.sampling.noise_removal
     method = config.sampling.method.lower()
     if method == 'ode':
-        return get_ode_sampler(sde=sde, shape=shape, denoise=denoise, eps=eps)
+        return get_ode_sampler(sde=sde, shape=shape, denoise=denoise, eps=eps,
+                               device_loop=config.sampling.get('csd_device_loop', False))
     if method != 'pc':
         raise ValueError(f"Sampler name {config.sampling.method} unknown.")
     return get_pc_sampler(sde=sde, shape=shape, predictor=predictor, corrector=corrector, snr=snr,
@@ -39,11 +42,17 @@ def get_sampling_fn(config, sde, shape, eps, predictor='default', corrector='def
                           continuous=config.training.continuous, denoise=denoise, eps=eps)
 
 
-def get_ode_sampler(sde, shape, denoise=False, rtol=1e-5, atol=1e-5, method='RK45', eps=1e-3):
+def get_ode_sampler(sde, shape, denoise=False, rtol=1e-5, atol=1e-5, method='RK45', eps=1e-3, device_loop=False):
     """Probability-flow ODE sampler with a black-box solver (sampling/unconditional.py:93-158):
     ``ode_sampler(model, z=None) -> (samples, nfe)``.  The drift of the reverse-time ODE, f(x, t) - g(t)^2 score / 2
     (sde_lib.py:123-133), is linear in x for every SDE of sde_lib, so an evaluation is the score network plus one
-    ``csd_axpby`` with host scalars; the state crosses to the host per evaluation exactly as in the reference."""
+    ``csd_axpby`` with host scalars; the state crosses to the host per evaluation exactly as in the reference.
+
+    ``device_loop=True`` integrates with ``ode_solver.solve`` instead: the same step-size controller, the float64 state and the stage
+    derivatives in device memory.  An evaluation is the inference forward on the fp32 input that the stage combination wrote
+    (``csd_ode_combine``) and one fp64 drift pass (``csd_ode_drift``: a x + c h, c = -g^2 / (2 std)); per evaluation the host
+    uploads the coefficients and labels (20 B bytes) and per attempted step it reads one double.  RK45, a HipUNet on the GPU and a
+    VESDE / VPSDE / subVPSDE only: anything else raises NotImplementedError naming the reason, never the host loop."""
     from scipy import integrate
 
     from .. import ops
@@ -61,9 +70,49 @@ def get_ode_sampler(sde, shape, denoise=False, rtol=1e-5, atol=1e-5, method='RK4
         phi, g = _linear_sde_coeffs(sde, t)
         return ops.axpby(x, score_fn(x, t), alpha=phi, beta=-0.5 * g * g)
 
+    def device_solve(model, x):
+        """the final state (float64, flat) and nfe of the device-resident integration from sde.T to eps"""
+        import ctypes
+
+        from .. import likelihood, ode_solver
+        from .._lib import check, current_stream, lib, ptr
+        why = likelihood.why_not_device_loop(model, sde, False, method)
+        if why is not None:
+            raise NotImplementedError('get_ode_sampler(device_loop=True): ' + why)
+        dev, B, S = model.device, shape[0], model.image_size
+        D, net_stride = model.x_channels * S * S, model.out_channels * S * S
+        if tuple(x.shape) != (B, model.x_channels, S, S):
+            raise RuntimeError('the initial sample has shape %s, expected %s' % (tuple(x.shape), (B, model.x_channels, S, S)))
+        probe = likelihood._Probe(model)
+        score = mutils.get_score_fn(sde, probe, conditional=False, train=False, continuous=True)
+        model.eval()
+        model._ensure_packed()
+        ws = model._workspace(B)
+        x32 = torch.empty(B * D, dtype=torch.float32, device=dev)
+        out = torch.empty(B * net_stride, dtype=torch.float32, device=dev)
+        ring = ode_solver.CoefficientRing(B, dev)
+        p_a, p_c = ctypes.c_void_p(ring.a.data_ptr()), ctypes.c_void_p(ring.c.data_ptr())
+        stream = current_stream(dev)
+
+        def rhs(t, y, x32_, k_out):
+            ring.upload(*likelihood._row_coefficients(sde, score, probe, t, B, False))
+            check(lib().csd_unet_forward(model._h, ptr(model._packed), ptr(ws), ws.numel(), ptr(x32_), None, ptr(ring.labels), ptr(out),
+                                         B, None, 0.0, stream), 'unet_forward')
+            check(lib().csd_ode_drift(ptr(y), ptr(out), net_stride, p_a, p_c, ptr(k_out), B, D, stream), 'ode_drift')
+
+        be = ode_solver.DeviceBackend(x.to(device=dev).reshape(-1).double(), x32=x32)
+        res = ode_solver.solve(rhs, be, sde.T, eps, rtol, atol)
+        return res.y, res.nfev
+
     def ode_sampler(model, z=None):
         with torch.no_grad():
             x = sde.prior_sampling(shape).to(model.device) if z is None else z
+            if device_loop:
+                xf, nfe = device_solve(model, x)
+                x = xf.reshape(shape).type(torch.float32)
+                if denoise:
+                    x = denoise_update_fn(model, x)
+                return x, nfe
 
             def ode_func(t, xf):
                 xt = mutils.from_flattened_numpy(xf, shape).to(model.device).type(torch.float32)

@@ -527,6 +527,35 @@ size_t csd_pf_ode_scratch_bytes(int B, int64_t D);
 int csd_pf_ode_rhs(const double* y, const float* h, const float* v, const float* eps, int64_t net_stride, const double* a,
                    const double* c, double* out, int B, int64_t D, void* scratch, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Embedded Runge-Kutta 5(4) on a device-resident state (csrc/ode_rk45.hip): the vector arithmetic of one Dormand-Prince step for
+ * the probability-flow ODE sampler and the likelihood, so that the state and the stage derivatives never leave the device and a
+ * step costs the host one 8-byte read.  y, ynew, out [n] and K [7 rows, row j at K + j * k_stride, |k_stride| >= n] are float64.
+ * A negative k_stride walks the rows backwards: the last stage of an accepted step becomes the first of the next without a copy.
+ * For the likelihood n = B * D + B (csd_pf_ode_rhs's layout: a K row is its `out`), for the sampler n = B * D.  A tableau row is
+ * passed by value (csd_ode_coef): no device table, no upload.
+ *   csd_ode_combine:      out[i] = y[i] + h * sum_{j < s} coef.c[j] * K[j * k_stride + i], 1 <= s <= 7 (j ascending); with
+ *       nx > 0 the same pass writes x32[i] = float(out[i]) for i < nx <= n (the network's fp32 input: no csd_pf_ode_state pass).
+ *       out may alias neither y nor the s rows of K that are read.
+ *   csd_ode_error_sumsq:  result[0] = sum_i (h * sum_{j < 7} E.c[j] * K[j * k_stride + i] / (atol + rtol * max(|y[i]|, |ynew[i]|)))^2
+ *   csd_ode_scaled_sumsq: result[0] = sum_i ((alpha * u[i] + beta * w[i]) / (atol + rtol * |y[i]|))^2; w may be NULL (beta unused).
+ *   csd_ode_drift:        out[b*D + i] = a[b] * y[b*D + i] + c[b] * h[b*net_stride + i]: csd_pf_ode_rhs without the divergence
+ *       sums (the ODE sampler's right-hand side); a, c [B] float64 on the device, h the raw network output (fp32).
+ *     y, ynew, K, out, x32 and scratch are 16-byte aligned (rows of an odd k_stride are read with 8-byte accesses).  result is a
+ *     device double.  The sums are fp64 and deterministic: one partial per workgroup, lanes in a fixed tree, then one workgroup adds
+ *     the partials in index order; no atomics.  scratch: csd_ode_scratch_bytes bytes for this n, not shared between streams.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct { double c[7]; } csd_ode_coef;
+size_t csd_ode_scratch_bytes(int64_t n);
+int csd_ode_combine(const double* y, const double* K, int64_t k_stride, int s, csd_ode_coef coef, double h, double* out, float* x32,
+                    int64_t nx, int64_t n, void* stream);
+int csd_ode_error_sumsq(const double* y, const double* ynew, const double* K, int64_t k_stride, csd_ode_coef E, double h, double atol,
+                        double rtol, int64_t n, double* result, void* scratch, void* stream);
+int csd_ode_scaled_sumsq(const double* u, const double* w, double alpha, double beta, const double* y, double atol, double rtol,
+                         int64_t n, double* result, void* scratch, void* stream);
+int csd_ode_drift(const double* y, const float* h, int64_t net_stride, const double* a, const double* c, double* out, int B, int64_t D,
+                  void* stream);
+
 #ifdef __cplusplus
 }
 #endif

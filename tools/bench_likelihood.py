@@ -6,7 +6,14 @@ at B = 64 and NCSN++ 256 x 256 at B = 8, random weights.  One JSON line per shap
   bwd_input_ms / bwd_full_ms   csd_unet_backward_ex(grads = NULL, d_x) against csd_unet_backward (every parameter gradient)
   nfe, s_per_image  one full likelihood (scipy RK45, rtol = atol = 1e-5, eps = 1e-5) of the batch
 
-  python tools/bench_likelihood.py [--shapes sr3,ncsnpp256] [--reps 5] [--no-full] [--rhs-only N]
+--device-loop adds the device-resident RK45 (ode_solver.py, csrc/ode_rk45.hip) beside scipy's host loop, same process, same inputs,
+the two loops alternating --full-reps times (times are the mean, every run is listed):
+
+  s_per_image_device_loop, nfe_device_loop, device_vs_host     the full likelihood with device_loop=True; ratio of the two times
+  and one more line, 'ode sampler ncsnpp256' (get_ode_sampler, NCSN++ 256 x 256 VE, B = 8, rtol = atol = 1e-5, no denoising step):
+  ms_per_evaluation / ms_per_evaluation_device_loop            wall time of a whole sample / nfe on each loop, beside forward_ms
+
+  python tools/bench_likelihood.py [--shapes sr3,ncsnpp256] [--reps 5] [--no-full] [--rhs-only N] [--device-loop] [--full-reps 1]
 --rhs-only N: N right-hand-side evaluations of SR3-160 and nothing else (the rocprofv3 kernel trace of DESIGN.md)."""
 import argparse
 import ctypes
@@ -121,6 +128,58 @@ def rhs_ms(model, sde, x, y, e, cond, reps):
     return dt
 
 
+def timed(fn):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    out = fn()
+    torch.cuda.synchronize()
+    return time.perf_counter() - t0, out
+
+
+def full_likelihood(r, model, sde, cond, x, y, e, device_loop, reps):
+    """one full likelihood of the batch on the host loop and - device_loop - on the device loop, alternating"""
+    B = x.shape[0]
+    get = likelihood.get_conditional_likelihood_fn if cond else likelihood.get_likelihood_fn
+    runs = {False: [], True: []}
+    for _ in range(reps):
+        for on_device in ((False, True) if device_loop else (False,)):
+            fn = get(sde, lambda v: v, device_loop=True) if on_device else get(sde, lambda v: v)
+            dt, (bpd, _, nfe) = timed(lambda: fn(model, x, y, epsilon=e) if cond else fn(model, x, epsilon=e))
+            runs[on_device].append((dt / B, int(nfe), float(bpd.mean())))
+    mean = lambda on_device: sum(t for t, _, _ in runs[on_device]) / len(runs[on_device])     # noqa: E731
+    r['nfe'], r['s_per_image'], r['bpd_mean'] = runs[False][0][1], mean(False), runs[False][0][2]
+    if device_loop:
+        r['nfe_device_loop'], r['s_per_image_device_loop'], r['bpd_mean_device_loop'] = runs[True][0][1], mean(True), runs[True][0][2]
+        r['device_vs_host'] = mean(True) / mean(False)
+        r['s_per_image_runs'] = {'host': [t for t, _, _ in runs[False]], 'device_loop': [t for t, _, _ in runs[True]]}
+
+
+def ode_sampler_line(precision, reps, full_reps):
+    """get_ode_sampler on both loops at the NCSN++-256 shape (SR3-160 is conditional; the ODE sampler is unconditional)"""
+    from conditional_score_diffusion_amd.sampling.unconditional import get_ode_sampler
+    model, sde, _ = ncsnpp256(precision)
+    B, S = 8, model.image_size
+    shape = (B, model.x_channels, S, S)
+    z = (torch.from_numpy(np.random.RandomState(1).standard_normal(shape).astype(np.float32)) * float(sde.sigma_max)).to(dev)
+    lab = torch.full((B,), float(np.log(3.7)), device=dev)
+    r = {'workload': 'ode sampler ncsnpp256', 'batch': B, 'precision': precision}
+    r['forward_ms'] = forward_ms(model, z, None, lab, reps)
+    runs = {False: [], True: []}
+    for _ in range(full_reps):
+        for on_device in (False, True):
+            fn = get_ode_sampler(sde, shape, denoise=False, eps=1e-5, device_loop=on_device)
+            dt, (x, nfe) = timed(lambda: fn(model, z=z))
+            runs[on_device].append((dt * 1e3 / nfe, int(nfe), x))
+    mean = lambda on_device: sum(t for t, _, _ in runs[on_device]) / len(runs[on_device])     # noqa: E731
+    r['nfe'], r['ms_per_evaluation'] = runs[False][0][1], mean(False)
+    r['nfe_device_loop'], r['ms_per_evaluation_device_loop'] = runs[True][0][1], mean(True)
+    r['device_vs_host'] = mean(True) / mean(False)
+    r['ms_per_evaluation_runs'] = {'host': [t for t, _, _ in runs[False]], 'device_loop': [t for t, _, _ in runs[True]]}
+    xh, xd = runs[False][0][2], runs[True][0][2]
+    r['sample_max_rel_diff'] = float((xh - xd).abs().max() / xh.abs().max())
+    print(json.dumps(r), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--shapes', default='sr3,ncsnpp256')
@@ -128,6 +187,8 @@ def main():
     ap.add_argument('--precision', default='fp16x3')
     ap.add_argument('--no-full', action='store_true', help='skip the full likelihood (nfe, seconds per image)')
     ap.add_argument('--rhs-only', type=int, default=0, metavar='N')
+    ap.add_argument('--device-loop', action='store_true', help='also time the device-resident RK45 loop, and the ODE sampler on both')
+    ap.add_argument('--full-reps', type=int, default=1, help='runs of the full likelihood / the ODE sampler per loop')
     a = ap.parse_args()
     if a.rhs_only:
         model, sde, cond = sr3(a.precision)
@@ -146,13 +207,11 @@ def main():
         r['bwd_input_ms'], r['bwd_full_ms'] = backward_ms(model, x, y, lab, a.reps)
         r['bwd_input_vs_full'] = r['bwd_input_ms'] / r['bwd_full_ms']
         if not a.no_full:
-            fn = (likelihood.get_conditional_likelihood_fn if cond else likelihood.get_likelihood_fn)(sde, lambda v: v)
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            bpd, _, nfe = fn(model, x, y, epsilon=e) if cond else fn(model, x, epsilon=e)
-            dt = time.perf_counter() - t0
-            r['nfe'], r['s_per_image'], r['bpd_mean'] = int(nfe), dt / B, float(bpd.mean())
+            full_likelihood(r, model, sde, cond, x, y, e, a.device_loop, a.full_reps)
         print(json.dumps(r), flush=True)
+        del model
+    if a.device_loop and not a.no_full:
+        ode_sampler_line(a.precision, a.reps, a.full_reps)
 
 
 if __name__ == '__main__':
