@@ -37,8 +37,9 @@ static int build_packed_layout(Net& n) {
     PackedConv pc;
     int rc;
     if (last && net_ns && taps == 9 && c1 == 0 && srcs.size() == 1 && srcs[0].layout == 0 && srcs[0].cout_off == 0 &&
-        (srcs[0].cin_src <= 0 || srcs[0].cin_src == c0) && pw16_taps_supported(c0, cout, net_ns)) {
-      // the network's last layer (nf -> 3 channels): one pointwise contraction to 27 tap-partial channels + a gather (conv_pw16.hip)
+        (srcs[0].cin_src <= 0 || srcs[0].cin_src == c0) && n.cfg.act == CSD_ACT_SWISH && pw16_taps_supported(c0, cout, net_ns)) {
+      // the network's last layer (nf -> 3 channels): one pointwise contraction to 27 tap-partial channels + a gather (conv_pw16.hip).
+      // SiLU networks only: it is the one activation pw16_kernel's prologue applies; any other head takes the ordinary 3x3 path below
       if ((rc = proto_conv(&pc.proto, c0, 0, pw16_taps_cout(cout), 1))) return rc;
       pc.ns = net_ns;
       pc.pw = true;

@@ -96,6 +96,9 @@ struct Builder {
       if (!norm || src1 != NONE || stride != 1 || up || pad != 1 || temb_col != NONE) {
         set_error("tap-partial conv on an unsupported layer"); rc = CSD_ERR_INVALID; return NONE;
       }
+      if (act != CSD_ACT_SWISH) {      // (pw16_kernel's prologue knows SiLU only: build_packed_layout keeps every other head off this form)
+        set_error("tap-partial conv: activation %d is not supported (SiLU only)", act); rc = CSD_ERR_INVALID; return NONE;
+      }
       Op o;
       o.kind = OP_CONV;
       o.cp = pc.proto;

@@ -83,15 +83,30 @@ def test_conv2d_fp16_mfma(B, Cin, Cout, H, ks, stride, up2, precision, tol):
 
 
 @pytest.mark.parametrize('B,C,H,G,act', [(2, 32, 20, 32, 'swish'), (3, 96, 10, 32, 'none'), (2, 288, 5, 32, 'swish'),
-                                         (1, 96, 160, 32, 'swish'), (2, 64, 8, 16, 'relu')])
+                                         (1, 96, 160, 32, 'swish'), (2, 64, 8, 16, 'relu'), (2, 288, 5, 32, 'lrelu'),
+                                         (2, 288, 5, 32, 'elu'), (3, 96, 16, 32, 'lrelu'), (3, 96, 16, 32, 'elu')])
 def test_groupnorm_act(B, C, H, G, act):
     from conditional_score_diffusion_amd import ops
     x = rnd(B, C, H, H, seed=4) * 3 + 0.7
     ga, be = 1 + 0.1 * rnd(C, seed=5), 0.1 * rnd(C, seed=6)
     ref = F.group_norm(x, G, ga, be, eps=1e-6)
-    ref = {'swish': F.silu, 'none': lambda v: v, 'relu': F.relu}[act](ref)
+    ref = {'swish': F.silu, 'none': lambda v: v, 'relu': F.relu, 'lrelu': lambda v: F.leaky_relu(v, 0.2), 'elu': F.elu}[act](ref)
     out = ops.groupnorm_act(x.to(dev()), ga.to(dev()), be.to(dev()), groups=G, eps=1e-6, act=act)
     assert rel(out, ref) < 5e-6
+
+
+def test_groupnorm_act_large_mean():
+    """mean 200, standard deviation 1: E[x^2] - E[x]^2 formed in fp32 would lose the variance (200^2 / 1 = 2^15.3 of fp32's 2^24) -
+    against a float64 group_norm, at test_groupnorm_act's bound"""
+    from conditional_score_diffusion_amd import ops
+    B, C, H, G = 2, 96, 16, 32
+    x = rnd(B, C, H, H, seed=4) + 200.0
+    ga, be = 1 + 0.1 * rnd(C, seed=5), 0.1 * rnd(C, seed=6)
+    ref = F.silu(F.group_norm(x.double(), G, ga.double(), be.double(), eps=1e-6))
+    out = ops.groupnorm_act(x.to(dev()), ga.to(dev()), be.to(dev()), groups=G, eps=1e-6, act='swish')
+    err = rel(out, ref)
+    print('groupnorm_act, mean 200 / std 1: %.3e' % err)
+    assert err < 5e-6
 
 
 @pytest.mark.parametrize('B,C,H', [(2, 64, 5), (2, 32, 10), (1, 192, 20), (2, 96, 16), (3, 288, 10), (2, 288, 5)])
@@ -119,13 +134,14 @@ def test_attention_peaked_softmax():
 
 
 @pytest.mark.parametrize('B,K,N,act', [(64, 384, 6336, 'swish'), (1, 96, 384, 'none'), (70, 300, 37, 'swish'), (3, 258, 16, 'none'),
-                                       (130, 7, 5, 'swish'), (5, 512, 130, 'relu')])
+                                       (130, 7, 5, 'swish'), (5, 512, 130, 'relu'), (70, 300, 37, 'lrelu'), (70, 300, 37, 'elu'),
+                                       (3, 258, 16, 'lrelu'), (3, 258, 16, 'elu')])
 def test_linear_ragged_shapes(B, K, N, act):
     """csd_linear (lane = sample, LDS-staged operands): batches over 64 (two sample blocks), K not a multiple of 4 (dword path) and of the
     256-wide chunk, N not a multiple of the 16 features of a workgroup, the input activation - against fp64"""
     from conditional_score_diffusion_amd import ops
     x, w, b = rnd(B, K, seed=K + B), rnd(N, K, seed=N) * (K ** -0.5), rnd(N, seed=3)
-    xa = {'swish': F.silu, 'relu': F.relu, 'none': (lambda t: t)}[act](x.double())
+    xa = {'swish': F.silu, 'relu': F.relu, 'none': (lambda t: t), 'lrelu': (lambda t: F.leaky_relu(t, 0.2)), 'elu': F.elu}[act](x.double())
     ref = xa @ w.double().t() + b.double()
     out = ops.linear(x.to(dev()), w.to(dev()), b.to(dev()), act_in=act)
     assert rel(out, ref) < 1e-5

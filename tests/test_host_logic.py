@@ -417,7 +417,24 @@ def _digest_configs():
     out['ddpm_no_resamp_conv'].model.csd_digest_no_resamp_conv = True       # (see _plan_digests)
     out['ddpm_unconditional'] = cases.make_config(name='ddpm', nf=32, ch_mult=(1, 2, 2, 2), attn_resolutions=(10,), image_size=80)
     out['ddpm_unconditional'].model.conditional = False
+    # networks that are not SiLU: no fused-prologue conv and no tap-partial head anywhere (build_packed_layout)
+    out['sr3_tiny_elu'] = cases.case_config('sr3_tiny')[0]
+    out['sr3_tiny_elu'].model.nonlinearity = 'elu'
+    out['ncsnpp_fourier_skip_relu'] = cases.make_ncsnpp_config(**cases.NCSNPP_CASES['ncsnpp_fourier_skip'][0])
+    out['ncsnpp_fourier_skip_relu'].model.nonlinearity = 'relu'
     return out
+
+
+def test_unknown_activation_raises_at_construction():
+    """config.model.nonlinearity outside swish / relu / lrelu / elu (models/layers.py:29-41) fails when the model is built, in both
+    families - never later, never with another activation in its place"""
+    from conditional_score_diffusion_amd.models import utils as mutils
+    import conditional_score_diffusion_amd.models.ncsnpp      # noqa: F401  (registers the model names)
+    for cfg in (cases.case_config('sr3_tiny')[0], cases.make_ncsnpp_config()):
+        for bad in ('gelu', 'none'):
+            cfg.model.nonlinearity = bad
+            with pytest.raises(NotImplementedError):
+                mutils.create_model(cfg)
 
 
 def _plan_digests():
