@@ -181,6 +181,12 @@ SIGNATURES = {
     'csd_ode_error_sumsq': (_i, [_vp, _vp, _vp, _i64, OdeCoef, _d, _d, _d, _i64, _vp, _vp, _vp]),
     'csd_ode_scaled_sumsq': (_i, [_vp, _vp, _d, _d, _vp, _d, _d, _i64, _vp, _vp, _vp]),
     'csd_ode_drift': (_i, [_vp, _vp, _i64, _vp, _vp, _vp, _i, _i64, _vp]),
+    'csd_conv3d_block_scratch_bytes': (_sz, [_i, _i]),
+    'csd_conv3d_block': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _f, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    'csd_avgpool3d_2_ndhwc': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    'csd_nearest_up2_3d_ndhwc': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    'csd_groupnorm_scale_shift_scratch_bytes': (_sz, [_i, _i, _i, _i]),
+    'csd_groupnorm_scale_shift': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp, _vp]),
 }
 
 

@@ -113,6 +113,83 @@ def conv3x3_block(x0, weight, bias=None, x1=None, nscale=None, nshift=None, temb
     return (y, stats) if want_stats else y
 
 
+def conv3d_block(x0, weight, bias=None, x1=None, nscale=None, nshift=None, act='swish', temb=None, res=None, out_scale=1.0,
+                 precision='fp16x3'):
+    """The 3-D ResnetBlock convolution with its prologue fused (models/layers.py:632-675 with dim = 3): y = (Conv3x3x3(act(x*nscale +
+    nshift)) + bias + temb[:, None, None, None, :] + res) * out_scale on channels-last fp32 tensors [B,D,H,W,C]; x = x0 (| x1: virtual
+    concat); weight [Cout, C0+C1, 3, 3, 3].  nscale = nshift = None: the convolution reads x as it is.  csd_conv3d_block."""
+    x0, weight = _c(x0, 'x0'), _c(weight, 'weight')
+    if x0.dim() != 5:
+        raise RuntimeError('conv3d_block: x0 %s is not [B, D, H, W, C]' % (tuple(x0.shape),))
+    B, D, H, W, C0 = x0.shape
+    C1 = 0
+    if x1 is not None:
+        x1 = _c(x1, 'x1')
+        if tuple(x1.shape[:4]) != (B, D, H, W):
+            raise RuntimeError('conv3d_block: x1 %s does not match x0 %s' % (tuple(x1.shape), tuple(x0.shape)))
+        C1 = x1.shape[4]
+    Cout = weight.shape[0]
+    if tuple(weight.shape) != (Cout, C0 + C1, 3, 3, 3):
+        raise RuntimeError('conv3d_block: weight %s does not match %d input channels' % (tuple(weight.shape), C0 + C1))
+    if precision not in _lib.PREC_IDS or act not in _lib.ACT_IDS:
+        raise ValueError('conv3d_block: unknown precision %r or activation %r' % (precision, act))
+    bias, nscale, nshift, temb, res = [None if t is None else _c(t, 't') for t in (bias, nscale, nshift, temb, res)]
+    for t, shp, name in ((bias, (Cout,), 'bias'), (nscale, (B, C0 + C1), 'nscale'), (nshift, (B, C0 + C1), 'nshift'),
+                         (res, (B, D, H, W, Cout), 'res')):
+        if t is not None and tuple(t.shape) != shp:
+            raise RuntimeError('conv3d_block: %s %s is not %s' % (name, tuple(t.shape), shp))
+    if temb is not None and (temb.dim() != 2 or temb.shape[0] != B):
+        raise RuntimeError('conv3d_block: temb %s is not [B, >= Cout]' % (tuple(temb.shape),))
+    if any(t is not None and t.device != x0.device for t in (weight, x1, bias, nscale, nshift, temb, res)):
+        raise RuntimeError('conv3d_block: every operand must be on one device')
+    y = torch.empty(B, D, H, W, Cout, dtype=torch.float32, device=x0.device)
+    sc = _scratch(lib().csd_conv3d_block_scratch_bytes(C0 + C1, Cout), x0.device)
+    check(lib().csd_conv3d_block(ptr(x0), ptr(x1), ptr(weight), ptr(bias), ptr(nscale), ptr(nshift), _lib.ACT_IDS[act], ptr(temb),
+                                 temb.shape[1] if temb is not None else 0, ptr(res), float(out_scale), ptr(y), B, C0, C1, Cout, D, H, W,
+                                 _lib.PREC_IDS[precision], ptr(sc), current_stream(x0.device)), 'conv3d_block')
+    return y
+
+
+def avg_pool3d_2(x):
+    """nn.AvgPool3d(2, 2) (models/layers.py:617) on a channels-last volume [B,D,H,W,C] -> [B,D/2,H/2,W/2,C]."""
+    x = _c(x, 'x')
+    B, D, H, W, C = x.shape
+    y = torch.empty(B, D // 2, H // 2, W // 2, C, dtype=torch.float32, device=x.device)
+    check(lib().csd_avgpool3d_2_ndhwc(ptr(x), ptr(y), B, D, H, W, C, current_stream(x.device)), 'avg_pool3d_2')
+    return y
+
+
+def nearest_up2_3d(x):
+    """F.interpolate(x, 2 * size, mode='nearest') (models/layers.py:601) on a channels-last volume [B,D,H,W,C]."""
+    x = _c(x, 'x')
+    B, D, H, W, C = x.shape
+    y = torch.empty(B, 2 * D, 2 * H, 2 * W, C, dtype=torch.float32, device=x.device)
+    check(lib().csd_nearest_up2_3d_ndhwc(ptr(x), ptr(y), B, D, H, W, C, current_stream(x.device)), 'nearest_up2_3d')
+    return y
+
+
+def groupnorm_scale_shift(x0, gamma, beta, x1=None, groups=32, eps=1e-6):
+    """GroupNorm statistics of x = x0 (| x1) on channels-last tensors [B, ..., C] without the normalised tensor: (nscale, nshift), each
+    [B, C0+C1] = rstd*gamma and beta - mean*rstd*gamma - the prologue operands of conv3d_block / conv3x3_block."""
+    x0, gamma, beta = _c(x0, 'x0'), _c(gamma, 'gamma'), _c(beta, 'beta')
+    B, C0 = x0.shape[0], x0.shape[-1]
+    S = x0.numel() // max(B * C0, 1)
+    C1 = 0
+    if x1 is not None:
+        x1 = _c(x1, 'x1')
+        C1 = x1.shape[-1]
+        if tuple(x1.shape[:-1]) != tuple(x0.shape[:-1]):
+            raise RuntimeError('groupnorm_scale_shift: x1 %s does not match x0 %s' % (tuple(x1.shape), tuple(x0.shape)))
+    if tuple(gamma.shape) != (C0 + C1,) or tuple(beta.shape) != (C0 + C1,):
+        raise RuntimeError('groupnorm_scale_shift: gamma / beta are not [%d]' % (C0 + C1))
+    nscale = torch.empty(B, C0 + C1, dtype=torch.float32, device=x0.device)
+    nshift = torch.empty_like(nscale)
+    sc = _scratch(lib().csd_groupnorm_scale_shift_scratch_bytes(B, C0 + C1, S, groups), x0.device)
+    check(lib().csd_groupnorm_scale_shift(ptr(x0), ptr(x1), ptr(gamma), ptr(beta), ptr(nscale), ptr(nshift), B, C0, C1, S, groups,
+                                          float(eps), ptr(sc), current_stream(x0.device)), 'groupnorm_scale_shift')
+    return nscale, nshift
+
+
 def attention(q, k, v):
     """softmax(q.k C^-1/2) v over H*W positions (models/layers.py:584-588)."""
     q, k, v = _c(q, 'q'), _c(k, 'k'), _c(v, 'v')

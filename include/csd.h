@@ -556,6 +556,36 @@ int csd_ode_scaled_sumsq(const double* u, const double* w, double alpha, double 
 int csd_ode_drift(const double* y, const float* h, int64_t net_stride, const double* a, const double* c, double* out, int B, int64_t D,
                   void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * 3-D operators of the ddpm3D score networks (csrc/conv3d.hip; reference models/ddpm3D.py:38-171 with models/layers.py:119-132 ddpm_conv3x3
+ * dim = 3, :593-629 Upsample / Downsample dim = 3, :632-675 ResnetBlockDDPM dim = 3).  Channels-last fp32 tensors [B, D, H, W, C].
+ * ---------------------------------------------------------------------------------------- */
+/* The 3-D counterpart of csd_conv3x3_block: y = (Conv3x3x3(act(x*nscale + nshift)) + bias + temb + res) * out_scale, stride 1, zero padding 1
+ * in all three dimensions.  x = x0 [B,D,H,W,C0] (| x1 [B,D,H,W,C1] or NULL with C1 = 0: virtual concat, no copy); weight in the
+ * reference's state_dict layout [Cout, C0+C1, 3, 3, 3]; bias [Cout] or NULL; nscale / nshift [B, C0+C1] (csd_groupnorm_scale_shift) or both
+ * NULL: the convolution reads x as it is and `act` is ignored (the stem, the shortcut Conv_2); act = CSD_ACT_*; temb [B, temb_stride] or
+ * NULL (column c of sample b is added to cout c); res [B,D,H,W,Cout] or NULL (added).  The padding is applied AFTER the prologue: a voxel
+ * outside the volume contributes exactly 0.  The result is bitwise repeatable and independent of the sample's position in the batch.
+ * precision: CSD_PREC_F16X3 (split-fp16 operands on v_mfma_f32_32x32x16_f16, fp32 accumulate) or CSD_PREC_F32 (the exact yardstick: one
+ * fp32 fmaf chain per output, swish with expf and a true division, not tuned); CSD_PREC_F16 / CSD_PREC_F16F8 return CSD_ERR_INVALID.
+ * Domain: any B, D, H, W >= 1 and Cout >= 1; with C1 = 0 any C0 >= 1 (C0 not a multiple of 16 runs on the direct fp32 kernel in both
+ * modes); with C1 > 0 both C0 and C1 multiples of 16; one sample of the widest tensor below 2 GiB.  Anything else returns
+ * CSD_ERR_INVALID and writes nothing.  scratch holds the packed weight: csd_conv3d_block_scratch_bytes(C0 + C1, Cout). */
+size_t csd_conv3d_block_scratch_bytes(int Cin, int Cout);
+int csd_conv3d_block(const float* x0, const float* x1, const float* weight, const float* bias, const float* nscale, const float* nshift,
+                     int act, const float* temb, int temb_stride, const float* res, float out_scale, float* y, int B, int C0, int C1,
+                     int Cout, int D, int H, int W, int precision, void* scratch, void* stream);
+/* nn.AvgPool3d(kernel_size=2, stride=2) (models/layers.py:617): x [B,D,H,W,C] -> out [B,D/2,H/2,W/2,C]; D, H, W even */
+int csd_avgpool3d_2_ndhwc(const float* x, float* out, int B, int D, int H, int W, int C, void* stream);
+/* F.interpolate(x, 2 * size, mode='nearest') on a volume (models/layers.py:601): x [B,D,H,W,C] -> out [B,2D,2H,2W,C] */
+int csd_nearest_up2_3d_ndhwc(const float* x, float* out, int B, int D, int H, int W, int C, void* stream);
+/* GroupNorm statistics without the normalised tensor: nscale / nshift [B, C0+C1] = rstd*gamma and beta - mean*rstd*gamma per
+ * (sample, channel) of x = x0 [B,S,C0] (| x1 [B,S,C1] or NULL with C1 = 0) over S positions - the prologue operands of csd_conv3d_block
+ * and csd_conv3x3_block.  C0 and C1 multiples of 4.  scratch: csd_groupnorm_scale_shift_scratch_bytes(B, C0+C1, S, groups). */
+size_t csd_groupnorm_scale_shift_scratch_bytes(int B, int C, int S, int groups);
+int csd_groupnorm_scale_shift(const float* x0, const float* x1, const float* gamma, const float* beta, float* nscale, float* nshift, int B,
+                              int C0, int C1, int S, int groups, float eps, void* scratch, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

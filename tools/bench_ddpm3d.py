@@ -1,0 +1,196 @@
+"""Side bench of the 3-D DDPM score network (models/ddpm3d.py, csrc/conv3d.hip) at the shape of the reference's MRI -> PET config
+(configs/ve/inverse_problems/MRI_to_PET/MRI_to_PET_slices3D.py): ``ddpm3D_paired``, B = 4, 2 x 96 x 96 x 16, nf 64, ch_mult (1, 1, 2, 2),
+2 residual blocks per level, swish, fp16x3.
+
+    python tools/bench_ddpm3d.py [--batch 4] [--warmup 2] [--repeats 5] [--evals 3] [--small]
+
+Writes profiles/ddpm3d_bench.json (``--out`` to change) and prints it:
+  network      evaluations per second: `repeats` windows of `evals` forwards each between device synchronisations, median and spread
+  classes      one extra forward with a device-event pair around every operator call, summed per kernel class (the event pairs serialise
+               the launches, so the classes add up to more than the untimed forward; shares are what to read)
+  layers       csd_conv3d_block (GroupNorm prologue + bias epilogue, weight pack included: it runs in every call) at the two dominant
+               layers, 64 -> 64 at 96 x 96 x 16 and 128 -> 128 at 24 x 24 x 4, as achieved TFLOP/s = 2 * 27 * Cin * Cout * voxels * B / time;
+               and, as a yardstick outside the code under test, torch's own fp32 F.conv3d (channels-first, no prologue) at the same two
+               layers on the same GPU in the same run, the two alternating.
+``--small`` runs the same code at a toy shape (a rehearsal of the script; its numbers measure overheads).
+Needs the GPU: there is no CPU path.
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import torch
+import torch.nn.functional as F
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, 'oracle')]
+from conditional_score_diffusion_amd import ops  # noqa: E402
+from conditional_score_diffusion_amd.config_dict import ConfigDict  # noqa: E402
+from conditional_score_diffusion_amd.models import ddpm3d  # noqa: E402
+from conditional_score_diffusion_amd.models import utils as mutils  # noqa: E402
+
+
+def make_config(vol, nf, ch_mult, nrb):
+    c = ConfigDict()
+    c.training = ConfigDict(continuous=True, sde='vesde')
+    c.data = ConfigDict(centered=False, shape_x=[1] + list(vol), shape_y=[1] + list(vol), num_channels=2)
+    c.model = ConfigDict(name='ddpm3D_paired', nf=nf, ch_mult=tuple(ch_mult), num_res_blocks=nrb, dropout=0.1, resamp_with_conv=False,
+                         conditional=True, nonlinearity='swish', input_channels=2, output_channels=2, csd_precision='fp16x3')
+    return c
+
+
+def conv_flops(model, B, vol):
+    """2 * MACs of every 3x3x3 convolution of one evaluation"""
+    total = 0.0
+    ext = list(vol)
+    lvl = 0
+    for kind, a in model._mods:
+        v = (ext[0] >> lvl) * (ext[1] >> lvl) * (ext[2] >> lvl)
+        if kind == 'conv':
+            total += 2.0 * 27 * a['cin'] * a['cout'] * v * B
+        elif kind == 'res':
+            n = a['cin'] * a['cout'] + a['cout'] * a['cout'] + (a['cin'] * a['cout'] if a['cin'] != a['cout'] else 0)
+            total += 2.0 * 27 * n * v * B
+        elif kind == 'down':
+            lvl += 1
+        elif kind == 'up':
+            lvl -= 1
+    return total
+
+
+class ClassTimer:
+    """device-event pairs around the operator calls of models/ddpm3d.py, summed per kernel class"""
+
+    CLASSES = {'conv3d_block': 'conv3d_block', 'groupnorm_scale_shift': 'gn_stats', 'avg_pool3d_2': 'resample', 'nearest_up2_3d': 'resample',
+               'linear': 'embedding', 'timestep_embedding': 'embedding', 'axpby': 'other'}
+
+    def __init__(self):
+        self.pairs = []
+
+    def wrap(self, name, fn):
+        def timed(*a, **k):
+            cls = self.CLASSES[name]
+            if name == 'conv3d_block' and a[0].shape[-1] % 16:
+                cls = 'conv3d_block_direct'
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            out = fn(*a, **k)
+            e1.record()
+            self.pairs.append((cls, e0, e1))
+            return out
+        return timed
+
+    def run(self, fn):
+        saved = {n: getattr(ops, n) for n in self.CLASSES}
+        try:
+            for n, f in saved.items():
+                setattr(ops, n, self.wrap(n, f))
+            t0 = torch.cuda.Event(enable_timing=True)
+            t1 = torch.cuda.Event(enable_timing=True)
+            t0.record()
+            fn()
+            t1.record()
+        finally:
+            for n, f in saved.items():
+                setattr(ops, n, f)
+        torch.cuda.synchronize()
+        ms, calls = {}, {}
+        for cls, e0, e1 in self.pairs:
+            ms[cls] = ms.get(cls, 0.0) + e0.elapsed_time(e1)
+            calls[cls] = calls.get(cls, 0) + 1
+        return {'total_ms': t0.elapsed_time(t1), 'classes': {c: {'ms': ms[c], 'calls': calls[c]} for c in sorted(ms)}}
+
+
+def timed_windows(fn, warmup, repeats, inner):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    out = []
+    for _ in range(repeats):
+        t0 = time.perf_counter()
+        for _ in range(inner):
+            fn()
+        torch.cuda.synchronize()
+        out.append((time.perf_counter() - t0) / inner)
+    return out
+
+
+def layer_bench(B, vol, C, warmup, repeats, dev):
+    """csd_conv3d_block against torch's fp32 F.conv3d at one layer, alternating windows"""
+    g = torch.Generator(device='cpu').manual_seed(0)
+    x = torch.randn(B, *vol, C, generator=g).to(dev)
+    w = (torch.randn(C, C, 3, 3, 3, generator=g) * (2.0 / (27 * 2 * C)) ** 0.5).to(dev)
+    b = torch.zeros(C, device=dev)
+    ns, nh = torch.ones(B, C, device=dev), torch.zeros(B, C, device=dev)
+    xc = x.permute(0, 4, 1, 2, 3).contiguous()
+    flops = 2.0 * 27 * C * C * vol[0] * vol[1] * vol[2] * B
+    inner = max(1, int(2e12 / flops / 10))          # windows of >= ~0.1 s at a few TFLOP/s, more at speed
+    ours = lambda: ops.conv3d_block(x, w, b, nscale=ns, nshift=nh, act='swish', precision='fp16x3')      # noqa: E731
+    theirs = lambda: F.conv3d(xc, w, b, padding=1)                                                        # noqa: E731
+    t_o, t_t = [], []
+    for f in (ours, theirs):
+        for _ in range(warmup):
+            f()
+    torch.cuda.synchronize()
+    for _ in range(repeats):
+        t_o += timed_windows(ours, 0, 1, inner)
+        t_t += timed_windows(theirs, 0, 1, inner)
+    mo, mt = statistics.median(t_o), statistics.median(t_t)
+    return {'layer': '%d->%d at %dx%dx%d, B=%d' % (C, C, vol[0], vol[1], vol[2], B), 'gflop': flops / 1e9, 'calls_per_window': inner,
+            'conv3d_block_fp16x3': {'ms': mo * 1e3, 'ms_min': min(t_o) * 1e3, 'ms_max': max(t_o) * 1e3, 'tflops': flops / mo / 1e12},
+            'torch_fp32_conv3d': {'ms': mt * 1e3, 'ms_min': min(t_t) * 1e3, 'ms_max': max(t_t) * 1e3, 'tflops': flops / mt / 1e12},
+            'conv3d_block_over_torch': mt / mo}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--batch', type=int, default=4)
+    ap.add_argument('--warmup', type=int, default=2)
+    ap.add_argument('--repeats', type=int, default=5)
+    ap.add_argument('--evals', type=int, default=3)
+    ap.add_argument('--small', action='store_true')
+    ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'ddpm3d_bench.json'))
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit('bench_ddpm3d.py needs the MI355X: there is no CPU path')
+    dev = torch.device('cuda:0')
+    vol, nf, ch_mult, nrb = ((12, 12, 8), 32, (1, 2), 1) if args.small else ((96, 96, 16), 64, (1, 1, 2, 2), 2)
+    B = args.batch
+    torch.manual_seed(0)
+    model = mutils.create_model(make_config(vol, nf, ch_mult, nrb))
+    assert isinstance(model, ddpm3d.DDPM3D_paired)
+    with torch.no_grad():       # the reference zero-initialises Conv_1 and the head: give them weights so that nothing is degenerate
+        for k, v in model.state_dict().items():
+            if v.dim() == 5:
+                v.copy_((torch.rand_like(v) * 2 - 1) * (3.0 / (27 * (v.shape[0] + v.shape[1]) / 2)) ** 0.5)
+    model = model.to(dev).eval()
+    x = (5.0 * torch.randn(B, 1, *vol)).to(dev)
+    y = torch.rand(B, 1, *vol).to(dev)
+    labels = torch.linspace(3., 420.5, B).to(dev)
+    fwd = lambda: model({'x': x, 'y': y}, labels)         # noqa: E731
+    out = fwd()
+    torch.cuda.synchronize()
+    assert all(torch.isfinite(v).all() for v in out.values())
+    win = timed_windows(fwd, args.warmup, args.repeats, args.evals)
+    med = statistics.median(win)
+    flops = conv_flops(model, B, vol)
+    res = {'device': torch.cuda.get_device_name(0), 'model': 'ddpm3D_paired', 'precision': 'fp16x3', 'batch': B, 'volume': list(vol), 'nf': nf,
+           'ch_mult': list(ch_mult), 'num_res_blocks': nrb, 'small': bool(args.small),
+           'network': {'evals_per_s': 1.0 / med, 'volumes_per_s': B / med, 'ms_per_eval': med * 1e3, 'ms_min': min(win) * 1e3,
+                       'ms_max': max(win) * 1e3, 'windows': len(win), 'evals_per_window': args.evals, 'conv_gflop_per_eval': flops / 1e9,
+                       'conv_tflops_end_to_end': flops / med / 1e12},
+           'profile_pass': ClassTimer().run(fwd)}
+    lv = [((12, 12, 8), 32), ((6, 6, 4), 64)] if args.small else [((96, 96, 16), 64), ((24, 24, 4), 128)]
+    res['layers'] = [layer_bench(B, v, C, args.warmup, args.repeats, dev) for v, C in lv]
+    res['torch'] = torch.__version__
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, 'w') as f:
+        json.dump(res, f, indent=1)
+    print(json.dumps(res))
+
+
+if __name__ == '__main__':
+    main()
