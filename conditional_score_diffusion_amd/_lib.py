@@ -185,6 +185,10 @@ SIGNATURES = {
     'csd_conv3d_block': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _f, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     'csd_avgpool3d_2_ndhwc': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
     'csd_nearest_up2_3d_ndhwc': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    'csd_conv3d_wgrad_scratch_bytes': (_sz, [_i, _i, _i, _i, _i, _i, _i]),
+    'csd_conv3d_wgrad': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    'csd_conv3d_dgrad_scale_scratch_bytes': (_sz, [_i]),
+    'csd_conv3d_dgrad_scale': (_i, [_vp, _vp, _vp, _vp, _i, _i64, _i, _vp, _vp]),
     'csd_groupnorm_scale_shift_scratch_bytes': (_sz, [_i, _i, _i, _i]),
     'csd_groupnorm_scale_shift': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp, _vp]),
 }

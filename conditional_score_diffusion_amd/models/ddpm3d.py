@@ -21,8 +21,17 @@ Refused, with the reason (never a silent fallback):
                               dimensions: a conv2d on a 5-D tensor)
   ``conditional=False``       the reference raises NameError (its module list is only created under ``if conditional``)
   an odd extent at a pooled level, precisions other than fp32 / fp16x3 (ValueError)
-  training mode and input gradients: training, backward and likelihood of the 3-D networks are not provided
+  training mode and input gradients on CPU tensors (there is no CPU path); the likelihood of the 3-D networks is not provided
 Sampling runs on the step-by-step predictor / corrector loop (``sampling.fused.fusable`` is False for these classes).
+
+Training and input gradients (GPU tensors): in training mode, and in eval mode when ``x.requires_grad`` under autograd, the forward is
+the differentiable, operator-granular one (``_grad_forward``): the layers of ResnetBlockDDPM as grad_ops_3d / grad_ops autograd nodes
+(GroupNorm + act -> Conv_0 -> + Dense_0(act(temb)) -> GroupNorm + act -> Dropout_0 -> Conv_1, + the shortcut), whose backward passes
+are HIP kernels: csd_conv3d_wgrad (split bf16 / fp32), the scale-invariant data gradient on csd_conv3d_block,
+csd_groupnorm_act_backward_nhwc, the pooling / upsampling adjoints.  The up path's concatenation is a ``torch.cat`` there (data
+movement; autograd splits the gradient), the boundary permutes stay torch.  Dropout masks are a pure function of the Philox key
+``dropout_seed`` and the stream id ``_train_calls << 16 | index`` (the scheme of ddpm.py's operator path); dropout is off in eval
+mode.  For the paired classes only ``x`` takes a gradient.  The inference forward is not touched by any of this.
 """
 import os
 
@@ -72,6 +81,9 @@ class DDPM3D(nn.Module):
         self.output_channels = m.output_channels
         if nf % 32:
             raise ValueError('ddpm3D: nf = %d is not divisible into the 32 GroupNorm groups' % nf)
+        self._dropout = float(get('dropout', 0.0) or 0.0)
+        self._train_calls = 0
+        self.dropout_seed = int(getattr(config, 'seed', 0) or 0)   # Philox key of the dropout masks
 
         # ---- module list, in the order of DDPM3D.__init__ (models/ddpm3D.py:56-105) ----
         mods = [('linear', dict(cin=nf, cout=nf * 4)), ('linear', dict(cin=nf * 4, cout=nf * 4)),
@@ -155,10 +167,13 @@ class DDPM3D(nn.Module):
 
     # ---- forward: DDPM3D.forward (models/ddpm3D.py:107-171) ----
     def forward(self, x, labels):
-        if self.training:
-            raise NotImplementedError('ddpm3D: training mode is not provided (no backward of the 3-D operators); call model.eval()')
-        if torch.is_grad_enabled() and x.requires_grad:
-            raise NotImplementedError('ddpm3D: input gradients (and the likelihood built on them) are not provided')
+        want_grad = torch.is_grad_enabled() and x.requires_grad
+        if (self.training or want_grad) and not x.is_cuda:
+            if self.training:
+                raise NotImplementedError('ddpm3D: training mode is not provided on CPU tensors (the 3-D backward operators are HIP kernels, '
+                                          'there is no CPU path); move the model and the batch to the GPU, or call model.eval()')
+            raise NotImplementedError('ddpm3D: input gradients are not provided on CPU tensors (the 3-D backward operators are HIP '
+                                      'kernels, there is no CPU path)')
         if x.dim() != 5 or x.shape[1] != self.input_channels:
             raise ValueError('ddpm3D: input %s is not [B, %d, D, H, W]' % (tuple(x.shape), self.input_channels))
         ext = tuple(x.shape[2:])
@@ -168,6 +183,8 @@ class DDPM3D(nn.Module):
         require_gpu_tensor(x, 'x')
         require_gpu_tensor(labels, 'labels')
         mods, nodes = self._mods, self.all_modules
+        if (self.training and torch.is_grad_enabled()) or want_grad:
+            return self._grad_forward(x, labels)
         with torch.no_grad():
             temb = ops.timestep_embedding(labels.contiguous().float(), self.nf)
             temb = ops.linear(temb, nodes[0].weight, nodes[0].bias)
@@ -203,6 +220,64 @@ class DDPM3D(nn.Module):
             i += 1
             assert i == len(nodes)
             return h.permute(0, 4, 1, 2, 3).contiguous()                 # NDHWC -> NCDHW
+
+
+    # ---- the differentiable forward: training mode, or eval mode with x.requires_grad ----
+    def _grad_forward(self, x, labels):
+        """The forward above as autograd nodes (grad_ops_3d / grad_ops): same layers, same kernels for the convolutions (without the
+        fused prologue: GroupNorm + act is its own node, whose output the weight gradient needs), dropout in training mode."""
+        from .. import grad_ops_3d as G
+        mods, nodes, p, act = self._mods, self.all_modules, self.precision, self.act
+        drop_p = self._dropout if self.training else 0.0
+        self._train_calls += 1
+        drop = [0]
+
+        def res(node, a, h, temb):
+            t = G.groupnorm_act(h, node.GroupNorm_0.weight, node.GroupNorm_0.bias, act=act)
+            t = G.conv3d(t, node.Conv_0.weight, node.Conv_0.bias, p)
+            t = G.bias_add(t, G.linear(temb, node.Dense_0.weight, node.Dense_0.bias, act_in=act))
+            t = G.groupnorm_act(t, node.GroupNorm_1.weight, node.GroupNorm_1.bias, act=act)
+            drop[0] += 1
+            t = G.dropout(t, drop_p, self.dropout_seed, (self._train_calls << 16) + drop[0])
+            t = G.conv3d(t, node.Conv_1.weight, node.Conv_1.bias, p)
+            if a['cin'] != a['cout']:
+                h = G.conv3d(h, node.Conv_2.weight, node.Conv_2.bias, p)
+            return G.axpby(h, t)
+
+        temb = ops.timestep_embedding(labels.contiguous().float(), self.nf)
+        temb = G.linear(temb, nodes[0].weight, nodes[0].bias)
+        temb = G.linear(temb, nodes[1].weight, nodes[1].bias, act_in=act)
+        h = x.float().permute(0, 2, 3, 4, 1).contiguous()                # NCDHW -> NDHWC (1 or 2 channels)
+        if not self.centered:
+            h = G.axpby(h, None, alpha=2.0, gamma=-1.0)
+        i = 2
+        hs = [G.conv3d(h, nodes[i].weight, nodes[i].bias, p)]
+        i += 1
+        for i_level in range(self.num_resolutions):
+            for _ in range(self.num_res_blocks):
+                hs.append(res(nodes[i], mods[i][1], hs[-1], temb))
+                i += 1
+            if i_level != self.num_resolutions - 1:
+                hs.append(G.avg_pool3d_2(hs[-1]))
+                i += 1
+        h = hs[-1]
+        for _ in range(2):
+            h = res(nodes[i], mods[i][1], h, temb)
+            i += 1
+        for i_level in reversed(range(self.num_resolutions)):
+            for _ in range(self.num_res_blocks + 1):
+                h = res(nodes[i], mods[i][1], torch.cat([h, hs.pop()], dim=-1), temb)      # data movement; autograd splits the gradient
+                i += 1
+            if i_level != 0:
+                h = G.nearest_up2_3d(h)
+                i += 1
+        assert not hs
+        h = G.groupnorm_act(h, nodes[i].weight, nodes[i].bias, act=act)
+        i += 1
+        h = G.conv3d(h, nodes[i].weight, nodes[i].bias, p)
+        i += 1
+        assert i == len(nodes)
+        return h.permute(0, 4, 1, 2, 3).contiguous()                     # NDHWC -> NCDHW
 
 
 class DDPM3D_paired(DDPM3D):

@@ -68,6 +68,8 @@ class Trainer:
         config, model, sde = self.config, self.model, self.sde
         t = config.training
         conditional = isinstance(sde, dict) or model.__class__.__name__ != 'DDPM' and getattr(model, 'y_channels', 0) > 0
+        # the 3-D classes take {'x', 'y'} by their class (they have no y_channels): conditional for the paired ones, not for ddpm3D
+        conditional = conditional or model.__class__.__name__ in ('DDPM3D_paired', 'DDPM3D_paired_SR3')
         self.loss_fn = losses.get_general_sde_loss_fn(sde, True, conditional=conditional, reduce_mean=t.reduce_mean,
                                                       continuous=t.continuous, likelihood_weighting=t.likelihood_weighting)
         self.eval_loss_fn = losses.get_general_sde_loss_fn(sde, False, conditional=conditional, reduce_mean=t.reduce_mean,

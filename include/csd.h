@@ -575,6 +575,28 @@ size_t csd_conv3d_block_scratch_bytes(int Cin, int Cout);
 int csd_conv3d_block(const float* x0, const float* x1, const float* weight, const float* bias, const float* nscale, const float* nshift,
                      int act, const float* temb, int temb_stride, const float* res, float out_scale, float* y, int B, int C0, int C1,
                      int Cout, int D, int H, int W, int precision, void* scratch, void* stream);
+/* Weight gradient of csd_conv3d_block's convolution: dw[co][ci][kd][kh][kw] = sum over b and voxels v of dy[b, v, co] * a[b, v + tap, ci],
+ * a [B,D,H,W,Cin] (the convolution's input AFTER its prologue), dy [B,D,H,W,Cout], channels-last fp32; dw [Cout, Cin, 3, 3, 3] (the
+ * reference's state_dict layout, overwritten).  Zero padding 1, stride 1: a voxel outside the volume contributes exactly 0 (masked).
+ * precision: CSD_PREC_F16X3 = split-bf16 operands on v_mfma_f32_32x32x16_bf16 (hi = truncated bf16, lo = bf16(x - hi), products
+ * hi*hi + hi*lo + lo*hi, fp32 accumulate: no exponent-range limit, unlike the forward's fp16 halves); CSD_PREC_F32 = the exact yardstick
+ * (one fp32 fmaf chain per weight and K split, not tuned).  Rule for thin layers: with min(Cin, Cout) < 8 (the 1- / 2-channel stem and
+ * head) CSD_PREC_F16X3 runs the fp32 kernel too - a 32 x 32 MFMA tile would be at least 75 % padding.
+ * K splits are runs of voxels of ONE sample, their number depends on the volume and the channel counts only, and they are summed in
+ * fp64 in split order: no atomics, bitwise repeatable, and a sample's contribution does not depend on B or on the other samples.
+ * Domain: any B, D, H, W >= 1, any Cin, Cout >= 1 (one sample of the widest tensor below 2 GiB); anything else, another precision or a
+ * null pointer returns CSD_ERR_INVALID and writes nothing.  scratch: csd_conv3d_wgrad_scratch_bytes(...) device bytes (0 = invalid). */
+size_t csd_conv3d_wgrad_scratch_bytes(int B, int Cin, int Cout, int D, int H, int W, int precision);
+int csd_conv3d_wgrad(const float* a, const float* dy, float* dw, int B, int Cin, int Cout, int D, int H, int W, int precision,
+                     void* scratch, void* stream);
+/* Range-safe data gradient dx = csd_conv3d_block(dy; flip(W)^T): the forward kernel's fp16 hi | lo operands lose their lo half below
+ * ~6e-5, where loss gradients live.  rowscale[b] = 2^(4 - floor(log2 max|dy_b|)) (1 for an all-zero or non-finite sample), and
+ * nscale[b][c] = rowscale[b], nshift[b][c] = 0 for c < C are csd_conv3d_block's prologue operands with act = none: an EXACT multiply in
+ * its staging that puts max|dy_b| into [16, 32).  csd_scale_rows(dx, dx, rowscale, divide = 1) undoes it exactly.
+ * dy [B, per_sample]; scratch: csd_conv3d_dgrad_scale_scratch_bytes(B). */
+size_t csd_conv3d_dgrad_scale_scratch_bytes(int B);
+int csd_conv3d_dgrad_scale(const float* dy, float* rowscale, float* nscale, float* nshift, int B, int64_t per_sample, int C, void* scratch,
+                           void* stream);
 /* nn.AvgPool3d(kernel_size=2, stride=2) (models/layers.py:617): x [B,D,H,W,C] -> out [B,D/2,H/2,W/2,C]; D, H, W even */
 int csd_avgpool3d_2_ndhwc(const float* x, float* out, int B, int D, int H, int W, int C, void* stream);
 /* F.interpolate(x, 2 * size, mode='nearest') on a volume (models/layers.py:601): x [B,D,H,W,C] -> out [B,2D,2H,2W,C] */

@@ -12,6 +12,11 @@ Writes profiles/ddpm3d_bench.json (``--out`` to change) and prints it:
                layers, 64 -> 64 at 96 x 96 x 16 and 128 -> 128 at 24 x 24 x 4, as achieved TFLOP/s = 2 * 27 * Cin * Cout * voxels * B / time;
                and, as a yardstick outside the code under test, torch's own fp32 F.conv3d (channels-first, no prologue) at the same two
                layers on the same GPU in the same run, the two alternating.
+``--train`` measures training instead and writes it under the key ``training`` of the same file (the other keys are kept):
+  steps        Trainer.train_step (loss, backward on the grad_ops_3d operators, clip + Adam + EMA) of ``ddpm3D_paired`` with the two-SDE
+               loss at B = 2 (``--batch`` is ignored), steps per second over `repeats` windows of `evals` steps
+  wgrad        csd_conv3d_wgrad (split bf16) at the same two layers as achieved TFLOP/s = 2 * 27 * Cin * Cout * voxels * B / time, beside
+               torch's own fp32 conv3d weight gradient (torch.nn.grad.conv3d_weight, channels-first), the two alternating
 ``--small`` runs the same code at a toy shape (a rehearsal of the script; its numbers measure overheads).
 Needs the GPU: there is no CPU path.
 """
@@ -145,6 +150,66 @@ def layer_bench(B, vol, C, warmup, repeats, dev):
             'conv3d_block_over_torch': mt / mo}
 
 
+def wgrad_bench(B, vol, C, warmup, repeats, dev):
+    """csd_conv3d_wgrad (split bf16) against torch's fp32 conv3d weight gradient at one layer, alternating windows"""
+    from conditional_score_diffusion_amd import grad_ops_3d as G
+    g = torch.Generator(device='cpu').manual_seed(0)
+    a = torch.randn(B, *vol, C, generator=g).to(dev)
+    dy = torch.randn(B, *vol, C, generator=g).to(dev)
+    ac, dyc = a.permute(0, 4, 1, 2, 3).contiguous(), dy.permute(0, 4, 1, 2, 3).contiguous()
+    flops = 2.0 * 27 * C * C * vol[0] * vol[1] * vol[2] * B
+    inner = max(1, int(2e12 / flops / 10))
+    ours = lambda: G.conv3d_wgrad(a, dy, 'fp16x3')                                                      # noqa: E731
+    theirs = lambda: torch.nn.grad.conv3d_weight(ac, (C, C, 3, 3, 3), dyc, padding=1)                  # noqa: E731
+    t_o, t_t = [], []
+    for f in (ours, theirs):
+        for _ in range(warmup):
+            f()
+    torch.cuda.synchronize()
+    for _ in range(repeats):
+        t_o += timed_windows(ours, 0, 1, inner)
+        t_t += timed_windows(theirs, 0, 1, inner)
+    mo, mt = statistics.median(t_o), statistics.median(t_t)
+    return {'layer': '%d->%d at %dx%dx%d, B=%d' % (C, C, vol[0], vol[1], vol[2], B), 'gflop': flops / 1e9, 'calls_per_window': inner,
+            'conv3d_wgrad_split_bf16': {'ms': mo * 1e3, 'ms_min': min(t_o) * 1e3, 'ms_max': max(t_o) * 1e3, 'tflops': flops / mo / 1e12},
+            'torch_fp32_conv3d_weight': {'ms': mt * 1e3, 'ms_min': min(t_t) * 1e3, 'ms_max': max(t_t) * 1e3, 'tflops': flops / mt / 1e12},
+            'conv3d_wgrad_over_torch': mt / mo}
+
+
+def train_bench(args, dev):
+    from conditional_score_diffusion_amd import sde_lib, train
+    vol, nf, ch_mult, nrb = ((12, 12, 8), 32, (1, 2), 1) if args.small else ((96, 96, 16), 64, (1, 1, 2, 2), 2)
+    B = 2
+    cfg = make_config(vol, nf, ch_mult, nrb)
+    cfg.training.likelihood_weighting = cfg.training.reduce_mean = True
+    cfg.model.ema_rate = 0.999
+    cfg.model.num_scales, cfg.model.sigma_min_y, cfg.model.sigma_max_y = 1000, 0.01, 1.
+    cfg.optim = ConfigDict(weight_decay=0, optimizer='Adam', lr=2e-4, beta1=0.9, eps=1e-8, warmup=100, grad_clip=1)
+    cfg.seed = 42
+    torch.manual_seed(0)
+    model = mutils.create_model(cfg)
+    with torch.no_grad():
+        for k, v in model.state_dict().items():
+            if v.dim() == 5:
+                v.copy_((torch.rand_like(v) * 2 - 1) * (3.0 / (27 * (v.shape[0] + v.shape[1]) / 2)) ** 0.5)
+    model = model.to(dev)
+    sde = {'x': sde_lib.cVESDE(0.01, 30., 1000), 'y': sde_lib.VESDE(0.01, 1., 1000)}
+    tr = train.Trainer(cfg, model, sde)
+    batch = (torch.rand(B, 1, *vol).to(dev), torch.rand(B, 1, *vol).to(dev))
+    losses = []
+    step = lambda: losses.append(tr.train_step(batch))      # noqa: E731
+    win = timed_windows(step, args.warmup, args.repeats, args.evals)
+    vals = [float(v) for v in losses]
+    assert all(v == v and abs(v) != float('inf') for v in vals), vals
+    med = statistics.median(win)
+    lv = [((12, 12, 8), 32), ((6, 6, 4), 64)] if args.small else [((96, 96, 16), 64), ((24, 24, 4), 128)]
+    return {'device': torch.cuda.get_device_name(0), 'model': 'ddpm3D_paired', 'precision': 'fp16x3', 'batch': B, 'volume': list(vol), 'nf': nf,
+            'ch_mult': list(ch_mult), 'num_res_blocks': nrb, 'small': bool(args.small), 'dropout': 0.1,
+            'steps': {'steps_per_s': 1.0 / med, 'ms_per_step': med * 1e3, 'ms_min': min(win) * 1e3, 'ms_max': max(win) * 1e3, 'windows': len(win),
+                      'steps_per_window': args.evals, 'first_loss': vals[0], 'last_loss': vals[-1]},
+            'wgrad': [wgrad_bench(B, v, C, args.warmup, args.repeats, dev) for v, C in lv], 'torch': torch.__version__}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--batch', type=int, default=4)
@@ -152,11 +217,23 @@ def main():
     ap.add_argument('--repeats', type=int, default=5)
     ap.add_argument('--evals', type=int, default=3)
     ap.add_argument('--small', action='store_true')
+    ap.add_argument('--train', action='store_true')
     ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'ddpm3d_bench.json'))
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit('bench_ddpm3d.py needs the MI355X: there is no CPU path')
     dev = torch.device('cuda:0')
+    if args.train:
+        res = {}
+        if os.path.exists(args.out):
+            with open(args.out) as f:
+                res = json.load(f)
+        res['training'] = train_bench(args, dev)
+        os.makedirs(os.path.dirname(args.out), exist_ok=True)
+        with open(args.out, 'w') as f:
+            json.dump(res, f, indent=1)
+        print(json.dumps(res['training']))
+        return
     vol, nf, ch_mult, nrb = ((12, 12, 8), 32, (1, 2), 1) if args.small else ((96, 96, 16), 64, (1, 1, 2, 2), 2)
     B = args.batch
     torch.manual_seed(0)
