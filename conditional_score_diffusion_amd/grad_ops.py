@@ -27,7 +27,7 @@ from ._lib import check, current_stream, lib, ptr
 
 def _sum_inner(x, rows):
     x = x.contiguous()
-    out = torch.empty(rows, dtype=torch.float32, device=x.device)
+    out = ops._out(rows, torch.float32, x.device)
     check(lib().csd_sum_inner(ptr(x), ptr(out), rows, x.numel() // rows, current_stream(x.device)), 'sum_inner')
     return out
 
@@ -35,14 +35,14 @@ def _sum_inner(x, rows):
 def _sum_rows(x):
     x = x.contiguous()
     R, C = x.shape
-    out = torch.empty(C, dtype=torch.float32, device=x.device)
+    out = ops._out(C, torch.float32, x.device)
     check(lib().csd_sum_rows(ptr(x), ptr(out), R, C, current_stream(x.device)), 'sum_rows')
     return out
 
 
 def _act(x, act, dy=None):
     x = x.contiguous()
-    out = torch.empty_like(x)
+    out = ops._out(x.shape, x.dtype, x.device)
     check(lib().csd_act(ptr(x), ptr(dy.contiguous()) if dy is not None else None, ptr(out), _lib.ACT_IDS[act], x.numel(),
                         current_stream(x.device)), 'act')
     return out
@@ -50,7 +50,7 @@ def _act(x, act, dy=None):
 
 def _mul(a, b):
     a, b = a.contiguous(), b.contiguous()
-    out = torch.empty_like(a)
+    out = ops._out(a.shape, a.dtype, a.device)
     check(lib().csd_mul(ptr(a), ptr(b), ptr(out), a.numel(), current_stream(a.device)), 'mul')
     return out
 
@@ -91,7 +91,7 @@ class _Conv2d(torch.autograd.Function):
                     ones = torch.ones(2, 2, dtype=torch.float32, device=dy.device)
                     dx = ops._upfirdn2d_raw(dx, ones, (1, 1), (2, 2), (0, 0, 0, 0))
         if ctx.needs_input_grad[1]:
-            dw = torch.empty_like(weight)
+            dw = ops._out(weight.shape, weight.dtype, weight.device)
             sc = ops._scratch(lib().csd_conv_wgrad_scratch_bytes(B, Cin, Cout, H, W, k, stride, int(up2)), x.device)
             check(lib().csd_conv2d_wgrad_ex(ptr(x), ptr(dy), ptr(dw), B, Cin, Cout, H, W, k, stride, 1 if dpad else 0, int(up2),
                                             0 if precision == 'fp32' else 4, ptr(sc), current_stream(x.device)), 'conv2d_wgrad')
@@ -123,9 +123,9 @@ class _GroupNormAct(torch.autograd.Function):
         groups, eps, act = ctx.cfg
         dy = dy.contiguous()
         B, C, H, W = x.shape
-        dx = torch.empty_like(x)
-        dg = torch.empty(B, C, dtype=torch.float32, device=x.device)
-        db = torch.empty(B, C, dtype=torch.float32, device=x.device)
+        dx = ops._out(x.shape, x.dtype, x.device)
+        dg = ops._out((B, C), torch.float32, x.device)
+        db = ops._out((B, C), torch.float32, x.device)
         check(lib().csd_groupnorm_act_backward(ptr(x), ptr(gamma), ptr(beta), ptr(dy), ptr(dx), ptr(dg), ptr(db), B, C, H, W,
                                                groups, eps, _lib.ACT_IDS[act], current_stream(x.device)), 'groupnorm_act_backward')
         return dx, _sum_rows(dg), _sum_rows(db), None, None, None
@@ -147,7 +147,7 @@ class _Attention(torch.autograd.Function):
         q, k, v = ctx.saved_tensors
         do = do.contiguous()
         B, C, H, W = q.shape
-        dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
+        dq, dk, dv = (ops._out(t.shape, t.dtype, t.device) for t in (q, k, v))
         sc = ops._scratch(lib().csd_attention_backward_scratch_bytes(B, C, H, W), q.device)
         check(lib().csd_attention_backward(ptr(q), ptr(k), ptr(v), ptr(do), ptr(dq), ptr(dk), ptr(dv), B, C, H, W, ptr(sc),
                                            current_stream(q.device)), 'attention_backward')
@@ -175,12 +175,12 @@ class _Linear(torch.autograd.Function):
         N = weight.shape[0]
         dx = dw = db = None
         if ctx.needs_input_grad[0]:
-            da = torch.empty_like(x)                                  # d act_in(x)[b,k] = sum_n dy[b,n] W[n,k]
+            da = ops._out(x.shape, x.dtype, x.device)                 # d act_in(x)[b,k] = sum_n dy[b,n] W[n,k]
             bgemm(dy, weight, da, B, K, N, (N, 1), (K, 1), (K, 1))
             dx = da if act_in == 'none' else _act(x, act_in, da)
         if ctx.needs_input_grad[1]:
             a = x if act_in == 'none' else _act(x, act_in)
-            dw = torch.empty_like(weight)                             # dW[n,k] = sum_b dy[b,n] a[b,k]
+            dw = ops._out(weight.shape, weight.dtype, weight.device)  # dW[n,k] = sum_b dy[b,n] a[b,k]
             bgemm(dy, a, dw, N, K, B, (1, N), (K, 1), (K, 1))
         if has_bias and ctx.needs_input_grad[2]:
             db = _sum_rows(dy)
@@ -253,7 +253,7 @@ def scale_rows(x, scale, divide=False):
 class _Dropout(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, p, seed, stream_id):
-        out, mask = torch.empty_like(x), torch.empty_like(x)
+        out, mask = ops._out(x.shape, x.dtype, x.device), ops._out(x.shape, x.dtype, x.device)
         check(lib().csd_dropout(ptr(x), ptr(out), ptr(mask), float(p), int(seed), int(stream_id), x.numel(),
                                 current_stream(x.device)), 'dropout')
         ctx.save_for_backward(mask)

@@ -39,7 +39,7 @@ def conv3d_wgrad(a, dy, precision='fp16x3'):
     B, D, H, W, Cin = a.shape
     Cout = dy.shape[4]
     prec = _lib.PREC_IDS[precision]
-    dw = torch.empty(Cout, Cin, 3, 3, 3, dtype=torch.float32, device=a.device)
+    dw = ops._out((Cout, Cin, 3, 3, 3), torch.float32, a.device)
     sc = ops._scratch(lib().csd_conv3d_wgrad_scratch_bytes(B, Cin, Cout, D, H, W, prec), a.device)
     check(lib().csd_conv3d_wgrad(ptr(a), ptr(dy), ptr(dw), B, Cin, Cout, D, H, W, prec, ptr(sc), current_stream(a.device)), 'conv3d_wgrad')
     return dw
@@ -53,9 +53,9 @@ def conv3d_dgrad(dy, weight, precision='fp16x3'):
     B, D, H, W, Cout = dy.shape
     wt = weight.flip(2, 3, 4).transpose(0, 1).contiguous()               # [Cin, Cout, 3, 3, 3]: data movement only
     dev = dy.device
-    rowscale = torch.empty(B, dtype=torch.float32, device=dev)
-    nscale = torch.empty(B, Cout, dtype=torch.float32, device=dev)
-    nshift = torch.empty(B, Cout, dtype=torch.float32, device=dev)
+    rowscale = ops._out(B, torch.float32, dev)
+    nscale = ops._out((B, Cout), torch.float32, dev)
+    nshift = ops._out((B, Cout), torch.float32, dev)
     sc = ops._scratch(lib().csd_conv3d_dgrad_scale_scratch_bytes(B), dev)
     check(lib().csd_conv3d_dgrad_scale(ptr(dy), ptr(rowscale), ptr(nscale), ptr(nshift), B, dy.numel() // B, Cout, ptr(sc),
                                        current_stream(dev)), 'conv3d_dgrad_scale')

@@ -32,7 +32,7 @@ def _conv_raw(x, weight, bias, stride, dpad, up2, precision, layout):
         raise RuntimeError('conv2d: weight %s does not match %d input channels' % (tuple(weight.shape), Cin))
     s = 2 if up2 else 1
     OH, OW = H * s // stride, W * s // stride
-    y = torch.empty((B, OH, OW, Cout) if layout & OUT_NHWC else (B, Cout, OH, OW), dtype=torch.float32, device=x.device)
+    y = ops._out((B, OH, OW, Cout) if layout & OUT_NHWC else (B, Cout, OH, OW), torch.float32, x.device)
     sc = ops._scratch(lib().csd_conv_scratch_bytes(B, Cin, Cout, H, W, k, int(up2)), x.device)
     check(lib().csd_conv2d_ex(ptr(x), ptr(weight), ptr(bias), ptr(y), B, Cin, Cout, H, W, k, stride, 1 if dpad else 0, int(up2),
                               _lib.PREC_IDS[precision], layout, ptr(sc), current_stream(x.device)), 'conv2d_ex')
@@ -42,7 +42,7 @@ def _conv_raw(x, weight, bias, stride, dpad, up2, precision, layout):
 def _sum_pixels(x):
     """[B, H, W, C] -> [B, C]"""
     B, H, W, C = x.shape
-    out = torch.empty(B, C, dtype=torch.float32, device=x.device)
+    out = ops._out((B, C), torch.float32, x.device)
     sc = ops._scratch(lib().csd_sum_pixels_scratch_bytes(B, H * W, C), x.device)
     check(lib().csd_sum_pixels_nhwc(ptr(x), ptr(out), B, H * W, C, ptr(sc), current_stream(x.device)), 'sum_pixels_nhwc')
     return out
@@ -75,7 +75,7 @@ class _Conv2d(torch.autograd.Function):
             if stride == 2:
                 if not out_nhwc:
                     raise RuntimeError('stride-2 convolutions live inside the NHWC graph')
-                z = torch.empty(B, H, W, Cout, dtype=torch.float32, device=dy.device)
+                z = ops._out((B, H, W, Cout), torch.float32, dy.device)
                 check(lib().csd_zero_insert_odd_nhwc(ptr(dy), ptr(z), B, H // 2, W // 2, Cout, current_stream(dy.device)),
                       'zero_insert_odd_nhwc')
                 dx = _conv_raw(z, wt, None, 1, False, False, precision, lay)
@@ -83,10 +83,10 @@ class _Conv2d(torch.autograd.Function):
                 dx = _conv_raw(dy, wt, None, 1, False, False, precision, lay)
                 if up2:
                     full = dx
-                    dx = torch.empty(B, H, W, Cin, dtype=torch.float32, device=dy.device)
+                    dx = ops._out((B, H, W, Cin), torch.float32, dy.device)
                     check(lib().csd_sumpool2_nhwc(ptr(full), ptr(dx), B, H, W, Cin, current_stream(dy.device)), 'sumpool2_nhwc')
         if ctx.needs_input_grad[1]:
-            dw = torch.empty_like(weight)
+            dw = ops._out(weight.shape, weight.dtype, weight.device)
             sc = ops._scratch(lib().csd_conv_wgrad_scratch_bytes(B, Cin, Cout, H, W, k, stride, int(up2)), x.device)
             check(lib().csd_conv2d_wgrad_ex(ptr(x), ptr(dy), ptr(dw), B, Cin, Cout, H, W, k, stride, 1 if dpad else 0, int(up2),
                                             layout | (0 if precision == 'fp32' else SPLIT_BF16), ptr(sc),
@@ -113,9 +113,9 @@ class _GroupNormAct(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, gamma, beta, groups, eps, act):
         B, H, W, C = x.shape
-        y = torch.empty_like(x)
-        rs = torch.empty(B, C, dtype=torch.float32, device=x.device)
-        ms = torch.empty(B, C, dtype=torch.float32, device=x.device)
+        y = ops._out(x.shape, x.dtype, x.device)
+        rs = ops._out((B, C), torch.float32, x.device)
+        ms = ops._out((B, C), torch.float32, x.device)
         sc = ops._scratch(lib().csd_groupnorm_nhwc_scratch_bytes(B, C, H * W), x.device)
         check(lib().csd_groupnorm_act_nhwc(ptr(x), ptr(gamma), ptr(beta), ptr(y), ptr(rs), ptr(ms), B, C, H * W, groups, eps,
                                            _lib.ACT_IDS[act], ptr(sc), current_stream(x.device)), 'groupnorm_act_nhwc')
@@ -129,8 +129,8 @@ class _GroupNormAct(torch.autograd.Function):
         groups, act = ctx.cfg
         dy = dy.contiguous()
         B, H, W, C = x.shape
-        dx = torch.empty_like(x)
-        rows = torch.empty(B, 2 * C, dtype=torch.float32, device=x.device)       # [dgamma row | dbeta row] per sample: ONE batch reduction
+        dx = ops._out(x.shape, x.dtype, x.device)
+        rows = ops._out((B, 2 * C), torch.float32, x.device)       # [dgamma row | dbeta row] per sample: ONE batch reduction
         sc = ops._scratch(lib().csd_groupnorm_nhwc_scratch_bytes(B, C, H * W), x.device)
         check(lib().csd_groupnorm_act_backward_nhwc(ptr(x), ptr(gamma), ptr(beta), ptr(rs), ptr(ms), ptr(dy), ptr(dx), ptr(rows),
                                                     ctypes.c_void_p(rows.data_ptr() + 4 * C), 2 * C, B, C, H * W, groups,
@@ -150,7 +150,7 @@ class _Attention(torch.autograd.Function):
     @staticmethod
     def forward(ctx, qkv):
         B, H, W, C3 = qkv.shape
-        out = torch.empty(B, H, W, C3 // 3, dtype=torch.float32, device=qkv.device)
+        out = ops._out((B, H, W, C3 // 3), torch.float32, qkv.device)
         check(lib().csd_attention_nhwc(ptr(qkv), ptr(out), B, H * W, C3 // 3, current_stream(qkv.device)), 'attention_nhwc')
         ctx.save_for_backward(qkv)
         return out
@@ -160,7 +160,7 @@ class _Attention(torch.autograd.Function):
         qkv, = ctx.saved_tensors
         do = do.contiguous()
         B, H, W, C3 = qkv.shape
-        dqkv = torch.empty_like(qkv)
+        dqkv = ops._out(qkv.shape, qkv.dtype, qkv.device)
         sc = ops._scratch(lib().csd_attention_backward_scratch_bytes(B, C3 // 3, H * W, 1), qkv.device)
         check(lib().csd_attention_backward_nhwc(ptr(qkv), ptr(do), ptr(dqkv), B, H * W, C3 // 3, ptr(sc),
                                                 current_stream(qkv.device)), 'attention_backward_nhwc')
@@ -177,7 +177,7 @@ class _BiasAdd(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, bias):
         B, H, W, C = x.shape
-        out = torch.empty_like(x)
+        out = ops._out(x.shape, x.dtype, x.device)
         check(lib().csd_bias_add_nhwc(ptr(x), ptr(bias), ptr(out), B, H * W, C, current_stream(x.device)), 'bias_add_nhwc')
         return out
 

@@ -33,7 +33,7 @@ import numpy as np
 import torch
 from scipy import integrate
 
-from . import sde_lib
+from . import ops, sde_lib
 from ._lib import check, current_stream, lib, ptr
 from .models import utils as mutils
 
@@ -130,7 +130,7 @@ class _FusedRHS:
         need = lib().csd_unet_train_workspace_bytes(model._h, B, 0.0)
         if need == 0:
             raise RuntimeError('libcsd_hip: cannot plan the likelihood graph at batch %d: %s' % (B, lib().csd_last_error().decode()))
-        self.ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        self.ws = ops._scratch(need, dev)
         n = B * self.D
         self.n = n
         if host_state:              # (the state lives with scipy; host_state=False: with ode_solver on the device, see device_rhs)
@@ -146,7 +146,7 @@ class _FusedRHS:
         self.dout = torch.zeros(B, oc, S, S, dtype=torch.float32, device=dev)     # d_out = eps on the x channels
         self.dout[:, :cx].copy_(epsilon)
         self.y = y.to(device=dev, dtype=torch.float32).contiguous() if model.y_channels else None
-        self.scratch = torch.empty(lib().csd_pf_ode_scratch_bytes(B, self.D), dtype=torch.uint8, device=dev)
+        self.scratch = ops._scratch(lib().csd_pf_ode_scratch_bytes(B, self.D), dev)
         self.stream = current_stream(dev)
         if host_state:
             base = self.up.data_ptr()

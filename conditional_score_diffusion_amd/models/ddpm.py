@@ -20,7 +20,7 @@ import os
 import torch
 import torch.nn as nn
 
-from .. import _lib
+from .. import _lib, ops
 from .._lib import check, current_stream, lib, ptr, require_gpu_tensor
 from . import utils
 
@@ -186,7 +186,7 @@ class HipUNet(nn.Module):
                   'set_param')
         nbytes = lib().csd_unet_packed_bytes(self._h)
         if self._packed is None or self._packed.numel() < nbytes or self._packed.device != dev:
-            self._packed = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            self._packed = ops._scratch(nbytes, dev)
         check(lib().csd_unet_pack(self._h, ptr(self._packed), current_stream(dev)), 'unet_pack')
         self._packed_key = key
 
@@ -195,7 +195,7 @@ class HipUNet(nn.Module):
         if need == 0:
             raise RuntimeError('libcsd_hip: cannot plan batch %d: %s' % (B, lib().csd_last_error().decode()))
         if self._ws is None or self._ws.numel() < need or self._ws.device != self.device:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+            self._ws = ops._scratch(need, self.device)
         return self._ws
 
     def stats(self, B):
@@ -221,7 +221,7 @@ class HipUNet(nn.Module):
             y = y.contiguous()
         self._ensure_packed()
         ws = self._workspace(B)
-        out = torch.empty(B, self.out_channels, S, S, dtype=torch.float32, device=x.device)
+        out = ops._out((B, self.out_channels, S, S), torch.float32, x.device)
         check(lib().csd_unet_forward(self._h, ptr(self._packed), ptr(ws), ws.numel(), ptr(x.contiguous()),
                                      ptr(y) if self.y_channels else None, ptr(labels), ptr(out), B,
                                      ptr(y_noise) if y_noise is not None else None, float(y_sigma),
@@ -264,7 +264,7 @@ class HipUNet(nn.Module):
             raise RuntimeError('libcsd_hip: cannot plan the training graph at batch %d: %s' % (B, lib().csd_last_error().decode()))
         if self._train_ws is None or self._train_ws.numel() < need or self._train_ws.device != self.device:
             self._train_ws = None
-            self._train_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+            self._train_ws = ops._scratch(need, self.device)
         return self._train_ws
 
     def _train_params(self):
@@ -410,10 +410,10 @@ class _PlannedNet(torch.autograd.Function):
         # the shared training workspace belongs to ONE live forward; a second one (e.g. a monitoring forward between a training
         # forward and its backward) gets a workspace of its own, released with its autograd context
         shared = not model._train_ws_busy
-        ws = model._train_workspace(B) if shared else torch.empty(
-            lib().csd_unet_train_workspace_bytes(model._h, B, model._dropout), dtype=torch.uint8, device=x.device)
+        ws = model._train_workspace(B) if shared else ops._scratch(
+            lib().csd_unet_train_workspace_bytes(model._h, B, model._dropout), x.device)
         table = (ctypes.c_void_p * len(params))(*[p.data_ptr() for p in params])
-        out = torch.empty(B, model.out_channels, model.image_size, model.image_size, dtype=torch.float32, device=x.device)
+        out = ops._out((B, model.out_channels, model.image_size, model.image_size), torch.float32, x.device)
         check(lib().csd_unet_train_forward(model._h, table, ptr(ws), ws.numel(), ptr(x), ptr(y) if y is not None else None,
                                            ptr(labels), ptr(out), B, model._dropout, model.dropout_seed, model._train_calls,
                                            current_stream(x.device)), 'unet_train_forward')
@@ -443,17 +443,17 @@ class _PlannedNet(torch.autograd.Function):
         # when the kernels wrote .grad themselves; otherwise autograd's accumulation runs after them)
         model._last_backward_direct = direct
         if direct:
-            grads = [torch.empty(shape, dtype=torch.float32, device=dout.device) if g is False else g
+            grads = [ops._out(shape, torch.float32, dout.device) if g is False else g
                      for g, (shape, _) in zip(ctx.sink, ctx.shapes)]
         else:
             offs = [0]
             for _, n in ctx.shapes:
                 offs.append(offs[-1] + (n + 3) // 4 * 4)
-            flat = torch.empty(offs[-1], dtype=torch.float32, device=dout.device)
+            flat = ops._out(offs[-1], torch.float32, dout.device)
             grads = [flat[o:o + n].view(shape) for o, (shape, n) in zip(offs, ctx.shapes)]
         gtable = (ctypes.c_void_p * len(grads))(*[g.data_ptr() for g in grads])
         # d loss / d x from the same call when autograd asks for it (csd_unet_backward_ex: the parameter gradients are unchanged)
-        dx = torch.empty(B, model.x_channels, model.image_size, model.image_size, dtype=torch.float32, device=dout.device) \
+        dx = ops._out((B, model.x_channels, model.image_size, model.image_size), torch.float32, dout.device) \
             if ctx.needs_input_grad[1] else None
         check(lib().csd_unet_backward_ex(model._h, ctx.table, gtable, ptr(dx), ptr(ctx.ws), ctx.ws.numel(), ptr(dout), B, ctx.call,
                                          current_stream(dout.device)), 'unet_backward')
@@ -479,9 +479,9 @@ class _InputGradNet(torch.autograd.Function):
         need = lib().csd_unet_train_workspace_bytes(model._h, B, 0.0)
         if need == 0:
             raise RuntimeError('libcsd_hip: cannot plan the input-gradient graph at batch %d: %s' % (B, lib().csd_last_error().decode()))
-        ws = torch.empty(need, dtype=torch.uint8, device=x.device)
+        ws = ops._scratch(need, x.device)
         table = (ctypes.c_void_p * len(params))(*[p.data_ptr() for p in params])
-        out = torch.empty(B, model.out_channels, model.image_size, model.image_size, dtype=torch.float32, device=x.device)
+        out = ops._out((B, model.out_channels, model.image_size, model.image_size), torch.float32, x.device)
         check(lib().csd_unet_train_forward(model._h, table, ptr(ws), ws.numel(), ptr(x), ptr(y), ptr(labels), ptr(out), B, 0.0,
                                            model.dropout_seed, call, current_stream(x.device)), 'unet_train_forward')
         import weakref
@@ -493,7 +493,7 @@ class _InputGradNet(torch.autograd.Function):
     def backward(ctx, dout):
         model, B = ctx.model, ctx.B
         dout = dout.contiguous()
-        dx = torch.empty(B, model.x_channels, model.image_size, model.image_size, dtype=torch.float32, device=dout.device)
+        dx = ops._out((B, model.x_channels, model.image_size, model.image_size), torch.float32, dout.device)
         check(lib().csd_unet_backward_ex(model._h, ctx.table, None, ptr(dx), ptr(ctx.ws), ctx.ws.numel(), ptr(dout), B, ctx.call,
                                          current_stream(dout.device)), 'unet_backward_ex')
         ctx.fin()

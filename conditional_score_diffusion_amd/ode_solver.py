@@ -136,6 +136,7 @@ class DeviceBackend:
     def __init__(self, y0, x32=None):
         import torch
 
+        from . import ops
         from ._lib import current_stream, lib
         if not (y0.is_cuda and y0.dtype == torch.float64 and y0.dim() == 1):
             raise RuntimeError('DeviceBackend needs a flat float64 state on the GPU')
@@ -153,7 +154,7 @@ class DeviceBackend:
         self.nx = self.x32.numel()
         if self.nx:
             self.x32.copy_(self.y[:self.nx])
-        self.scratch = torch.empty(self.lib.csd_ode_scratch_bytes(n), dtype=torch.uint8, device=dev)
+        self.scratch = ops._scratch(self.lib.csd_ode_scratch_bytes(n), dev)
         self.res = torch.empty(2, dtype=torch.float64, device=dev)
         self.res_host = torch.empty(2, dtype=torch.float64).pin_memory()
         self._rows = [self.K[j * self.stride:j * self.stride + n] for j in range(7)]

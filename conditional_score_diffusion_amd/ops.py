@@ -13,7 +13,14 @@ from ._lib import check, current_stream, lib, ptr, require_gpu_tensor
 
 
 def _scratch(nbytes, device):
-    return torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=device)
+    """A caller-owned byte buffer (scratch, workspace, packed weights) of exactly the size a ``csd_*_bytes`` entry declared.  A declared
+    size of 0 (the operator is expected to refuse the call) still gets an address.  Every such buffer of the package comes from here."""
+    return torch.empty(int(nbytes) or 256, dtype=torch.uint8, device=device)
+
+
+def _out(shape, dtype, device):
+    """A result tensor that the library writes in full (never reads).  Every output of the package comes from here."""
+    return torch.empty(shape, dtype=dtype, device=device)
 
 
 def _c(t, name):
@@ -25,7 +32,7 @@ def groupnorm_act(x, gamma, beta, groups=32, eps=1e-6, act='none'):
     """act(GroupNorm(x)) - nn.GroupNorm + get_act (models/layers.py:571,638,646)."""
     x, gamma, beta = _c(x, 'x'), _c(gamma, 'gamma'), _c(beta, 'beta')
     B, C, H, W = x.shape
-    y = torch.empty_like(x)
+    y = _out(x.shape, x.dtype, x.device)
     sc = _scratch(lib().csd_groupnorm_scratch_bytes(B, C, H, W), x.device)
     check(lib().csd_groupnorm_act(ptr(x), ptr(gamma), ptr(beta), ptr(y), B, C, H, W, groups, eps,
                                   _lib.ACT_IDS[act], ptr(sc), current_stream(x.device)), 'groupnorm_act')
@@ -45,7 +52,7 @@ def conv2d(x, weight, bias=None, stride=1, downsample_pad=False, up2=False, prec
         raise RuntimeError('conv2d: weight %s does not match input channels %d' % (tuple(weight.shape), Cin))
     OH = (H * (2 if up2 else 1)) // stride
     OW = (W * (2 if up2 else 1)) // stride
-    y = torch.empty(B, Cout, OH, OW, dtype=torch.float32, device=x.device)
+    y = _out((B, Cout, OH, OW), torch.float32, x.device)
     sc = _scratch(lib().csd_conv_scratch_bytes(B, Cin, Cout, H, W, kh, int(up2)), x.device)
     check(lib().csd_conv2d(ptr(x), ptr(weight), ptr(bias), ptr(y), B, Cin, Cout, H, W, kh, stride,
                            1 if downsample_pad else 0, int(up2), _lib.PREC_IDS[precision], ptr(sc),
@@ -79,7 +86,7 @@ def fir_pyr_conv(x, weight, bias=None, res=None, fir_kernel=(1, 3, 3, 1), out_sc
         if len(fir_kernel) != 4:
             raise NotImplementedError('fir_pyr_conv: 4-tap FIR kernels only')
         taps = (ctypes.c_float * 4)(*[float(v) for v in fir_kernel])
-    y = torch.empty(B, H // 2, H // 2, Cout, dtype=torch.float32, device=x.device)
+    y = _out((B, H // 2, H // 2, Cout), torch.float32, x.device)
     sc = _scratch(lib().csd_fir_pyr_conv_scratch_bytes(Cin, Cout), x.device)
     check(lib().csd_fir_pyr_conv(ptr(x), ptr(weight), ptr(bias), ptr(res), ptr(y), B, Cin, Cout, H, Cin,
                                  ctypes.cast(taps, ctypes.c_void_p) if taps is not None else None, float(out_scale), ptr(sc),
@@ -103,8 +110,8 @@ def conv3x3_block(x0, weight, bias=None, x1=None, nscale=None, nshift=None, temb
         raise RuntimeError('conv3x3_block: weight %s does not match %d input channels' % (tuple(weight.shape), C0 + C1))
     opt = [None if t is None else _c(t, 't') for t in (bias, nscale, nshift, temb, res)]
     bias, nscale, nshift, temb, res = opt
-    y = torch.empty(B, H, W, Cout, dtype=torch.float32, device=x0.device)
-    stats = torch.empty(B * ((H + 15) // 16) * ((W + 15) // 16), Cout, 2, dtype=torch.float64, device=x0.device) if want_stats else None
+    y = _out((B, H, W, Cout), torch.float32, x0.device)
+    stats = _out((B * ((H + 15) // 16) * ((W + 15) // 16), Cout, 2), torch.float64, x0.device) if want_stats else None
     sc = _scratch(lib().csd_conv3x3_block_scratch_bytes(C0 + C1, Cout), x0.device)
     check(lib().csd_conv3x3_block(ptr(x0), ptr(x1), ptr(weight), ptr(bias), ptr(nscale), ptr(nshift), ptr(temb),
                                   temb.shape[1] if temb is not None else 0, ptr(res), float(out_scale), ptr(y), ptr(stats),
@@ -142,7 +149,7 @@ def conv3d_block(x0, weight, bias=None, x1=None, nscale=None, nshift=None, act='
         raise RuntimeError('conv3d_block: temb %s is not [B, >= Cout]' % (tuple(temb.shape),))
     if any(t is not None and t.device != x0.device for t in (weight, x1, bias, nscale, nshift, temb, res)):
         raise RuntimeError('conv3d_block: every operand must be on one device')
-    y = torch.empty(B, D, H, W, Cout, dtype=torch.float32, device=x0.device)
+    y = _out((B, D, H, W, Cout), torch.float32, x0.device)
     sc = _scratch(lib().csd_conv3d_block_scratch_bytes(C0 + C1, Cout), x0.device)
     check(lib().csd_conv3d_block(ptr(x0), ptr(x1), ptr(weight), ptr(bias), ptr(nscale), ptr(nshift), _lib.ACT_IDS[act], ptr(temb),
                                  temb.shape[1] if temb is not None else 0, ptr(res), float(out_scale), ptr(y), B, C0, C1, Cout, D, H, W,
@@ -154,7 +161,7 @@ def avg_pool3d_2(x):
     """nn.AvgPool3d(2, 2) (models/layers.py:617) on a channels-last volume [B,D,H,W,C] -> [B,D/2,H/2,W/2,C]."""
     x = _c(x, 'x')
     B, D, H, W, C = x.shape
-    y = torch.empty(B, D // 2, H // 2, W // 2, C, dtype=torch.float32, device=x.device)
+    y = _out((B, D // 2, H // 2, W // 2, C), torch.float32, x.device)
     check(lib().csd_avgpool3d_2_ndhwc(ptr(x), ptr(y), B, D, H, W, C, current_stream(x.device)), 'avg_pool3d_2')
     return y
 
@@ -163,7 +170,7 @@ def nearest_up2_3d(x):
     """F.interpolate(x, 2 * size, mode='nearest') (models/layers.py:601) on a channels-last volume [B,D,H,W,C]."""
     x = _c(x, 'x')
     B, D, H, W, C = x.shape
-    y = torch.empty(B, 2 * D, 2 * H, 2 * W, C, dtype=torch.float32, device=x.device)
+    y = _out((B, 2 * D, 2 * H, 2 * W, C), torch.float32, x.device)
     check(lib().csd_nearest_up2_3d_ndhwc(ptr(x), ptr(y), B, D, H, W, C, current_stream(x.device)), 'nearest_up2_3d')
     return y
 
@@ -182,8 +189,8 @@ def groupnorm_scale_shift(x0, gamma, beta, x1=None, groups=32, eps=1e-6):
             raise RuntimeError('groupnorm_scale_shift: x1 %s does not match x0 %s' % (tuple(x1.shape), tuple(x0.shape)))
     if tuple(gamma.shape) != (C0 + C1,) or tuple(beta.shape) != (C0 + C1,):
         raise RuntimeError('groupnorm_scale_shift: gamma / beta are not [%d]' % (C0 + C1))
-    nscale = torch.empty(B, C0 + C1, dtype=torch.float32, device=x0.device)
-    nshift = torch.empty_like(nscale)
+    nscale = _out((B, C0 + C1), torch.float32, x0.device)
+    nshift = _out(nscale.shape, nscale.dtype, nscale.device)
     sc = _scratch(lib().csd_groupnorm_scale_shift_scratch_bytes(B, C0 + C1, S, groups), x0.device)
     check(lib().csd_groupnorm_scale_shift(ptr(x0), ptr(x1), ptr(gamma), ptr(beta), ptr(nscale), ptr(nshift), B, C0, C1, S, groups,
                                           float(eps), ptr(sc), current_stream(x0.device)), 'groupnorm_scale_shift')
@@ -194,7 +201,7 @@ def attention(q, k, v):
     """softmax(q.k C^-1/2) v over H*W positions (models/layers.py:584-588)."""
     q, k, v = _c(q, 'q'), _c(k, 'k'), _c(v, 'v')
     B, C, H, W = q.shape
-    out = torch.empty_like(q)
+    out = _out(q.shape, q.dtype, q.device)
     sc = _scratch(lib().csd_attention_scratch_bytes(B, C, H, W), q.device)
     check(lib().csd_attention(ptr(q), ptr(k), ptr(v), ptr(out), B, C, H, W, ptr(sc), current_stream(q.device)),
           'attention')
@@ -209,7 +216,7 @@ def _upfirdn2d_raw(x, kernel, up, down, pad4):
     (ux, uy), (dx, dy), (px0, px1, py0, py1) = up, down, pad4
     OH = (H * uy + py0 + py1 - kh) // dy + 1
     OW = (W * ux + px0 + px1 - kw) // dx + 1
-    out = torch.empty(N, C, OH, OW, dtype=torch.float32, device=x.device)
+    out = _out((N, C, OH, OW), torch.float32, x.device)
     check(lib().csd_upfirdn2d(ptr(x), ptr(kernel), ptr(out), N, C, H, W, kh, kw, ux, uy, dx, dy, px0, px1, py0, py1,
                               current_stream(x.device)), 'upfirdn2d')
     return out
@@ -267,7 +274,7 @@ def upfirdn2d(x, kernel, up=1, down=1, pad=(0, 0)):
 def fused_leaky_relu(x, bias, negative_slope=0.2, scale=2 ** 0.5):
     """Forward of op.fused_leaky_relu (op/fused_act.py:86-97): lrelu(x + b[c]) * scale."""
     x, bias = _c(x, 'x'), _c(bias, 'bias')
-    out = torch.empty_like(x)
+    out = _out(x.shape, x.dtype, x.device)
     inner = 1
     for s in x.shape[2:]:
         inner *= s
@@ -279,14 +286,14 @@ def fused_leaky_relu(x, bias, negative_slope=0.2, scale=2 ** 0.5):
 def nearest_up2(x):
     x = _c(x, 'x')
     N, C, H, W = x.shape
-    out = torch.empty(N, C, 2 * H, 2 * W, dtype=torch.float32, device=x.device)
+    out = _out((N, C, 2 * H, 2 * W), torch.float32, x.device)
     check(lib().csd_nearest_up2(ptr(x), ptr(out), N, C, H, W, current_stream(x.device)), 'nearest_up2')
     return out
 
 
 def timestep_embedding(t, dim):
     t = _c(t, 't')
-    out = torch.empty(t.shape[0], dim, dtype=torch.float32, device=t.device)
+    out = _out((t.shape[0], dim), torch.float32, t.device)
     check(lib().csd_timestep_embedding(ptr(t), ptr(out), t.shape[0], dim, current_stream(t.device)),
           'timestep_embedding')
     return out
@@ -300,7 +307,7 @@ def linear(x, weight, bias=None, act_in='none'):
         bias = _c(bias, 'bias')
     B, K = x.shape
     N = weight.shape[0]
-    out = torch.empty(B, N, dtype=torch.float32, device=x.device)
+    out = _out((B, N), torch.float32, x.device)
     check(lib().csd_linear(ptr(x), ptr(weight), ptr(bias), ptr(out), B, K, N, _lib.ACT_IDS[act_in],
                            current_stream(x.device)), 'linear')
     return out
@@ -309,7 +316,7 @@ def linear(x, weight, bias=None, act_in='none'):
 def fourier_embedding(t, W):
     """GaussianFourierProjection (models/layerspp.py:32-41): [sin(2 pi W t), cos(2 pi W t)]."""
     t, W = _c(t, 't'), _c(W, 'W')
-    out = torch.empty(t.shape[0], 2 * W.shape[0], dtype=torch.float32, device=t.device)
+    out = _out((t.shape[0], 2 * W.shape[0]), torch.float32, t.device)
     check(lib().csd_fourier_embedding(ptr(t), ptr(W), ptr(out), t.shape[0], W.shape[0], current_stream(t.device)),
           'fourier_embedding')
     return out
@@ -322,7 +329,7 @@ def axpby(a, b=None, alpha=1.0, beta=1.0, gamma=0.0, post=1.0):
         b = _c(b, 'b')
         if b.shape != a.shape:
             raise RuntimeError('axpby: shapes %s and %s differ' % (tuple(a.shape), tuple(b.shape)))
-    out = torch.empty_like(a)
+    out = _out(a.shape, a.dtype, a.device)
     check(lib().csd_axpby(ptr(a), ptr(b), ptr(out), float(alpha), float(beta), float(gamma), float(post), a.numel(),
                           current_stream(a.device)), 'axpby')
     return out
@@ -334,7 +341,7 @@ def bias_add_nchw(x, bias, act='none'):
     B, C = x.shape[0], x.shape[1]
     inner = x.numel() // (B * C)
     stride = C if bias.dim() == 2 else 0
-    out = torch.empty_like(x)
+    out = _out(x.shape, x.dtype, x.device)
     check(lib().csd_bias_add_nchw(ptr(x), ptr(bias), ptr(out), B, C, inner, stride, _lib.ACT_IDS[act],
                                   current_stream(x.device)), 'bias_add_nchw')
     return out
@@ -342,7 +349,7 @@ def bias_add_nchw(x, bias, act='none'):
 
 def randn(shape, seed, stream_id, device):
     """Counter-based standard normals (Philox4x32-10): same (seed, stream_id) -> same tensor."""
-    out = torch.empty(*shape, dtype=torch.float32, device=device)
+    out = _out(shape, torch.float32, device)
     check(lib().csd_randn(ptr(out), out.numel(), int(seed), int(stream_id), current_stream(out.device)), 'randn')
     return out
 
@@ -367,7 +374,7 @@ def inpaint_blend(x, data, mask, z=None, mean_scale=1.0, std=0.0, seed=0, stream
     for name, t in tensors[1:]:
         if t.shape != x.shape:
             raise RuntimeError('inpaint_blend: %s has shape %s, x has %s' % (name, tuple(t.shape), tuple(x.shape)))
-    xm = torch.empty_like(x) if x_mean else None
+    xm = _out(x.shape, x.dtype, x.device) if x_mean else None
     check(lib().csd_inpaint_blend(_addr(x, 'x'), ptr(xm), _addr(data, 'data'), _addr(mask, 'mask'),
                                   _addr(z, 'z') if z is not None else None, float(mean_scale), float(std), x.numel(), int(seed),
                                   int(stream_id), current_stream(x.device)), 'inpaint_blend')
@@ -377,7 +384,7 @@ def inpaint_blend(x, data, mask, z=None, mean_scale=1.0, std=0.0, seed=0, stream
 def scale_rows(x, scale, divide=False):
     """x[b] * scale[b] (or / scale[b]) - divide_by_sigmas (models/utils.py:50-74)."""
     x, scale = _c(x, 'x'), _c(scale, 'scale')
-    out = torch.empty_like(x)
+    out = _out(x.shape, x.dtype, x.device)
     B = x.shape[0]
     check(lib().csd_scale_rows(ptr(out), ptr(x), ptr(scale), int(divide), B, x.numel() // B,
                                current_stream(x.device)), 'scale_rows')
@@ -389,7 +396,7 @@ def langevin_step(x, net, z, std, snr, alpha=1.0):
     SDEs, 1 for the VE SDEs; returns (x, x_mean)."""
     x, net, z = _c(x, 'x'), _c(net, 'net'), _c(z, 'z')
     B = x.shape[0]
-    x_mean = torch.empty_like(x)
+    x_mean = _out(x.shape, x.dtype, x.device)
     sc = _scratch(lib().csd_update_scratch_bytes(B), x.device)
     check(lib().csd_langevin_step(ptr(x), ptr(x_mean), ptr(net), ptr(z), float(std), float(snr), float(alpha), B,
                                   x.numel() // B, ptr(sc), current_stream(x.device)), 'langevin_step')
@@ -400,7 +407,7 @@ def row_norms(x):
     """||x_b||_2 per sample -> [B] (fp64 accumulation on the device)."""
     x = _c(x, 'x')
     B = x.shape[0]
-    out = torch.empty(B, dtype=torch.float32, device=x.device)
+    out = _out(B, torch.float32, x.device)
     check(lib().csd_row_norms(ptr(x), ptr(out), B, x.numel() // B, current_stream(x.device)), 'row_norms')
     return out
 
@@ -408,7 +415,7 @@ def row_norms(x):
 def affine_noise_step(x, score, z, p, a, c):
     """In-place x_mean = p*x + a*score; x = x_mean + c*z (Euler-Maruyama / ancestral / annealed-Langevin updates)."""
     x, score, z = _c(x, 'x'), _c(score, 'score'), _c(z, 'z')
-    x_mean = torch.empty_like(x)
+    x_mean = _out(x.shape, x.dtype, x.device)
     check(lib().csd_affine_noise_step(ptr(x), ptr(x_mean), ptr(score), ptr(z), float(p), float(a), float(c),
                                       x.numel(), current_stream(x.device)), 'affine_noise_step')
     return x, x_mean
@@ -422,7 +429,7 @@ def reverse_diffusion_step(x, net, z, std, G, drift=None, probability_flow=False
     reverse ODE (half the score term, no noise; ``z`` is still read).  Without either, the VE kernel runs as before."""
     x, net, z = _c(x, 'x'), _c(net, 'net'), _c(z, 'z')
     B = x.shape[0]
-    x_mean = torch.empty_like(x)
+    x_mean = _out(x.shape, x.dtype, x.device)
     if drift is None and not probability_flow:
         check(lib().csd_reverse_diffusion_step(ptr(x), ptr(x_mean), ptr(net), ptr(z), float(std), float(G), B,
                                                x.numel() // B, current_stream(x.device)), 'reverse_diffusion_step')

@@ -12,7 +12,7 @@ import weakref
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, ops
 from ._lib import check, current_stream, lib, ptr
 
 
@@ -142,9 +142,9 @@ class FusedAdam(torch.optim.Optimizer):
         self.flat.zero_grad()
 
     def grad_norm(self):
-        out = torch.empty(1, dtype=torch.float32, device=self.flat.grad.device)
+        out = ops._out(1, torch.float32, self.flat.grad.device)
         if self._norm_scratch is None:
-            self._norm_scratch = torch.empty(lib().csd_global_norm_scratch_bytes(), dtype=torch.uint8, device=out.device)
+            self._norm_scratch = ops._scratch(lib().csd_global_norm_scratch_bytes(), out.device)
         check(lib().csd_global_norm(ptr(self.flat.grad), ptr(out), self.flat.numel, ptr(self._norm_scratch),
                                     current_stream(out.device)), 'global_norm')
         return out

@@ -301,9 +301,10 @@ def run(model, sde, shape, y, p_steps, snr, eps, denoise, noise_tape=None, seed=
     model.eval()
     model._ensure_packed()
     ws = model._workspace(B)
-    scratch = torch.empty(lib().csd_pc_scratch_bytes(model._h, B), dtype=torch.uint8, device=dev)
+    scratch_bytes = lib().csd_pc_inpaint_scratch_bytes if inpaint is not None else lib().csd_pc_scratch_bytes
+    scratch = ops._scratch(scratch_bytes(model._h, B), dev)
     n_rec = p_steps + (1 if inpaint is not None else 0)
-    rec = torch.empty((n_rec,) + tuple(x.shape), dtype=torch.float32, device=dev) if record else None
+    rec = ops._out((n_rec,) + tuple(x.shape), torch.float32, dev) if record else None
     rec_steps = rec
     ip = None
     if inpaint is not None:

@@ -480,3 +480,58 @@ def test_plan_digests_equal_the_pinned_ones(golden_dir):
     assert sorted(got) == sorted(want)
     diff = ['%s B=%s' % (k, b) for k in want for b in want[k] if got[k].get(b) != want[k][b]]
     assert not diff, '%d of %d digests differ, first: %s' % (len(diff), sum(len(v) for v in want.values()), diff[:8])
+
+
+def test_every_sizing_entry_has_a_guarded_buffer_test():
+    """tests/guarded.py:SIZING names, for every csd_*_bytes entry of the ABI, the tests of tests/test_gpu_buffers.py that run in a
+    buffer of exactly the size the entry declared (those tests assert from the seam's record that it really did): a new sizing entry
+    without a row fails here, and so does a row that names no test"""
+    import ast
+    import guarded
+    from conditional_score_diffusion_amd import _lib
+    sizing = sorted(n for n in _lib.SIGNATURES if n.endswith('_bytes'))
+    assert len(sizing) >= 22
+    assert sorted(guarded.SIZING) == sizing, set(guarded.SIZING) ^ set(sizing)
+    tree = ast.parse(open(os.path.join(ROOT, 'tests', 'test_gpu_buffers.py')).read())
+    tests = {f.name: f for f in tree.body if isinstance(f, ast.FunctionDef) and f.name.startswith('test_')}
+    for entry, ids in guarded.SIZING.items():
+        assert ids, entry
+        for tid in ids:
+            fn = tests.get(tid.split('[')[0])
+            assert fn is not None, '%s: tests/test_gpu_buffers.py has no %s' % (entry, tid)
+            assert 'fills' in [a.arg for a in fn.args.args], '%s does not run through the guarded seam' % tid
+            assert entry in guarded.entries_of(tid.split('[')[0], tid)
+
+
+def test_allocation_seam_defaults_and_guarded_helper():
+    """ops._scratch / ops._out allocate what the code always allocated (a declared size of 0 still gets an address); the test seam
+    swaps both and the sizing entries in and out, and a guarded buffer notices one changed byte on either side"""
+    import guarded
+    from conditional_score_diffusion_amd import _lib, ops
+    cpu = torch.device('cpu')
+    assert ops._scratch(1000, cpu).shape == (1000,) and ops._scratch(1000, cpu).dtype == torch.uint8
+    assert ops._scratch(3, cpu).numel() == 3 and ops._scratch(0, cpu).numel() == 256
+    t = ops._out((2, 3), torch.float64, cpu)
+    assert t.shape == (2, 3) and t.dtype == torch.float64 and t.is_contiguous() and ops._out(5, torch.float32, cpu).shape == (5,)
+    saved = (ops._scratch, ops._out, _lib.lib().csd_update_scratch_bytes)
+    with guarded.seam(0xFF) as rec:
+        n = _lib.lib().csd_update_scratch_bytes(3)
+        assert n == saved[2](3) and rec.sizing_calls == [('csd_update_scratch_bytes', n)]
+        sc = ops._scratch(n, cpu)
+        odd = ops._scratch(n + 1, cpu)
+        out = ops._out((3, 5), torch.float32, cpu)
+        assert sc.numel() == n and odd.numel() == n + 1 and bool((sc == 0xFF).all())
+        assert out.shape == (3, 5) and bool(torch.isnan(out).all()) and bool(torch.isnan(out.view(torch.float16)).all())
+        assert rec.sized_by == {'csd_update_scratch_bytes': 1, None: 1} and rec.outputs == 1
+        rec.check_guards()
+        with pytest.raises(AssertionError):
+            rec.assert_sized_by([])                          # (the n + 1 bytes that no entry declared)
+        out.view(-1)[-1] = 1.0                               # inside the body: fine
+        rec.check_guards()
+        sc[:1].as_strided((1,), (1,), sc.storage_offset() + n)[0] = 0      # the first byte behind the scratch
+        with pytest.raises(AssertionError, match='1 behind'):
+            rec.check_guards()
+    assert (ops._scratch, ops._out, _lib.lib().csd_update_scratch_bytes) == saved
+    body, chk = guarded.guarded(0, cpu, 0x00)
+    assert body.numel() == 0
+    chk()
