@@ -30,7 +30,8 @@ class UNetConfig(ctypes.Structure):
                 ('resamp_with_conv', ctypes.c_int32), ('conditional', ctypes.c_int32),
                 ('centered', ctypes.c_int32), ('act', ctypes.c_int32), ('precision', ctypes.c_int32),
                 ('skip_rescale', ctypes.c_int32), ('progressive', ctypes.c_int32), ('progressive_input', ctypes.c_int32),
-                ('embedding_type', ctypes.c_int32), ('n_fir', ctypes.c_int32), ('fir_kernel', ctypes.c_float * 8)]
+                ('embedding_type', ctypes.c_int32), ('n_fir', ctypes.c_int32), ('fir_kernel', ctypes.c_float * 8),
+                ('vol', ctypes.c_int32 * 3)]       # arch 2: D, H, W
 
 
 class PCParams(ctypes.Structure):

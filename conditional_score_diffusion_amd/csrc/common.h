@@ -317,6 +317,30 @@ int bridge_update_launch(const float* y0, float* state, const float* z, float w0
 int avgpool2_launch(const float* in, float* out, int B, int H, int W, int C, hipStream_t s);
 int nearest_up2_nhwc_launch(const float* in, float* out, int B, int H, int W, int C, hipStream_t s);
 
+// conv3d.hip: csd_conv3d_block in pieces, for a caller that packs a layer's weight once (the planned 3-D network, unet3d.h).
+// conv3d_launch runs the kernel csd_conv3d_block would run (same brick, same NT) on `wpack` = what conv3d_pack_launch wrote
+struct Conv3dCall {
+  const float* x0 = nullptr;
+  const float* x1 = nullptr;
+  const void* wpack = nullptr;
+  const float* bias = nullptr;
+  const float* nscale = nullptr;
+  const float* nshift = nullptr;
+  const float* temb = nullptr;
+  const float* res = nullptr;
+  float* out = nullptr;
+  int temb_stride = 0, act = 0;
+  float out_scale = 1.f;
+  int B = 0, C0 = 0, C1 = 0, Cout = 0, D = 0, H = 0, W = 0, precision = 0;
+};
+bool conv3d_is_direct(int precision, int C0);                   // the fp32 direct kernel (CSD_PREC_F32, or C0 no multiple of 16)
+size_t conv3d_wpack_size(int Cin, int Cout, bool direct);      // bytes of one packed weight (MFMA: with the weight ring's slack)
+int conv3d_pack_launch(const float* weight, void* wpack, int Cin, int Cout, bool direct, hipStream_t s);
+int conv3d_launch(const Conv3dCall& c, hipStream_t s);
+// x, y (+ y_sigma * y_noise) NCDHW -> (2v - 1 unless centered) -> 3x3x3 convolution -> NDHWC; wpack in the direct layout
+int conv3d_stem_launch(const float* x, const float* y, const float* y_noise, float y_sigma, const void* wpack, const float* bias, float* out,
+                       int B, int Cx, int Cy, int Cout, int D, int H, int W, int centered, hipStream_t s);
+
 // wgrad_bf16.hip: weight gradient of a stride-1 3x3 / 1x1 convolution with split-bf16 operands (NHWC x, dy; partial [S][Cout][Cin][taps])
 int wgrad_bf16_launch(const float* xh, const float* dyh, float* partial, int B, int H, int W, int Cin, int Cout, int ksize, int S,
                       int per_split, hipStream_t s);

@@ -162,6 +162,49 @@ __global__ __launch_bounds__(C3_THREADS) void conv3d_direct_kernel(const Conv3dA
   k.out[idx] = ((acc + (k.bias ? k.bias[co] : 0.f)) + add) * k.out_scale;
 }
 
+// ---- input boundary + stem of the planned network (unet3d.h): x [B, Cx, D, H, W] and y [B, Cy, D, H, W] (NCDHW, y optional) -> the first
+// 3x3x3 convolution's output [B, D, H, W, Cout].  The network input v = y + y_sigma * y_noise (y only, when y_noise is given), then 2v - 1
+// unless `centered`, is formed per tap in registers (2v is exact, so the value equals the one a separate pass would store); the
+// convolution restates conv3d_direct_kernel's chain: taps outer, channels inner, x channels before y channels, one fp32 fmaf chain, a tap
+// outside the volume is skipped.  Weights in the direct layout [tap][Cin][Cout].
+__global__ __launch_bounds__(C3_THREADS) void conv3d_stem_kernel(const float* __restrict__ xs, const float* __restrict__ ys,
+                                                                 const float* __restrict__ yn, float ysig, const float* __restrict__ wt,
+                                                                 const float* __restrict__ bias, float* __restrict__ out, int B, int Cx,
+                                                                 int Cy, int Cout, int D, int H, int W, int centered) {
+  const size_t vox = (size_t)D * H * W;
+  const size_t total = (size_t)B * vox * Cout;
+  const size_t idx = (size_t)blockIdx.x * C3_THREADS + threadIdx.x;
+  if (idx >= total) return;
+  const int co = (int)(idx % Cout);
+  const size_t v = idx / Cout;
+  const int b = (int)(v / vox);
+  const int vi = (int)(v - (size_t)b * vox);
+  const int x = vi % W;
+  const int h = (vi / W) % H;
+  const int d = vi / (W * H);
+  const int Cin = Cx + Cy;
+  float acc = 0.f;
+  for (int tap = 0; tap < C3_TAPS; ++tap) {
+    const int dd = d + tap / 9 - 1, hh = h + (tap / 3) % 3 - 1, ww = x + tap % 3 - 1;
+    if (dd < 0 || dd >= D || hh < 0 || hh >= H || ww < 0 || ww >= W) continue;
+    const size_t sp = ((size_t)dd * H + hh) * W + ww;
+    const float* wp = wt + (size_t)tap * Cin * Cout + co;
+    for (int ci = 0; ci < Cx; ++ci) {
+      float xv = xs[((size_t)b * Cx + ci) * vox + sp];
+      if (!centered) xv = 2.f * xv - 1.f;
+      acc = fmaf(xv, wp[(size_t)ci * Cout], acc);
+    }
+    for (int ci = 0; ci < Cy; ++ci) {
+      const size_t j = ((size_t)b * Cy + ci) * vox + sp;
+      float yv = ys[j];
+      if (yn) yv = yv + yn[j] * ysig;
+      if (!centered) yv = 2.f * yv - 1.f;
+      acc = fmaf(yv, wp[(size_t)(Cx + ci) * Cout], acc);
+    }
+  }
+  out[idx] = ((acc + (bias ? bias[co] : 0.f)) + 0.f) * 1.0f;      // (the direct kernel's epilogue without residual / temb, out_scale 1)
+}
+
 // ---- implicit GEMM on the fp16 matrix cores, split operands -----------------------------------------------------------------------------
 template <int NT>
 __global__ __launch_bounds__(C3_THREADS, 2) void conv3d_mfma_kernel(const Conv3dArgs k) {
@@ -401,6 +444,78 @@ __global__ void nearest_up2_3d_kernel(const float* __restrict__ in, float* __res
 }
 
 }  // namespace
+
+// ---- the pieces of csd_conv3d_block for a caller that keeps packed weights (the planned 3-D network, unet3d.h) ------------------------
+bool conv3d_is_direct(int precision, int C0) { return precision == CSD_PREC_F32 || C0 % 16 != 0; }
+
+size_t conv3d_wpack_size(int Cin, int Cout, bool direct) {
+  return direct ? (size_t)C3_TAPS * Cin * Cout * sizeof(float) : mfma_pack_bytes(Cin, Cout);
+}
+
+int conv3d_pack_launch(const float* weight, void* wpack, int Cin, int Cout, bool direct, hipStream_t s) {
+  if (direct) {
+    const size_t nw = (size_t)C3_TAPS * Cin * Cout;
+    hipLaunchKernelGGL(conv3d_pack_direct_kernel, dim3((unsigned)std::min<size_t>(cdiv64(nw, 256), 4096)), dim3(256), 0, s, weight,
+                       static_cast<float*>(wpack), Cin, Cout, nw);
+    CSD_LAUNCH_CHECK();
+    return CSD_OK;
+  }
+  const int nck = Cin / C3_KC, ntiles = cdiv(Cout, 32);
+  const size_t nh = (size_t)ntiles * nck * C3_TAPS * 512;
+  hipLaunchKernelGGL(conv3d_pack_mfma_kernel, dim3((unsigned)std::min<size_t>(cdiv64(nh, 256), 4096)), dim3(256), 0, s, weight,
+                     static_cast<_Float16*>(wpack), Cin, Cout, nck, nh);
+  CSD_LAUNCH_CHECK();
+  return CSD_OK;
+}
+
+int conv3d_launch(const Conv3dCall& c, hipStream_t s) {
+  const int Cin = c.C0 + c.C1;
+  const size_t vox = (size_t)c.D * c.H * c.W;
+  Conv3dArgs a;
+  memset(&a, 0, sizeof(a));
+  a.x0 = c.x0; a.x1 = c.x1; a.wpack = c.wpack; a.bias = c.bias; a.nscale = c.nscale; a.nshift = c.nshift; a.temb = c.temb; a.res = c.res;
+  a.out = c.out;
+  a.temb_stride = c.temb_stride; a.act = c.act; a.out_scale = c.out_scale;
+  a.B = c.B; a.D = c.D; a.H = c.H; a.W = c.W; a.C0 = c.C0; a.C1 = c.C1; a.Cout = c.Cout;
+
+  if (conv3d_is_direct(c.precision, c.C0)) {      // exact yardstick; thin layers (the stem)
+    const size_t total = (size_t)c.B * vox * c.Cout;
+    const size_t nb = cdiv64(total, C3_THREADS);
+    CSD_REQUIRE(nb < ((size_t)1 << 31), "conv3d_block: %zu outputs exceed the direct kernel's grid", total);
+    hipLaunchKernelGGL(conv3d_direct_kernel, dim3((unsigned)nb), dim3(C3_THREADS), 0, s, a);
+    CSD_LAUNCH_CHECK();
+    return CSD_OK;
+  }
+
+  a.nck = Cin / C3_KC;
+  a.ntiles = cdiv(c.Cout, 32);
+  const int NT = a.ntiles >= 3 ? 4 : a.ntiles;
+  a.n_groups = cdiv(a.ntiles, NT);
+  if (c.W >= 3) { a.TD = 4; a.TH = 8; a.TW = 4; }
+  else { a.TD = 8; a.TH = 8; a.TW = 2; }
+  a.nbd = cdiv(c.D, a.TD); a.nbh = cdiv(c.H, a.TH); a.nbw = cdiv(c.W, a.TW);
+  const size_t nblocks = (size_t)c.B * a.nbd * a.nbh * a.nbw * a.n_groups;
+  CSD_REQUIRE(nblocks < ((size_t)1 << 31), "conv3d_block: %zu workgroups exceed the grid", nblocks);
+  const int npatch = (a.TD + 2) * (a.TH + 2) * (a.TW + 2);
+  const size_t lds = (size_t)2 * npatch * C3_PSB + (size_t)(C3_NPIX + npatch) * sizeof(int);
+  switch (NT) {
+    case 1: return conv3d_mfma_launch<1>(a, (int)nblocks, lds, s);
+    case 2: return conv3d_mfma_launch<2>(a, (int)nblocks, lds, s);
+    default: return conv3d_mfma_launch<4>(a, (int)nblocks, lds, s);
+  }
+}
+
+int conv3d_stem_launch(const float* x, const float* y, const float* y_noise, float y_sigma, const void* wpack, const float* bias, float* out,
+                       int B, int Cx, int Cy, int Cout, int D, int H, int W, int centered, hipStream_t s) {
+  const size_t total = (size_t)B * D * H * W * Cout;
+  const size_t nb = cdiv64(total, C3_THREADS);
+  CSD_REQUIRE(nb >= 1 && nb < ((size_t)1 << 31), "conv3d_stem: %zu outputs exceed the kernel's grid", total);
+  hipLaunchKernelGGL(conv3d_stem_kernel, dim3((unsigned)nb), dim3(C3_THREADS), 0, s, x, y, y_noise, y_sigma, static_cast<const float*>(wpack),
+                     bias, out, B, Cx, Cy, Cout, D, H, W, centered);
+  CSD_LAUNCH_CHECK();
+  return CSD_OK;
+}
+
 }  // namespace csd
 
 using namespace csd;
@@ -431,45 +546,13 @@ extern "C" int csd_conv3d_block(const float* x0, const float* x1, const float* w
               "conv3d_block: one sample (%dx%dx%d voxels, %d channels) exceeds the kernel's 2 GiB per-sample addressing", D, H, W, std::max(Cin, Cout));
   hipStream_t s = (hipStream_t)stream;
   void* wpack = reinterpret_cast<void*>((reinterpret_cast<uintptr_t>(scratch) + 255) & ~(uintptr_t)255);
-  Conv3dArgs a;
-  memset(&a, 0, sizeof(a));
-  a.x0 = x0; a.x1 = x1; a.wpack = wpack; a.bias = bias; a.nscale = nscale; a.nshift = nshift; a.temb = temb; a.res = res; a.out = y;
-  a.temb_stride = temb_stride; a.act = act; a.out_scale = out_scale;
-  a.B = B; a.D = D; a.H = H; a.W = W; a.C0 = C0; a.C1 = C1; a.Cout = Cout;
-
-  if (precision == CSD_PREC_F32 || C0 % 16 != 0) {      // exact yardstick; thin layers (the stem)
-    const size_t nw = (size_t)C3_TAPS * Cin * Cout;
-    hipLaunchKernelGGL(conv3d_pack_direct_kernel, dim3((unsigned)std::min<size_t>(cdiv64(nw, 256), 4096)), dim3(256), 0, s, weight,
-                       static_cast<float*>(wpack), Cin, Cout, nw);
-    CSD_LAUNCH_CHECK();
-    const size_t total = (size_t)B * vox * Cout;
-    const size_t nb = cdiv64(total, C3_THREADS);
-    CSD_REQUIRE(nb < ((size_t)1 << 31), "conv3d_block: %zu outputs exceed the direct kernel's grid", total);
-    hipLaunchKernelGGL(conv3d_direct_kernel, dim3((unsigned)nb), dim3(C3_THREADS), 0, s, a);
-    CSD_LAUNCH_CHECK();
-    return CSD_OK;
-  }
-
-  a.nck = Cin / C3_KC;
-  a.ntiles = cdiv(Cout, 32);
-  const int NT = a.ntiles >= 3 ? 4 : a.ntiles;
-  a.n_groups = cdiv(a.ntiles, NT);
-  if (W >= 3) { a.TD = 4; a.TH = 8; a.TW = 4; }
-  else { a.TD = 8; a.TH = 8; a.TW = 2; }
-  a.nbd = cdiv(D, a.TD); a.nbh = cdiv(H, a.TH); a.nbw = cdiv(W, a.TW);
-  const size_t nblocks = (size_t)B * a.nbd * a.nbh * a.nbw * a.n_groups;
-  CSD_REQUIRE(nblocks < ((size_t)1 << 31), "conv3d_block: %zu workgroups exceed the grid", nblocks);
-  const size_t nh = (size_t)a.ntiles * a.nck * C3_TAPS * 512;
-  hipLaunchKernelGGL(conv3d_pack_mfma_kernel, dim3((unsigned)std::min<size_t>(cdiv64(nh, 256), 4096)), dim3(256), 0, s, weight,
-                     static_cast<_Float16*>(wpack), Cin, Cout, a.nck, nh);
-  CSD_LAUNCH_CHECK();
-  const int npatch = (a.TD + 2) * (a.TH + 2) * (a.TW + 2);
-  const size_t lds = (size_t)2 * npatch * C3_PSB + (size_t)(C3_NPIX + npatch) * sizeof(int);
-  switch (NT) {
-    case 1: return conv3d_mfma_launch<1>(a, (int)nblocks, lds, s);
-    case 2: return conv3d_mfma_launch<2>(a, (int)nblocks, lds, s);
-    default: return conv3d_mfma_launch<4>(a, (int)nblocks, lds, s);
-  }
+  Conv3dCall c;
+  c.x0 = x0; c.x1 = x1; c.wpack = wpack; c.bias = bias; c.nscale = nscale; c.nshift = nshift; c.temb = temb; c.res = res; c.out = y;
+  c.temb_stride = temb_stride; c.act = act; c.out_scale = out_scale;
+  c.B = B; c.C0 = C0; c.C1 = C1; c.Cout = Cout; c.D = D; c.H = H; c.W = W; c.precision = precision;
+  const int rc = conv3d_pack_launch(weight, wpack, Cin, Cout, conv3d_is_direct(precision, C0), s);
+  if (rc) return rc;
+  return conv3d_launch(c, s);
 }
 
 extern "C" int csd_avgpool3d_2_ndhwc(const float* x, float* out, int B, int D, int H, int W, int C, void* stream) {

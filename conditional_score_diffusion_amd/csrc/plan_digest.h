@@ -24,7 +24,7 @@ struct Fnv {
 
 static uint64_t digest_params(const Net& n) {
   Fnv h;
-  for (const Param& p : n.params) { h.s(p.name); h.i(p.ndim); for (int64_t d : p.shape) h.i(d); }
+  for (const Param& p : n.params) { h.s(p.name); h.i(p.ndim); for (int j = 0; j < 4; ++j) h.i(p.shape[j]); }      // (4: arch 0 / 1 have no 5-D parameter)
   return h.h;
 }
 
@@ -86,6 +86,7 @@ static uint64_t digest_train(csd_unet* net, int B, float dropout_p) {
 // out: (a) parameter table, (b) packed layout, (c) inference plan for B, (d) training dry run for B (0 where there is none)
 extern "C" int csd_unet_debug_digest(csd_unet* net, int B, float dropout_p, uint64_t out[4]) {
   CSD_REQUIRE(net && out, "debug_digest: null argument");
+  CSD_REQUIRE(net->net.cfg.arch != 2, "debug_digest: the 3-D networks (arch 2) have no digest");
   Plan* pl = nullptr;
   const int rc = build_plan(net->net, B, &pl);
   if (rc) return rc;

@@ -1074,6 +1074,8 @@ struct TG {
 static int train_check(const csd_unet* net) {
   CSD_REQUIRE(net, "train: null handle");
   const csd_unet_config& c = net->net.cfg;
+  CSD_REQUIRE(c.arch != 2, "train graph: the 3-D networks (arch 2) have no planned training graph, input gradient or probability-flow "
+                           "right-hand side; they train on the per-operator path");
   CSD_REQUIRE(c.arch == 0 || c.arch == 1, "train graph: arch %d has no planned training graph", c.arch);
   if (c.arch == 0) CSD_REQUIRE(c.resamp_with_conv, "train graph: resamp_with_conv = False is not provided");
   CSD_REQUIRE((c.x_channels + c.y_channels) >= 1, "train graph: no input channels");

@@ -9,8 +9,9 @@
 // launches on ONE stream: no per-step host objects, no allocation, no synchronisation.
 //
 // One translation unit in pieces: this file (structs, the topology = build_modules, the parameter table, the C ABI, the PC sampler),
-// unet_layout.h (packed-weight layout + pack_all), unet_plan.h (Builder + build_plan), unet_run.h (run_plan), train_graph.h (training
-// forward / backward), plan_digest.h (csd_unet_debug_digest).
+// unet_layout.h (packed-weight layout + pack_all), unet_plan.h (Builder + build_plan), unet_run.h (run_plan), unet3d.h (the 3-D DDPM
+// family, arch 2: topology, packed layout, plan and executor on conv3d.hip's kernels), train_graph.h (training forward / backward),
+// plan_digest.h (csd_unet_debug_digest).
 #include <stdarg.h>
 #include <string.h>
 
@@ -76,7 +77,7 @@ struct ProfScope {
 struct Param {
   std::string name;
   int ndim;
-  int64_t shape[4];
+  int64_t shape[5];        // (5-D: the 3-D family's convolution weights)
   int64_t numel;
   const float* ptr = nullptr;
 };
@@ -168,6 +169,37 @@ struct Plan {
   double flops = 0, bytes = 0;
 };
 
+// ---- arch 2 (unet3d.h): one packed convolution weight, one launch (or GroupNorm launch pair) of the plan, the plan of one batch size ----
+struct Conv3Slot {
+  int param_w = -1, param_b = -1;
+  int cin = 0, c0 = 0, cout = 0;      // c0: channels of the first source (decides the kernel, like csd_conv3d_block's C0)
+  bool direct = false;
+  size_t off = 0;                     // float offset in the packed buffer
+};
+enum Op3Kind { O3_TEMB, O3_LINEAR, O3_STEM, O3_GN, O3_CONV, O3_POOL, O3_UP, O3_TO_NCDHW };
+struct Op3 {
+  Op3Kind kind;
+  size_t a = NONE, b = NONE, out = NONE;       // workspace float offsets: sources (b: the virtual concat's second), destination
+  size_t ns = NONE, nh = NONE;                 // GroupNorm scale / shift: O3_GN writes them, O3_CONV reads them
+  size_t res = NONE, partial = NONE;           // conv: residual; GroupNorm: its fp64 partial sums
+  size_t temb_col = NONE;                      // conv: first column of its Dense_0 rows inside dense_all
+  size_t pk_w = NONE, pk_b = NONE;             // linear over packed (concatenated) weights: float offsets in the packed buffer
+  int slot = -1;                               // conv / stem: its Conv3Slot
+  int pw = -1, pb = -1;                        // parameter indices: linear weight / bias, GroupNorm gamma / beta
+  int C0 = 0, C1 = 0, Cout = 0, D = 0, H = 0, W = 0, K = 0, N = 0, act = 0;
+  bool out_external = false;                   // writes the caller's output
+  int cls = CSD_PROF_OTHER;
+  double flops = 0, bytes = 0;
+};
+struct Plan3 {
+  int B = 0;
+  std::vector<Op3> ops;
+  size_t ws_floats = 0;
+  size_t dense_off = NONE;                     // [B, dense_total]: Dense_0(act(temb)) of every residual block
+  int64_t launches = 0;
+  double flops = 0, bytes = 0;
+};
+
 class Arena {
  public:
   Arena() {}
@@ -243,6 +275,10 @@ struct Net {
   std::vector<struct CopyDesc> copy_host;
   hipEvent_t copy_ev = nullptr;
   std::map<int, std::unique_ptr<Plan>> plans;
+  // arch 2 (unet3d.h)
+  std::vector<Conv3Slot> slots3;
+  std::map<std::string, int> slot3_by_name;          // "3.Conv_0", "2" ...
+  std::map<int, std::unique_ptr<Plan3>> plans3;
   int in_cpad = 8;
   // second stream for the ResnetBlock shortcut contraction (independent of the block's GroupNorm -> conv chain until the second conv
   // adds it): an HBM-bound pointwise kernel that fills the CUs a 3x3 launch leaves idle in its last round
@@ -292,7 +328,7 @@ struct Net {
     p.numel = 1;
     int i = 0;
     for (auto s : shape) { p.shape[i++] = s; p.numel *= s; }
-    for (; i < 4; ++i) p.shape[i] = 1;
+    for (; i < 5; ++i) p.shape[i] = 1;
     params.push_back(p);
     pindex[name] = (int)params.size() - 1;
     return (int)params.size() - 1;
@@ -489,6 +525,7 @@ static int build_modules(Net& n) {
 #include "unet_layout.h"
 #include "unet_plan.h"
 #include "unet_run.h"
+#include "unet3d.h"
 
 // =====================================================================================================
 // C ABI
@@ -547,9 +584,9 @@ extern "C" int csd_unet_create(const csd_unet_config* cfg, csd_unet** out) {
   CSD_REQUIRE(cfg && out, "unet_create: null argument");
   std::unique_ptr<csd_unet> h(new csd_unet());
   h->net.cfg = *cfg;
-  int rc = build_modules(h->net);
+  int rc = cfg->arch == 2 ? build_modules3d(h->net) : build_modules(h->net);
   if (rc) return rc;
-  rc = build_packed_layout(h->net);
+  rc = cfg->arch == 2 ? build_packed_layout3d(h->net) : build_packed_layout(h->net);
   if (rc) return rc;
   *out = h.release();
   return CSD_OK;
@@ -564,12 +601,12 @@ extern "C" void csd_unet_destroy(csd_unet* net) {
 
 extern "C" int csd_unet_num_params(const csd_unet* net) { return net ? (int)net->net.params.size() : 0; }
 
-extern "C" int csd_unet_param_info(const csd_unet* net, int index, const char** name, int* ndim, int64_t shape[4]) {
+extern "C" int csd_unet_param_info(const csd_unet* net, int index, const char** name, int* ndim, int64_t shape[]) {
   CSD_REQUIRE(net && index >= 0 && index < (int)net->net.params.size(), "param_info: index %d out of range", index);
   const Param& p = net->net.params[index];
   if (name) *name = p.name.c_str();
   if (ndim) *ndim = p.ndim;
-  if (shape) for (int i = 0; i < 4; ++i) shape[i] = p.shape[i];
+  if (shape) for (int i = 0; i < (is3d(net->net) ? 5 : 4); ++i) shape[i] = p.shape[i];
   return CSD_OK;
 }
 
@@ -590,11 +627,16 @@ extern "C" size_t csd_unet_packed_bytes(const csd_unet* net) { return net ? net-
 extern "C" int csd_unet_pack(csd_unet* net, void* packed, void* stream) {
   CSD_REQUIRE(net && packed, "pack: null argument");
   CSD_REQUIRE((reinterpret_cast<uintptr_t>(packed) & 255) == 0, "pack: packed buffer must be 256-byte aligned");
+  if (is3d(net->net)) return pack_all3d(net->net, static_cast<float*>(packed), (hipStream_t)stream);
   return pack_all(net->net, static_cast<float*>(packed), (hipStream_t)stream);
 }
 
 extern "C" size_t csd_unet_workspace_bytes(csd_unet* net, int B) {
   if (!net) return 0;
+  if (is3d(net->net)) {
+    Plan3* p3 = nullptr;
+    return build_plan3d(net->net, B, &p3) ? 0 : p3->ws_floats * sizeof(float);
+  }
   Plan* pl = nullptr;
   if (build_plan(net->net, B, &pl)) return 0;
   return pl->ws_floats * sizeof(float);
@@ -602,6 +644,15 @@ extern "C" size_t csd_unet_workspace_bytes(csd_unet* net, int B) {
 
 extern "C" int csd_unet_stats(csd_unet* net, int B, int64_t* launches, double* flops, double* bytes) {
   CSD_REQUIRE(net, "stats: null handle");
+  if (is3d(net->net)) {
+    Plan3* p3 = nullptr;
+    const int rc3 = build_plan3d(net->net, B, &p3);
+    if (rc3) return rc3;
+    if (launches) *launches = p3->launches;
+    if (flops) *flops = p3->flops;
+    if (bytes) *bytes = p3->bytes;
+    return CSD_OK;
+  }
   Plan* pl = nullptr;
   int rc = build_plan(net->net, B, &pl);
   if (rc) return rc;
@@ -611,14 +662,28 @@ extern "C" int csd_unet_stats(csd_unet* net, int B, int64_t* launches, double* f
   return CSD_OK;
 }
 
-static int check_forward_args(csd_unet* net, const void* packed, void* ws, size_t ws_bytes, int B, Plan** pl) {
+// one validated "evaluate the network at batch B" of a handle: the 2-D plan (arch 0 / 1) or the 3-D plan (arch 2)
+struct Evaluator {
+  Net* n = nullptr;
+  Plan* pl = nullptr;
+  Plan3* p3 = nullptr;
+  int run(const float* pk, float* ws, const float* x, const float* y, const float* labels, float* out, const float* y_noise, float y_sigma,
+          hipStream_t s) const {
+    if (p3) return run_plan3d(*n, *p3, pk, ws, x, y, labels, out, y_noise, y_sigma, s);
+    return run_plan(*n, *pl, pk, ws, x, y, labels, out, y_noise, y_sigma, s);
+  }
+};
+
+static int check_forward_args(csd_unet* net, const void* packed, void* ws, size_t ws_bytes, int B, Evaluator* ev) {
   CSD_REQUIRE(net && packed && ws, "forward: null argument");
   if (!net->net.packed_once) { set_error("forward: csd_unet_pack has not been called"); return CSD_ERR_STATE; }
   CSD_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 255) == 0, "forward: workspace must be 256-byte aligned");
-  int rc = build_plan(net->net, B, pl);
+  ev->n = &net->net;
+  int rc = is3d(net->net) ? build_plan3d(net->net, B, &ev->p3) : build_plan(net->net, B, &ev->pl);
   if (rc) return rc;
-  if (ws_bytes < (*pl)->ws_floats * sizeof(float)) {
-    set_error("forward: workspace too small (%zu < %zu bytes)", ws_bytes, (*pl)->ws_floats * sizeof(float));
+  const size_t need = (ev->p3 ? ev->p3->ws_floats : ev->pl->ws_floats) * sizeof(float);
+  if (ws_bytes < need) {
+    set_error("forward: workspace too small (%zu < %zu bytes)", ws_bytes, need);
     return CSD_ERR_WORKSPACE;
   }
   return CSD_OK;
@@ -627,23 +692,24 @@ static int check_forward_args(csd_unet* net, const void* packed, void* ws, size_
 extern "C" int csd_unet_forward(csd_unet* net, const void* packed, void* workspace, size_t workspace_bytes,
                                 const float* x, const float* y, const float* labels, float* out, int B,
                                 const float* y_noise, float y_sigma, void* stream) {
-  Plan* pl = nullptr;
-  int rc = check_forward_args(net, packed, workspace, workspace_bytes, B, &pl);
+  Evaluator ev;
+  int rc = check_forward_args(net, packed, workspace, workspace_bytes, B, &ev);
   if (rc) return rc;
   CSD_REQUIRE(x && out, "forward: null x/out");
   CSD_REQUIRE((net->net.cfg.y_channels == 0) == (y == nullptr), "forward: y must be given iff y_channels > 0");
   CSD_REQUIRE(!net->net.cfg.conditional || labels, "forward: labels required for a conditional network");
-  return run_plan(net->net, *pl, static_cast<const float*>(packed), static_cast<float*>(workspace), x, y, labels,
-                  out, y_noise, y_sigma, (hipStream_t)stream);
+  return ev.run(static_cast<const float*>(packed), static_cast<float*>(workspace), x, y, labels, out, y_noise, y_sigma,
+                (hipStream_t)stream);
 }
 
 // ---- fused PC sampler -------------------------------------------------------------------------------
+// HW below is the per-sample element count of one channel (sample_elems): image_size^2, or D*H*W for the 3-D family.
 // scratch layout (floats): net_out [B*Co*HW] | x_mean [B*Cx*HW] | z [B*Cx*HW] | zy [B*Cy*HW] | labels [B]
 //                          | partial (double) [B*64*2]
 extern "C" size_t csd_pc_scratch_bytes(const csd_unet* net, int B) {
   if (!net) return 0;
   const csd_unet_config& c = net->net.cfg;
-  const size_t hw = (size_t)c.image_size * c.image_size;
+  const size_t hw = sample_elems(c);
   size_t fl = 0;
   fl += align_up((size_t)B * c.out_channels * hw, 64);
   fl += 2 * align_up((size_t)B * c.x_channels * hw, 64);
@@ -660,7 +726,7 @@ __global__ void fill_labels_kernel(float* dst, float v, int B) {
 
 // one validated view of a csd_pc_* call: scratch carved up, noise bookkeeping per step
 struct PCCtx {
-  Net* n; Plan* pl; const float* pk; float* ws;
+  Evaluator ev; const float* pk; float* ws;
   float *net_out, *x_mean, *z, *zy, *labels, *ystate;
   double* partial;
   int* nonfinite;                                    // device flag of the finiteness contract (behind the norm partials)
@@ -716,8 +782,8 @@ struct PCCtx {
 static int pc_setup(PCCtx* c, csd_unet* net, const void* packed, void* workspace, size_t workspace_bytes, void* scratch,
                     size_t scratch_bytes, float* x, const float* y, int B, const csd_pc_params* p, void* stream,
                     const csd_pc_inpaint_params* ip = nullptr, bool inpaint = false) {
-  Plan* pl = nullptr;
-  int rc = check_forward_args(net, packed, workspace, workspace_bytes, B, &pl);
+  CSD_REQUIRE(!(inpaint && net && is3d(net->net)), "pc_inpaint: inpainting is not provided for the 3-D networks (arch 2) on the device loop");
+  int rc = check_forward_args(net, packed, workspace, workspace_bytes, B, &c->ev);
   if (rc) return rc;
   CSD_REQUIRE(p && x && scratch, "pc_sample: null argument");
   CSD_REQUIRE(p->n_steps >= 1 && p->labels && p->std_x, "pc_sample: per-step scalar arrays missing");
@@ -738,8 +804,8 @@ static int pc_setup(PCCtx* c, csd_unet* net, const void* packed, void* workspace
     return CSD_ERR_WORKSPACE;
   }
   CSD_REQUIRE((reinterpret_cast<uintptr_t>(scratch) & 255) == 0, "pc_sample: scratch must be 256-byte aligned");
-  const size_t hw = (size_t)cf.image_size * cf.image_size;
-  c->n = &net->net; c->pl = pl; c->pk = static_cast<const float*>(packed); c->ws = static_cast<float*>(workspace);
+  const size_t hw = sample_elems(cf);
+  c->pk = static_cast<const float*>(packed); c->ws = static_cast<float*>(workspace);
   c->p = p; c->x = x; c->y = y; c->B = B; c->s = (hipStream_t)stream;
   if (inpaint) {
     CSD_REQUIRE(ip && ip->data && ip->mask && ip->mean_scale && ip->std, "pc_inpaint: data, mask, mean_scale and std are required");
@@ -803,7 +869,7 @@ static int pc_phase(const PCCtx& c, int i, int phase, int part, float* sums_out,
     }
     const float* zyp = nullptr;
     if (c.perturb_y) { zyp = c.noise(i, k0, c.zy, c.ny); if (!zyp) return CSD_ERR_HIP; }
-    rc = run_plan(*c.n, *c.pl, c.pk, c.ws, c.x, c.path ? c.ystate : c.y, c.labels, c.net_out, zyp, c.perturb_y ? p->std_y[i] : 0.f, c.s);
+    rc = c.ev.run(c.pk, c.ws, c.x, c.path ? c.ystate : c.y, c.labels, c.net_out, zyp, c.perturb_y ? p->std_y[i] : 0.f, c.s);
     if (rc) return rc;
     zp = c.path ? c.noise_path(i, kp, c.z, c.nx) : c.noise(i, k0 + (c.perturb_y ? 1 : 0), c.z, c.nx);
     if (!zp) return CSD_ERR_HIP;

@@ -183,7 +183,9 @@ class GradSync:
         all-reduce on a communication stream that waits for ITS event only: the late layers' gradients are reduced while the
         backward of the early layers still runs.  Without a process group (or off the GPU) nothing is registered."""
         self._model, self._events, self._comm, self._epoch = None, None, None, 0
-        if not self.grouped or not self.flat.grad.is_cuda or getattr(model, '_h', None) is None:
+        from .models.ddpm import HipUNet
+        # (a planned 3-D network owns a handle too, but trains on the per-operator path: it has no planned backward to mark)
+        if not self.grouped or not self.flat.grad.is_cuda or getattr(model, '_h', None) is None or not isinstance(model, HipUNet):
             return False
         from ._lib import check, lib
         # names of the FLAT buffer's parameters, in its order (a frozen parameter is not in it: indices into the model's full

@@ -40,7 +40,58 @@ def _fan_avg_uniform(shape, scale, is_nin):
     return (torch.rand(*shape) * 2. - 1.) * math.sqrt(3 * var)
 
 
-class HipUNet(nn.Module):
+class _HandleSurface:
+    """What a network that owns a ``csd_unet`` handle offers to its callers (``sampling/fused.py``, the likelihood, the benches): the
+    handle ``_h``, the packed weights ``_packed`` (``_ensure_packed()`` packs again when a parameter moved or changed), the activation
+    workspace ``_workspace(B)`` and ``stats(B)``.  Expects ``_h``, ``_param_names``, ``_packed``, ``_packed_key``, ``_ws`` and ``device``
+    on the instance.  Every byte buffer comes from ``ops._scratch``."""
+
+    def __del__(self):
+        try:
+            if getattr(self, '_h', None):
+                lib().csd_unet_destroy(self._h)
+                self._h = None
+        except Exception:
+            pass
+
+    # -- packing -----------------------------------------------------------------------------------
+    def _ensure_packed(self):
+        params = dict(self.named_parameters())
+        key = (_lib.WEIGHT_EPOCH[0],) + tuple((p.data_ptr(), p._version) for p in params.values())
+        if self._packed is not None and key == self._packed_key:
+            return
+        dev = self.device
+        if dev.type != 'cuda':
+            raise RuntimeError('the HIP score network runs on the MI355X only: move the model with .to("cuda") '
+                               '(parameters are on %s); there is no CPU fallback' % dev)
+        for name in self._param_names:
+            p = params[name]
+            if p.dtype != torch.float32 or not p.is_contiguous():
+                raise RuntimeError('parameter %s must be contiguous float32' % name)
+            check(lib().csd_unet_set_param(self._h, name.encode(), ctypes.c_void_p(p.data_ptr()), p.numel()),
+                  'set_param')
+        nbytes = lib().csd_unet_packed_bytes(self._h)
+        if self._packed is None or self._packed.numel() < nbytes or self._packed.device != dev:
+            self._packed = ops._scratch(nbytes, dev)
+        check(lib().csd_unet_pack(self._h, ptr(self._packed), current_stream(dev)), 'unet_pack')
+        self._packed_key = key
+
+    def _workspace(self, B):
+        need = lib().csd_unet_workspace_bytes(self._h, B)
+        if need == 0:
+            raise RuntimeError('libcsd_hip: cannot plan batch %d: %s' % (B, lib().csd_last_error().decode()))
+        if self._ws is None or self._ws.numel() < need or self._ws.device != self.device:
+            self._ws = ops._scratch(need, self.device)
+        return self._ws
+
+    def stats(self, B):
+        """(kernel launches, algorithmic FLOPs, algorithmic bytes) of one evaluation at batch B."""
+        n, fl, by = ctypes.c_int64(), ctypes.c_double(), ctypes.c_double()
+        check(lib().csd_unet_stats(self._h, B, ctypes.byref(n), ctypes.byref(fl), ctypes.byref(by)), 'unet_stats')
+        return n.value, fl.value, by.value
+
+
+class HipUNet(nn.Module, _HandleSurface):
     """Base adapter. Subclasses fix (x_channels, y_channels) conventions."""
 
     arch = 0
@@ -159,50 +210,6 @@ class HipUNet(nn.Module):
     @property
     def device(self):
         return next(self.parameters()).device
-
-    def __del__(self):
-        try:
-            if getattr(self, '_h', None):
-                lib().csd_unet_destroy(self._h)
-                self._h = None
-        except Exception:
-            pass
-
-    # -- packing -----------------------------------------------------------------------------------
-    def _ensure_packed(self):
-        params = dict(self.named_parameters())
-        key = (_lib.WEIGHT_EPOCH[0],) + tuple((p.data_ptr(), p._version) for p in params.values())
-        if self._packed is not None and key == self._packed_key:
-            return
-        dev = self.device
-        if dev.type != 'cuda':
-            raise RuntimeError('the HIP score network runs on the MI355X only: move the model with .to("cuda") '
-                               '(parameters are on %s); there is no CPU fallback' % dev)
-        for name in self._param_names:
-            p = params[name]
-            if p.dtype != torch.float32 or not p.is_contiguous():
-                raise RuntimeError('parameter %s must be contiguous float32' % name)
-            check(lib().csd_unet_set_param(self._h, name.encode(), ctypes.c_void_p(p.data_ptr()), p.numel()),
-                  'set_param')
-        nbytes = lib().csd_unet_packed_bytes(self._h)
-        if self._packed is None or self._packed.numel() < nbytes or self._packed.device != dev:
-            self._packed = ops._scratch(nbytes, dev)
-        check(lib().csd_unet_pack(self._h, ptr(self._packed), current_stream(dev)), 'unet_pack')
-        self._packed_key = key
-
-    def _workspace(self, B):
-        need = lib().csd_unet_workspace_bytes(self._h, B)
-        if need == 0:
-            raise RuntimeError('libcsd_hip: cannot plan batch %d: %s' % (B, lib().csd_last_error().decode()))
-        if self._ws is None or self._ws.numel() < need or self._ws.device != self.device:
-            self._ws = ops._scratch(need, self.device)
-        return self._ws
-
-    def stats(self, B):
-        """(kernel launches, algorithmic FLOPs, algorithmic bytes) of one evaluation at batch B."""
-        n, fl, by = ctypes.c_int64(), ctypes.c_double(), ctypes.c_double()
-        check(lib().csd_unet_stats(self._h, B, ctypes.byref(n), ctypes.byref(fl), ctypes.byref(by)), 'unet_stats')
-        return n.value, fl.value, by.value
 
     # -- evaluation --------------------------------------------------------------------------------
     def _run(self, x, y, labels, y_noise=None, y_sigma=0.0):

@@ -22,7 +22,17 @@ Refused, with the reason (never a silent fallback):
   ``conditional=False``       the reference raises NameError (its module list is only created under ``if conditional``)
   an odd extent at a pooled level, precisions other than fp32 / fp16x3 (ValueError)
   training mode and input gradients on CPU tensors (there is no CPU path); the likelihood of the 3-D networks is not provided
-Sampling runs on the step-by-step predictor / corrector loop (``sampling.fused.fusable`` is False for these classes).
+By default sampling runs on the step-by-step predictor / corrector loop (``sampling.fused.fusable`` is False for a default model).
+
+The planned path (opt-in: ``config.model.csd_planned = True``, the constructor argument ``planned=True`` or ``$CSD_PLANNED=1``): the model
+creates a ``csd_unet`` handle (``csd_unet_config.arch = 2``) for the volume ``config.data.shape_x[1:]`` at construction.  In eval mode
+without input gradients ``forward`` is then ONE ``csd_unet_forward``: the weights are packed once (and again when a parameter changes),
+every buffer lies at a fixed offset of one workspace, x and y go in separately as NCDHW (no torch ``cat`` / ``permute`` / ``axpby``), the
+result is bitwise the operator path's.  ``sampling.fused.fusable`` accepts such a model, so the PC samplers run volumes on the fused
+device loop (``csd_pc_sample``).  A forward on another volume raises ValueError (the operator path accepts any volume); construction
+refuses what the library refuses (an odd pooled extent of the configured volume, a ``ch_mult`` whose up path has a block without
+Conv_2).  Training mode and input gradients keep ``_grad_forward``.  Inpainting, the likelihood and the ODE sampler on the device are not
+provided for the 3-D networks.  Making the planned path the default is a separate, later decision.
 
 Training and input gradients (GPU tensors): in training mode, and in eval mode when ``x.requires_grad`` under autograd, the forward is
 the differentiable, operator-granular one (``_grad_forward``): the layers of ResnetBlockDDPM as grad_ops_3d / grad_ops autograd nodes
@@ -33,23 +43,24 @@ movement; autograd splits the gradient), the boundary permutes stay torch.  Drop
 ``dropout_seed`` and the stream id ``_train_calls << 16 | index`` (the scheme of ddpm.py's operator path); dropout is off in eval
 mode.  For the paired classes only ``x`` takes a gradient.  The inference forward is not touched by any of this.
 """
+import ctypes
 import os
 
 import torch
 import torch.nn as nn
 
 from .. import _lib, ops
-from .._lib import require_gpu_tensor
+from .._lib import check, current_stream, lib, ptr, require_gpu_tensor
 from . import utils
-from .ddpm import _Node, _fan_avg_uniform
+from .ddpm import _HandleSurface, _Node, _fan_avg_uniform
 
 _PRECISIONS = ('fp32', 'f32', 'fp16x3')
 
 
-class DDPM3D(nn.Module):
+class DDPM3D(nn.Module, _HandleSurface):
     """``ddpm3D`` (models/ddpm3D.py:38-171): model(x [B, C, D, H, W], labels [B]) -> [B, output_channels, D, H, W]."""
 
-    def __init__(self, config, precision=None):
+    def __init__(self, config, precision=None, planned=None):
         super().__init__()
         m, d = config.model, config.data
         get = (lambda k, dflt=None: m.get(k, dflt)) if hasattr(m, 'get') else (lambda k, dflt=None: getattr(m, k, dflt))
@@ -114,6 +125,92 @@ class DDPM3D(nn.Module):
         mods.append(('conv', dict(cin=in_ch, cout=self.output_channels, init_scale=0.)))
         self._mods = mods
         self.all_modules = nn.ModuleList([self._make_node(k, a) for k, a in mods])
+        if planned is None:
+            planned = get('csd_planned')
+        if planned is None:
+            planned = os.environ.get('CSD_PLANNED', '0').strip().lower() not in ('', '0', 'false', 'no', 'off')
+        self.planned = bool(planned)
+        self._h = self._packed = self._packed_key = self._ws = None
+        if self.planned:
+            self._create_handle(config)
+
+    # ---- the planned path: one csd_unet handle (arch 2) for the configured volume ----
+    def _channels(self, config):
+        """(x channels, y channels) of the network input"""
+        return int(config.model.input_channels), 0
+
+    def _create_handle(self, config):
+        m, d = config.model, config.data
+        vol = tuple(int(v) for v in d.shape_x[1:])
+        if len(vol) != 3:
+            raise ValueError('ddpm3D (planned): config.data.shape_x = %s is not [C, D, H, W]' % (list(d.shape_x),))
+        for lvl in range(self.num_resolutions - 1):
+            if any((e >> lvl) % 2 or (e >> lvl) < 2 for e in vol):
+                raise ValueError('ddpm3D (planned): the configured volume %s has an odd extent at level %d, which the 2x2x2 average pool '
+                                 'cannot halve' % (vol, lvl))
+        self.volume = vol
+        self.x_channels, self.y_channels = self._channels(config)
+        if self.x_channels + self.y_channels != self.input_channels:
+            raise ValueError('ddpm3D (planned): shape_x[0] + shape_y[0] = %d + %d channels, the network takes input_channels = %d'
+                             % (self.x_channels, self.y_channels, self.input_channels))
+        cfg = _lib.UNetConfig()
+        cfg.arch = 2
+        cfg.nf = self.nf
+        cfg.n_levels = self.num_resolutions
+        for i, v in enumerate(m.ch_mult):
+            cfg.ch_mult[i] = int(v)
+        cfg.num_res_blocks = self.num_res_blocks
+        cfg.x_channels, cfg.y_channels, cfg.out_channels = self.x_channels, self.y_channels, int(self.output_channels)
+        cfg.resamp_with_conv, cfg.conditional, cfg.centered = 0, 1, int(self.centered)
+        cfg.act = _lib.ACT_IDS[self.act]
+        cfg.precision = _lib.PREC_IDS[self.precision]
+        for i in range(3):
+            cfg.vol[i] = vol[i]
+        self._cfg = cfg
+        h = ctypes.c_void_p()
+        check(lib().csd_unet_create(ctypes.byref(cfg), ctypes.byref(h)), 'unet_create')
+        self._h = h
+        # the library rebuilds the module list from the config: its parameter table must be this module's state_dict
+        name, ndim, shape = ctypes.c_char_p(), ctypes.c_int(), (ctypes.c_int64 * 5)()
+        table = []
+        for i in range(lib().csd_unet_num_params(h)):
+            check(lib().csd_unet_param_info(h, i, ctypes.byref(name), ctypes.byref(ndim), shape), 'param_info')
+            table.append((name.value.decode(), tuple(shape[j] for j in range(ndim.value))))
+        mine = [(k, tuple(p.shape)) for k, p in self.named_parameters()]
+        if table != mine:
+            raise RuntimeError('ddpm3D (planned): the library\'s parameter table differs from the module\'s state_dict')
+        self._param_names = [k for k, _ in table]
+
+    def _use_plan(self, x):
+        """eval mode without input gradients: the planned evaluation; training mode and x.requires_grad keep _grad_forward"""
+        want_grad = torch.is_grad_enabled() and x.requires_grad
+        return self.planned and not ((self.training and torch.is_grad_enabled()) or want_grad)
+
+    def _planned_forward(self, x, y, labels):
+        """one csd_unet_forward: x [B, Cx, D, H, W], y [B, Cy, D, H, W] or None -> [B, output_channels, D, H, W]"""
+        vol = self.volume
+        if x.dim() != 5 or x.shape[1] != self.x_channels:
+            raise ValueError('ddpm3D: input %s is not [B, %d, D, H, W]' % (tuple(x.shape), self.x_channels))
+        if tuple(x.shape[2:]) != vol:
+            raise ValueError('ddpm3D (planned): the input volume %s is not the configured volume %s (config.data.shape_x[1:]), for which '
+                             'the plan was made; the operator path (csd_planned = False) accepts any volume' % (tuple(x.shape[2:]), vol))
+        require_gpu_tensor(x, 'x')
+        require_gpu_tensor(labels, 'labels')
+        B = x.shape[0]
+        if self.y_channels:
+            require_gpu_tensor(y, 'y')
+            if tuple(y.shape) != (B, self.y_channels) + vol:
+                raise ValueError('ddpm3D: y %s is not %s' % (tuple(y.shape), (B, self.y_channels) + vol))
+            y = y.contiguous()
+        labels = labels.contiguous()
+        if tuple(labels.shape) != (B,):
+            raise ValueError('ddpm3D: labels must have shape [%d]' % B)
+        self._ensure_packed()
+        ws = self._workspace(B)
+        out = ops._out((B, int(self.output_channels)) + vol, torch.float32, x.device)
+        check(lib().csd_unet_forward(self._h, ptr(self._packed), ptr(ws), ws.numel(), ptr(x.contiguous()), ptr(y) if self.y_channels else None,
+                                     ptr(labels), ptr(out), B, None, 0.0, current_stream(x.device)), 'unet_forward')
+        return out
 
     # ---- parameters: names, shapes and initialisation of the reference ----
     def _make_node(self, kind, a):
@@ -167,6 +264,8 @@ class DDPM3D(nn.Module):
 
     # ---- forward: DDPM3D.forward (models/ddpm3D.py:107-171) ----
     def forward(self, x, labels):
+        if self._use_plan(x) and not (self.training and not x.is_cuda):
+            return self._planned_forward(x, None, labels)
         want_grad = torch.is_grad_enabled() and x.requires_grad
         if (self.training or want_grad) and not x.is_cuda:
             if self.training:
@@ -280,21 +379,32 @@ class DDPM3D(nn.Module):
         return h.permute(0, 4, 1, 2, 3).contiguous()                     # NDHWC -> NCDHW
 
 
-class DDPM3D_paired(DDPM3D):
+class _Paired3D(DDPM3D):
+    def _channels(self, config):
+        return int(config.data.shape_x[0]), int(config.data.shape_y[0])
+
+    def _paired(self, x, y, labels):
+        """the network on (x, y): planned, x and y go to the library separately; else the concatenated input on the operator path"""
+        if self._use_plan(x) and not (self.training and not x.is_cuda):
+            return self._planned_forward(x, y, labels)
+        return DDPM3D.forward(self, torch.cat((x, y), dim=1), labels)
+
+
+class DDPM3D_paired(_Paired3D):
     """``ddpm3D_paired`` (models/ddpm3D.py:173-184): concatenates x and y, returns both halves."""
 
     def forward(self, input_dict, labels):
         x, y = input_dict['x'], input_dict['y']
         xc = x.size(1)
-        out = super().forward(torch.cat((x, y), dim=1), labels)
+        out = self._paired(x, y, labels)
         return {'x': out[:, :xc], 'y': out[:, xc:]}
 
 
-class DDPM3D_paired_SR3(DDPM3D):
+class DDPM3D_paired_SR3(_Paired3D):
     """``ddpm3D_paired_SR3`` (models/ddpm3D.py:186-196): concatenates x and y, returns the score of x."""
 
     def forward(self, input_dict, labels):
-        return super().forward(torch.cat((input_dict['x'], input_dict['y']), dim=1), labels)
+        return self._paired(input_dict['x'], input_dict['y'], labels)
 
 
 utils.register_model(DDPM3D, name='ddpm3D')

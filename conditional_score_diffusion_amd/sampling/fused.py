@@ -47,8 +47,10 @@ _VP_FAMILY = _VP + (sde_lib.subVPSDE,)
 def fusable(model, sde, predictor, corrector, c_steps, probability_flow, continuous, use_path=False):
     """True when (model, sde, predictor, corrector) runs on the fused device loop: a VE SDE (or the two-SDE VE pair), a VPSDE, cVPSDE
     or subVPSDE with any registered predictor (reverse diffusion, Euler-Maruyama, ancestral sampling, none) and corrector (Langevin,
-    annealed Langevin dynamics, none) that the SDE's class supports in the step-by-step classes."""
+    annealed Langevin dynamics, none) that the SDE's class supports in the step-by-step classes.  The model is a HipUNet or a planned
+    3-D network (models/ddpm3d.py with ``csd_planned``): both own a csd_unet handle that the loop evaluates."""
     from ..models.ddpm import HipUNet
+    from ..models.ddpm3d import DDPM3D
     from . import predictors as P
     c_sde = sde['x'] if isinstance(sde, dict) else sde
     if isinstance(sde, dict):                   # the two-SDE setting: VE members only (models/utils.py:171-188 refuses the others)
@@ -68,7 +70,8 @@ def fusable(model, sde, predictor, corrector, c_steps, probability_flow, continu
     ok_time = continuous or isinstance(c_sde, _VP_FAMILY)
     # use_path (the bridge for y_t): two-SDE setting only
     ok_path = (not use_path) or isinstance(sde, dict)
-    return (isinstance(model, HipUNet) and ok_sde and c_steps == 1 and ok_pf and ok_time and ok_path)
+    ok_model = isinstance(model, HipUNet) or (isinstance(model, DDPM3D) and model.planned)
+    return (ok_model and ok_sde and c_steps == 1 and ok_pf and ok_time and ok_path)
 
 
 def _index(c_sde, t1):
@@ -237,6 +240,8 @@ def run(model, sde, shape, y, p_steps, snr, eps, denoise, noise_tape=None, seed=
     ``torch.distributed.all_reduce``) - no host synchronisation anywhere."""
     if seed is None:
         seed = fresh_seed()
+    if inpaint is not None and len(shape) == 5:
+        raise NotImplementedError('inpainting on the device loop is not provided for the 3-D networks (csd_pc_inpaint_* refuse them)')
     c_sde = sde['x'] if isinstance(sde, dict) else sde
     dev = model.device
     if dev.type != 'cuda':

@@ -90,7 +90,8 @@ int csd_profile_stop_ex(int n_classes, double* ms, int64_t* launches, double* fl
 #define CSD_MAX_ATTN 8
 
 typedef struct csd_unet_config {
-  int32_t arch;                 /* 0 = DDPM family (models/ddpm.py); 1 = NCSN++ (models/ncsnpp.py), see below */
+  int32_t arch;                 /* 0 = DDPM family (models/ddpm.py); 1 = NCSN++ (models/ncsnpp.py); 2 = 3-D DDPM family
+                                   (models/ddpm3D.py), see below */
   int32_t nf;                   /* config.model.nf                                           */
   int32_t n_levels;             /* len(config.model.ch_mult)                                 */
   int32_t ch_mult[CSD_MAX_LEVELS];
@@ -114,7 +115,23 @@ typedef struct csd_unet_config {
   int32_t embedding_type;       /* 0 'positional', 1 'fourier' (W [nf] is parameter all_modules.0.W) */
   int32_t n_fir;                /* taps of config.model.fir_kernel (<= 8)                    */
   float fir_kernel[8];
+  /* ---- arch 2 (3-D DDPM family, models/ddpm3D.py) only: the extents of the volume behind the channel, D, H, W (config.data.shape_x[1:]).
+   * arch 2 ignores image_size, the attention fields and the arch-1 fields above; arch 0 / 1 ignore vol. ---- */
+  int32_t vol[3];
 } csd_unet_config;
+
+/* arch 2: x [B, x_channels, D, H, W], y [B, y_channels, D, H, W] (NULL iff y_channels == 0; ddpm3D has none, the paired classes take
+ * both counts from shape_x[0] / shape_y[0]), out [B, out_channels, D, H, W], all NCDHW.  The handle serves csd_unet_create / destroy,
+ * num_params / param_info / set_param, packed_bytes / pack / workspace_bytes, forward / stats and csd_pc_scratch_bytes / csd_pc_sample /
+ * csd_pc_step_begin / csd_pc_step_end with unchanged signatures: csd_unet_pack runs csd_conv3d_block's weight pack once per layer,
+ * csd_unet_forward is the layer list of DDPM3D.forward on the kernels of csd_conv3d_block / csd_groupnorm_scale_shift /
+ * csd_avgpool3d_2_ndhwc / csd_nearest_up2_3d_ndhwc at fixed workspace offsets (bitwise what the per-operator calls give, repeatable,
+ * independent of the batch position).  csd_unet_create refuses, with the reason: resamp_with_conv, conditional = 0, nf % 32 != 0, an
+ * extent that is odd or below 2 at a pooled level, a precision other than CSD_PREC_F32 / CSD_PREC_F16X3, and a ch_mult for which an up
+ * block's concatenated input is as wide as its output (that block has no Conv_2).  The training entries (csd_unet_train_*,
+ * csd_unet_backward*), csd_pc_inpaint_* and csd_unet_debug_digest return CSD_ERR_INVALID for an arch-2 handle (csd_unet_train_workspace_bytes
+ * returns 0) with a message that names 3-D; the probability-flow entries (csd_pf_ode_*) take no handle and their callers go through the
+ * training entries. */
 
 typedef struct csd_unet csd_unet;
 
@@ -122,9 +139,10 @@ int csd_unet_create(const csd_unet_config* cfg, csd_unet** out);
 void csd_unet_destroy(csd_unet* net);
 
 /* Parameter table, in reference state_dict order/naming ("all_modules.3.Conv_0.weight", ...).
- * Layouts are the reference's: conv OIHW, NIN.W [in,out], Linear [out,in]. */
+ * Layouts are the reference's: conv OIHW, NIN.W [in,out], Linear [out,in].  arch 0 / 1: `shape` receives 4 entries.  arch 2: the
+ * convolution weights are [Cout, Cin, 3, 3, 3] (ndim 5) and `shape` must hold 5 entries (all 5 are written for every parameter). */
 int csd_unet_num_params(const csd_unet* net);
-int csd_unet_param_info(const csd_unet* net, int index, const char** name, int* ndim, int64_t shape[4]);
+int csd_unet_param_info(const csd_unet* net, int index, const char** name, int* ndim, int64_t shape[]);
 /* Register the device address of one parameter (fp32, contiguous, reference layout). */
 int csd_unet_set_param(csd_unet* net, const char* name, const void* dev_ptr, int64_t numel);
 
@@ -138,7 +156,7 @@ size_t csd_unet_workspace_bytes(csd_unet* net, int B);
 
 /* One network evaluation = model(x | {'x','y'}, labels) of models/utils.py:134-150 in eval mode.
  *   x      [B, x_channels, S, S]   y [B, y_channels, S, S] (NULL iff y_channels == 0)
- *   labels [B]                     out [B, out_channels, S, S]
+ *   labels [B]                     out [B, out_channels, S, S]          (arch 2: D, H, W in place of S, S)
  *   y_noise/y_sigma: optional fused perturbation y_t = y + y_sigma * y_noise
  *                    (sampling/conditional.py:104-110); pass NULL / 0 to use y as is. */
 int csd_unet_forward(csd_unet* net, const void* packed, void* workspace, size_t workspace_bytes,
@@ -192,7 +210,8 @@ typedef struct csd_pc_params {
 } csd_pc_params;
 
 /* x: [B, x_channels, S, S] in: prior sample (VE: already scaled by sigma_max); out: result.
- * y: [B, y_channels, S, S] or NULL.  scratch: csd_pc_scratch_bytes() device bytes.
+ * y: [B, y_channels, S, S] or NULL.  scratch: csd_pc_scratch_bytes() device bytes.  An arch-2 handle runs the same loop on volumes
+ * ([.., D, H, W] in place of [.., S, S]): same update kernels, noise order, tape layout, Philox stream numbering and contract.
  * Finiteness contract: the Langevin corrector's norms (which see every element of the score and of the noise) and one pass over the
  * returned state set a device flag; csd_pc_sample reads it back behind the stream before it returns - its ONE synchronisation - and
  * fails with CSD_ERR_NONFINITE rather than hand back NaN images (csd_pc_step_end does the same after the last step). */

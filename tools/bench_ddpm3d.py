@@ -2,7 +2,7 @@
 (configs/ve/inverse_problems/MRI_to_PET/MRI_to_PET_slices3D.py): ``ddpm3D_paired``, B = 4, 2 x 96 x 96 x 16, nf 64, ch_mult (1, 1, 2, 2),
 2 residual blocks per level, swish, fp16x3.
 
-    python tools/bench_ddpm3d.py [--batch 4] [--warmup 2] [--repeats 5] [--evals 3] [--small]
+    python tools/bench_ddpm3d.py [--batch 4] [--warmup 2] [--repeats 5] [--evals 3] [--small] [--train | --planned]
 
 Writes profiles/ddpm3d_bench.json (``--out`` to change) and prints it:
   network      evaluations per second: `repeats` windows of `evals` forwards each between device synchronisations, median and spread
@@ -17,6 +17,14 @@ Writes profiles/ddpm3d_bench.json (``--out`` to change) and prints it:
                loss at B = 2 (``--batch`` is ignored), steps per second over `repeats` windows of `evals` steps
   wgrad        csd_conv3d_wgrad (split bf16) at the same two layers as achieved TFLOP/s = 2 * 27 * Cin * Cout * voxels * B / time, beside
                torch's own fp32 conv3d weight gradient (torch.nn.grad.conv3d_weight, channels-first), the two alternating
+``--planned`` measures the planned path (``csd_planned``: one csd_unet_forward per evaluation, the PC loop on the device) beside the
+operator path in the same run and writes it under the key ``planned`` (the other keys are kept):
+  network      evaluations per second of the operator path and of the planned path on the same weights and inputs, `repeats` windows of
+               `evals` forwards each, the two alternating; whether the two outputs are bitwise equal; launches, workspace and packed bytes;
+               one extra forward of each path with an event pair around every launch, summed per kernel class
+  pc           ms per predictor-corrector step of the two-SDE conditional sampler (cVESDE / VESDE, reverse diffusion + Langevin): the fused
+               device loop on the planned model beside the step-by-step loop on the operator-path model, 10 steps after 2 of warm-up,
+               `repeats` runs each, alternating
 ``--small`` runs the same code at a toy shape (a rehearsal of the script; its numbers measure overheads).
 Needs the GPU: there is no CPU path.
 """
@@ -210,6 +218,88 @@ def train_bench(args, dev):
             'wgrad': [wgrad_bench(B, v, C, args.warmup, args.repeats, dev) for v, C in lv], 'torch': torch.__version__}
 
 
+def planned_bench(args, dev):
+    from conditional_score_diffusion_amd import sde_lib
+    from conditional_score_diffusion_amd._lib import lib
+    from conditional_score_diffusion_amd.sampling import conditional, fused
+    from conditional_score_diffusion_amd.sampling.correctors import get_corrector
+    from conditional_score_diffusion_amd.sampling.predictors import get_predictor
+    vol, nf, ch_mult, nrb = ((12, 12, 8), 32, (1, 2), 1) if args.small else ((96, 96, 16), 64, (1, 1, 2, 2), 2)
+    B = args.batch
+    torch.manual_seed(0)
+    op_model = mutils.create_model(make_config(vol, nf, ch_mult, nrb))
+    with torch.no_grad():
+        for k, v in op_model.state_dict().items():
+            if v.dim() == 5:
+                v.copy_((torch.rand_like(v) * 2 - 1) * (3.0 / (27 * (v.shape[0] + v.shape[1]) / 2)) ** 0.5)
+    cfg = make_config(vol, nf, ch_mult, nrb)
+    cfg.model.csd_planned = True
+    model = mutils.create_model(cfg)
+    model.load_state_dict(op_model.state_dict())
+    op_model, model = op_model.to(dev).eval(), model.to(dev).eval()
+    x = (5.0 * torch.randn(B, 1, *vol)).to(dev)
+    y = torch.rand(B, 1, *vol).to(dev)
+    labels = torch.linspace(3., 420.5, B).to(dev)
+    fwd_op = lambda: op_model({'x': x, 'y': y}, labels)      # noqa: E731
+    fwd_pl = lambda: model({'x': x, 'y': y}, labels)         # noqa: E731
+    a, b = fwd_op(), fwd_pl()
+    torch.cuda.synchronize()
+    equal = all(torch.equal(a[k], b[k]) for k in a)
+    assert all(torch.isfinite(v).all() for v in b.values())
+    for f in (fwd_op, fwd_pl):
+        timed_windows(f, args.warmup, 0, 0)
+    t_op, t_pl = [], []
+    for _ in range(args.repeats):
+        t_op += timed_windows(fwd_op, 0, 1, args.evals)
+        t_pl += timed_windows(fwd_pl, 0, 1, args.evals)
+    m_op, m_pl = statistics.median(t_op), statistics.median(t_pl)
+    launches, flops, nbytes = model.stats(B)
+    # one extra forward each with an event pair around every launch (planned: the library's own profiler), summed per class
+    from conditional_score_diffusion_amd import _lib
+    prof_op = ClassTimer().run(fwd_op)
+    _lib.profile_select(None, 1)
+    _lib.profile_start()
+    fwd_pl()
+    prof_pl = {c: {'ms': v['ms'], 'launches': v['launches']} for c, v in _lib.profile_stop().items() if v['launches']}
+    side = lambda t, m: {'evals_per_s': 1.0 / m, 'ms_per_eval': m * 1e3, 'ms_min': min(t) * 1e3, 'ms_max': max(t) * 1e3}      # noqa: E731
+    net = {'operator_path': side(t_op, m_op), 'planned': side(t_pl, m_pl), 'planned_over_operator': m_op / m_pl, 'bitwise_equal': equal,
+           'windows': len(t_pl), 'evals_per_window': args.evals, 'planned_launches': launches, 'planned_gflop': flops / 1e9,
+           'workspace_bytes': int(lib().csd_unet_workspace_bytes(model._h, B)), 'packed_bytes': int(lib().csd_unet_packed_bytes(model._h)),
+           'profile_pass': {'operator_path': prof_op, 'planned': prof_pl}}
+
+    # the PC sampler: fused device loop (planned model) beside the step-by-step loop (operator-path model)
+    sde = {'x': sde_lib.cVESDE(0.01, 30., 1000), 'y': sde_lib.VESDE(0.01, 1., 1000)}
+    pred, corr = get_predictor('conditional_reverse_diffusion'), get_corrector('conditional_langevin')
+    assert fused.fusable(model, sde, pred, corr, 1, False, True) and not fused.fusable(op_model, sde, pred, corr, 1, False, True)
+    shape = (B, 1) + tuple(vol)
+    mk = lambda n: conditional.get_pc_conditional_sampler(sde, shape, pred, corr, snr=0.16, p_steps=n, c_steps=1, continuous=True,      # noqa: E731
+                                                          denoise=True, eps=1e-5)
+    steps = 10
+
+    def run(sampler, m):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out, _ = sampler(m, y)
+        torch.cuda.synchronize()
+        assert torch.isfinite(out).all()
+        return time.perf_counter() - t0
+
+    t_f, t_s = [], []
+    run(mk(2), model)
+    run(mk(2), op_model)
+    for _ in range(args.repeats):
+        t_f.append(run(mk(steps), model) / steps)
+        t_s.append(run(mk(steps), op_model) / steps)
+    m_f, m_s = statistics.median(t_f), statistics.median(t_s)
+    pc = {'steps': steps, 'warmup_steps': 2, 'runs': args.repeats,
+          'fused_loop': {'ms_per_step': m_f * 1e3, 'ms_min': min(t_f) * 1e3, 'ms_max': max(t_f) * 1e3},
+          'step_by_step': {'ms_per_step': m_s * 1e3, 'ms_min': min(t_s) * 1e3, 'ms_max': max(t_s) * 1e3},
+          'fused_over_step_by_step': m_s / m_f,
+          'pc_scratch_bytes': int(lib().csd_pc_scratch_bytes(model._h, B))}
+    return {'device': torch.cuda.get_device_name(0), 'model': 'ddpm3D_paired', 'precision': 'fp16x3', 'batch': B, 'volume': list(vol), 'nf': nf,
+            'ch_mult': list(ch_mult), 'num_res_blocks': nrb, 'small': bool(args.small), 'network': net, 'pc': pc, 'torch': torch.__version__}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--batch', type=int, default=4)
@@ -218,21 +308,23 @@ def main():
     ap.add_argument('--evals', type=int, default=3)
     ap.add_argument('--small', action='store_true')
     ap.add_argument('--train', action='store_true')
+    ap.add_argument('--planned', action='store_true')
     ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'ddpm3d_bench.json'))
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit('bench_ddpm3d.py needs the MI355X: there is no CPU path')
     dev = torch.device('cuda:0')
-    if args.train:
+    if args.train or args.planned:
         res = {}
         if os.path.exists(args.out):
             with open(args.out) as f:
                 res = json.load(f)
-        res['training'] = train_bench(args, dev)
+        key = 'training' if args.train else 'planned'
+        res[key] = train_bench(args, dev) if args.train else planned_bench(args, dev)
         os.makedirs(os.path.dirname(args.out), exist_ok=True)
         with open(args.out, 'w') as f:
             json.dump(res, f, indent=1)
-        print(json.dumps(res['training']))
+        print(json.dumps(res[key]))
         return
     vol, nf, ch_mult, nrb = ((12, 12, 8), 32, (1, 2), 1) if args.small else ((96, 96, 16), 64, (1, 1, 2, 2), 2)
     B = args.batch
