@@ -209,8 +209,12 @@ int pw16_pack_weight_taps(const ConvPlan& p, int ns, const float* w, int cout, v
 int tapsum_launch(const float* part, const float* bias, const float* res, float* out, int B, int H, int W, int cout, int nchw,
                   float out_scale, hipStream_t s);
 // stem.hip: cat(x, y [+ sigma z]) + 2v - 1 + NCHW -> NHWC + the first 3 x 3 conv (<= 8 -> Cout channels) + GroupNorm tile partials, one launch
-bool stem_supported(int Cx, int Cy, int Cout, int S, int ns);
-size_t stem_packed_bytes(int Cout, int ns);
+// padded channel count of an assembled network input of MORE than 8 channels: the next multiple of 16, with exact zeros in the padding
+// (the one rule behind Net::in_cpad, stem_wide_kernel's Cpad and csd_input_conv; up to 8 channels each keeps its own width)
+static inline int wide_cpad(int cin) { return (cin + 15) / 16 * 16; }
+bool stem_supported(int Cx, int Cy, int Cout, int S, int ns);      // the kernels cover the shape
+bool stem_planned(int Cx, int Cy, int Cout, int S, int ns);        // ... and a network's plan uses them for it (where they measured faster)
+size_t stem_packed_bytes(int Cin, int Cout, int ns);      // Cin = Cx + Cy: <= 8 stem_kernel's layout, 9 .. 32 stem_wide_kernel's
 int stem_pack_weight(const float* w, int Cin, int Cout, int ns, void* wpack, hipStream_t s);
 int stem_tiles_per_image(int S);
 int stem_launch(const float* x, const float* y, const float* y_noise, float y_sigma, const void* wpack, const float* bias, float* out,

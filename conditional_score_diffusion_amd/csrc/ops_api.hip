@@ -231,6 +231,56 @@ extern "C" int csd_conv2d_ex(const float* x, const float* weight, const float* b
   return conv2d_impl(x, weight, bias, nullptr, nullptr, y, B, Cin, Cout, H, W, ksize, stride, pad_mode, up2, precision, layout, scratch, stream);
 }
 
+// ---- the DDPM family's first layer as an operator: cat(x, y [+ sigma z]), 2v - 1, NCHW -> NHWC, 3x3 conv to Cout channels ----------
+// fused = 1: stem.hip's one launch (stem_kernel up to 8 input channels, stem_wide_kernel for 9 .. 32); fused = 0: what the plan runs
+// where the fused layer does not apply - assemble_input at the padded width, then the generic convolution.  The padded width follows
+// the network's rule (unet_layout.h): up to 8 channels 8 (fp32) / 16 (fp16 modes), above 8 the next multiple of 16.
+static int input_conv_cpad(int cin, int ns) { return cin > 8 ? wide_cpad(cin) : (ns ? 16 : 8); }
+// scratch: that of a 32-input-channel 3x3 convolution, csd_conv_scratch_bytes(B, 32, Cout, S, S, 3, 0): the assembled input at up to 32
+// channels | the packed weight of whichever kernel takes it (none is larger than the 32-channel layouts api_packed_floats covers) | the padded bias
+extern "C" int csd_input_conv(const float* x, const float* y, const float* y_noise, float y_sigma, const float* weight, const float* bias,
+                              float* out, double* stats, int B, int Cx, int Cy, int Cout, int S, int centered, int precision, int fused,
+                              void* scratch, void* stream) {
+  CSD_REQUIRE(x && weight && bias && out && scratch, "input_conv: null argument");
+  CSD_REQUIRE(B >= 1 && Cx >= 1 && Cy >= 0 && Cx + Cy <= CSD_MAX_IO_CHANNELS && Cout >= 1 && S >= 1, "input_conv: bad shape");
+  CSD_REQUIRE((Cy == 0) == (y == nullptr), "input_conv: y must be given iff Cy > 0");
+  CSD_REQUIRE(precision >= CSD_PREC_F32 && precision <= CSD_PREC_F16F8, "input_conv: bad precision id %d", precision);
+  CSD_REQUIRE((reinterpret_cast<uintptr_t>(scratch) & 255) == 0, "input_conv: scratch must be 256-byte aligned");
+  hipStream_t s = (hipStream_t)stream;
+  int ns = precision_ns(precision);
+  const int cin = Cx + Cy, cpad = input_conv_cpad(cin, ns);
+  float* f = static_cast<float*>(scratch);
+  float* xh = f; f += al64((size_t)B * S * S * 32);
+  float* wp = f;
+  int rc;
+  ConvPlan p32;
+  if ((rc = conv_api_plan(&p32, B, 32, Cout, S, S, 3, 1, 0, 0))) return rc;
+  if (fused) {
+    CSD_REQUIRE(ns && stem_supported(Cx, Cy, Cout, S, ns), "input_conv: the fused first layer does not cover %d+%d -> %d channels at %dx%d in this precision",
+                Cx, Cy, Cout, S, S);
+    if ((rc = stem_pack_weight(weight, cin, Cout, ns, wp, s))) return rc;
+    return stem_launch(x, y, y_noise, y_sigma, wp, bias, out, stats, B, Cx, Cy, Cout, S, centered, ns, s);
+  }
+  CSD_REQUIRE(!stats, "input_conv: tile statistics come from the fused layer only");
+  ConvPlan p;
+  if ((rc = conv_api_plan(&p, B, cpad, Cout, S, S, 3, 1, 0, 0))) return rc;
+  float* bp = wp + api_packed_floats(p32, 32);
+  if (ns) {
+    CSD_REQUIRE(conv16_supported(p), "input_conv: no fp16 kernel for %d padded channels", cpad);
+    if ((rc = conv16_plan_tiles(&p, ns))) return rc;
+  }
+  if ((rc = assemble_input_launch(x, y, y_noise, y_sigma, xh, B, Cx, Cy, S * S, cpad, centered, s))) return rc;
+  rc = ns ? conv16_pack_weight(p, ns, weight, 0, cin, Cout, 0, wp, s) : conv_pack_weight(p, weight, 0, cin, Cout, 0, wp, s);
+  if (rc) return rc;
+  CSD_CHECK_HIP(hipMemsetAsync(bp, 0, (size_t)p.CoutPad * sizeof(float), s));
+  CSD_CHECK_HIP(hipMemcpyAsync(bp, bias, (size_t)Cout * sizeof(float), hipMemcpyDeviceToDevice, s));
+  ConvArgs a;
+  memset(&a, 0, sizeof(a));
+  a.src0 = xh; a.wpack = wp; a.bias = bp; a.out = out;
+  a.out_stride = Cout; a.out_nchw = 0; a.out_scale = 1.f;
+  return ns ? conv16_launch(p, ns, a, s) : conv_launch(p, a, s);
+}
+
 // ---- ResnetBlock convolution with the fused GroupNorm + SiLU prologue (conv_ff.hip) ---------------------------------
 extern "C" size_t csd_conv3x3_block_scratch_bytes(int Cin, int Cout) {
   ConvPlan p;

@@ -13,6 +13,9 @@
 // raw inputs are not GroupNorm-ed, so the e4m3 correction form does not apply) or hi*hi only (NS = 1: the plain fp16 mode); the pixels are
 // the M operand, so every output store covers whole 128-byte lines.  The loop's only wait on global memory (the next tile's patch, requested
 // before the K loop) sits after the K loop: gfx9's in-order vmcnt makes a load wait also a wait for every older store.
+//
+// stem_wide_kernel (below) is the same layer for 9 .. 32 assembled channels, padded to Cpad = 16 or 32: K = tap * Cpad + channel, one or
+// two MFMA K steps per tap.
 #include <hip/hip_runtime.h>
 
 #include "common.h"
@@ -231,16 +234,179 @@ __global__ __launch_bounds__(256, 4) void stem_kernel(const StemArgs k) {
 }
 
 // ---------------------------------------------------------------------------------------------
+// The wide first layer: 9 .. 32 assembled channels (the 16 + 16 slab networks, the 12 Haar bands, 9 + 3), padded with exact zeros to
+// CP = 16 * KS channels.  Same tile (16 x 8 pixels, one 32-pixel M tile per wave), same products, same epilogue and statistics as
+// stem_kernel; what differs is where the operands live:
+//   * K = tap * CP + channel: K step s = tap * KS + ks holds channels 16 ks .. 16 ks + 15 of one tap, lanes of K half kh the upper / lower 8.
+//     All 9 KS steps are full - there is no padding tap.
+//   * the weight fragments of ALL cout groups no longer fit LDS (9 taps x 2 K steps x 4 cout tiles x 2 planes = 144 KB at nf 128), so a
+//     workgroup serves ONE cout group (blockIdx.y; 32 NT couts: <= 108 KB for NT = 3, CP = 32, two planes) for all its tiles: the fragments
+//     are copied to LDS once per workgroup, the patch is assembled once per (tile, cout group).  The input side is re-read per cout group
+//     (1 .. 4 groups), which is small beside the layer's output (nf * 4 bytes per pixel against <= 32 * 4).
+//   * the patch is kept as CP / 8 chunk planes [chunk][pixel] of 8 halves: consecutive pixels are consecutive 16-byte slots for the
+//     A-operand reads and for the writes.
+// The tile walk is a plain grid-stride loop; a tile's patch is assembled by all 256 threads (item = (chunk, patch pixel), coalesced
+// along W), out-of-image pixels and the padding channels are written as exact zeros (masked, never clamped: no load is issued for them).
+// S % 16 == 0, so every tile is whole.
+template <int NT, int NS, int KS, bool YN>
+__global__ __launch_bounds__(256, 2) void stem_wide_kernel(const StemArgs k) {
+  constexpr int CH = 2 * KS;                        // 8-channel chunks of a pixel
+  constexpr int NSTEP = 9 * KS;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  half8* const phi = reinterpret_cast<half8*>(smem);                     // [CH][ST_PLANE]
+  half8* const plo = phi + CH * ST_PLANE;                                // (NS == 2)
+  float* const red = reinterpret_cast<float*>(smem + NS * CH * ST_PLANE * 16);      // [4 waves][NT * 32 couts][2]
+  float* const bl = red + 4 * NT * 32 * 2;                                // bias of this cout group [NT * 32]
+  half8* const wl = reinterpret_cast<half8*>(bl + NT * 32);              // this cout group's weight fragments
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int kh = lane >> 5, p32 = lane & 31;
+  const int S = k.S, Cx = k.Cx, Cy = k.Cy, Cout = k.Cout;
+  const int ng = blockIdx.y;
+  const size_t HW = (size_t)S * S;
+
+  wg_copy_to_lds<256, 8>(reinterpret_cast<char*>(wl), reinterpret_cast<const char*>(k.w) + (size_t)ng * NSTEP * NT * NS * 1024,
+                         NSTEP * NT * NS * 1024, tid);
+  if (tid < NT * 32) bl[tid] = k.bias[ng * NT * 32 + tid];
+
+  const int pix0 = (wave * 2 + (p32 >> 4)) * ST_PW + (p32 & 15);
+  const float wunscale = 1.0f / C16_WSCALE;
+  const half8* const wq = wl + lane;
+
+  for (int tile = blockIdx.x; tile < k.nblocks; tile += gridDim.x) {
+    const int b = tile / k.tpi, tin = tile - b * k.tpi;
+    const int ty0 = (tin / k.tiles_x) * ST_TH, tx0 = (tin - (tin / k.tiles_x) * k.tiles_x) * 16;
+
+    // ---- assemble the 18 x 10 patch: cat(x, y [+ sigma z]), 2v - 1, fp16 hi | lo split, zeros outside the image and beyond Cx + Cy ----
+    for (int it = tid; it < CH * ST_NPIX; it += 256) {
+      const int q = it / ST_NPIX, pp = it - q * ST_NPIX;
+      const int py = pp / ST_PW, px = pp - py * ST_PW;
+      const int gy = ty0 + py - 1, gx = tx0 + px - 1;
+      const bool inimg = (unsigned)gy < (unsigned)S && (unsigned)gx < (unsigned)S;
+      const size_t pix = inimg ? (size_t)gy * S + gx : 0;
+      half8 h, l;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        const int c = q * 8 + e;
+        float v = 0.f;
+        if (inimg && c < Cx) {
+          v = k.x[((size_t)b * Cx + c) * HW + pix];
+          v = k.centered ? v : 2.f * v - 1.f;
+        } else if (inimg && c < Cx + Cy) {
+          const size_t j = ((size_t)b * Cy + (c - Cx)) * HW + pix;
+          v = k.y[j];
+          if (YN) v = v + k.yn[j] * k.ysig;
+          v = k.centered ? v : 2.f * v - 1.f;
+        }
+        h[e] = (_Float16)v;
+        l[e] = (_Float16)(v - (float)h[e]);
+      }
+      phi[q * ST_PLANE + pp] = h;
+      if (NS == 2) plo[q * ST_PLANE + pp] = l;
+    }
+    ff_barrier();                        // the patch (first tile: and the weights, the bias) is in LDS; the previous tile's partials are read
+
+    // ---- K loop: 9 taps x KS steps of 16 channels ----
+    floatx16 acc[NT];
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[nt][r] = 0.f;
+#pragma unroll
+    for (int s = 0; s < NSTEP; ++s) {
+      const int tap = s / KS, ks = s - tap * KS;
+      const int idx = (ks * 2 + kh) * ST_PLANE + pix0 + (tap / 3) * ST_PW + tap % 3;
+      const half8 bh = phi[idx];
+      half8 bl16;
+      if (NS == 2) bl16 = plo[idx];
+#pragma unroll
+      for (int nt = 0; nt < NT; ++nt) {
+        const half8 wh = wq[((s * NT + nt) * NS) * 64];
+        if (NS == 2) {      // small products first
+          const half8 wlo = wq[((s * NT + nt) * NS + 1) * 64];
+          acc[nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bh, wlo, acc[nt], 0, 0, 0);
+          acc[nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bl16, wh, acc[nt], 0, 0, 0);
+        }
+        acc[nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bh, wh, acc[nt], 0, 0, 0);
+      }
+    }
+
+    // ---- epilogue: un-scale, bias, NHWC stores (stem_kernel's: a lane holds ONE cout of 16 pixels, whole 128-byte lines per store) ----
+    float* const obase = k.out + (((size_t)b * S + ty0 + wave * 2) * S + tx0) * Cout + ng * NT * 32;      // uniform
+    const unsigned lane_off = (unsigned)(4 * kh * Cout + p32);
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt) {
+      const float bv = bl[nt * 32 + p32];
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        float* const ub = obase + ((size_t)(r >> 3) * S + 8 * ((r >> 2) & 1) + (r & 3)) * Cout + nt * 32;
+        acc[nt][r] = acc[nt][r] * wunscale + bv;
+        ub[lane_off] = acc[nt][r];
+      }
+    }
+
+    // ---- GroupNorm partials of the written tile, as stem_kernel leaves them: (sum, sum of squares) per (tile, cout) ----
+    if (k.stats) {
+#pragma unroll
+      for (int nt = 0; nt < NT; ++nt) {
+        float vs = 0.f, vq = 0.f;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          vs += acc[nt][r];
+          vq = fmaf(acc[nt][r], acc[nt][r], vq);
+        }
+        vs += __shfl_xor(vs, 32);
+        vq += __shfl_xor(vq, 32);
+        if (kh == 0) {
+          red[(wave * NT * 32 + nt * 32 + p32) * 2 + 0] = vs;
+          red[(wave * NT * 32 + nt * 32 + p32) * 2 + 1] = vq;
+        }
+      }
+    }
+    ff_barrier();                        // the partials are in LDS; every wave has read this tile's patch
+    if (k.stats && tid < NT * 32) {
+      double s = 0.0, q = 0.0;
+#pragma unroll
+      for (int wv = 0; wv < 4; ++wv) {
+        s += (double)red[(wv * NT * 32 + tid) * 2 + 0];
+        q += (double)red[(wv * NT * 32 + tid) * 2 + 1];
+      }
+      double* dst = k.stats + ((size_t)tile * Cout + ng * NT * 32 + tid) * 2;
+      dst[0] = s;
+      dst[1] = q;
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
 static inline int stem_nt(int cout) { return cout % 96 == 0 ? 3 : 2; }
+
+// padded channel count of the assembled input inside the kernels: 8 (stem_kernel) up to 8 real channels, the next multiple of 16 above
+static inline int stem_cpad(int cin) { return cin <= 8 ? 8 : wide_cpad(cin); }
+static inline size_t stem_wide_lds(int cpad, int nt, int planes) {
+  return (size_t)planes * (cpad / 8) * ST_PLANE * 16 + 4 * (size_t)nt * 32 * 2 * 4 + (size_t)nt * 32 * 4 + (size_t)9 * (cpad / 16) * nt * planes * 1024;
+}
 
 bool stem_supported(int Cx, int Cy, int Cout, int S, int ns) {
   if (CSD_TUNE_ENV("CSD_NO_STEM")) return false;
-  return ns >= 1 && ns <= 3 && Cx > 0 && Cy >= 0 && Cx + Cy <= 8 && S % 16 == 0 && S >= 16 && (Cout % 96 == 0 || Cout % 64 == 0);
+  if (!(ns >= 1 && ns <= 3 && Cx > 0 && Cy >= 0 && S % 16 == 0 && S >= 16 && (Cout % 96 == 0 || Cout % 64 == 0))) return false;
+  if (Cx + Cy <= 8) return true;
+  return Cx + Cy <= 32 && stem_wide_lds(stem_cpad(Cx + Cy), stem_nt(Cout), ns >= 2 ? 2 : 1) <= 160 * 1024;
 }
 
-size_t stem_packed_bytes(int Cout, int ns) {
+// what a network's plan runs as the fused layer: every shape stem_kernel covers, and stem_wide_kernel where it measured faster than the
+// assemble pass + generic convolution: at 16 padded channels.  At 32 its one-cout-group weight fragments (72 - 108 KB)
+// leave one workgroup per CU and it measured slower, so the plan keeps the fallback there; csd_input_conv still reaches the kernel
+bool stem_planned(int Cx, int Cy, int Cout, int S, int ns) {
+  return stem_supported(Cx, Cy, Cout, S, ns) && stem_cpad(Cx + Cy) <= 16;
+}
+
+size_t stem_packed_bytes(int Cin, int Cout, int ns) {
   const int nt = stem_nt(Cout), planes = ns >= 2 ? 2 : 1;
-  return (size_t)(Cout / (32 * nt)) * ST_KSTEPS * nt * planes * 1024;
+  const int ksteps = Cin <= 8 ? ST_KSTEPS : 9 * (stem_cpad(Cin) / 16);
+  return (size_t)(Cout / (32 * nt)) * ksteps * nt * planes * 1024;
 }
 
 // weights in A-fragment order: [cout group][K step][cout tile][plane][lane = (k half << 5) | cout row][8 halves]; k = tap * 8 + channel,
@@ -264,8 +430,36 @@ __global__ void stem_pack_kernel(const float* __restrict__ w, _Float16* __restri
   wpack[idx] = pl == 0 ? hi : (_Float16)(v - (float)hi);
 }
 
+// the wide layer's: [cout group][K step = tap * KS + ks][cout tile][plane][lane = (k half << 5) | cout row][8 halves], channel
+// 16 ks + 8 (k half) + e; channels >= Cin (the padding) are exact zeros
+__global__ void stem_wide_pack_kernel(const float* __restrict__ w, _Float16* __restrict__ wpack, int Cin, int Cout, int planes, int nt,
+                                      int ks_per_tap, size_t n_halves) {
+  const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= n_halves) return;
+  const int e = (int)(idx & 7);
+  const int ln = (int)((idx >> 3) & 63);
+  size_t rest = idx >> 9;
+  const int pl = (int)(rest % planes); rest /= planes;
+  const int t = (int)(rest % nt); rest /= nt;
+  const int s = (int)(rest % (9 * ks_per_tap));
+  const int ng = (int)(rest / (9 * ks_per_tap));
+  const int tap = s / ks_per_tap, ks = s - tap * ks_per_tap;
+  const int cin = ks * 16 + (ln >> 5) * 8 + e;
+  const int cout = (ng * nt + t) * 32 + (ln & 31);
+  float v = 0.f;
+  if (cin < Cin && cout < Cout) v = w[((size_t)cout * Cin + cin) * 9 + tap] * C16_WSCALE;
+  const _Float16 hi = (_Float16)v;
+  wpack[idx] = pl == 0 ? hi : (_Float16)(v - (float)hi);
+}
+
 int stem_pack_weight(const float* w, int Cin, int Cout, int ns, void* wpack, hipStream_t s) {
-  const size_t n = stem_packed_bytes(Cout, ns) / 2;
+  const size_t n = stem_packed_bytes(Cin, Cout, ns) / 2;
+  if (Cin > 8) {
+    hipLaunchKernelGGL(stem_wide_pack_kernel, dim3((unsigned)cdiv64(n, 256)), dim3(256), 0, s, w, (_Float16*)wpack, Cin, Cout,
+                       ns >= 2 ? 2 : 1, stem_nt(Cout), stem_cpad(Cin) / 16, n);
+    CSD_LAUNCH_CHECK();
+    return CSD_OK;
+  }
   hipLaunchKernelGGL(stem_pack_kernel, dim3((unsigned)cdiv64(n, 256)), dim3(256), 0, s, w, (_Float16*)wpack, Cin, Cout,
                      ns >= 2 ? 2 : 1, stem_nt(Cout), n);
   CSD_LAUNCH_CHECK();
@@ -288,6 +482,29 @@ int stem_launch(const float* x, const float* y, const float* y_noise, float y_si
   k.centered = centered;
   k.abl = CSD_TUNE_ENV("CSD_STEM_ABL") ? atoi(CSD_TUNE_ENV("CSD_STEM_ABL")) : 0;
   const int planes = ns >= 2 ? 2 : 1;
+  if (k.Cx + k.Cy > 8 || Cx + Cy > 8) {      // the wide layer: one cout group per workgroup row, a grid-stride walk over the tiles
+    const int cpad = stem_cpad(Cx + Cy);      // (the weights were packed for Cx + Cy channels, with or without y)
+    const size_t lds = stem_wide_lds(cpad, nt, planes);
+    int per_cu = (int)((160 * 1024) / lds);
+    if (per_cu > 2) per_cu = 2;               // (__launch_bounds__(256, 2))
+    if (per_cu < 1) per_cu = 1;
+    const int want = std::max(1, device_cu_count8() * per_cu / k.n_groups);
+    const dim3 grid((unsigned)std::min(k.nblocks, want), (unsigned)k.n_groups);
+    const bool ynw = y_noise != nullptr && k.Cy > 0;
+    auto gow = [&](auto kern) -> int {
+      CSD_SET_MAX_LDS_ONCE(kern);
+      hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, k);
+      return CSD_OK;
+    };
+    int rcw;
+#define CSD_STEM_WIDE(NT_, NS_, KS_) (ynw ? gow(stem_wide_kernel<NT_, NS_, KS_, true>) : gow(stem_wide_kernel<NT_, NS_, KS_, false>))
+    if (cpad == 16) rcw = nt == 3 ? (planes == 2 ? CSD_STEM_WIDE(3, 2, 1) : CSD_STEM_WIDE(3, 1, 1)) : (planes == 2 ? CSD_STEM_WIDE(2, 2, 1) : CSD_STEM_WIDE(2, 1, 1));
+    else rcw = nt == 3 ? (planes == 2 ? CSD_STEM_WIDE(3, 2, 2) : CSD_STEM_WIDE(3, 1, 2)) : (planes == 2 ? CSD_STEM_WIDE(2, 2, 2) : CSD_STEM_WIDE(2, 1, 2));
+#undef CSD_STEM_WIDE
+    if (rcw) return rcw;
+    CSD_LAUNCH_CHECK();
+    return CSD_OK;
+  }
   const size_t lds = 2 * ST_PLANE * 16 + 4 * (size_t)nt * 32 * 2 * 4 + (size_t)k.n_groups * ST_KSTEPS * nt * planes * 1024 + (size_t)Cout * 4;
   CSD_REQUIRE(lds <= 160 * 1024, "stem: %d couts need %zu bytes of LDS", Cout, lds);
   const int n_cu = device_cu_count8();

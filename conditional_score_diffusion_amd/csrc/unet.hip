@@ -369,7 +369,11 @@ static int build_modules(Net& n) {
     CSD_REQUIRE(c.nf % 32 == 0, "unet: nf=%d must be a multiple of 32 (GroupNorm(32) + 32-wide MFMA tiles)", c.nf);
     CSD_REQUIRE(c.image_size % (1 << (c.n_levels - 1)) == 0, "unet: image_size %d not divisible by 2^%d",
                 c.image_size, c.n_levels - 1);
-    CSD_REQUIRE(c.x_channels >= 1 && c.x_channels + c.y_channels <= 8, "unet: x+y channels must be <= 8");
+    // (the input is assembled into in_cpad <= 32 channels: unet_layout.h; the head's NCHW store covers one 32-cout tile)
+    CSD_REQUIRE(c.x_channels >= 1 && c.y_channels >= 0 && c.x_channels + c.y_channels <= CSD_MAX_IO_CHANNELS,
+                "unet: x+y channels must be <= %d (got %d+%d)", CSD_MAX_IO_CHANNELS, c.x_channels, c.y_channels);
+    CSD_REQUIRE(c.out_channels >= 1 && c.out_channels <= CSD_MAX_IO_CHANNELS, "unet: out_channels must be in 1 .. %d (got %d)",
+                CSD_MAX_IO_CHANNELS, c.out_channels);
     CSD_REQUIRE(c.act >= CSD_ACT_SWISH && c.act <= CSD_ACT_ELU, "unet: bad activation id %d", c.act);
     CSD_REQUIRE(c.precision >= CSD_PREC_F32 && c.precision <= CSD_PREC_F16F8, "unet: bad precision id %d", c.precision);
   } else {

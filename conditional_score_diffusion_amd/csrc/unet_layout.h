@@ -26,6 +26,11 @@ static int build_packed_layout(Net& n) {
   // the 6 -> nf stem: with the input padded to 16 channels (zeros) it runs on the fp16 matrix cores like every other 3x3 (one K step
   // per tap) instead of the fp32 ones (36 MFMAs of 64 cycles per 32 pixels: 380 us per evaluation at 160^2, B = 64, MFMA-bound)
   if (n.cfg.arch == 0 && net_ns && !CSD_TUNE_ENV("CSD_STEM_F32")) n.in_cpad = 16;
+  // more than 8 assembled channels (DDPM family only: 9 .. CSD_MAX_IO_CHANNELS): the next multiple of 16 in every precision - the fp32
+  // kernel's and the fp16 kernels' K chunk alike.  Everything that reads the assembled tensor or packs the first layer's weights takes
+  // its width from in_cpad: OP_ASSEMBLE and its buffer (unet_plan.h), the first layer's proto / pack below (zero weights for the padding
+  // channels), stem.hip's own padding (stem_cpad: the same wide_cpad)
+  if (n.cfg.x_channels + n.cfg.y_channels > 8) n.in_cpad = wide_cpad(n.cfg.x_channels + n.cfg.y_channels);
   // quad schedule: measured faster than the loader/consumer one in the split (3-MFMA) mode only
   const bool use_q = net_ns == 2 && !CSD_TUNE_ENV("CSD_NO_Q");
   int cur_res = n.cfg.image_size;    // resolution of the layer being laid out
@@ -112,13 +117,13 @@ static int build_packed_layout(Net& n) {
   const bool pp = c.arch == 1;
   // the first layer of both families in the fp16 modes: input assembly + 3x3 conv + the next GroupNorm's partials as one launch (stem.hip)
   auto stem_layout = [&](Module& m) -> bool {
-    if (!(net_ns && m.cin == c.x_channels + c.y_channels && stem_supported(c.x_channels, c.y_channels, m.cout, c.image_size, net_ns)))
+    if (!(net_ns && m.cin == c.x_channels + c.y_channels && stem_planned(c.x_channels, c.y_channels, m.cout, c.image_size, net_ns)))
       return false;
     PackedConv pc;
     if (proto_conv(&pc.proto, n.in_cpad, 0, m.cout, 9)) return false;
     pc.ns = net_ns;
     pc.stem = true;
-    pc.w_off = take(stem_packed_bytes(m.cout, net_ns) / sizeof(float) + 1);
+    pc.w_off = take(stem_packed_bytes(m.cin, m.cout, net_ns) / sizeof(float) + 1);
     pc.b_off = take((size_t)pc.proto.CoutPad + 96);
     pc.srcs = {{n.P(mname(m.idx, "weight")), n.P(mname(m.idx, "bias")), 0, m.cout, 0, m.cin}};
     n.pconv_by_name[std::to_string(m.idx)] = (int)n.pconvs.size();

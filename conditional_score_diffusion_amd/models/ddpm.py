@@ -40,6 +40,13 @@ def _fan_avg_uniform(shape, scale, is_nin):
     return (torch.rand(*shape) * 2. - 1.) * math.sqrt(3 * var)
 
 
+def _model_key(config, key, default):
+    """config.model.<key>, or `default` where the config does not set it"""
+    m = config.model
+    v = m.get(key, None) if hasattr(m, 'get') else getattr(m, key, None)
+    return default if v is None else v
+
+
 class _HandleSurface:
     """What a network that owns a ``csd_unet`` handle offers to its callers (``sampling/fused.py``, the likelihood, the benches): the
     handle ``_h``, the packed weights ``_packed`` (``_ensure_packed()`` packs again when a parameter moved or changed), the activation
@@ -511,8 +518,13 @@ class _InputGradNet(torch.autograd.Function):
 class DDPM(HipUNet):
     """Unconditional DDPM U-Net: ``model(x, labels) -> Tensor`` (models/ddpm.py:80-213)."""
 
+    # (configs that leave model.input_channels / output_channels out - configs/ve/haarflow/*.py: the 12 Haar bands - name the image's
+    # channels in data.num_channels)
     def _channels(self, config):
-        return int(config.model.input_channels), 0
+        return int(_model_key(config, 'input_channels', config.data.num_channels)), 0
+
+    def _out_channels(self, config):
+        return _model_key(config, 'output_channels', config.data.num_channels)
 
     def forward(self, x, labels):
         return self._run(x, None, labels)

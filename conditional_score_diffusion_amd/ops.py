@@ -94,6 +94,38 @@ def fir_pyr_conv(x, weight, bias=None, res=None, fir_kernel=(1, 3, 3, 1), out_sc
     return y
 
 
+def input_conv(x, y, weight, bias, y_noise=None, y_sigma=0.0, centered=False, precision='fp16x3', fused=True, want_stats=False):
+    """The DDPM family's first layer (models/ddpm.py:163-168, :283 and the first conv3x3): conv3x3(2 cat(x, y + y_sigma y_noise) - 1) on
+    NCHW fp32 x [B, Cx, S, S], y [B, Cy, S, S] or None; weight [Cout, Cx + Cy, 3, 3], bias [Cout]; up to 32 input channels.
+    ``fused``: the one-launch layer of csrc/stem.hip; otherwise the assembled, padded input and the generic convolution (what a
+    network's plan runs where the fused layer does not apply).  csd_input_conv.  Returns out [B, S, S, Cout] NHWC (and, fused with
+    ``want_stats``, the (sum, sum of squares) of every 16 x 8 tile of it)."""
+    x, weight, bias = _c(x, 'x'), _c(weight, 'weight'), _c(bias, 'bias')
+    B, Cx, S, S2 = x.shape
+    Cy = 0
+    if y is not None:
+        y = _c(y, 'y')
+        Cy = y.shape[1]
+        if tuple(y.shape) != (B, Cy, S, S):
+            raise RuntimeError('input_conv: y %s does not match x %s' % (tuple(y.shape), tuple(x.shape)))
+    Cout = weight.shape[0]
+    if S != S2 or tuple(weight.shape) != (Cout, Cx + Cy, 3, 3) or tuple(bias.shape) != (Cout,):
+        raise RuntimeError('input_conv: x %s / weight %s / bias %s do not match' % (tuple(x.shape), tuple(weight.shape), tuple(bias.shape)))
+    if y_noise is not None:
+        y_noise = _c(y_noise, 'y_noise')
+        if y is None or tuple(y_noise.shape) != tuple(y.shape):
+            raise RuntimeError('input_conv: y_noise must have the shape of y')
+    out = _out((B, S, S, Cout), torch.float32, x.device)
+    stats = _out((B * (S // 16) * (S // 8), Cout, 2), torch.float64, x.device) if want_stats else None
+    if Cx + Cy > 32:
+        raise RuntimeError('input_conv: at most 32 input channels (got %d + %d)' % (Cx, Cy))
+    sc = _scratch(lib().csd_conv_scratch_bytes(B, 32, Cout, S, S, 3, 0), x.device)      # (the 32-channel convolution's: include/csd.h)
+    check(lib().csd_input_conv(ptr(x), ptr(y), ptr(y_noise), float(y_sigma), ptr(weight), ptr(bias), ptr(out), ptr(stats), B, Cx, Cy,
+                               Cout, S, int(bool(centered)), _lib.PREC_IDS[precision], int(bool(fused)), ptr(sc),
+                               current_stream(x.device)), 'input_conv')
+    return (out, stats) if want_stats else out
+
+
 def conv3x3_block(x0, weight, bias=None, x1=None, nscale=None, nshift=None, temb=None, res=None, out_scale=1.0,
                   precision='fp16x3', want_stats=False):
     """The ResnetBlock convolution with its prologue fused (models/layers.py:632-675): y = Conv3x3(SiLU(x*nscale + nshift))

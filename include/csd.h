@@ -88,6 +88,10 @@ int csd_profile_stop_ex(int n_classes, double* ms, int64_t* launches, double* fl
  * ---------------------------------------------------------------------------------------- */
 #define CSD_MAX_LEVELS 8
 #define CSD_MAX_ATTN 8
+/* arch 0 (DDPM family): x_channels + y_channels and out_channels may each be up to this many (the 16-slice MRI -> PET slabs: 16 + 16 in,
+ * 32 out; the Haar-band models: 12; the SR-flow Haar models: 9 + 3).  Above 8 input channels the assembled input is padded to the next
+ * multiple of 16 with exact zeros.  arch 1 (NCSN++) keeps x_channels + y_channels <= 8. */
+#define CSD_MAX_IO_CHANNELS 32
 
 typedef struct csd_unet_config {
   int32_t arch;                 /* 0 = DDPM family (models/ddpm.py); 1 = NCSN++ (models/ncsnpp.py); 2 = 3-D DDPM family
@@ -99,9 +103,9 @@ typedef struct csd_unet_config {
   int32_t n_attn;               /* len(config.model.attn_resolutions)                        */
   int32_t attn_resolutions[CSD_MAX_ATTN];
   int32_t image_size;           /* config.data.effective_image_size                          */
-  int32_t x_channels;           /* channels of x                                             */
+  int32_t x_channels;           /* channels of x (arch 0: x + y <= CSD_MAX_IO_CHANNELS)        */
   int32_t y_channels;           /* channels of the condition y (0: unconditional 'ddpm')     */
-  int32_t out_channels;         /* config.model.output_channels                              */
+  int32_t out_channels;         /* config.model.output_channels (arch 0: <= CSD_MAX_IO_CHANNELS) */
   int32_t resamp_with_conv;
   int32_t conditional;          /* config.model.conditional (time embedding on/off)          */
   int32_t centered;             /* config.data.centered: 0 -> h = 2x-1 (models/ddpm.py:163-168)*/
@@ -429,6 +433,21 @@ int csd_ema_update(float* ema, const float* param, int64_t n, float decay, void*
  * NHWC forms of the training operators (csrc/train_nhwc.hip): the differentiable DDPM-family graph keeps activations in
  * the library's internal layout [B, H, W, C], so no layer pays an NCHW<->NHWC change.  Same kernels as above.
  * ---------------------------------------------------------------------------------------- */
+/* The DDPM family's first layer as an operator (models/ddpm.py:163-168 + :283 + the first conv3x3): out [B, S, S, Cout] NHWC =
+ * conv3x3(2 cat(x, y + y_sigma y_noise) - 1) (no 2v - 1 when centered), x [B, Cx, S, S], y [B, Cy, S, S] (NULL iff Cy == 0), y_noise
+ * like y or NULL, weight OIHW [Cout, Cx + Cy, 3, 3], bias [Cout]; Cx + Cy <= CSD_MAX_IO_CHANNELS.
+ *   fused = 1: the one-launch layer of csrc/stem.hip (fp16-operand precisions, S % 16 == 0, Cout % 64 == 0 or % 96 == 0; up to 8 input
+ *              channels stem_kernel, 9 .. 32 stem_wide_kernel); stats (or NULL): [B * (S / 16) * (S / 8)][Cout][2] doubles, the (sum, sum of
+ *              squares) of every 16 x 8 tile of the written tensor.  An unsupported shape is CSD_ERR_INVALID, never another kernel.
+ *   fused = 0: what a network's plan runs where the fused layer does not apply: the input assembled at its padded width (up to 8
+ *              channels: 8 in CSD_PREC_F32, 16 otherwise; above 8 the next multiple of 16; exact zeros in the padding), then the generic
+ *              3x3 convolution of that precision.  stats must be NULL.
+ * scratch: csd_conv_scratch_bytes(B, 32, Cout, S, S, 3, 0) device bytes - those of a 32-input-channel 3x3 convolution - 256-byte aligned
+ * (assembled input, packed weight, padded bias). */
+int csd_input_conv(const float* x, const float* y, const float* y_noise, float y_sigma, const float* weight, const float* bias, float* out,
+                   double* stats, int B, int Cx, int Cy, int Cout, int S, int centered, int precision, int fused, void* scratch,
+                   void* stream);
+
 /* The ResnetBlock convolution with its prologue fused (csrc/conv_ff.hip; reference models/layers.py:632-675: Conv(act(GroupNorm(x)))
  * [+ Dense(temb)] [+ x]): 3x3, stride 1, pad 1 on NHWC fp32 tensors.  x0 [B,H,W,C0] (+ x1 [B,H,W,C1] or NULL: virtual concat),
  * H % 16 == 0, W % 16 == 0 (CSD_PREC_F16X3 layers of the Winograd form - an even number >= 4 of 16-channel stages - also H % 8 == 0, W % 8 == 0
