@@ -83,6 +83,15 @@ static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 static inline int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
 #ifdef __HIPCC__
+// csd_unet_config.x_squeeze: element offset, inside one sample's x block, of squeezed channel c = 4 ci + 2 dy + dx at pixel (i, j) of the
+// S x S map (hw = S * S, p = i * S + j): the image [ci][2i + dy][2j + dx] of 2S x 2S.  The dx pair of a channel pair is 8 contiguous bytes.
+__device__ __forceinline__ unsigned sq_image_off(int c, int p, int i, int S, int hw) {
+  return (unsigned)((c >> 2) * 4 * hw + 2 * (p + i * S) + ((c >> 1) & 1) * 2 * S + (c & 1));
+}
+// row p / S of pixel p of an S x S map from the correctly rounded rcp_s = 1.f / S: exact for S <= 1024 (p + 0.5 < 2^23 is exact, the
+// product is off by less than S * 2^-23 <= 2^-13 while (p + 0.5) / S stays 1 / (2 S) >= 2^-11 away from an integer) - three
+// instructions per store where an integer division is twenty (csd_unet_create holds x_squeeze to image_size <= 1024)
+__device__ __forceinline__ int sq_row(int p, float rcp_s) { return (int)(((float)p + 0.5f) * rcp_s); }
 // Workgroup copy global -> LDS of `bytes` (a multiple of 16): DEPTH 16-byte loads per thread IN FLIGHT before the first store.  The plain
 // loop `for (i = tid * 16; i < bytes; i += THREADS * 16) lds[i] = src[i]` compiles to load / s_waitcnt vmcnt(0) / ds_write per
 // iteration - one L2 round trip (~0.7 us) per 4 KiB of the workgroup: the 72 - 144 KiB weight copy of a pw16 workgroup was 12 - 25 us of
@@ -148,6 +157,7 @@ struct ConvArgs {
   int out_stride;           // channels of the destination tensor (NHWC) - ignored for nchw
   int out_coff;             // channel offset inside the destination tensor
   int out_nchw;             // 1: write [B,Cout,OH,OW]
+  int out_sq = 0;           // out_nchw and > 0: the first out_sq channels are stored as the 2x image of csd_unet_config.x_squeeze (sq_image_off)
   int act;                  // activation applied after the norm prologue
   float out_scale;          // multiplies the final value (1, or 1/sqrt(2) for skip_rescale)
   double* stats;            // fp16 3x3 kernel: per-tile GroupNorm partials [tile][Cout][2] (sum, sum of squares) or null
@@ -207,7 +217,7 @@ bool pw16_taps_supported(int cin, int cout, int ns);
 int pw16_taps_cout(int cout);
 int pw16_pack_weight_taps(const ConvPlan& p, int ns, const float* w, int cout, void* wpack, hipStream_t s);
 int tapsum_launch(const float* part, const float* bias, const float* res, float* out, int B, int H, int W, int cout, int nchw,
-                  float out_scale, hipStream_t s);
+                  float out_scale, hipStream_t s, int out_sq = 0);
 // stem.hip: cat(x, y [+ sigma z]) + 2v - 1 + NCHW -> NHWC + the first 3 x 3 conv (<= 8 -> Cout channels) + GroupNorm tile partials, one launch
 // padded channel count of an assembled network input of MORE than 8 channels: the next multiple of 16, with exact zeros in the padding
 // (the one rule behind Net::in_cpad, stem_wide_kernel's Cpad and csd_input_conv; up to 8 channels each keeps its own width)
@@ -218,7 +228,7 @@ size_t stem_packed_bytes(int Cin, int Cout, int ns);      // Cin = Cx + Cy: <= 8
 int stem_pack_weight(const float* w, int Cin, int Cout, int ns, void* wpack, hipStream_t s);
 int stem_tiles_per_image(int S);
 int stem_launch(const float* x, const float* y, const float* y_noise, float y_sigma, const void* wpack, const float* bias, float* out,
-                double* stats, int B, int Cx, int Cy, int Cout, int S, int centered, int ns, hipStream_t s);
+                double* stats, int B, int Cx, int Cy, int Cout, int S, int centered, int ns, hipStream_t s, int x_squeeze = 0);
 // y16 = fp16 split of act(x*scale + shift): hi plane (and lo plane when ns == 2), NHWC halves [B*HW][C0+C1]
 // statistics + finalize + apply + split of a small map in one launch (norm.hip); gn_fused16_groups() == 0: use the three-launch form
 int gn_fused16_groups(int HW, int C0, int C1, int G);
@@ -283,7 +293,7 @@ int linear_launch(const float* in, const float* W, const float* bias, float* out
 // NCHW x (+ y (+ sigma*noise)) -> NHWC [B,H,W,Cpad], v -> 2v-1 unless centered
 int assemble_input_launch(const float* x, const float* y, const float* y_noise, float y_sigma,
                           float* out, int B, int Cx, int Cy, int HW, int Cpad, int centered,
-                          hipStream_t s);
+                          hipStream_t s, int x_squeeze = 0, int S = 0);
 // scale multiplies the kernel (after the forward gain), flip reverses the taps: the transposed operators of the training graph
 int fir_resample_nhwc_launch(const float* in, float* out, int B, int H, int W, int C, const float* taps4, int up, hipStream_t s,
                              float scale = 1.f, int flip = 0);
@@ -316,6 +326,10 @@ int bias_add_nchw_launch(const float* x, const float* bias, float* out, int B, i
                          hipStream_t s);
 int nchw_to_nhwc_launch(const float* in, float* out, int B, int C, int HW, int Cw, int ld, hipStream_t s);
 int nhwc_to_nchw_launch(const float* in, float* out, int B, int C, int HW, int Cstride, hipStream_t s);
+// csd_unet_config.x_squeeze at the training graph's boundary: img [B, C / 4, 2S, 2S] (img_ld floats per sample) <-> sq [B, C, S, S]
+// (sq_ld floats per sample), sq[b, 4 ci + 2 dy + dx, i, j] = img[b, ci, 2i + dy, 2j + dx]
+int sq_gather_launch(const float* img, size_t img_ld, float* sq, size_t sq_ld, int B, int C, int S, hipStream_t s);
+int sq_scatter_launch(const float* sq, size_t sq_ld, float* img, size_t img_ld, int B, int C, int S, hipStream_t s);
 int bridge_update_launch(const float* y0, float* state, const float* z, float w0, float w1, float sd, int has_prev, size_t n,
                          hipStream_t s);
 int avgpool2_launch(const float* in, float* out, int B, int H, int W, int C, hipStream_t s);

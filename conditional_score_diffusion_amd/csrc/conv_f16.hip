@@ -179,6 +179,7 @@ int g_c16_dbg_blocks = 0;
 int g_c16_dbg_max = 0, g_c16_dbg_n = 0;
 
 int conv16_launch(const ConvPlan& p, int ns, const ConvArgs& a, hipStream_t s, bool in16) {
+  CSD_REQUIRE(!(a.out_sq && p.LC), "conv16: the x_squeeze store is not provided on the loader / consumer schedule");
   Conv16KArgs k;
   k.a = a;
   k.a.dbg = nullptr;

@@ -567,7 +567,21 @@ __global__ __launch_bounds__(192, 2) void conv_f16_kernel(const void* __restrict
 #pragma unroll
         for (int r = 0; r < 16; ++r) addv[g][r] += tv[g][r];
     }
-    if (nchw) {
+    if (nchw && k.a.out_sq) {      // csd_unet_config.x_squeeze: the first out_sq channels land at their image positions (sq_image_off)
+      const float rcp_ow = 1.0f / (float)k.OW;
+#pragma unroll
+      for (int g = 0; g < GRP; ++g)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int o = oidx[g][r];
+          const int db = btab[(g0 + g) * 32 + (r & 3) + 8 * (r >> 2) + 4 * kg] - b0;
+          const float val = ((acc[g0 + g][r] * wunscale + bv) + addv[g][r]) * k.a.out_scale;
+          const int p = pix0 + o - db * ohw;
+          const unsigned in_s = col < k.a.out_sq ? sq_image_off(col, p, sq_row(p, rcp_ow), k.OW, ohw) : (unsigned)(col * ohw + p);
+          const unsigned off = o >= 0 ? ((unsigned)(db * k.Cout * ohw) + in_s) * 4u : OOB;
+          __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(val), out_r, off, 0, 0);
+        }
+    } else if (nchw) {
 #pragma unroll
       for (int g = 0; g < GRP; ++g)
 #pragma unroll

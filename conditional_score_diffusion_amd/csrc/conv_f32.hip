@@ -311,7 +311,18 @@ __global__ __launch_bounds__(CONV_THREADS, 1) void conv_f32_kernel(const float* 
 #pragma unroll
       for (int r = 0; r < 16; ++r) addv[r] += tv[r];
     }
-    if (nchw) {
+    if (nchw && k.a.out_sq) {      // csd_unet_config.x_squeeze: the first out_sq channels land at their image positions (sq_image_off)
+      const float rcp_ow = 1.0f / (float)k.OW;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int o = oidx[r], db = bidx[r] - b0;
+        const float val = ((acc[n][r] + bv) + addv[r]) * k.a.out_scale;
+        const int p = pix0 + o - db * ohw;
+        const unsigned in_s = col < k.a.out_sq ? sq_image_off(col, p, sq_row(p, rcp_ow), k.OW, ohw) : (unsigned)(col * ohw + p);
+        const unsigned off = (cv && o >= 0) ? ((unsigned)(db * k.Cout * ohw) + in_s) * 4u : OOB;
+        __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(val), out_r, off, 0, 0);
+      }
+    } else if (nchw) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int o = oidx[r], db = bidx[r] - b0;

@@ -153,9 +153,12 @@ int linear_launch(const float* in, const float* W, const float* bias, float* out
 
 // ---- network input: cat(x, y [+ sigma*z]) , 2v-1, NCHW -> NHWC padded to Cpad channels --------
 // (models/ddpm.py:163-168,283; sampling/conditional.py:104-110)
+// SQ (csd_unet_config.x_squeeze): x is the image [B, Cx / 4, 2S, 2S]; channel 4 ci + 2 dy + dx of pixel (i, j) is image pixel
+// (2i + dy, 2j + dx) of channel ci - the dx pair is read as one aligned 8-byte load (2S is even)
+template <bool SQ>
 __global__ void assemble_input_kernel(const float* __restrict__ x, const float* __restrict__ y,
                                       const float* __restrict__ yn, float ysig, float* __restrict__ out,
-                                      int Cx, int Cy, int HW, int Cpad, int centered, size_t total) {
+                                      int Cx, int Cy, int HW, int Cpad, int centered, size_t total, int S) {
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total;
        i += (size_t)gridDim.x * blockDim.x) {
     const size_t pix = i / Cpad;             // b*HW + p
@@ -164,7 +167,13 @@ __global__ void assemble_input_kernel(const float* __restrict__ x, const float* 
     const size_t p = pix - b * HW;
     float v = 0.f;
     if (c < Cx) {
-      v = x[(b * Cx + c) * HW + p];
+      if (SQ) {
+        const int pi = (int)p, row = pi / S;
+        const float2 v2 = *reinterpret_cast<const float2*>(x + b * Cx * HW + sq_image_off(c & ~1, pi, row, S, HW));
+        v = (c & 1) ? v2.y : v2.x;
+      } else {
+        v = x[(b * Cx + c) * HW + p];
+      }
       if (!centered) v = 2.f * v - 1.f;
     } else if (c < Cx + Cy) {
       const size_t j = (b * Cy + (c - Cx)) * HW + p;
@@ -177,11 +186,67 @@ __global__ void assemble_input_kernel(const float* __restrict__ x, const float* 
 }
 
 int assemble_input_launch(const float* x, const float* y, const float* y_noise, float y_sigma, float* out,
-                          int B, int Cx, int Cy, int HW, int Cpad, int centered, hipStream_t s) {
+                          int B, int Cx, int Cy, int HW, int Cpad, int centered, hipStream_t s, int x_squeeze, int S) {
   const size_t total = (size_t)B * HW * Cpad;
   const int grid = (int)std::min<size_t>(cdiv64(total, 256), 8192);
-  hipLaunchKernelGGL(assemble_input_kernel, dim3(grid), dim3(256), 0, s, x, y, y_noise, y_sigma, out, Cx, Cy,
-                     HW, Cpad, centered, total);
+  if (x_squeeze) {
+    CSD_REQUIRE(Cx % 4 == 0 && S > 0 && S * S == HW && (reinterpret_cast<uintptr_t>(x) & 7) == 0,
+                "assemble_input: x_squeeze needs x_channels %% 4 == 0 (got %d) and an 8-byte aligned x", Cx);
+    hipLaunchKernelGGL(assemble_input_kernel<true>, dim3(grid), dim3(256), 0, s, x, y, y_noise, y_sigma, out, Cx, Cy,
+                       HW, Cpad, centered, total, S);
+  } else {
+    hipLaunchKernelGGL(assemble_input_kernel<false>, dim3(grid), dim3(256), 0, s, x, y, y_noise, y_sigma, out, Cx, Cy,
+                       HW, Cpad, centered, total, S);
+  }
+  CSD_LAUNCH_CHECK();
+  return CSD_OK;
+}
+
+// ---- csd_unet_config.x_squeeze at the training graph's boundary: one thread per dx pair (an 8-byte access on the image side, two
+// coalesced 4-byte accesses on the squeezed side) --------------------------------------------------
+template <bool GATHER>
+__global__ void sq_boundary_kernel(const float* __restrict__ src, float* __restrict__ dst, size_t img_ld, size_t sq_ld, int Ci, int S,
+                                   size_t total) {
+  for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (size_t)gridDim.x * blockDim.x) {
+    const int j = (int)(t % S);
+    size_t r = t / S;
+    const int row = (int)(r % (2 * S)); r /= 2 * S;      // image row 2i + dy
+    const int ci = (int)(r % Ci);
+    const size_t b = r / Ci;
+    const size_t io = b * img_ld + ((size_t)ci * 2 * S + row) * 2 * S + 2 * j;
+    const size_t so = b * sq_ld + ((size_t)(4 * ci + 2 * (row & 1)) * S + (row >> 1)) * S + j;
+    if (GATHER) {
+      const float2 v = *reinterpret_cast<const float2*>(src + io);
+      dst[so] = v.x;
+      dst[so + (size_t)S * S] = v.y;
+    } else {
+      *reinterpret_cast<float2*>(dst + io) = make_float2(src[so], src[so + (size_t)S * S]);
+    }
+  }
+}
+
+static int sq_boundary_check(const float* img, size_t img_ld, int C, int S) {
+  CSD_REQUIRE(C % 4 == 0 && S > 0 && img_ld % 2 == 0 && (reinterpret_cast<uintptr_t>(img) & 7) == 0,
+              "x_squeeze: the image side needs x_channels %% 4 == 0 (got %d) and 8-byte aligned samples", C);
+  return CSD_OK;
+}
+
+int sq_gather_launch(const float* img, size_t img_ld, float* sq, size_t sq_ld, int B, int C, int S, hipStream_t s) {
+  int rc = sq_boundary_check(img, img_ld, C, S);
+  if (rc) return rc;
+  const size_t total = (size_t)B * (C / 4) * 2 * S * S;
+  hipLaunchKernelGGL(sq_boundary_kernel<true>, dim3((unsigned)std::min<size_t>(cdiv64(total, 256), 8192)), dim3(256), 0, s, img, sq, img_ld,
+                     sq_ld, C / 4, S, total);
+  CSD_LAUNCH_CHECK();
+  return CSD_OK;
+}
+
+int sq_scatter_launch(const float* sq, size_t sq_ld, float* img, size_t img_ld, int B, int C, int S, hipStream_t s) {
+  int rc = sq_boundary_check(img, img_ld, C, S);
+  if (rc) return rc;
+  const size_t total = (size_t)B * (C / 4) * 2 * S * S;
+  hipLaunchKernelGGL(sq_boundary_kernel<false>, dim3((unsigned)std::min<size_t>(cdiv64(total, 256), 8192)), dim3(256), 0, s, sq, img, img_ld,
+                     sq_ld, C / 4, S, total);
   CSD_LAUNCH_CHECK();
   return CSD_OK;
 }

@@ -16,6 +16,11 @@
 //
 // stem_wide_kernel (below) is the same layer for 9 .. 32 assembled channels, padded to Cpad = 16 or 32: K = tap * Cpad + channel, one or
 // two MFMA K steps per tap.
+//
+// SQ (a compile-time variant of both kernels; csd_unet_config.x_squeeze, the 2x super-resolution networks): x is the HIGH-resolution
+// image [B, Cx / 4, 2S, 2S] and channel 4 ci + 2 dy + dx of patch pixel (gy, gx) is its pixel (2 gy + dy, 2 gx + dx) - pure addressing,
+// the dx pair read as one aligned 8-byte load (a wave still covers whole lines of the image rows it touches).  Out-of-image patch
+// pixels stay masked zeros.  The SQ = false instantiations are the code they were.
 #include <hip/hip_runtime.h>
 
 #include "common.h"
@@ -42,7 +47,7 @@ struct StemArgs {
 #define ST_PLANE 184               // pixels per LDS plane
 #define ST_KSTEPS 5
 
-template <int NT, int NS, bool YN>
+template <int NT, int NS, bool YN, bool SQ>
 __global__ __launch_bounds__(256, 4) void stem_kernel(const StemArgs k) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   half8* const phi = reinterpret_cast<half8*>(smem);
@@ -92,8 +97,10 @@ __global__ __launch_bounds__(256, 4) void stem_kernel(const StemArgs k) {
     cn[c] = (YN && isy) ? k.yn + (size_t)(c - Cx) * HW : k.x;
     cs[c] = isx ? (size_t)Cx * HW : (isy ? (size_t)Cy * HW : 0);
   }
+  // SQ (Cx == 4: one image channel): x channels 2 dy, 2 dy + 1 are one float2 of image row 2 gy + dy; channels 4 .. 7 are y or absent
+  const float2* const xp0 = reinterpret_cast<const float2*>(k.x);
   // load_pixel only REQUESTS the values (raw registers); finish_pixel - called where the wait belongs - assembles them
-  struct Raw { float x[8], n[8]; bool inimg; };
+  struct Raw { float x[8], n[8]; float2 p[2]; bool inimg; };      // (p: SQ only)
   auto load_pixel = [&](int w, Raw& r) __attribute__((always_inline)) {
     const int b = w / k.tpi, tin = w - b * k.tpi;
     const int ty0 = (tin / k.tiles_x) * ST_TH, tx0 = (tin - (tin / k.tiles_x) * k.tiles_x) * 16;
@@ -101,9 +108,25 @@ __global__ __launch_bounds__(256, 4) void stem_kernel(const StemArgs k) {
     r.inimg = !ST_ABL(4) && tid < ST_NPIX && (unsigned)gy < (unsigned)S && (unsigned)gx < (unsigned)S;      // (zero padding applies to the
     const unsigned pix = r.inimg ? (unsigned)(gy * S + gx) : 0u;                                              // ASSEMBLED tensor: 0, not -1)
     // (uniform 64-bit base + 32-bit lane offset: the saddr form of global_load - one address register for all the loads)
+    if (SQ) {
+      const unsigned pix2 = r.inimg ? (unsigned)(2 * gy * S + gx) : 0u;      // float2 index of image pixel (2 gy, 2 gx): (4 gy S + 2 gx) / 2
+      r.p[0] = (xp0 + (size_t)b * (2 * HW))[pix2];
+      r.p[1] = (xp0 + (size_t)b * (2 * HW))[pix2 + (unsigned)S];      // (image row 2 gy + 1: 2S floats on)
+      // (y from ONE uniform base + a 32-bit offset per channel: the eight 64-bit channel pointers of the plain variant would not fit
+      // the scalar registers beside the image pointers)
+      const float* const yb = (Cy ? k.y : k.x) + (size_t)b * Cy * HW;
 #pragma unroll
-    for (int c = 0; c < 8; ++c) r.x[c] = (cp[c] + (size_t)b * cs[c])[pix];
-    if (YN) {
+      for (int c = 4; c < 8; ++c) r.x[c] = yb[pix + (c - 4 < Cy ? (unsigned)(c - 4) * (unsigned)HW : 0u)];
+      if (YN) {
+        const float* const nb = k.yn + (size_t)b * Cy * HW;
+#pragma unroll
+        for (int c = 4; c < 8; ++c) r.n[c] = nb[pix + (c - 4 < Cy ? (unsigned)(c - 4) * (unsigned)HW : 0u)];
+      }
+    } else {
+#pragma unroll
+      for (int c = 0; c < 8; ++c) r.x[c] = (cp[c] + (size_t)b * cs[c])[pix];
+    }
+    if (YN && !SQ) {
 #pragma unroll
       for (int c = 0; c < 8; ++c) r.n[c] = (cn[c] + (size_t)b * cs[c])[pix];
     }
@@ -113,8 +136,8 @@ __global__ __launch_bounds__(256, 4) void stem_kernel(const StemArgs k) {
       half8 h, l;
 #pragma unroll
       for (int c = 0; c < 8; ++c) {
-        float t = r.x[c];
-        if (YN) t = (c >= Cx && c < Cx + Cy) ? t + r.n[c] * k.ysig : t;
+        float t = (SQ && c < 4) ? ((c & 1) ? r.p[c >> 1].y : r.p[c >> 1].x) : r.x[c];
+        if (YN && !(SQ && c < 4)) t = (c >= Cx && c < Cx + Cy) ? t + r.n[c] * k.ysig : t;
         t = k.centered ? t : 2.f * t - 1.f;
         const float v = (r.inimg && c < Cx + Cy) ? t : 0.f;
         h[c] = (_Float16)v;
@@ -248,7 +271,7 @@ __global__ __launch_bounds__(256, 4) void stem_kernel(const StemArgs k) {
 // The tile walk is a plain grid-stride loop; a tile's patch is assembled by all 256 threads (item = (chunk, patch pixel), coalesced
 // along W), out-of-image pixels and the padding channels are written as exact zeros (masked, never clamped: no load is issued for them).
 // S % 16 == 0, so every tile is whole.
-template <int NT, int NS, int KS, bool YN>
+template <int NT, int NS, int KS, bool YN, bool SQ>
 __global__ __launch_bounds__(256, 2) void stem_wide_kernel(const StemArgs k) {
   constexpr int CH = 2 * KS;                        // 8-channel chunks of a pixel
   constexpr int NSTEP = 9 * KS;
@@ -291,7 +314,11 @@ __global__ __launch_bounds__(256, 2) void stem_wide_kernel(const StemArgs k) {
       for (int e = 0; e < 8; ++e) {
         const int c = q * 8 + e;
         float v = 0.f;
-        if (inimg && c < Cx) {
+        if (SQ && inimg && c < Cx) {      // (Cx % 4 == 0: channel c and its dx partner c ^ 1 are both x; one 8-byte load serves the pair)
+          const float2 v2 = *reinterpret_cast<const float2*>(k.x + (size_t)b * Cx * HW + sq_image_off(c & ~1, (int)pix, gy, S, (int)HW));
+          v = (e & 1) ? v2.y : v2.x;
+          v = k.centered ? v : 2.f * v - 1.f;
+        } else if (inimg && c < Cx) {
           v = k.x[((size_t)b * Cx + c) * HW + pix];
           v = k.centered ? v : 2.f * v - 1.f;
         } else if (inimg && c < Cx + Cy) {
@@ -469,8 +496,11 @@ int stem_pack_weight(const float* w, int Cin, int Cout, int ns, void* wpack, hip
 int stem_tiles_per_image(int S) { return (S / 16) * (S / ST_TH); }
 
 int stem_launch(const float* x, const float* y, const float* y_noise, float y_sigma, const void* wpack, const float* bias, float* out,
-                double* stats, int B, int Cx, int Cy, int Cout, int S, int centered, int ns, hipStream_t s) {
+                double* stats, int B, int Cx, int Cy, int Cout, int S, int centered, int ns, hipStream_t s, int x_squeeze) {
   CSD_REQUIRE(stem_supported(Cx, Cy, Cout, S, ns), "stem: unsupported shape (%d+%d -> %d channels, %dx%d)", Cx, Cy, Cout, S, S);
+  CSD_REQUIRE(!x_squeeze || (Cx % 4 == 0 && (Cx + Cy > 8 || Cx == 4) && (reinterpret_cast<uintptr_t>(x) & 7) == 0),
+              "stem: x_squeeze needs x_channels %% 4 == 0 (x_channels = 4 up to 8 assembled channels; got %d) and an 8-byte aligned x", Cx);
+  const bool sq = x_squeeze != 0;
   StemArgs k;
   k.x = x; k.y = y; k.yn = y_noise; k.ysig = y_sigma;
   k.w = reinterpret_cast<const _Float16*>(wpack); k.bias = bias; k.out = out; k.stats = stats;
@@ -497,7 +527,9 @@ int stem_launch(const float* x, const float* y, const float* y_noise, float y_si
       return CSD_OK;
     };
     int rcw;
-#define CSD_STEM_WIDE(NT_, NS_, KS_) (ynw ? gow(stem_wide_kernel<NT_, NS_, KS_, true>) : gow(stem_wide_kernel<NT_, NS_, KS_, false>))
+#define CSD_STEM_WIDE(NT_, NS_, KS_)                                                                                        \
+  (sq ? (ynw ? gow(stem_wide_kernel<NT_, NS_, KS_, true, true>) : gow(stem_wide_kernel<NT_, NS_, KS_, false, true>))       \
+      : (ynw ? gow(stem_wide_kernel<NT_, NS_, KS_, true, false>) : gow(stem_wide_kernel<NT_, NS_, KS_, false, false>)))
     if (cpad == 16) rcw = nt == 3 ? (planes == 2 ? CSD_STEM_WIDE(3, 2, 1) : CSD_STEM_WIDE(3, 1, 1)) : (planes == 2 ? CSD_STEM_WIDE(2, 2, 1) : CSD_STEM_WIDE(2, 1, 1));
     else rcw = nt == 3 ? (planes == 2 ? CSD_STEM_WIDE(3, 2, 2) : CSD_STEM_WIDE(3, 1, 2)) : (planes == 2 ? CSD_STEM_WIDE(2, 2, 2) : CSD_STEM_WIDE(2, 1, 2));
 #undef CSD_STEM_WIDE
@@ -520,10 +552,17 @@ int stem_launch(const float* x, const float* y, const float* y_noise, float y_si
   };
   int rc;
   const bool yn = y_noise != nullptr && k.Cy > 0;
-  if (nt == 3 && planes == 2) rc = yn ? go(stem_kernel<3, 2, true>) : go(stem_kernel<3, 2, false>);
-  else if (nt == 3) rc = yn ? go(stem_kernel<3, 1, true>) : go(stem_kernel<3, 1, false>);
-  else if (planes == 2) rc = yn ? go(stem_kernel<2, 2, true>) : go(stem_kernel<2, 2, false>);
-  else rc = yn ? go(stem_kernel<2, 1, true>) : go(stem_kernel<2, 1, false>);
+  // (SQ exists for the split-operand modes only: with one plane its y-noise variants do not fit 128 VGPRs without spilling, and the plan
+  // of the plain fp16 mode keeps the assemble pass there - unet_layout.h)
+  CSD_REQUIRE(!sq || planes == 2, "stem: x_squeeze on up to 8 channels is provided for the split-operand modes (fp16x3 / fp16f8) only");
+  if (nt == 3 && planes == 2)
+    rc = sq ? (yn ? go(stem_kernel<3, 2, true, true>) : go(stem_kernel<3, 2, false, true>))
+            : (yn ? go(stem_kernel<3, 2, true, false>) : go(stem_kernel<3, 2, false, false>));
+  else if (nt == 3) rc = yn ? go(stem_kernel<3, 1, true, false>) : go(stem_kernel<3, 1, false, false>);
+  else if (planes == 2)
+    rc = sq ? (yn ? go(stem_kernel<2, 2, true, true>) : go(stem_kernel<2, 2, false, true>))
+            : (yn ? go(stem_kernel<2, 2, true, false>) : go(stem_kernel<2, 2, false, false>));
+  else rc = yn ? go(stem_kernel<2, 1, true, false>) : go(stem_kernel<2, 1, false, false>);
   if (rc) return rc;
   CSD_LAUNCH_CHECK();
   return CSD_OK;

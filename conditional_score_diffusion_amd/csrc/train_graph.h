@@ -507,8 +507,14 @@ struct TG {
     // network input: cat(x, y) NCHW (models/ddpm.py:275-298 wrappers), 2h - 1 for data in [0, 1] (:163-168; ncsnpp.py:266-268)
     const size_t hw = (size_t)S * S;
     st.xin = alloc((size_t)B * cio * hw);
+    // x_squeeze: x, out (and d_out, d_x of the backward) are images at the C ABI; the graph itself runs on the squeezed NCHW tensors, so
+    // the copy of x into the network input gathers, and the head writes a workspace tensor that is scattered into the caller's `out`
+    const bool sq = c.x_squeeze != 0;
+    float* const out_caller = out;
+    if (sq) out = alloc((size_t)B * c.out_channels * hw);
     if (!dry) {
-      CSD_CHECK_HIP(hipMemcpy2DAsync(st.xin, cio * hw * 4, x, cx * hw * 4, cx * hw * 4, B, hipMemcpyDeviceToDevice, s));
+      if (sq) TG_RUN(sq_gather_launch(x, cx * hw, st.xin, cio * hw, B, cx, S, s));
+      else CSD_CHECK_HIP(hipMemcpy2DAsync(st.xin, cio * hw * 4, x, cx * hw * 4, cx * hw * 4, B, hipMemcpyDeviceToDevice, s));
       if (cy) CSD_CHECK_HIP(hipMemcpy2DAsync(st.xin + cx * hw, cio * hw * 4, y, cy * hw * 4, cy * hw * 4, B, hipMemcpyDeviceToDevice, s));
       if (!c.centered) TG_RUN(csd_axpby(st.xin, nullptr, st.xin, 2.f, 0.f, -1.f, 1.f, (int64_t)((size_t)B * cio * hw), s));
     }
@@ -619,6 +625,13 @@ struct TG {
       if (m.push) hs.push_back(h);
     }
     CSD_REQUIRE(hs.empty(), "train_forward: the skip stack is not empty behind the last module");
+    if (sq && !dry) {
+      const size_t ld = (size_t)c.out_channels * hw;
+      TG_RUN(sq_scatter_launch(out, ld, out_caller, ld, B, cx, S, s));
+      if (c.out_channels > cx)
+        CSD_CHECK_HIP(hipMemcpy2DAsync(out_caller + cx * hw, ld * 4, out + cx * hw, ld * 4, (c.out_channels - cx) * hw * 4, B,
+                                       hipMemcpyDeviceToDevice, s));
+    }
     st.fwd_top = top;
     return CSD_OK;
   }
@@ -860,6 +873,8 @@ struct TG {
     const int cx = n.cfg.x_channels, S = to.H;
     const size_t np = (size_t)B * cx * S * S;
     const size_t mk = top;
+    float* const d_x_caller = d_x;
+    if (n.cfg.x_squeeze) d_x = alloc(np);            // (the squeezed gradient; scattered into the caller's image below)
     float* w = nullptr;
     int rc = x_weight_slice(W(m.idx, "weight"), n.cfg.nf, 9, &w); if (rc) return rc;
     rc = conv(to.g, w, nullptr, d_x, n.cfg.nf, cx, S, 3, 1, 0, 0, 1 | 4); if (rc) return rc;
@@ -869,6 +884,10 @@ struct TG {
       rc = add_into(d_x, u, np); if (rc) return rc;
     }
     if (dres0) { rc = add_into(d_x, dres0, np); if (rc) return rc; }
+    if (n.cfg.x_squeeze) {
+      TG_RUN(sq_scatter_launch(d_x, (size_t)cx * S * S, d_x_caller, (size_t)cx * S * S, B, cx, S, s));
+      d_x = d_x_caller;
+    }
     top = mk;
     return CSD_OK;
   }
@@ -878,6 +897,18 @@ struct TG {
     const int nf = c.nf;
     top = st.fwd_top;
     int rc;
+    if (c.x_squeeze) {                               // d_out arrives in the layout of `out`: gather its x block, copy the rest
+      const int S = c.image_size, cx = c.x_channels;
+      const size_t hw = (size_t)S * S, ld = (size_t)c.out_channels * hw;
+      float* dn = alloc((size_t)B * ld);
+      if (!dry) {
+        TG_RUN(sq_gather_launch(d_out, ld, dn, ld, B, cx, S, s));
+        if (c.out_channels > cx)
+          CSD_CHECK_HIP(hipMemcpy2DAsync(dn + cx * hw, ld * 4, d_out + cx * hw, ld * 4, (c.out_channels - cx) * hw * 4, B,
+                                         hipMemcpyDeviceToDevice, s));
+      }
+      d_out = dn;
+    }
     float* dtemb_act = nullptr;                      // sum over the blocks of dDense . W: gradient w.r.t. act(temb2)
     dpyr = nullptr;
     dres0 = nullptr;

@@ -376,6 +376,13 @@ static int build_modules(Net& n) {
                 CSD_MAX_IO_CHANNELS, c.out_channels);
     CSD_REQUIRE(c.act >= CSD_ACT_SWISH && c.act <= CSD_ACT_ELU, "unet: bad activation id %d", c.act);
     CSD_REQUIRE(c.precision >= CSD_PREC_F32 && c.precision <= CSD_PREC_F16F8, "unet: bad precision id %d", c.precision);
+    if (c.x_squeeze) {      // the 2x super-resolution networks: x is the image [B, x_channels / 4, 2S, 2S] (include/csd.h)
+      CSD_REQUIRE(c.x_squeeze == 1, "unet: x_squeeze must be 0 or 1 (got %d)", c.x_squeeze);
+      CSD_REQUIRE(c.x_channels % 4 == 0, "unet: x_squeeze needs x_channels %% 4 == 0 (got x_channels = %d)", c.x_channels);
+      CSD_REQUIRE(c.image_size <= 1024, "unet: x_squeeze is provided up to image_size 1024 (got %d)", c.image_size);
+      CSD_REQUIRE(c.out_channels >= c.x_channels, "unet: x_squeeze needs out_channels >= x_channels (got %d < %d)", c.out_channels,
+                  c.x_channels);
+    }
   } else {
     CSD_REQUIRE(c.n_levels >= 1 && c.n_levels <= CSD_MAX_LEVELS, "ncsnpp: bad n_levels %d", c.n_levels);
     CSD_REQUIRE(c.nf % 8 == 0, "ncsnpp: nf=%d must be a multiple of 8", c.nf);
@@ -588,6 +595,8 @@ extern "C" int csd_unet_create(const csd_unet_config* cfg, csd_unet** out) {
   CSD_REQUIRE(cfg && out, "unet_create: null argument");
   std::unique_ptr<csd_unet> h(new csd_unet());
   h->net.cfg = *cfg;
+  CSD_REQUIRE(!cfg->x_squeeze || cfg->arch == 0, "unet_create: x_squeeze = %d is provided for the DDPM family (arch 0) only, not arch %d",
+              cfg->x_squeeze, cfg->arch);
   int rc = cfg->arch == 2 ? build_modules3d(h->net) : build_modules(h->net);
   if (rc) return rc;
   rc = cfg->arch == 2 ? build_packed_layout3d(h->net) : build_packed_layout(h->net);
@@ -787,6 +796,8 @@ static int pc_setup(PCCtx* c, csd_unet* net, const void* packed, void* workspace
                     size_t scratch_bytes, float* x, const float* y, int B, const csd_pc_params* p, void* stream,
                     const csd_pc_inpaint_params* ip = nullptr, bool inpaint = false) {
   CSD_REQUIRE(!(inpaint && net && is3d(net->net)), "pc_inpaint: inpainting is not provided for the 3-D networks (arch 2) on the device loop");
+  CSD_REQUIRE(!(inpaint && net && net->net.cfg.x_squeeze), "pc_inpaint: inpainting is not provided for a handle with x_squeeze (the 2x "
+              "super-resolution networks are conditional)");
   int rc = check_forward_args(net, packed, workspace, workspace_bytes, B, &c->ev);
   if (rc) return rc;
   CSD_REQUIRE(p && x && scratch, "pc_sample: null argument");

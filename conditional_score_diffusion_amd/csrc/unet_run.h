@@ -41,11 +41,11 @@ static int run_plan(Net& n, const Plan& pl, const float* pk, float* ws, const fl
     switch (o.kind) {
       case OP_ASSEMBLE:
         rc = assemble_input_launch(x, y, y_noise, y_sigma, W(o.out), Bo, c.x_channels, c.y_channels, S * S,
-                                   n.in_cpad, c.centered, so);
+                                   n.in_cpad, c.centered, so, c.x_squeeze, S);
         break;
       case OP_STEM:
         rc = stem_launch(x, y, y_noise, y_sigma, pk + o.pk0, pk + o.pk1, W(o.out), reinterpret_cast<double*>(W(o.stats)), Bo,
-                         c.x_channels, c.y_channels, o.i0, S, c.centered, o.i4, so);
+                         c.x_channels, c.y_channels, o.i0, S, c.centered, o.i4, so, c.x_squeeze);
         break;
       case OP_TEMB:
         rc = timestep_embedding_launch(labels, W(o.out), Bo, o.i0, so);
@@ -99,6 +99,7 @@ static int run_plan(Net& n, const Plan& pl, const float* pk, float* ws, const fl
         a.temb_stride = o.temb_stride;
         a.out_stride = o.cp.Cout; a.out_coff = 0;
         a.out_nchw = o.out_external;
+        a.out_sq = (o.out_external && c.x_squeeze) ? c.x_channels : 0;
         a.act = o.act;
         a.out_scale = o.fscale;
         a.dbg = nullptr;
@@ -129,7 +130,8 @@ static int run_plan(Net& n, const Plan& pl, const float* pk, float* ws, const fl
                                  o.i4 != 0, o.fscale, so);
         break;
       case OP_TAPSUM:
-        rc = tapsum_launch(W(o.a), pk + o.pk1, W(o.c), o.out_external ? out : W(o.out), Bo, o.i0, o.i1, o.i2, o.out_external, o.fscale, so);
+        rc = tapsum_launch(W(o.a), pk + o.pk1, W(o.c), o.out_external ? out : W(o.out), Bo, o.i0, o.i1, o.i2, o.out_external, o.fscale, so,
+                           (o.out_external && c.x_squeeze) ? c.x_channels : 0);
         break;
       default:
         set_error("unet: unknown op");

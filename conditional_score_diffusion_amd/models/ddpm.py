@@ -1,7 +1,7 @@
 """DDPM-family score networks as thin adapters over the HIP graph executor.
 
-Registers the reference's names ``ddpm``, ``ddpm_paired_SR3`` and ``ddpm_paired``
-(models/ddpm.py:80,275,287) with the reference's constructor / call signatures:
+Registers the reference's names ``ddpm``, ``ddpm_paired_SR3``, ``ddpm_paired`` and ``ddpm_2xSR``
+(models/ddpm.py:80,275,287,300) with the reference's constructor / call signatures:
 
     model = create_model(config)              # cls(config)
     out = model(x | {'x': x, 'y': y}, labels) # Tensor | {'x': .., 'y': ..}
@@ -102,6 +102,7 @@ class HipUNet(nn.Module, _HandleSurface):
     """Base adapter. Subclasses fix (x_channels, y_channels) conventions."""
 
     arch = 0
+    x_squeeze = 0          # 1: x is the high-resolution image [B, x_channels / 4, 2S, 2S] (csd_unet_config.x_squeeze; DDPM_2xSR)
 
     def __init__(self, config, precision=None):
         super().__init__()
@@ -154,6 +155,7 @@ class HipUNet(nn.Module, _HandleSurface):
         cfg.centered = int(self.centered)
         cfg.act = _lib.ACT_IDS[act]
         cfg.precision = _lib.PREC_IDS[precision]
+        cfg.x_squeeze = int(self.x_squeeze)
         self._extra_config(cfg, config)
         self._cfg = cfg
         self._h = ctypes.c_void_p()
@@ -218,6 +220,18 @@ class HipUNet(nn.Module, _HandleSurface):
     def device(self):
         return next(self.parameters()).device
 
+    # -- shapes at the library boundary ------------------------------------------------------------
+    def _x_shape(self, B):
+        """x (and d_x) of one call: [B, x_channels, S, S], or the image [B, x_channels / 4, 2S, 2S] of a squeezed network"""
+        S = self.image_size
+        return (B, self.x_channels // 4, 2 * S, 2 * S) if self.x_squeeze else (B, self.x_channels, S, S)
+
+    def _out_shape(self, B):
+        """the buffer csd_unet_forward / csd_unet_train_forward write: [B, out_channels, S, S]; a squeezed network's is flat per sample
+        (the x block in image layout, then the other channels at S x S - ``DDPM_2xSR._split``)"""
+        S = self.image_size
+        return (B, self.out_channels * S * S) if self.x_squeeze else (B, self.out_channels, S, S)
+
     # -- evaluation --------------------------------------------------------------------------------
     def _run(self, x, y, labels, y_noise=None, y_sigma=0.0):
         require_gpu_tensor(x, 'x')
@@ -230,12 +244,12 @@ class HipUNet(nn.Module, _HandleSurface):
                 raise RuntimeError('the fused y-perturbation is a sampling feature; it has no input gradient')
             return self._input_grad_forward(x, y, labels)
         labels = self._check_io(x, y, labels)
-        B, S = x.shape[0], self.image_size
+        B = x.shape[0]
         if self.y_channels:
             y = y.contiguous()
         self._ensure_packed()
         ws = self._workspace(B)
-        out = ops._out((B, self.out_channels, S, S), torch.float32, x.device)
+        out = ops._out(self._out_shape(B), torch.float32, x.device)
         check(lib().csd_unet_forward(self._h, ptr(self._packed), ptr(ws), ws.numel(), ptr(x.contiguous()),
                                      ptr(y) if self.y_channels else None, ptr(labels), ptr(out), B,
                                      ptr(y_noise) if y_noise is not None else None, float(y_sigma),
@@ -246,8 +260,8 @@ class HipUNet(nn.Module, _HandleSurface):
     def _check_io(self, x, y, labels):
         """shapes of one call's x, y, labels; returns the labels as a contiguous float32 tensor on x's device"""
         B, S = x.shape[0], self.image_size
-        if tuple(x.shape) != (B, self.x_channels, S, S):
-            raise RuntimeError('x has shape %s, expected %s' % (tuple(x.shape), (B, self.x_channels, S, S)))
+        if tuple(x.shape) != self._x_shape(B):
+            raise RuntimeError('x has shape %s, expected %s' % (tuple(x.shape), self._x_shape(B)))
         if self.y_channels:
             require_gpu_tensor(y, 'y')
             if tuple(y.shape) != (B, self.y_channels, S, S):
@@ -307,6 +321,9 @@ class HipUNet(nn.Module, _HandleSurface):
             raise NotImplementedError('training with resamp_with_conv=False is not provided')
         if self.train_executor == 'planned' and self.arch == 0 and self.train_layout == 'nhwc':
             return self._train_forward_planned(x, y, labels)
+        if self.x_squeeze:
+            raise NotImplementedError('a squeezed network (ddpm_2xSR) trains on the planned graph only (CSD_TRAIN_EXECUTOR=planned, '
+                                      'CSD_TRAIN_LAYOUT=nhwc)')
         nhwc = self.train_layout == 'nhwc'
         if nhwc:
             from .. import grad_ops_nhwc as G
@@ -427,7 +444,7 @@ class _PlannedNet(torch.autograd.Function):
         ws = model._train_workspace(B) if shared else ops._scratch(
             lib().csd_unet_train_workspace_bytes(model._h, B, model._dropout), x.device)
         table = (ctypes.c_void_p * len(params))(*[p.data_ptr() for p in params])
-        out = ops._out((B, model.out_channels, model.image_size, model.image_size), torch.float32, x.device)
+        out = ops._out(model._out_shape(B), torch.float32, x.device)
         check(lib().csd_unet_train_forward(model._h, table, ptr(ws), ws.numel(), ptr(x), ptr(y) if y is not None else None,
                                            ptr(labels), ptr(out), B, model._dropout, model.dropout_seed, model._train_calls,
                                            current_stream(x.device)), 'unet_train_forward')
@@ -467,8 +484,7 @@ class _PlannedNet(torch.autograd.Function):
             grads = [flat[o:o + n].view(shape) for o, (shape, n) in zip(offs, ctx.shapes)]
         gtable = (ctypes.c_void_p * len(grads))(*[g.data_ptr() for g in grads])
         # d loss / d x from the same call when autograd asks for it (csd_unet_backward_ex: the parameter gradients are unchanged)
-        dx = ops._out((B, model.x_channels, model.image_size, model.image_size), torch.float32, dout.device) \
-            if ctx.needs_input_grad[1] else None
+        dx = ops._out(model._x_shape(B), torch.float32, dout.device) if ctx.needs_input_grad[1] else None
         check(lib().csd_unet_backward_ex(model._h, ctx.table, gtable, ptr(dx), ptr(ctx.ws), ctx.ws.numel(), ptr(dout), B, ctx.call,
                                          current_stream(dout.device)), 'unet_backward')
         if ctx.fin is not None:          # (the backward releases the workspace itself; the finalizer of this context must not fire later)
@@ -495,7 +511,7 @@ class _InputGradNet(torch.autograd.Function):
             raise RuntimeError('libcsd_hip: cannot plan the input-gradient graph at batch %d: %s' % (B, lib().csd_last_error().decode()))
         ws = ops._scratch(need, x.device)
         table = (ctypes.c_void_p * len(params))(*[p.data_ptr() for p in params])
-        out = ops._out((B, model.out_channels, model.image_size, model.image_size), torch.float32, x.device)
+        out = ops._out(model._out_shape(B), torch.float32, x.device)
         check(lib().csd_unet_train_forward(model._h, table, ptr(ws), ws.numel(), ptr(x), ptr(y), ptr(labels), ptr(out), B, 0.0,
                                            model.dropout_seed, call, current_stream(x.device)), 'unet_train_forward')
         import weakref
@@ -507,7 +523,7 @@ class _InputGradNet(torch.autograd.Function):
     def backward(ctx, dout):
         model, B = ctx.model, ctx.B
         dout = dout.contiguous()
-        dx = ops._out((B, model.x_channels, model.image_size, model.image_size), torch.float32, dout.device)
+        dx = ops._out(model._x_shape(B), torch.float32, dout.device)
         check(lib().csd_unet_backward_ex(model._h, ctx.table, None, ptr(dx), ptr(ctx.ws), ctx.ws.numel(), ptr(dout), B, ctx.call,
                                          current_stream(dout.device)), 'unet_backward_ex')
         ctx.fin()
@@ -552,3 +568,34 @@ class DDPM_paired(_Paired):
         out = self._run(input_dict['x'], input_dict['y'], labels)
         c = self.x_channels
         return {'x': out[:, :c], 'y': out[:, c:]}
+
+
+@utils.register_model(name='ddpm_2xSR')
+class DDPM_2xSR(_Paired):
+    """One 2x stage of the sequential super-resolution cascades (models/ddpm.py:39-52,300-314): the DDPM U-Net behind a parameter-free
+    space-to-depth squeeze of x.  ``forward({'x': [B, cx, 2S, 2S], 'y': [B, cy, S, S]}, labels) -> {'x': [B, cx, 2S, 2S],
+    'y': [B, cy, S, S]}`` with S = data.effective_image_size.  The squeeze is addressing inside the library's boundary kernels
+    (csd_unet_config.x_squeeze): no squeezed copy of x, and the returned ``'x'`` is a view of the buffer the network wrote.  The
+    parameters are the reference ``DDPM_2xSR``'s (the squeeze has none)."""
+
+    x_squeeze = 1
+
+    def __init__(self, config, precision=None):
+        d = config.data
+        hi, S, lo = int(d.shape_x[1]), int(d.effective_image_size), int(d.shape_y[1])
+        if not (hi == 2 * S == 2 * lo and int(d.shape_x[2]) == hi and int(d.shape_y[2]) == lo):
+            raise ValueError('ddpm_2xSR: the image side data.shape_x[1] = %d must be twice data.effective_image_size = %d and twice '
+                             'data.shape_y[1] = %d (square images)' % (hi, S, lo))
+        super().__init__(config, precision)
+
+    def _channels(self, config):
+        cx = 4 * int(config.data.shape_x[0])
+        return cx, int(config.model.input_channels) - cx
+
+    def _split(self, out):
+        B, S = out.shape[0], self.image_size
+        n = self.x_channels * S * S
+        return {'x': out[:, :n].view(self._x_shape(B)), 'y': out[:, n:].view(B, self.out_channels - self.x_channels, S, S)}
+
+    def forward(self, input_dict, labels):
+        return self._split(self._run(input_dict['x'], input_dict['y'], labels))

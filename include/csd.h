@@ -122,7 +122,24 @@ typedef struct csd_unet_config {
   /* ---- arch 2 (3-D DDPM family, models/ddpm3D.py) only: the extents of the volume behind the channel, D, H, W (config.data.shape_x[1:]).
    * arch 2 ignores image_size, the attention fields and the arch-1 fields above; arch 0 / 1 ignore vol. ---- */
   int32_t vol[3];
+  /* ---- arch 0 only: the 2x super-resolution networks (models/ddpm.py:39-52,300-314, DDPM_2xSR).  1: x is the HIGH-resolution image
+   * [B, x_channels / 4, 2S, 2S] (S = image_size) and the network sees its space-to-depth squeeze,
+   *     x'[b, 4c + 2dy + dx, i, j] = x[b, c, 2i + dy, 2j + dx],
+   * so x_channels stays the count the NETWORK sees (a multiple of 4).  The library's boundary kernels address the image directly: no
+   * squeezed copy of x exists.  See "x_squeeze" below.  0 (a zero-initialised struct): x is [B, x_channels, S, S] as before. ---- */
+  int32_t x_squeeze;
 } csd_unet_config;
+
+/* x_squeeze = 1 (arch 0; csd_unet_create refuses it for arch 1 / 2 and refuses x_channels % 4 != 0, out_channels < x_channels and
+ * image_size > 1024, naming the field).  With
+ * Ci = x_channels / 4 and HW = S * S, every per-sample element count is unchanged (x_channels * HW), only the layout of the x block is
+ * the image's:
+ *   x (csd_unet_forward, csd_unet_train_forward), d_x (csd_unet_backward_ex), the state x and every `record` row of csd_pc_sample /
+ *   csd_pc_step_begin / csd_pc_step_end                                       [B, Ci, 2S, 2S]
+ *   out, d_out: per sample out_channels * HW floats - first the x block as the image [Ci, 2S, 2S] (x_channels * HW floats), then
+ *   the remaining out_channels - x_channels channels as [., S, S]; needs out_channels >= x_channels
+ *   y, y_noise                                                                 [B, y_channels, S, S] as before
+ * csd_pc_inpaint_* and csd_unet_debug_digest return CSD_ERR_INVALID for a squeezed handle. */
 
 /* arch 2: x [B, x_channels, D, H, W], y [B, y_channels, D, H, W] (NULL iff y_channels == 0; ddpm3D has none, the paired classes take
  * both counts from shape_x[0] / shape_y[0]), out [B, out_channels, D, H, W], all NCDHW.  The handle serves csd_unet_create / destroy,
