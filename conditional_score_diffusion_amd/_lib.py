@@ -31,6 +31,7 @@ class UNetConfig(ctypes.Structure):
                 ('centered', ctypes.c_int32), ('act', ctypes.c_int32), ('precision', ctypes.c_int32),
                 ('skip_rescale', ctypes.c_int32), ('progressive', ctypes.c_int32), ('progressive_input', ctypes.c_int32),
                 ('embedding_type', ctypes.c_int32), ('n_fir', ctypes.c_int32), ('fir_kernel', ctypes.c_float * 8),
+                ('y_scale', ctypes.c_int32),       # arch 0 / 1: K >= 2 = y is [B, y_channels, S / K, S / K] (the Kx super-resolution networks)
                 ('vol', ctypes.c_int32 * 3),       # arch 2: D, H, W
                 ('x_squeeze', ctypes.c_int32)]     # arch 0: 1 = x is the image [B, x_channels / 4, 2S, 2S] (the 2x super-resolution networks)
 
@@ -85,6 +86,7 @@ SIGNATURES = {
                               ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
     'csd_profile_stop_ex': (_i, [_i, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_i64), ctypes.POINTER(ctypes.c_double),
                                  ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
+    'csd_unet_config_size': (_sz, []),
     'csd_unet_create': (_i, [ctypes.POINTER(UNetConfig), ctypes.POINTER(_vp)]),
     'csd_unet_destroy': (None, [_vp]),
     'csd_unet_num_params': (_i, [_vp]),
@@ -130,6 +132,9 @@ SIGNATURES = {
     'csd_linear': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     'csd_fourier_embedding': (_i, [_vp, _vp, _vp, _i, _i, _vp]),
     'csd_axpby': (_i, [_vp, _vp, _vp, _f, _f, _f, _f, _i64, _vp]),
+    'csd_bilinear_up': (_i, [_vp, _vp, _i64, _i, _i, _vp]),
+    'csd_bilinear_down': (_i, [_vp, _vp, _i64, _i, _i, _vp]),
+    'csd_bilinear_down_adjoint': (_i, [_vp, _vp, _i64, _i, _i, _vp]),
     'csd_bias_add_nchw': (_i, [_vp, _vp, _vp, _i, _i, _i64, _i, _i, _vp]),
     'csd_randn': (_i, [_vp, _i64, _u64, _u64, _vp]),
     'csd_scale_rows': (_i, [_vp, _vp, _vp, _i, _i, _i64, _vp]),
@@ -156,6 +161,7 @@ SIGNATURES = {
     'csd_act': (_i, [_vp, _vp, _vp, _i, _i64, _vp]),
     'csd_mul': (_i, [_vp, _vp, _vp, _i64, _vp]),
     'csd_input_conv': (_i, [_vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    'csd_input_conv_kx': (_i, [_vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     'csd_conv3x3_block_scratch_bytes': (_sz, [_i, _i]),
     'csd_conv3x3_block': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _f, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     'csd_conv2d_ex': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
@@ -210,6 +216,9 @@ def lib():
             fn = getattr(l, name)   # AttributeError here = header/library out of sync
             fn.restype = res
             fn.argtypes = args
+        if l.csd_unet_config_size() != ctypes.sizeof(UNetConfig):
+            raise RuntimeError('libcsd_hip.so at %s has a csd_unet_config of %d bytes, this binding one of %d: rebuild the library'
+                               % (LIB_PATH, l.csd_unet_config_size(), ctypes.sizeof(UNetConfig)))
         _lib = l
     return _lib
 

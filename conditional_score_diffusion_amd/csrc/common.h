@@ -92,6 +92,59 @@ __device__ __forceinline__ unsigned sq_image_off(int c, int p, int i, int S, int
 // product is off by less than S * 2^-23 <= 2^-13 while (p + 0.5) / S stays 1 / (2 S) >= 2^-11 away from an integer) - three
 // instructions per store where an integer division is twenty (csd_unet_create holds x_squeeze to image_size <= 1024)
 __device__ __forceinline__ int sq_row(int p, float rcp_s) { return (int)(((float)p + 0.5f) * rcp_s); }
+// csd_unet_config.y_scale = K: the bilinear resampling of torch's F.interpolate(mode = 'bilinear', align_corners = False, no
+// antialias) between a side-s map and its K times larger side-S map, S = K s.  Upwards the source coordinate of output index o is
+// max((o + 0.5) / K - 0.5, 0) = max(2o + 1 - K, 0) / (2K): the tap i0 is the integer quotient and the weight of i1 = min(i0 + 1, s - 1) is
+// the remainder over 2K - exact integers, no floor of a float.  Every kernel that resamples goes through these functions, and their
+// arithmetic is spelled in single roundings (no contraction left to the compiler): a value does not depend on which kernel computed it.
+struct BilinTap { int i0, i1; float w1; };
+__device__ __forceinline__ BilinTap bilin_up_tap(int o, int K, int s) {
+  const int num = 2 * o + 1 - K;
+  BilinTap t;
+  t.i0 = num > 0 ? num / (2 * K) : 0;
+  t.w1 = num > 0 ? __fdiv_rn((float)(num - t.i0 * 2 * K), (float)(2 * K)) : 0.f;
+  t.i1 = min(t.i0 + 1, s - 1);
+  return t;
+}
+// the value of an output pixel from its four (possibly perturbed) taps a b / c d and the weights of the second column / row, combined
+// as torch does: wy0 (wx0 a + wx1 b) + wy1 (wx0 c + wx1 d)
+__device__ __forceinline__ float bilin_combine(float a, float b, float c, float d, float wx1, float wy1) {
+  const float wx0 = __fsub_rn(1.f, wx1), wy0 = __fsub_rn(1.f, wy1);
+  const float top = __fmaf_rn(wx1, b, __fmul_rn(wx0, a)), bot = __fmaf_rn(wx1, d, __fmul_rn(wx0, c));
+  return __fmaf_rn(wy1, bot, __fmul_rn(wy0, top));
+}
+// the perturbation of a tap, y + sig z at LOW resolution (then the upsample, as the reference does)
+__device__ __forceinline__ float bilin_perturb(float v, float z, float sig) { return __fmaf_rn(z, sig, v); }
+// output pixel (oy, ox) of the upsampled plane: the four taps of `plane` [s, s] (+ sig * the same taps of `noise` when noise != null)
+__device__ __forceinline__ float bilin_up(const float* __restrict__ plane, const float* __restrict__ noise, float sig, int oy, int ox,
+                                          int K, int s) {
+  const BilinTap ty = bilin_up_tap(oy, K, s), tx = bilin_up_tap(ox, K, s);
+  const int o00 = ty.i0 * s + tx.i0, o01 = ty.i0 * s + tx.i1, o10 = ty.i1 * s + tx.i0, o11 = ty.i1 * s + tx.i1;
+  float a = plane[o00], b = plane[o01], c = plane[o10], d = plane[o11];
+  if (noise) {
+    a = bilin_perturb(a, noise[o00], sig); b = bilin_perturb(b, noise[o01], sig);
+    c = bilin_perturb(c, noise[o10], sig); d = bilin_perturb(d, noise[o11], sig);
+  }
+  return bilin_combine(a, b, c, d, tx.w1, ty.w1);
+}
+// Downwards by an integer K the same formula lands on fixed taps: K even - the mean of the 2 x 2 block at rows / columns K i + K / 2 - 1,
+// K i + K / 2 (both weights 1 / 2); K odd - the single pixel K i + (K - 1) / 2.  bilin_down_first = the first of those rows / columns.
+__device__ __forceinline__ int bilin_down_first(int i, int K) { return K * i + ((K & 1) ? (K - 1) / 2 : K / 2 - 1); }
+__device__ __forceinline__ float bilin_down(const float* __restrict__ plane, int i, int j, int K, int S) {
+  const int r = bilin_down_first(i, K), c = bilin_down_first(j, K);
+  const float* q = plane + (size_t)r * S + c;
+  if (K & 1) return q[0];
+  return __fmul_rn(0.25f, __fadd_rn(__fadd_rn(q[0], q[1]), __fadd_rn(q[S], q[S + 1])));
+}
+// its adjoint at full-resolution pixel (r, c): a quarter (K odd: all) of the gradient of the block's output pixel when (r, c) is one of
+// its taps, else zero.  g [s, s].
+__device__ __forceinline__ float bilin_down_adjoint(const float* __restrict__ g, int r, int c, int K, int s) {
+  const int i = r / K, j = c / K, fr = bilin_down_first(i, K), fc = bilin_down_first(j, K);
+  const bool hit = (K & 1) ? (r == fr && c == fc) : ((r == fr || r == fr + 1) && (c == fc || c == fc + 1));
+  if (!hit) return 0.f;
+  const float v = g[i * s + j];
+  return (K & 1) ? v : __fmul_rn(0.25f, v);
+}
 // Workgroup copy global -> LDS of `bytes` (a multiple of 16): DEPTH 16-byte loads per thread IN FLIGHT before the first store.  The plain
 // loop `for (i = tid * 16; i < bytes; i += THREADS * 16) lds[i] = src[i]` compiles to load / s_waitcnt vmcnt(0) / ds_write per
 // iteration - one L2 round trip (~0.7 us) per 4 KiB of the workgroup: the 72 - 144 KiB weight copy of a pw16 workgroup was 12 - 25 us of
@@ -228,7 +281,10 @@ size_t stem_packed_bytes(int Cin, int Cout, int ns);      // Cin = Cx + Cy: <= 8
 int stem_pack_weight(const float* w, int Cin, int Cout, int ns, void* wpack, hipStream_t s);
 int stem_tiles_per_image(int S);
 int stem_launch(const float* x, const float* y, const float* y_noise, float y_sigma, const void* wpack, const float* bias, float* out,
-                double* stats, int B, int Cx, int Cy, int Cout, int S, int centered, int ns, hipStream_t s, int x_squeeze = 0);
+                double* stats, int B, int Cx, int Cy, int Cout, int S, int centered, int ns, hipStream_t s, int x_squeeze = 0,
+                int y_scale = 0, float* y_tmp = nullptr);      // (y_tmp: y_scale with y_noise - [B, Cy, S / K, S / K] floats of scratch)
+// out = y + sig * z in one rounding (bilin_perturb): the low-resolution perturbation in front of the y_scale first layer
+int bilinear_perturb_launch(const float* y, const float* z, float sig, float* out, size_t n, hipStream_t st);
 // y16 = fp16 split of act(x*scale + shift): hi plane (and lo plane when ns == 2), NHWC halves [B*HW][C0+C1]
 // statistics + finalize + apply + split of a small map in one launch (norm.hip); gn_fused16_groups() == 0: use the three-launch form
 int gn_fused16_groups(int HW, int C0, int C1, int G);
@@ -293,7 +349,7 @@ int linear_launch(const float* in, const float* W, const float* bias, float* out
 // NCHW x (+ y (+ sigma*noise)) -> NHWC [B,H,W,Cpad], v -> 2v-1 unless centered
 int assemble_input_launch(const float* x, const float* y, const float* y_noise, float y_sigma,
                           float* out, int B, int Cx, int Cy, int HW, int Cpad, int centered,
-                          hipStream_t s, int x_squeeze = 0, int S = 0);
+                          hipStream_t s, int x_squeeze = 0, int S = 0, int y_scale = 0);
 // scale multiplies the kernel (after the forward gain), flip reverses the taps: the transposed operators of the training graph
 int fir_resample_nhwc_launch(const float* in, float* out, int B, int H, int W, int C, const float* taps4, int up, hipStream_t s,
                              float scale = 1.f, int flip = 0);
@@ -330,6 +386,13 @@ int nhwc_to_nchw_launch(const float* in, float* out, int B, int C, int HW, int C
 // (sq_ld floats per sample), sq[b, 4 ci + 2 dy + dx, i, j] = img[b, ci, 2i + dy, 2j + dx]
 int sq_gather_launch(const float* img, size_t img_ld, float* sq, size_t sq_ld, int B, int C, int S, hipStream_t s);
 int sq_scatter_launch(const float* sq, size_t sq_ld, float* img, size_t img_ld, int B, int C, int S, hipStream_t s);
+// csd_unet_config.y_scale (bilin_up / bilin_down above) on [B, C] planes; a sample's planes start at b * src_ld / b * dst_ld floats.
+// up: src [., C, s, s] (+ sig * noise, same layout and stride, or null) -> dst [., C, K s, K s]; down: src [., C, S, S] -> dst
+// [., C, S / K, S / K]; down_adjoint: src = the gradient [., C, S / K, S / K] -> dst [., C, S, S] (every element written)
+int bilinear_up_launch(const float* src, const float* noise, float sig, size_t src_ld, float* dst, size_t dst_ld, int B, int C, int s, int K,
+                       hipStream_t st);
+int bilinear_down_launch(const float* src, size_t src_ld, float* dst, size_t dst_ld, int B, int C, int S, int K, hipStream_t st);
+int bilinear_down_adjoint_launch(const float* src, size_t src_ld, float* dst, size_t dst_ld, int B, int C, int S, int K, hipStream_t st);
 int bridge_update_launch(const float* y0, float* state, const float* z, float w0, float w1, float sd, int has_prev, size_t n,
                          hipStream_t s);
 int avgpool2_launch(const float* in, float* out, int B, int H, int W, int C, hipStream_t s);

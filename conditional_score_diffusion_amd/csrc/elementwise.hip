@@ -155,10 +155,12 @@ int linear_launch(const float* in, const float* W, const float* bias, float* out
 // (models/ddpm.py:163-168,283; sampling/conditional.py:104-110)
 // SQ (csd_unet_config.x_squeeze): x is the image [B, Cx / 4, 2S, 2S]; channel 4 ci + 2 dy + dx of pixel (i, j) is image pixel
 // (2i + dy, 2j + dx) of channel ci - the dx pair is read as one aligned 8-byte load (2S is even)
-template <bool SQ>
+// YS (csd_unet_config.y_scale = K): y and yn are LOW-resolution [B, Cy, S / K, S / K]; the network sees the bilinear upsample of
+// y + ysig yn (bilin_up, common.h) - four taps of a plane of a few KB, served by L2; no full-resolution copy of y exists
+template <bool SQ, bool YS>
 __global__ void assemble_input_kernel(const float* __restrict__ x, const float* __restrict__ y,
                                       const float* __restrict__ yn, float ysig, float* __restrict__ out,
-                                      int Cx, int Cy, int HW, int Cpad, int centered, size_t total, int S) {
+                                      int Cx, int Cy, int HW, int Cpad, int centered, size_t total, int S, int K) {
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total;
        i += (size_t)gridDim.x * blockDim.x) {
     const size_t pix = i / Cpad;             // b*HW + p
@@ -176,9 +178,15 @@ __global__ void assemble_input_kernel(const float* __restrict__ x, const float* 
       }
       if (!centered) v = 2.f * v - 1.f;
     } else if (c < Cx + Cy) {
-      const size_t j = (b * Cy + (c - Cx)) * HW + p;
-      v = y[j];
-      if (yn) v = v + yn[j] * ysig;
+      if (YS) {
+        const int pi = (int)p, row = pi / S, lo = S / K;
+        const size_t pl = (b * Cy + (c - Cx)) * (size_t)(lo * lo);
+        v = bilin_up(y + pl, yn ? yn + pl : nullptr, ysig, row, pi - row * S, K, lo);
+      } else {
+        const size_t j = (b * Cy + (c - Cx)) * HW + p;
+        v = y[j];
+        if (yn) v = v + yn[j] * ysig;
+      }
       if (!centered) v = 2.f * v - 1.f;
     }
     out[i] = v;
@@ -186,20 +194,84 @@ __global__ void assemble_input_kernel(const float* __restrict__ x, const float* 
 }
 
 int assemble_input_launch(const float* x, const float* y, const float* y_noise, float y_sigma, float* out,
-                          int B, int Cx, int Cy, int HW, int Cpad, int centered, hipStream_t s, int x_squeeze, int S) {
+                          int B, int Cx, int Cy, int HW, int Cpad, int centered, hipStream_t s, int x_squeeze, int S, int y_scale) {
   const size_t total = (size_t)B * HW * Cpad;
   const int grid = (int)std::min<size_t>(cdiv64(total, 256), 8192);
-  if (x_squeeze) {
+  if (y_scale) {
+    CSD_REQUIRE(!x_squeeze && y_scale >= 2 && Cy > 0 && S > 0 && S * S == HW && S % y_scale == 0,
+                "assemble_input: y_scale = %d needs y_channels > 0, no x_squeeze and image_size %% y_scale == 0 (image_size %d)", y_scale, S);
+    hipLaunchKernelGGL((assemble_input_kernel<false, true>), dim3(grid), dim3(256), 0, s, x, y, y_noise, y_sigma, out, Cx, Cy,
+                       HW, Cpad, centered, total, S, y_scale);
+  } else if (x_squeeze) {
     CSD_REQUIRE(Cx % 4 == 0 && S > 0 && S * S == HW && (reinterpret_cast<uintptr_t>(x) & 7) == 0,
                 "assemble_input: x_squeeze needs x_channels %% 4 == 0 (got %d) and an 8-byte aligned x", Cx);
-    hipLaunchKernelGGL(assemble_input_kernel<true>, dim3(grid), dim3(256), 0, s, x, y, y_noise, y_sigma, out, Cx, Cy,
-                       HW, Cpad, centered, total, S);
+    hipLaunchKernelGGL((assemble_input_kernel<true, false>), dim3(grid), dim3(256), 0, s, x, y, y_noise, y_sigma, out, Cx, Cy,
+                       HW, Cpad, centered, total, S, 0);
   } else {
-    hipLaunchKernelGGL(assemble_input_kernel<false>, dim3(grid), dim3(256), 0, s, x, y, y_noise, y_sigma, out, Cx, Cy,
-                       HW, Cpad, centered, total, S);
+    hipLaunchKernelGGL((assemble_input_kernel<false, false>), dim3(grid), dim3(256), 0, s, x, y, y_noise, y_sigma, out, Cx, Cy,
+                       HW, Cpad, centered, total, S, 0);
   }
   CSD_LAUNCH_CHECK();
   return CSD_OK;
+}
+
+// ---- csd_unet_config.y_scale: the resamplers on [B, C] planes (csd_bilinear_up / _down, the head's y block, the training graph's
+// boundary).  MODE 0: up (+ sig * noise), 1: down, 2: the adjoint of down.  One thread per destination element, coalesced stores; the
+// sources are read through L2 (up, adjoint: a low-resolution plane; down: four of K^2 pixels). ----------------------------------------
+template <int MODE>
+__global__ void bilinear_kernel(const float* __restrict__ src, const float* __restrict__ noise, float sig, size_t src_ld,
+                                float* __restrict__ dst, size_t dst_ld, int C, int hi, int K, size_t total) {
+  const int lo = hi / K, ds = MODE == 1 ? lo : hi, ss = MODE == 1 ? hi : lo;      // destination / source side
+  for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (size_t)gridDim.x * blockDim.x) {
+    const int ox = (int)(t % ds);
+    size_t r = t / ds;
+    const int oy = (int)(r % ds); r /= ds;
+    const int c = (int)(r % C);
+    const size_t b = r / C;
+    const size_t so = b * src_ld + (size_t)c * ss * ss;
+    float v;
+    if (MODE == 0) v = bilin_up(src + so, noise ? noise + so : nullptr, sig, oy, ox, K, lo);
+    else if (MODE == 1) v = bilin_down(src + so, oy, ox, K, hi);
+    else v = bilin_down_adjoint(src + so, oy, ox, K, lo);
+    dst[b * dst_ld + ((size_t)c * ds + oy) * ds + ox] = v;
+  }
+}
+
+template <int MODE>
+static int bilinear_launch(const float* src, const float* noise, float sig, size_t src_ld, float* dst, size_t dst_ld, int B, int C, int hi,
+                           int K, hipStream_t st) {
+  CSD_REQUIRE(src && dst && B > 0 && C > 0 && K >= 2 && hi >= K && hi % K == 0 && hi <= 32768,
+              "bilinear: needs a scale K >= 2 that divides the full-resolution side (side %d, K %d)", hi, K);
+  const int lo = hi / K, ds = MODE == 1 ? lo : hi, ss = MODE == 1 ? hi : lo;
+  CSD_REQUIRE(src_ld >= (size_t)C * ss * ss && dst_ld >= (size_t)C * ds * ds, "bilinear: a sample stride is shorter than its planes");
+  const size_t total = (size_t)B * C * ds * ds;
+  hipLaunchKernelGGL(bilinear_kernel<MODE>, dim3((unsigned)std::min<size_t>(cdiv64(total, 256), 8192)), dim3(256), 0, st, src, noise, sig,
+                     src_ld, dst, dst_ld, C, hi, K, total);
+  CSD_LAUNCH_CHECK();
+  return CSD_OK;
+}
+
+__global__ void bilinear_perturb_kernel(const float* __restrict__ y, const float* __restrict__ z, float sig, float* __restrict__ out, size_t n) {
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
+    out[i] = bilin_perturb(y[i], z[i], sig);
+}
+int bilinear_perturb_launch(const float* y, const float* z, float sig, float* out, size_t n, hipStream_t st) {
+  CSD_REQUIRE(y && z && out && n > 0, "bilinear_perturb: bad arguments");
+  hipLaunchKernelGGL(bilinear_perturb_kernel, dim3((unsigned)std::min<size_t>(cdiv64(n, 256), 8192)), dim3(256), 0, st, y, z, sig, out, n);
+  CSD_LAUNCH_CHECK();
+  return CSD_OK;
+}
+
+int bilinear_up_launch(const float* src, const float* noise, float sig, size_t src_ld, float* dst, size_t dst_ld, int B, int C, int s, int K,
+                       hipStream_t st) {
+  CSD_REQUIRE(s > 0 && K >= 2 && (int64_t)s * K <= 32768, "bilinear_up: bad side %d / scale %d", s, K);
+  return bilinear_launch<0>(src, noise, sig, src_ld, dst, dst_ld, B, C, s * K, K, st);
+}
+int bilinear_down_launch(const float* src, size_t src_ld, float* dst, size_t dst_ld, int B, int C, int S, int K, hipStream_t st) {
+  return bilinear_launch<1>(src, nullptr, 0.f, src_ld, dst, dst_ld, B, C, S, K, st);
+}
+int bilinear_down_adjoint_launch(const float* src, size_t src_ld, float* dst, size_t dst_ld, int B, int C, int S, int K, hipStream_t st) {
+  return bilinear_launch<2>(src, nullptr, 0.f, src_ld, dst, dst_ld, B, C, S, K, st);
 }
 
 // ---- csd_unet_config.x_squeeze at the training graph's boundary: one thread per dx pair (an 8-byte access on the image side, two

@@ -238,10 +238,15 @@ extern "C" int csd_conv2d_ex(const float* x, const float* weight, const float* b
 static int input_conv_cpad(int cin, int ns) { return cin > 8 ? wide_cpad(cin) : (ns ? 16 : 8); }
 // scratch: that of a 32-input-channel 3x3 convolution, csd_conv_scratch_bytes(B, 32, Cout, S, S, 3, 0): the assembled input at up to 32
 // channels | the packed weight of whichever kernel takes it (none is larger than the 32-channel layouts api_packed_floats covers) | the padded bias
-extern "C" int csd_input_conv(const float* x, const float* y, const float* y_noise, float y_sigma, const float* weight, const float* bias,
-                              float* out, double* stats, int B, int Cx, int Cy, int Cout, int S, int centered, int precision, int fused,
-                              void* scratch, void* stream) {
+// (y_scale = K >= 2: y and y_noise are [B, Cy, S / K, S / K] and the layer sees the bilinear upsample of y + y_sigma y_noise -
+// csd_input_conv_kx, the first layer of a csd_unet_config.y_scale network)
+static int input_conv_impl(const float* x, const float* y, const float* y_noise, float y_sigma, const float* weight, const float* bias,
+                           float* out, double* stats, int B, int Cx, int Cy, int Cout, int S, int centered, int precision, int fused,
+                           void* scratch, void* stream, int y_scale) {
   CSD_REQUIRE(x && weight && bias && out && scratch, "input_conv: null argument");
+  CSD_REQUIRE(!y_scale || (y_scale >= 2 && Cy >= 1 && Cx + Cy <= 8 && S % y_scale == 0),
+              "input_conv: y_scale = %d needs y channels, up to 8 assembled channels (got %d + %d) and S %% y_scale == 0 (S = %d)", y_scale,
+              Cx, Cy, S);
   CSD_REQUIRE(B >= 1 && Cx >= 1 && Cy >= 0 && Cx + Cy <= CSD_MAX_IO_CHANNELS && Cout >= 1 && S >= 1, "input_conv: bad shape");
   CSD_REQUIRE((Cy == 0) == (y == nullptr), "input_conv: y must be given iff Cy > 0");
   CSD_REQUIRE(precision >= CSD_PREC_F32 && precision <= CSD_PREC_F16F8, "input_conv: bad precision id %d", precision);
@@ -259,7 +264,9 @@ extern "C" int csd_input_conv(const float* x, const float* y, const float* y_noi
     CSD_REQUIRE(ns && stem_supported(Cx, Cy, Cout, S, ns), "input_conv: the fused first layer does not cover %d+%d -> %d channels at %dx%d in this precision",
                 Cx, Cy, Cout, S, S);
     if ((rc = stem_pack_weight(weight, cin, Cout, ns, wp, s))) return rc;
-    return stem_launch(x, y, y_noise, y_sigma, wp, bias, out, stats, B, Cx, Cy, Cout, S, centered, ns, s);
+    CSD_REQUIRE(!y_scale || (Cx <= 4 && Cy <= 4), "input_conv: the fused first layer covers y_scale up to 4 + 4 channels (got %d + %d)", Cx, Cy);
+    // (y_scale: the perturbed low-resolution y goes to the head of the scratch, which the fused path does not use otherwise)
+    return stem_launch(x, y, y_noise, y_sigma, wp, bias, out, stats, B, Cx, Cy, Cout, S, centered, ns, s, 0, y_scale, xh);
   }
   CSD_REQUIRE(!stats, "input_conv: tile statistics come from the fused layer only");
   ConvPlan p;
@@ -269,7 +276,7 @@ extern "C" int csd_input_conv(const float* x, const float* y, const float* y_noi
     CSD_REQUIRE(conv16_supported(p), "input_conv: no fp16 kernel for %d padded channels", cpad);
     if ((rc = conv16_plan_tiles(&p, ns))) return rc;
   }
-  if ((rc = assemble_input_launch(x, y, y_noise, y_sigma, xh, B, Cx, Cy, S * S, cpad, centered, s))) return rc;
+  if ((rc = assemble_input_launch(x, y, y_noise, y_sigma, xh, B, Cx, Cy, S * S, cpad, centered, s, 0, S, y_scale))) return rc;
   rc = ns ? conv16_pack_weight(p, ns, weight, 0, cin, Cout, 0, wp, s) : conv_pack_weight(p, weight, 0, cin, Cout, 0, wp, s);
   if (rc) return rc;
   CSD_CHECK_HIP(hipMemsetAsync(bp, 0, (size_t)p.CoutPad * sizeof(float), s));
@@ -279,6 +286,20 @@ extern "C" int csd_input_conv(const float* x, const float* y, const float* y_noi
   a.src0 = xh; a.wpack = wp; a.bias = bp; a.out = out;
   a.out_stride = Cout; a.out_nchw = 0; a.out_scale = 1.f;
   return ns ? conv16_launch(p, ns, a, s) : conv_launch(p, a, s);
+}
+
+extern "C" int csd_input_conv(const float* x, const float* y, const float* y_noise, float y_sigma, const float* weight, const float* bias,
+                              float* out, double* stats, int B, int Cx, int Cy, int Cout, int S, int centered, int precision, int fused,
+                              void* scratch, void* stream) {
+  return input_conv_impl(x, y, y_noise, y_sigma, weight, bias, out, stats, B, Cx, Cy, Cout, S, centered, precision, fused, scratch, stream, 0);
+}
+
+extern "C" int csd_input_conv_kx(const float* x, const float* y, const float* y_noise, float y_sigma, const float* weight,
+                                 const float* bias, float* out, double* stats, int B, int Cx, int Cy, int Cout, int S, int y_scale,
+                                 int centered, int precision, int fused, void* scratch, void* stream) {
+  CSD_REQUIRE(y_scale >= 2, "input_conv_kx: y_scale must be at least 2 (got %d)", y_scale);
+  return input_conv_impl(x, y, y_noise, y_sigma, weight, bias, out, stats, B, Cx, Cy, Cout, S, centered, precision, fused, scratch, stream,
+                         y_scale);
 }
 
 // ---- ResnetBlock convolution with the fused GroupNorm + SiLU prologue (conv_ff.hip) ---------------------------------
@@ -353,6 +374,26 @@ extern "C" int csd_axpby(const float* a, const float* b, float* out, float alpha
                          int64_t n, void* stream) {
   CSD_REQUIRE(a && out && n > 0, "axpby: bad arguments");
   return axpby_launch(a, b, out, alpha, beta, gamma, post, (size_t)n, (hipStream_t)stream);
+}
+
+// csd_unet_config.y_scale's resamplers as operators: the device functions of the network's boundary kernels (common.h: bilin_up,
+// bilin_down, bilin_down_adjoint) on n = B * C contiguous planes
+extern "C" int csd_bilinear_up(const float* y, float* out, int64_t n, int side, int scale, void* stream) {
+  CSD_REQUIRE(y && out && n > 0 && n <= INT32_MAX && side > 0, "bilinear_up: bad arguments");
+  const size_t s2 = (size_t)side * side;
+  return bilinear_up_launch(y, nullptr, 0.f, s2, out, s2 * scale * scale, (int)n, 1, side, scale, (hipStream_t)stream);
+}
+
+extern "C" int csd_bilinear_down(const float* v, float* out, int64_t n, int side, int scale, void* stream) {
+  CSD_REQUIRE(v && out && n > 0 && n <= INT32_MAX && side > 0 && scale >= 2, "bilinear_down: bad arguments");
+  const size_t s2 = (size_t)side * side;
+  return bilinear_down_launch(v, s2, out, s2 / ((size_t)scale * scale), (int)n, 1, side, scale, (hipStream_t)stream);
+}
+
+extern "C" int csd_bilinear_down_adjoint(const float* g, float* out, int64_t n, int side, int scale, void* stream) {
+  CSD_REQUIRE(g && out && n > 0 && n <= INT32_MAX && side > 0 && scale >= 2, "bilinear_down_adjoint: bad arguments");
+  const size_t s2 = (size_t)side * side;
+  return bilinear_down_adjoint_launch(g, s2 / ((size_t)scale * scale), out, s2, (int)n, 1, side, scale, (hipStream_t)stream);
 }
 
 extern "C" int csd_bias_add_nchw(const float* x, const float* bias, float* out, int B, int C, int64_t inner,

@@ -88,6 +88,7 @@ extern "C" int csd_unet_debug_digest(csd_unet* net, int B, float dropout_p, uint
   CSD_REQUIRE(net && out, "debug_digest: null argument");
   CSD_REQUIRE(net->net.cfg.arch != 2, "debug_digest: the 3-D networks (arch 2) have no digest");
   CSD_REQUIRE(!net->net.cfg.x_squeeze, "debug_digest: a handle with x_squeeze has no digest (its plan is the unsqueezed network's)");
+  CSD_REQUIRE(!net->net.cfg.y_scale, "debug_digest: a handle with y_scale has no digest (its plan is the paired network's)");
   Plan* pl = nullptr;
   const int rc = build_plan(net->net, B, &pl);
   if (rc) return rc;

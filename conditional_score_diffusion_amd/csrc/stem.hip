@@ -21,6 +21,15 @@
 // image [B, Cx / 4, 2S, 2S] and channel 4 ci + 2 dy + dx of patch pixel (gy, gx) is its pixel (2 gy + dy, 2 gx + dx) - pure addressing,
 // the dx pair read as one aligned 8-byte load (a wave still covers whole lines of the image rows it touches).  Out-of-image patch
 // pixels stay masked zeros.  The SQ = false instantiations are the code they were.
+//
+// YS (a compile-time variant of stem_kernel; csd_unet_config.y_scale = K, the direct Kx super-resolution networks): y and its noise are
+// LOW-resolution [B, Cy <= 4, S / K, S / K] (and Cx <= 4) and a y channel of patch pixel (gy, gx) is the bilinear upsample there (common.h: bilin_up_tap,
+// bilin_perturb, bilin_combine - the functions of the assemble pass and of csd_bilinear_up, so the value does not depend on the route).
+// The four taps per channel are REQUESTED in load_pixel like every other source value and combined in write_patch; a sample's
+// low-resolution planes are a few KB and stay in L2.  No full-resolution copy of y exists.  The perturbation of a sampling step,
+// y + sigma z at LOW resolution, is one small launch in front (bilinear_perturb_launch into the plan's scratch plane): holding the noise
+// taps as well does not fit the 128 registers of this kernel's occupancy, so YS exists with YN = false only.  x comes from ONE uniform
+// base + a 32-bit offset per channel (as SQ reads y).  The YS = false instantiations are the code they were.
 #include <hip/hip_runtime.h>
 
 #include "common.h"
@@ -36,6 +45,7 @@ struct StemArgs {
   float* out;
   double* stats;
   int B, S, Cx, Cy, Cout, tiles_x, tpi, n_groups, nblocks, centered;
+  int ys = 0;   // YS: csd_unet_config.y_scale
   int abl;      // tuning aid (tune build, CSD_STEM_ABL): 1 no output stores, 2 no statistics, 4 no source loads, 8 no MFMAs
 };
 
@@ -47,8 +57,9 @@ struct StemArgs {
 #define ST_PLANE 184               // pixels per LDS plane
 #define ST_KSTEPS 5
 
-template <int NT, int NS, bool YN, bool SQ>
+template <int NT, int NS, bool YN, bool SQ, bool YS>
 __global__ __launch_bounds__(256, 4) void stem_kernel(const StemArgs k) {
+  static_assert(!(YS && (YN || SQ)), "stem_kernel: YS excludes YN (the perturbation is a launch in front) and SQ");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   half8* const phi = reinterpret_cast<half8*>(smem);
   half8* const plo = phi + ST_PLANE;
@@ -93,18 +104,49 @@ __global__ __launch_bounds__(256, 4) void stem_kernel(const StemArgs k) {
 #pragma unroll
   for (int c = 0; c < 8; ++c) {
     const bool isx = c < Cx, isy = !isx && c < Cx + Cy;
-    cp[c] = isx ? k.x + (size_t)c * HW : (isy ? k.y + (size_t)(c - Cx) * HW : k.x);
-    cn[c] = (YN && isy) ? k.yn + (size_t)(c - Cx) * HW : k.x;
-    cs[c] = isx ? (size_t)Cx * HW : (isy ? (size_t)Cy * HW : 0);
+    // (YS: the y channels are not read at S x S - a dummy load here, their taps below)
+    cp[c] = isx ? k.x + (size_t)c * HW : ((isy && !YS) ? k.y + (size_t)(c - Cx) * HW : k.x);
+    cn[c] = (YN && isy && !YS) ? k.yn + (size_t)(c - Cx) * HW : k.x;
+    cs[c] = isx ? (size_t)Cx * HW : ((isy && !YS) ? (size_t)Cy * HW : 0);
   }
+  const int ylo = YS ? S / k.ys : 0;      // YS: side of the low-resolution planes
   // SQ (Cx == 4: one image channel): x channels 2 dy, 2 dy + 1 are one float2 of image row 2 gy + dy; channels 4 .. 7 are y or absent
   const float2* const xp0 = reinterpret_cast<const float2*>(k.x);
   // load_pixel only REQUESTS the values (raw registers); finish_pixel - called where the wait belongs - assembles them
-  struct Raw { float x[8], n[8]; float2 p[2]; bool inimg; };      // (p: SQ only)
+  struct Raw { float x[8], n[8]; float2 p[2]; float t[4][4], wx, wy; int w; bool inimg; };      // (p: SQ only; t, wx, wy: YS only; w: LATE only)
+  // sample b and image position (gy, gx) of this thread's patch pixel in tile w (LATE: write_patch finds the tile of its raw values)
+  auto patch_origin = [&](int w, int& b, int& gy, int& gx) __attribute__((always_inline)) {
+    b = w / k.tpi;
+    const int tin = w - b * k.tpi;
+    const int ty0 = (tin / k.tiles_x) * ST_TH, tx0 = (tin - (tin / k.tiles_x) * k.tiles_x) * 16;
+    gy = ty0 + py - 1; gx = tx0 + px - 1;
+  };
+  // YS: the four taps of y channel j < Cy <= 4 (absent channels and out-of-image pixels read element 0 and are never used).  NT = 2:
+  // requested with the rest of the patch, before the K loop.  NT = 3 (LATE): the 16 tap registers do not fit beside three accumulator
+  // tiles (64 bytes of scratch per lane when held across the K loop), so they are requested in write_patch, behind the K loop, where the
+  // youngest older stores are a whole K loop old - one exposed L2 round trip per tile, shared with three other workgroups of the CU.
+  constexpr bool LATE = YS && NT == 3;
+  auto load_taps = [&](int gy, int gx, int b, Raw& r) __attribute__((always_inline)) {
+    const BilinTap ty = bilin_up_tap(r.inimg ? gy : 0, k.ys, ylo), tx = bilin_up_tap(r.inimg ? gx : 0, k.ys, ylo);
+    r.wx = tx.w1; r.wy = ty.w1;
+    const unsigned o4[4] = {(unsigned)(ty.i0 * ylo + tx.i0), (unsigned)(ty.i0 * ylo + tx.i1), (unsigned)(ty.i1 * ylo + tx.i0),
+                            (unsigned)(ty.i1 * ylo + tx.i1)};
+    const unsigned lo2 = (unsigned)(ylo * ylo);
+    const float* const yb = k.y + (size_t)b * Cy * lo2;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const unsigned cb = j < Cy ? (unsigned)j * lo2 : 0u;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) r.t[j][q] = yb[cb + o4[q]];
+    }
+  };
   auto load_pixel = [&](int w, Raw& r) __attribute__((always_inline)) {
+    // (the arithmetic of patch_origin, spelled out as it always was: routing this through the lambda changed the register allocation of
+    // the existing instantiations - one spilled VGPR in stem_kernel<3, 1, false, false>)
     const int b = w / k.tpi, tin = w - b * k.tpi;
     const int ty0 = (tin / k.tiles_x) * ST_TH, tx0 = (tin - (tin / k.tiles_x) * k.tiles_x) * 16;
     const int gy = ty0 + py - 1, gx = tx0 + px - 1;
+    if (LATE) r.w = w;      // (uniform: a scalar register; write_patch requests the taps of the SAME tile from it)
     r.inimg = !ST_ABL(4) && tid < ST_NPIX && (unsigned)gy < (unsigned)S && (unsigned)gx < (unsigned)S;      // (zero padding applies to the
     const unsigned pix = r.inimg ? (unsigned)(gy * S + gx) : 0u;                                              // ASSEMBLED tensor: 0, not -1)
     // (uniform 64-bit base + 32-bit lane offset: the saddr form of global_load - one address register for all the loads)
@@ -122,22 +164,41 @@ __global__ __launch_bounds__(256, 4) void stem_kernel(const StemArgs k) {
 #pragma unroll
         for (int c = 4; c < 8; ++c) r.n[c] = nb[pix + (c - 4 < Cy ? (unsigned)(c - 4) * (unsigned)HW : 0u)];
       }
+    } else if (YS) {
+      const float* const xb = k.x + (size_t)b * Cx * HW;
+#pragma unroll
+      for (int c = 0; c < 4; ++c) r.x[c] = xb[pix + (c < Cx ? (unsigned)c * (unsigned)HW : 0u)];      // (YS: Cx <= 4)
     } else {
 #pragma unroll
       for (int c = 0; c < 8; ++c) r.x[c] = (cp[c] + (size_t)b * cs[c])[pix];
     }
-    if (YN && !SQ) {
+    if (YN && !SQ && !YS) {
 #pragma unroll
       for (int c = 0; c < 8; ++c) r.n[c] = (cn[c] + (size_t)b * cs[c])[pix];
     }
+    if (YS && !LATE) load_taps(gy, gx, b, r);
   };
-  auto write_patch = [&](const Raw& r) __attribute__((always_inline)) {      // assemble, split once: plane hi [pixel][8 ch], plane lo [pixel][8 ch]
+  auto write_patch = [&](Raw& r) __attribute__((always_inline)) {      // assemble, split once: plane hi [pixel][8 ch], plane lo [pixel][8 ch]
+    if (LATE) {      // (the taps of the tile load_pixel filled r for)
+      int b, gy, gx;
+      patch_origin(r.w, b, gy, gx);
+      load_taps(gy, gx, b, r);
+    }
     if (tid < ST_PLANE) {
       half8 h, l;
+      float yv[4];
+      if (YS) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) yv[j] = bilin_combine(r.t[j][0], r.t[j][1], r.t[j][2], r.t[j][3], r.wx, r.wy);
+      }
 #pragma unroll
       for (int c = 0; c < 8; ++c) {
-        float t = (SQ && c < 4) ? ((c & 1) ? r.p[c >> 1].y : r.p[c >> 1].x) : r.x[c];
-        if (YN && !(SQ && c < 4)) t = (c >= Cx && c < Cx + Cy) ? t + r.n[c] * k.ysig : t;
+        float t = (SQ && c < 4) ? ((c & 1) ? r.p[c >> 1].y : r.p[c >> 1].x) : ((YS && c >= 4) ? 0.f : r.x[c]);
+        if (YS) {
+#pragma unroll
+          for (int j = 0; j < 4; ++j) t = (c == Cx + j) ? yv[j] : t;
+        }
+        if (YN && !YS && !(SQ && c < 4)) t = (c >= Cx && c < Cx + Cy) ? t + r.n[c] * k.ysig : t;
         t = k.centered ? t : 2.f * t - 1.f;
         const float v = (r.inimg && c < Cx + Cy) ? t : 0.f;
         h[c] = (_Float16)v;
@@ -496,14 +557,26 @@ int stem_pack_weight(const float* w, int Cin, int Cout, int ns, void* wpack, hip
 int stem_tiles_per_image(int S) { return (S / 16) * (S / ST_TH); }
 
 int stem_launch(const float* x, const float* y, const float* y_noise, float y_sigma, const void* wpack, const float* bias, float* out,
-                double* stats, int B, int Cx, int Cy, int Cout, int S, int centered, int ns, hipStream_t s, int x_squeeze) {
+                double* stats, int B, int Cx, int Cy, int Cout, int S, int centered, int ns, hipStream_t s, int x_squeeze, int y_scale,
+                float* y_tmp) {
   CSD_REQUIRE(stem_supported(Cx, Cy, Cout, S, ns), "stem: unsupported shape (%d+%d -> %d channels, %dx%d)", Cx, Cy, Cout, S, S);
+  CSD_REQUIRE(!y_scale || (y_scale >= 2 && !x_squeeze && Cx <= 4 && Cy >= 1 && Cy <= 4 && S % y_scale == 0 && y),
+              "stem: y_scale = %d needs up to 4 x and 1 .. 4 y channels (got %d + %d), no x_squeeze and image_size %% y_scale == 0",
+              y_scale, Cx, Cy);
   CSD_REQUIRE(!x_squeeze || (Cx % 4 == 0 && (Cx + Cy > 8 || Cx == 4) && (reinterpret_cast<uintptr_t>(x) & 7) == 0),
               "stem: x_squeeze needs x_channels %% 4 == 0 (x_channels = 4 up to 8 assembled channels; got %d) and an 8-byte aligned x", Cx);
   const bool sq = x_squeeze != 0;
   StemArgs k;
   k.x = x; k.y = y; k.yn = y_noise; k.ysig = y_sigma;
   k.w = reinterpret_cast<const _Float16*>(wpack); k.bias = bias; k.out = out; k.stats = stats;
+  k.ys = y_scale;
+  if (y_scale && y_noise) {      // perturb at low resolution, then the kernel upsamples (no YN variant of YS: see the header)
+    CSD_REQUIRE(y_tmp, "stem: y_scale with y_noise needs the scratch plane");
+    const int lo = S / y_scale;
+    const int rcp = bilinear_perturb_launch(y, y_noise, y_sigma, y_tmp, (size_t)B * Cy * lo * lo, s);
+    if (rcp) return rcp;
+    k.y = y_tmp; k.yn = nullptr;
+  }
   k.B = B; k.S = S; k.Cx = Cx; k.Cy = y ? Cy : 0; k.Cout = Cout;
   k.tiles_x = S / 16; k.tpi = stem_tiles_per_image(S);
   const int nt = stem_nt(Cout);
@@ -551,18 +624,17 @@ int stem_launch(const float* x, const float* y, const float* y_noise, float y_si
     return CSD_OK;
   };
   int rc;
-  const bool yn = y_noise != nullptr && k.Cy > 0;
+  const bool yn = y_noise != nullptr && k.Cy > 0 && !y_scale;
   // (SQ exists for the split-operand modes only: with one plane its y-noise variants do not fit 128 VGPRs without spilling, and the plan
   // of the plain fp16 mode keeps the assemble pass there - unet_layout.h)
   CSD_REQUIRE(!sq || planes == 2, "stem: x_squeeze on up to 8 channels is provided for the split-operand modes (fp16x3 / fp16f8) only");
-  if (nt == 3 && planes == 2)
-    rc = sq ? (yn ? go(stem_kernel<3, 2, true, true>) : go(stem_kernel<3, 2, false, true>))
-            : (yn ? go(stem_kernel<3, 2, true, false>) : go(stem_kernel<3, 2, false, false>));
-  else if (nt == 3) rc = yn ? go(stem_kernel<3, 1, true, false>) : go(stem_kernel<3, 1, false, false>);
-  else if (planes == 2)
-    rc = sq ? (yn ? go(stem_kernel<2, 2, true, true>) : go(stem_kernel<2, 2, false, true>))
-            : (yn ? go(stem_kernel<2, 2, true, false>) : go(stem_kernel<2, 2, false, false>));
-  else rc = yn ? go(stem_kernel<2, 1, true, false>) : go(stem_kernel<2, 1, false, false>);
+  const bool ysv = y_scale != 0;
+#define CSD_STEM_YN(NT_, NS_, SQ_) (yn ? go(stem_kernel<NT_, NS_, true, SQ_, false>) : go(stem_kernel<NT_, NS_, false, SQ_, false>))
+  if (nt == 3 && planes == 2) rc = sq ? CSD_STEM_YN(3, 2, true) : (ysv ? go(stem_kernel<3, 2, false, false, true>) : CSD_STEM_YN(3, 2, false));
+  else if (nt == 3) rc = ysv ? go(stem_kernel<3, 1, false, false, true>) : CSD_STEM_YN(3, 1, false);
+  else if (planes == 2) rc = sq ? CSD_STEM_YN(2, 2, true) : (ysv ? go(stem_kernel<2, 2, false, false, true>) : CSD_STEM_YN(2, 2, false));
+  else rc = ysv ? go(stem_kernel<2, 1, false, false, true>) : CSD_STEM_YN(2, 1, false);
+#undef CSD_STEM_YN
   if (rc) return rc;
   CSD_LAUNCH_CHECK();
   return CSD_OK;

@@ -509,13 +509,17 @@ struct TG {
     st.xin = alloc((size_t)B * cio * hw);
     // x_squeeze: x, out (and d_out, d_x of the backward) are images at the C ABI; the graph itself runs on the squeezed NCHW tensors, so
     // the copy of x into the network input gathers, and the head writes a workspace tensor that is scattered into the caller's `out`
-    const bool sq = c.x_squeeze != 0;
+    // y_scale = K: y arrives at S / K and is upsampled into the network input (bilin_up); the head writes a workspace tensor whose y
+    // channels are downsampled into the caller's `out` (the x block is copied) - the layouts of include/csd.h
+    const bool sq = c.x_squeeze != 0, ys = c.y_scale != 0;
     float* const out_caller = out;
-    if (sq) out = alloc((size_t)B * c.out_channels * hw);
+    if (sq || ys) out = alloc((size_t)B * c.out_channels * hw);
     if (!dry) {
       if (sq) TG_RUN(sq_gather_launch(x, cx * hw, st.xin, cio * hw, B, cx, S, s));
       else CSD_CHECK_HIP(hipMemcpy2DAsync(st.xin, cio * hw * 4, x, cx * hw * 4, cx * hw * 4, B, hipMemcpyDeviceToDevice, s));
-      if (cy) CSD_CHECK_HIP(hipMemcpy2DAsync(st.xin + cx * hw, cio * hw * 4, y, cy * hw * 4, cy * hw * 4, B, hipMemcpyDeviceToDevice, s));
+      if (ys) TG_RUN(bilinear_up_launch(y, nullptr, 0.f, cy * (hw / ((size_t)c.y_scale * c.y_scale)), st.xin + cx * hw, cio * hw, B, cy,
+                                        S / c.y_scale, c.y_scale, s));
+      else if (cy) CSD_CHECK_HIP(hipMemcpy2DAsync(st.xin + cx * hw, cio * hw * 4, y, cy * hw * 4, cy * hw * 4, B, hipMemcpyDeviceToDevice, s));
       if (!c.centered) TG_RUN(csd_axpby(st.xin, nullptr, st.xin, 2.f, 0.f, -1.f, 1.f, (int64_t)((size_t)B * cio * hw), s));
     }
     std::vector<int> hs;                             // skip stack (tensor ids)
@@ -631,6 +635,12 @@ struct TG {
       if (c.out_channels > cx)
         CSD_CHECK_HIP(hipMemcpy2DAsync(out_caller + cx * hw, ld * 4, out + cx * hw, ld * 4, (c.out_channels - cx) * hw * 4, B,
                                        hipMemcpyDeviceToDevice, s));
+    }
+    if (ys && !dry) {
+      const size_t ld = (size_t)c.out_channels * hw, ldo = out_sample_elems(c);
+      CSD_CHECK_HIP(hipMemcpy2DAsync(out_caller, ldo * 4, out, ld * 4, cx * hw * 4, B, hipMemcpyDeviceToDevice, s));
+      if (c.out_channels > cx)
+        TG_RUN(bilinear_down_launch(out + cx * hw, ld, out_caller + cx * hw, ldo, B, c.out_channels - cx, S, c.y_scale, s));
     }
     st.fwd_top = top;
     return CSD_OK;
@@ -906,6 +916,17 @@ struct TG {
         if (c.out_channels > cx)
           CSD_CHECK_HIP(hipMemcpy2DAsync(dn + cx * hw, ld * 4, d_out + cx * hw, ld * 4, (c.out_channels - cx) * hw * 4, B,
                                          hipMemcpyDeviceToDevice, s));
+      }
+      d_out = dn;
+    }
+    if (c.y_scale) {                                 // d_out arrives in the layout of `out`: copy its x block, the adjoint of bilin_down for the rest
+      const int S = c.image_size, cx = c.x_channels;
+      const size_t hw = (size_t)S * S, ld = (size_t)c.out_channels * hw, ldo = out_sample_elems(c);
+      float* dn = alloc((size_t)B * ld);
+      if (!dry) {
+        CSD_CHECK_HIP(hipMemcpy2DAsync(dn, ld * 4, d_out, ldo * 4, cx * hw * 4, B, hipMemcpyDeviceToDevice, s));
+        if (c.out_channels > cx)
+          TG_RUN(bilinear_down_adjoint_launch(d_out + cx * hw, ldo, dn + cx * hw, ld, B, c.out_channels - cx, S, c.y_scale, s));
       }
       d_out = dn;
     }

@@ -165,6 +165,7 @@ struct Plan {
   int B = 0;
   std::vector<Op> ops;
   size_t ws_floats = 0;
+  size_t ys_out = NONE;               // y_scale: the head's full-resolution output [B, out_channels, S, S], behind every other tensor
   int64_t launches = 0;
   double flops = 0, bytes = 0;
 };
@@ -531,6 +532,14 @@ static int build_modules(Net& n) {
   return CSD_OK;
 }
 
+// floats of one sample of `out` / d_out / the sampler's net_out: out_channels planes, or with y_scale = K (arch 0 / 1) the x block at
+// S x S followed by the other channels downsampled to S / K (include/csd.h)
+static inline size_t out_sample_elems(const csd_unet_config& c) {
+  const size_t hw = c.arch == 2 ? (size_t)c.vol[0] * c.vol[1] * c.vol[2] : (size_t)c.image_size * c.image_size;
+  if (!c.y_scale) return (size_t)c.out_channels * hw;
+  return (size_t)c.x_channels * hw + (size_t)(c.out_channels - c.x_channels) * (hw / ((size_t)c.y_scale * c.y_scale));
+}
+
 }  // namespace csd
 
 #include "unet_layout.h"
@@ -591,12 +600,27 @@ extern "C" int csd_profile_stop_ex(int n_classes, double* ms, int64_t* launches,
 extern "C" const char* csd_version(void) { return "csd-hip 0.1 (gfx950)"; }
 extern "C" const char* csd_last_error(void) { return get_error(); }
 
+extern "C" size_t csd_unet_config_size(void) { return sizeof(csd_unet_config); }
+
 extern "C" int csd_unet_create(const csd_unet_config* cfg, csd_unet** out) {
   CSD_REQUIRE(cfg && out, "unet_create: null argument");
   std::unique_ptr<csd_unet> h(new csd_unet());
   h->net.cfg = *cfg;
   CSD_REQUIRE(!cfg->x_squeeze || cfg->arch == 0, "unet_create: x_squeeze = %d is provided for the DDPM family (arch 0) only, not arch %d",
               cfg->x_squeeze, cfg->arch);
+  if (cfg->y_scale) {      // the direct Kx super-resolution networks: y is [B, y_channels, S / K, S / K] (include/csd.h)
+    CSD_REQUIRE(cfg->y_scale >= 2, "unet_create: y_scale must be 0 or >= 2 (got %d)", cfg->y_scale);
+    CSD_REQUIRE(cfg->arch == 0 || cfg->arch == 1, "unet_create: y_scale = %d is provided for arch 0 / 1, not for the 3-D networks (arch %d)",
+                cfg->y_scale, cfg->arch);
+    CSD_REQUIRE(!cfg->x_squeeze, "unet_create: y_scale = %d and x_squeeze = %d exclude each other", cfg->y_scale, cfg->x_squeeze);
+    CSD_REQUIRE(cfg->y_channels > 0, "unet_create: y_scale = %d needs a conditioning image (y_channels = %d)", cfg->y_scale, cfg->y_channels);
+    CSD_REQUIRE(cfg->image_size > 0 && cfg->image_size % cfg->y_scale == 0, "unet_create: y_scale = %d must divide image_size = %d",
+                cfg->y_scale, cfg->image_size);
+    CSD_REQUIRE(cfg->x_channels + cfg->y_channels <= 8, "unet_create: y_scale = %d is provided up to 8 assembled channels (got %d + %d)",
+                cfg->y_scale, cfg->x_channels, cfg->y_channels);
+    CSD_REQUIRE(cfg->out_channels >= cfg->x_channels, "unet_create: y_scale = %d needs out_channels >= x_channels (got %d < %d)",
+                cfg->y_scale, cfg->out_channels, cfg->x_channels);
+  }
   int rc = cfg->arch == 2 ? build_modules3d(h->net) : build_modules(h->net);
   if (rc) return rc;
   rc = cfg->arch == 2 ? build_packed_layout3d(h->net) : build_packed_layout(h->net);
@@ -798,6 +822,8 @@ static int pc_setup(PCCtx* c, csd_unet* net, const void* packed, void* workspace
   CSD_REQUIRE(!(inpaint && net && is3d(net->net)), "pc_inpaint: inpainting is not provided for the 3-D networks (arch 2) on the device loop");
   CSD_REQUIRE(!(inpaint && net && net->net.cfg.x_squeeze), "pc_inpaint: inpainting is not provided for a handle with x_squeeze (the 2x "
               "super-resolution networks are conditional)");
+  CSD_REQUIRE(!(inpaint && net && net->net.cfg.y_scale), "pc_inpaint: inpainting is not provided for a handle with y_scale (the Kx "
+              "super-resolution networks are conditional)");
   int rc = check_forward_args(net, packed, workspace, workspace_bytes, B, &c->ev);
   if (rc) return rc;
   CSD_REQUIRE(p && x && scratch, "pc_sample: null argument");
@@ -828,8 +854,10 @@ static int pc_setup(PCCtx* c, csd_unet* net, const void* packed, void* workspace
     CSD_REQUIRE(!p->std_y && !p->path_coef, "pc_inpaint: std_y / path_coef belong to the conditional samplers");
     c->ip = ip;
   }
-  c->nx = (size_t)B * cf.x_channels * hw; c->ny = (size_t)B * cf.y_channels * hw;
-  const size_t no = (size_t)B * cf.out_channels * hw;
+  // (y_scale = K: y, its noise and the bridge's y_t live at S / K; a sample of net_out is the x block, then the downsampled y block)
+  const size_t hwy = cf.y_scale ? hw / ((size_t)cf.y_scale * cf.y_scale) : hw;
+  c->nx = (size_t)B * cf.x_channels * hw; c->ny = (size_t)B * cf.y_channels * hwy;
+  const size_t no = (size_t)B * out_sample_elems(cf);
   float* f = static_cast<float*>(scratch);
   c->net_out = f; f += align_up(no, 64);
   c->x_mean = f; f += align_up(c->nx, 64);
@@ -845,7 +873,7 @@ static int pc_setup(PCCtx* c, csd_unet* net, const void* packed, void* workspace
   c->nchunk = sumsq_nchunk(c->per);
   c->perturb_y = p->std_y != nullptr;
   // paired networks emit [score_x | score_y] per sample: the x block of sample b starts at b*out_channels*hw
-  c->net_stride = (int64_t)cf.out_channels * hw;
+  c->net_stride = (int64_t)out_sample_elems(cf);
   return CSD_OK;
 }
 

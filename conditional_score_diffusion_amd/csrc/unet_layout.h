@@ -122,6 +122,9 @@ static int build_packed_layout(Net& n) {
     // (x_squeeze on the <= 8 channel kernel: its SQ variant covers ONE squeezed image channel, x_channels = 4 - the 4 + 1 .. 4 + 4
     // networks - in the split-operand modes; 8 + 0 and the plain fp16 mode keep the assemble pass + generic convolution)
     if (c.x_squeeze && c.x_channels + c.y_channels <= 8 && (c.x_channels != 4 || net_ns < 2)) return false;
+    // (y_scale: the YS variant of the <= 8 channel kernel holds up to 4 x channels and the four taps of up to 4 y channels; other
+    // splits keep the assemble pass)
+    if (c.y_scale && (c.y_channels > 4 || c.x_channels > 4)) return false;
     PackedConv pc;
     if (proto_conv(&pc.proto, n.in_cpad, 0, m.cout, 9)) return false;
     pc.ns = net_ns;

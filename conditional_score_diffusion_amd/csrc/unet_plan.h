@@ -260,6 +260,8 @@ struct Builder {
     const int tpi = stem_tiles_per_image(S);
     o.stats = alloc_((size_t)B * tpi * m.cout * 2 * 2);      // doubles; never released (small)
     tile_stats[o.out] = TileStats{o.stats, tpi};
+    // y_scale: room for the perturbed low-resolution y + sigma z of a sampling step (never released: a few KB per sample)
+    if (c.y_scale) o.c = alloc_((size_t)B * c.y_channels * (S / c.y_scale) * (S / c.y_scale));
     o.cls = CSD_PROF_CONV3X3;
     pl.ops.push_back(o);
     const int cin = c.x_channels + c.y_channels;
@@ -746,6 +748,11 @@ static int build_plan(Net& n, int B, Plan** out) {
   split_conv3x3_classes(pl);
   if (!CSD_TUNE_ENV("CSD_CHUNK_SEQ")) interleave_chunks(pl);
   pl.ws_floats = bd.ar.peak();
+  if (c.y_scale) {      // the head writes a workspace tensor; run_plan's last launches fill the caller's `out` from it (unet_run.h)
+    pl.ys_out = pl.ws_floats;
+    pl.ws_floats += ((size_t)B * c.out_channels * S * S + 63) / 64 * 64;
+    pl.launches += 2;
+  }
   *out = plp.get();
   n.plans[B] = std::move(plp);
   return CSD_OK;

@@ -10,6 +10,9 @@ static int run_plan(Net& n, const Plan& pl, const float* pk, float* ws, const fl
   const int B = pl.B, S = c.image_size;
   auto W = [&](size_t off) -> float* { return off == NONE ? nullptr : ws + off; };
   bool side_pending = false;
+  // y_scale: the head's NCHW output goes to the plan's workspace tensor, the caller's `out` is filled behind the last op
+  float* const out_caller = out;
+  if (c.y_scale) out = W(pl.ys_out);
   for (const Op& o : pl.ops) {
     int rc = CSD_OK;
     // batch-chunk region: the chunk streams start behind everything enqueued so far; the caller's stream resumes behind all of them
@@ -41,11 +44,11 @@ static int run_plan(Net& n, const Plan& pl, const float* pk, float* ws, const fl
     switch (o.kind) {
       case OP_ASSEMBLE:
         rc = assemble_input_launch(x, y, y_noise, y_sigma, W(o.out), Bo, c.x_channels, c.y_channels, S * S,
-                                   n.in_cpad, c.centered, so, c.x_squeeze, S);
+                                   n.in_cpad, c.centered, so, c.x_squeeze, S, c.y_scale);
         break;
       case OP_STEM:
         rc = stem_launch(x, y, y_noise, y_sigma, pk + o.pk0, pk + o.pk1, W(o.out), reinterpret_cast<double*>(W(o.stats)), Bo,
-                         c.x_channels, c.y_channels, o.i0, S, c.centered, o.i4, so, c.x_squeeze);
+                         c.x_channels, c.y_channels, o.i0, S, c.centered, o.i4, so, c.x_squeeze, c.y_scale, W(o.c));
         break;
       case OP_TEMB:
         rc = timestep_embedding_launch(labels, W(o.out), Bo, o.i0, so);
@@ -138,6 +141,16 @@ static int run_plan(Net& n, const Plan& pl, const float* pk, float* ws, const fl
         rc = CSD_ERR_STATE;
     }
     if (rc) return rc;
+  }
+  if (c.y_scale) {      // out[b] = the x block [Cx, S, S] as the head wrote it, then bilin_down of the other channels [., S / K, S / K]
+    const size_t hw = (size_t)S * S, ld_src = (size_t)c.out_channels * hw, ld_dst = out_sample_elems(c);
+    ProfScope prof(CSD_PROF_OTHER, 0, 2.0 * B * ld_src * 4, s);
+    CSD_CHECK_HIP(hipMemcpy2DAsync(out_caller, ld_dst * 4, out, ld_src * 4, c.x_channels * hw * 4, B, hipMemcpyDeviceToDevice, s));
+    if (c.out_channels > c.x_channels) {
+      const int rc = bilinear_down_launch(out + c.x_channels * hw, ld_src, out_caller + c.x_channels * hw, ld_dst, B,
+                                          c.out_channels - c.x_channels, S, c.y_scale, s);
+      if (rc) return rc;
+    }
   }
   return CSD_OK;
 }

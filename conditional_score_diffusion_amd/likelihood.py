@@ -310,6 +310,10 @@ def get_conditional_likelihood_fn(sde, inverse_scaler, hutchinson_type='Rademach
         raise NotImplementedError(f"SDE class {sde.__class__.__name__} is not a conditional SDE (cVESDE / cVPSDE).")
 
     def likelihood_fn(model, x, y, epsilon=None):
+        if getattr(model, 'y_scale', 0):
+            raise NotImplementedError('the conditional likelihood is not provided for %s (the Kx super-resolution networks, '
+                                      'ddpm_KxSR / ncsnpp_KxSR)' % type(model).__name__)
+
         def drift_fn(xx, t):
             score_fn = mutils.get_score_fn(sde, model, conditional=True, train=False, continuous=True)
             rsde = sde.reverse(mutils.get_conditional_score_fn(score_fn, 'x'), probability_flow=True)

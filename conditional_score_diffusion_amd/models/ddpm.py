@@ -1,7 +1,7 @@
 """DDPM-family score networks as thin adapters over the HIP graph executor.
 
-Registers the reference's names ``ddpm``, ``ddpm_paired_SR3``, ``ddpm_paired`` and ``ddpm_2xSR``
-(models/ddpm.py:80,275,287,300) with the reference's constructor / call signatures:
+Registers the reference's names ``ddpm``, ``ddpm_paired_SR3``, ``ddpm_paired``, ``ddpm_2xSR`` and ``ddpm_KxSR``
+(models/ddpm.py:80,275,287,300,316) with the reference's constructor / call signatures:
 
     model = create_model(config)              # cls(config)
     out = model(x | {'x': x, 'y': y}, labels) # Tensor | {'x': .., 'y': ..}
@@ -103,6 +103,7 @@ class HipUNet(nn.Module, _HandleSurface):
 
     arch = 0
     x_squeeze = 0          # 1: x is the high-resolution image [B, x_channels / 4, 2S, 2S] (csd_unet_config.x_squeeze; DDPM_2xSR)
+    y_scale = 0            # K >= 2: y is the low-resolution image [B, y_channels, S / K, S / K] (csd_unet_config.y_scale; the KxSR classes)
 
     def __init__(self, config, precision=None):
         super().__init__()
@@ -156,6 +157,7 @@ class HipUNet(nn.Module, _HandleSurface):
         cfg.act = _lib.ACT_IDS[act]
         cfg.precision = _lib.PREC_IDS[precision]
         cfg.x_squeeze = int(self.x_squeeze)
+        cfg.y_scale = int(self.y_scale)
         self._extra_config(cfg, config)
         self._cfg = cfg
         self._h = ctypes.c_void_p()
@@ -226,10 +228,19 @@ class HipUNet(nn.Module, _HandleSurface):
         S = self.image_size
         return (B, self.x_channels // 4, 2 * S, 2 * S) if self.x_squeeze else (B, self.x_channels, S, S)
 
+    def _y_shape(self, B):
+        """y of one call: [B, y_channels, S, S], or [B, y_channels, S / K, S / K] with y_scale = K"""
+        s = self.image_size // self.y_scale if self.y_scale else self.image_size
+        return (B, self.y_channels, s, s)
+
     def _out_shape(self, B):
         """the buffer csd_unet_forward / csd_unet_train_forward write: [B, out_channels, S, S]; a squeezed network's is flat per sample
-        (the x block in image layout, then the other channels at S x S - ``DDPM_2xSR._split``)"""
+        (the x block in image layout, then the other channels at S x S - ``DDPM_2xSR._split``), and so is a y_scale network's (the x
+        block, then the other channels at S / K - ``_KxSR._split``)"""
         S = self.image_size
+        if self.y_scale:
+            s = S // self.y_scale
+            return (B, self.x_channels * S * S + (self.out_channels - self.x_channels) * s * s)
         return (B, self.out_channels * S * S) if self.x_squeeze else (B, self.out_channels, S, S)
 
     # -- evaluation --------------------------------------------------------------------------------
@@ -264,8 +275,8 @@ class HipUNet(nn.Module, _HandleSurface):
             raise RuntimeError('x has shape %s, expected %s' % (tuple(x.shape), self._x_shape(B)))
         if self.y_channels:
             require_gpu_tensor(y, 'y')
-            if tuple(y.shape) != (B, self.y_channels, S, S):
-                raise RuntimeError('y has shape %s, expected %s' % (tuple(y.shape), (B, self.y_channels, S, S)))
+            if tuple(y.shape) != self._y_shape(B):
+                raise RuntimeError('y has shape %s, expected %s' % (tuple(y.shape), self._y_shape(B)))
         labels = labels.to(device=x.device, dtype=torch.float32).contiguous()
         if labels.shape != (B,):
             raise RuntimeError('labels must have shape [%d]' % B)
@@ -323,6 +334,9 @@ class HipUNet(nn.Module, _HandleSurface):
             return self._train_forward_planned(x, y, labels)
         if self.x_squeeze:
             raise NotImplementedError('a squeezed network (ddpm_2xSR) trains on the planned graph only (CSD_TRAIN_EXECUTOR=planned, '
+                                      'CSD_TRAIN_LAYOUT=nhwc)')
+        if self.y_scale:
+            raise NotImplementedError('a network with y_scale (ddpm_KxSR) trains on the planned graph only (CSD_TRAIN_EXECUTOR=planned, '
                                       'CSD_TRAIN_LAYOUT=nhwc)')
         nhwc = self.train_layout == 'nhwc'
         if nhwc:
@@ -599,3 +613,42 @@ class DDPM_2xSR(_Paired):
 
     def forward(self, input_dict, labels):
         return self._split(self._run(input_dict['x'], input_dict['y'], labels))
+
+
+class _KxSR:
+    """The direct Kx super-resolution wrappers (models/ddpm.py:316-331, models/ncsnpp.py:435-450) over a paired network: with
+    S = data.target_resolution and K = data.scale, ``forward({'x': [B, cx, S, S], 'y': [B, cy, S / K, S / K]}, labels) ->
+    {'x': [B, cx, S, S], 'y': [B, cy, S / K, S / K]}``: the network sees the bilinear upsample of y and its y output is resized back.
+    Both resizes are ``F.interpolate(mode='bilinear', align_corners=False)`` without antialiasing - torchvision's ``Resize`` on tensors
+    when the reference was written - and live in the library's boundary kernels (csd_unet_config.y_scale): no upsampled copy of y.
+    The low-resolution side is ``target_resolution // scale`` (``data.shape_y`` of the direct configs still names S and only feeds
+    sigma_max_y).  No parameters beyond the paired network's."""
+
+    def _kx_validate(self, config, name):
+        d = config.data
+        S, K = int(d.target_resolution), int(d.scale)
+        if not (S == int(d.effective_image_size) == int(d.shape_x[1]) == int(d.shape_x[2])):
+            raise ValueError('%s: data.target_resolution = %d, data.effective_image_size = %d and data.shape_x[1:] = %s must name one '
+                             'square side' % (name, S, int(d.effective_image_size), list(d.shape_x[1:])))
+        if K < 2:
+            raise ValueError('%s: data.scale = %d must be at least 2' % (name, K))
+        if S % K:
+            raise ValueError('%s: data.scale = %d must divide data.target_resolution = %d' % (name, K, S))
+        object.__setattr__(self, 'y_scale', K)
+
+    def _split(self, out):
+        B, S = out.shape[0], self.image_size
+        s, n = S // self.y_scale, self.x_channels * S * S
+        return {'x': out[:, :n].view(self._x_shape(B)), 'y': out[:, n:].view(B, self.out_channels - self.x_channels, s, s)}
+
+    def forward(self, input_dict, labels):
+        return self._split(self._run(input_dict['x'], input_dict['y'], labels))
+
+
+@utils.register_model(name='ddpm_KxSR')
+class DDPM_KxSR(_KxSR, _Paired):
+    """``ddpm_KxSR`` (models/ddpm.py:316-331; configs/ve/srflow/celebAHQ160/direct/8x.py)."""
+
+    def __init__(self, config, precision=None):
+        self._kx_validate(config, 'ddpm_KxSR')
+        super().__init__(config, precision)

@@ -28,7 +28,7 @@ import torch.nn as nn
 from .. import _lib, ops
 from .._lib import require_gpu_tensor
 from . import utils
-from .ddpm import HipUNet, _Node, _fan_avg_uniform
+from .ddpm import HipUNet, _KxSR, _Node, _fan_avg_uniform
 
 
 def _groups(c):
@@ -458,6 +458,8 @@ class HipNCSNpp(HipUNet):
         THIS model's parameters - a twin whose nn.Parameters are the same objects, so gradients land in ``self.parameters()``."""
         if self.train_executor == 'planned':
             return self._train_forward_planned(x, y, labels)
+        if self.y_scale:
+            raise NotImplementedError('a network with y_scale (ncsnpp_KxSR) trains on the planned graph only (CSD_TRAIN_EXECUTOR=planned)')
         twin = self.__dict__.get('_twin')
         if twin is None:
             twin = NCSNpp(self._config, precision=self.precision)
@@ -516,6 +518,15 @@ class NCSNppPairedPlanned(HipNCSNpp):
         return {'x': out[:, :c], 'y': out[:, c:]}
 
 
+class NCSNpp_KxSR(_KxSR, NCSNppPairedPlanned):
+    """``ncsnpp_KxSR`` (models/ncsnpp.py:435-450; configs/ve/srflow/DF2K/direct/4x.py): ``ncsnpp_paired`` behind the bilinear
+    upsample of y, its y output resized back (models/ddpm.py: _KxSR)."""
+
+    def __init__(self, config, precision=None):
+        self._kx_validate(config, 'ncsnpp_KxSR')
+        super().__init__(config, precision)
+
+
 def create_ncsnpp(config, **kw):
     """``ncsnpp``: the planned graph executor (every option the HIP path covers runs on it)"""
     return NCSNppPlanned(config, **kw)
@@ -527,5 +538,6 @@ def create_ncsnpp_paired(config, **kw):
 
 utils.register_model(create_ncsnpp, name='ncsnpp')
 utils.register_model(create_ncsnpp_paired, name='ncsnpp_paired')
+utils.register_model(NCSNpp_KxSR, name='ncsnpp_KxSR')
 utils.register_model(NCSNpp, name='ncsnpp_ops')
 utils.register_model(NCSNpp_paired, name='ncsnpp_paired_ops')

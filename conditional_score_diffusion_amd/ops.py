@@ -94,19 +94,25 @@ def fir_pyr_conv(x, weight, bias=None, res=None, fir_kernel=(1, 3, 3, 1), out_sc
     return y
 
 
-def input_conv(x, y, weight, bias, y_noise=None, y_sigma=0.0, centered=False, precision='fp16x3', fused=True, want_stats=False):
+def input_conv(x, y, weight, bias, y_noise=None, y_sigma=0.0, centered=False, precision='fp16x3', fused=True, want_stats=False, y_scale=0):
     """The DDPM family's first layer (models/ddpm.py:163-168, :283 and the first conv3x3): conv3x3(2 cat(x, y + y_sigma y_noise) - 1) on
     NCHW fp32 x [B, Cx, S, S], y [B, Cy, S, S] or None; weight [Cout, Cx + Cy, 3, 3], bias [Cout]; up to 32 input channels.
     ``fused``: the one-launch layer of csrc/stem.hip; otherwise the assembled, padded input and the generic convolution (what a
     network's plan runs where the fused layer does not apply).  csd_input_conv.  Returns out [B, S, S, Cout] NHWC (and, fused with
-    ``want_stats``, the (sum, sum of squares) of every 16 x 8 tile of it)."""
+    ``want_stats``, the (sum, sum of squares) of every 16 x 8 tile of it).  ``y_scale = K >= 2``: y (and y_noise) are
+    [B, Cy, S / K, S / K] and the layer sees the bilinear upsample of y + y_sigma y_noise - the first layer of the Kx super-resolution
+    networks (csd_input_conv_kx; up to 8 channels)."""
     x, weight, bias = _c(x, 'x'), _c(weight, 'weight'), _c(bias, 'bias')
     B, Cx, S, S2 = x.shape
     Cy = 0
+    K = int(y_scale)
+    if K and (K < 2 or S % K or y is None):
+        raise RuntimeError('input_conv: y_scale = %d needs y and a scale >= 2 that divides S = %d' % (K, S))
+    sy = S // K if K else S
     if y is not None:
         y = _c(y, 'y')
         Cy = y.shape[1]
-        if tuple(y.shape) != (B, Cy, S, S):
+        if tuple(y.shape) != (B, Cy, sy, sy):
             raise RuntimeError('input_conv: y %s does not match x %s' % (tuple(y.shape), tuple(x.shape)))
     Cout = weight.shape[0]
     if S != S2 or tuple(weight.shape) != (Cout, Cx + Cy, 3, 3) or tuple(bias.shape) != (Cout,):
@@ -120,6 +126,11 @@ def input_conv(x, y, weight, bias, y_noise=None, y_sigma=0.0, centered=False, pr
     if Cx + Cy > 32:
         raise RuntimeError('input_conv: at most 32 input channels (got %d + %d)' % (Cx, Cy))
     sc = _scratch(lib().csd_conv_scratch_bytes(B, 32, Cout, S, S, 3, 0), x.device)      # (the 32-channel convolution's: include/csd.h)
+    if K:
+        check(lib().csd_input_conv_kx(ptr(x), ptr(y), ptr(y_noise), float(y_sigma), ptr(weight), ptr(bias), ptr(out), ptr(stats), B, Cx,
+                                      Cy, Cout, S, K, int(bool(centered)), _lib.PREC_IDS[precision], int(bool(fused)), ptr(sc),
+                                      current_stream(x.device)), 'input_conv_kx')
+        return (out, stats) if want_stats else out
     check(lib().csd_input_conv(ptr(x), ptr(y), ptr(y_noise), float(y_sigma), ptr(weight), ptr(bias), ptr(out), ptr(stats), B, Cx, Cy,
                                Cout, S, int(bool(centered)), _lib.PREC_IDS[precision], int(bool(fused)), ptr(sc),
                                current_stream(x.device)), 'input_conv')
@@ -365,6 +376,56 @@ def axpby(a, b=None, alpha=1.0, beta=1.0, gamma=0.0, post=1.0):
     check(lib().csd_axpby(ptr(a), ptr(b), ptr(out), float(alpha), float(beta), float(gamma), float(post), a.numel(),
                           current_stream(a.device)), 'axpby')
     return out
+
+
+def _planes(t, name, scale):
+    t = _c(t, name)
+    if t.dim() < 2 or t.shape[-1] != t.shape[-2]:
+        raise RuntimeError('%s must be [..., side, side] (got %s)' % (name, tuple(t.shape)))
+    if int(scale) < 2:
+        raise RuntimeError('%s: scale must be at least 2 (got %r)' % (name, scale))
+    return t, int(t.shape[-1]), int(scale), t.numel() // (t.shape[-1] * t.shape[-2])
+
+
+def bilinear_up(y, scale):
+    """``F.interpolate(y, scale_factor=K, mode='bilinear', align_corners=False)`` for an integer K >= 2 on [..., s, s]: the upsample of
+    csd_unet_config.y_scale (the same device function as the network's input kernels - csrc/common.h: bilin_up)."""
+    y, side, K, n = _planes(y, 'y', scale)
+    out = _out(tuple(y.shape[:-2]) + (side * K, side * K), torch.float32, y.device)
+    check(lib().csd_bilinear_up(ptr(y), ptr(out), n, side, K, current_stream(y.device)), 'bilinear_up')
+    return out
+
+
+def bilinear_down_adjoint(g, scale):
+    """the transpose of ``bilinear_down``: [..., s, s] -> [..., K s, K s], a quarter of g at the four centre pixels of each K x K block
+    (K odd: g at the centre pixel), zero elsewhere"""
+    g, side, K, n = _planes(g, 'g', scale)
+    out = _out(tuple(g.shape[:-2]) + (side * K, side * K), torch.float32, g.device)
+    check(lib().csd_bilinear_down_adjoint(ptr(g), ptr(out), n, side * K, K, current_stream(g.device)), 'bilinear_down_adjoint')
+    return out
+
+
+class _BilinearDown(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, v, K):
+        ctx.K = K
+        v, side, K, n = _planes(v, 'v', K)
+        if side % K:
+            raise RuntimeError('bilinear_down: scale %d must divide the side %d' % (K, side))
+        out = _out(tuple(v.shape[:-2]) + (side // K, side // K), torch.float32, v.device)
+        check(lib().csd_bilinear_down(ptr(v), ptr(out), n, side, K, current_stream(v.device)), 'bilinear_down')
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        return bilinear_down_adjoint(g, ctx.K), None
+
+
+def bilinear_down(v, scale):
+    """``F.interpolate(v, size=S // K, mode='bilinear', align_corners=False)`` (no antialias) for an integer K >= 2 that divides S, on
+    [..., S, S]: the mean of the 2 x 2 block at rows / columns K i + K / 2 - 1, K i + K / 2 (K even) or the pixel K i + (K - 1) / 2
+    (K odd) - the downsample of csd_unet_config.y_scale (csrc/common.h: bilin_down).  Differentiable (``bilinear_down_adjoint``)."""
+    return _BilinearDown.apply(v, int(scale))
 
 
 def bias_add_nchw(x, bias, act='none'):

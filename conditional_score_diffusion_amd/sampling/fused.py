@@ -247,6 +247,9 @@ def run(model, sde, shape, y, p_steps, snr, eps, denoise, noise_tape=None, seed=
     if dev.type != 'cuda':
         raise RuntimeError('the fused PC sampler runs on the MI355X only (model is on %s)' % dev)
     B = shape[0]
+    if y is not None and getattr(model, 'y_scale', 0) and tuple(y.shape) != model._y_shape(B):
+        # (with seed= nothing else looks at y: a full-resolution y would be read as the first y_channels (S / K)^2 floats of each sample)
+        raise RuntimeError('y has shape %s, %s takes the low-resolution %s' % (tuple(y.shape), type(model).__name__, model._y_shape(B)))
     ve = isinstance(c_sde, _VE)
     if not ve and isinstance(sde, dict):
         raise NotImplementedError('This combination of SDEs is not supported for conditional SDEs yet.')
@@ -266,6 +269,9 @@ def run(model, sde, shape, y, p_steps, snr, eps, denoise, noise_tape=None, seed=
     n_phases = (pid != 2) + (cid != 2)
     path_tab, path_std0 = None, 0.0
     if inpaint is not None:
+        if getattr(model, 'y_scale', 0):
+            raise NotImplementedError('inpainting on the device loop is not provided for %s (the Kx super-resolution networks, '
+                                      'ddpm_KxSR / ncsnpp_KxSR, are conditional; csd_pc_inpaint_* refuse y_scale)' % type(model).__name__)
         if y is not None or isinstance(sde, dict) or use_path:
             raise NotImplementedError('inpainting on the device loop runs unconditional networks on a single SDE')
         data, mask = inpaint
@@ -296,6 +302,17 @@ def run(model, sde, shape, y, p_steps, snr, eps, denoise, noise_tape=None, seed=
             expected = inpaint_tape_length(p_steps, cid != 2, pid != 2) - 1
         if len(tape) - 1 != expected:
             raise RuntimeError('noise tape holds %d draws after the prior, the loop needs %d' % (len(tape) - 1, expected))
+        if inpaint is None and flat is not None and getattr(model, 'y_scale', 0):
+            # y_scale networks (every other network keeps the check by draws above): elements, not only draws - an x draw has the
+            # state's size, a y draw that of the low-resolution y; the device loop finds each draw by these sizes
+            nx, ny = int(x.numel()), (int(y.numel()) if y is not None else 0)
+            if use_path:
+                floats = ny + p_steps * (ny + n_phases * nx)
+            else:
+                floats = n_phases * p_steps * (nx + (ny if std_y is not None else 0))
+            if flat.numel() != floats:
+                raise RuntimeError('noise tape holds %d elements after the prior, the loop needs %d (x draws of %d, y draws of %d)'
+                                   % (flat.numel(), floats, nx, ny))
     else:
         x = ops.randn(tuple(shape), seed, 0, dev)
         if ve:

@@ -119,6 +119,14 @@ typedef struct csd_unet_config {
   int32_t embedding_type;       /* 0 'positional', 1 'fourier' (W [nf] is parameter all_modules.0.W) */
   int32_t n_fir;                /* taps of config.model.fir_kernel (<= 8)                    */
   float fir_kernel[8];
+  /* ---- arch 0 / 1: the direct Kx super-resolution networks (models/ddpm.py:316-331 ddpm_KxSR, models/ncsnpp.py:435-450 NCSNpp_KxSR).
+   * K >= 2: y is the LOW-resolution image [B, y_channels, S / K, S / K] (S = image_size); the network sees its bilinear upsample to
+   * S x S and returns its y channels downsampled to S / K.  Both resizes are torch's F.interpolate(mode = 'bilinear',
+   * align_corners = False) WITHOUT antialiasing (what torchvision's Resize did on tensors when the reference was written).  The
+   * library's boundary kernels compute the taps themselves: no full-resolution copy of y exists in inference.  See "y_scale" below.
+   * 0 (a zero-initialised struct): y is [B, y_channels, S, S] as before.  The field stands in front of vol and x_squeeze, which stay the
+   * struct's last two fields (tests/test_sr_host.py pins them there); like every field here it is read by name, never by position. ---- */
+  int32_t y_scale;
   /* ---- arch 2 (3-D DDPM family, models/ddpm3D.py) only: the extents of the volume behind the channel, D, H, W (config.data.shape_x[1:]).
    * arch 2 ignores image_size, the attention fields and the arch-1 fields above; arch 0 / 1 ignore vol. ---- */
   int32_t vol[3];
@@ -129,6 +137,23 @@ typedef struct csd_unet_config {
    * squeezed copy of x exists.  See "x_squeeze" below.  0 (a zero-initialised struct): x is [B, x_channels, S, S] as before. ---- */
   int32_t x_squeeze;
 } csd_unet_config;
+/* sizeof(csd_unet_config) of the library at hand.  The struct grows with the library (y_scale was inserted in front of vol and
+ * x_squeeze, so their offsets moved): a caller compiled against an older header must be recompiled, and can tell by comparing this
+ * with its own sizeof before the first csd_unet_create (the Python binding does, conditional_score_diffusion_amd/_lib.py). */
+size_t csd_unet_config_size(void);
+
+/* y_scale = K >= 2 (arch 0 / 1; csd_unet_create returns CSD_ERR_INVALID, naming the field, for arch 2, together with x_squeeze, for
+ * y_channels == 0, image_size % K != 0, x_channels + y_channels > 8 and out_channels < x_channels).  With s = S / K:
+ *   y, y_noise (csd_unet_forward, csd_unet_train_forward, csd_pc_sample / csd_pc_step_begin / _end, the use_path bridge)
+ *                                                                              [B, y_channels, s, s]
+ *   the perturbation y + y_sigma y_noise / y + std_y z happens at s x s, then the upsample; every y draw of the noise tape / Philox
+ *   stream has y_channels * s * s elements per sample, the order of the draws is unchanged
+ *   out, d_out: per sample x_channels * S * S floats - the x block [x_channels, S, S] - then (out_channels - x_channels) * s * s
+ *   floats, the other channels downsampled: the mean of the 2 x 2 block at rows / columns K i + K / 2 - 1, K i + K / 2 (K even) or the
+ *   pixel K i + (K - 1) / 2 (K odd), which is what the bilinear formula gives for an integer K
+ *   x, d_x, the sampler's state, its noise and every `record` row               [B, x_channels, S, S] as before
+ * csd_unet_workspace_bytes grows by one [B, out_channels, S, S] tensor (the head's output before the downsample).
+ * csd_pc_inpaint_* and csd_unet_debug_digest return CSD_ERR_INVALID for such a handle. */
 
 /* x_squeeze = 1 (arch 0; csd_unet_create refuses it for arch 1 / 2 and refuses x_channels % 4 != 0, out_channels < x_channels and
  * image_size > 1024, naming the field).  With
@@ -390,6 +415,13 @@ int csd_fourier_embedding(const float* t, const float* W, float* out, int B, int
  * Combine 'sum' (:56-57), 2x - 1 (ncsnpp.py:266-268), pyramid sums (:352) */
 int csd_axpby(const float* a, const float* b, float* out, float alpha, float beta, float gamma, float post,
               int64_t n, void* stream);
+/* The resamplers of csd_unet_config.y_scale as operators, on n contiguous planes (the same device functions as the network's boundary
+ * kernels): csd_bilinear_up y [n, side, side] -> out [n, scale * side, scale * side]; csd_bilinear_down v [n, side, side] -> out
+ * [n, side / scale, side / scale] (side % scale == 0); csd_bilinear_down_adjoint g [n, side / scale, side / scale] -> out
+ * [n, side, side], the transpose of csd_bilinear_down (every element of out is written).  scale >= 2. */
+int csd_bilinear_up(const float* y, float* out, int64_t n, int side, int scale, void* stream);
+int csd_bilinear_down(const float* v, float* out, int64_t n, int side, int scale, void* stream);
+int csd_bilinear_down_adjoint(const float* g, float* out, int64_t n, int side, int scale, void* stream);
 /* out[b,c,:] = act(x[b,c,:] + bias[b*bias_stride + c]): h += Dense_0(act(temb))[:, :, None, None] */
 int csd_bias_add_nchw(const float* x, const float* bias, float* out, int B, int C, int64_t inner,
                       int bias_stride, int act, void* stream);
@@ -464,6 +496,12 @@ int csd_ema_update(float* ema, const float* param, int64_t n, float decay, void*
 int csd_input_conv(const float* x, const float* y, const float* y_noise, float y_sigma, const float* weight, const float* bias, float* out,
                    double* stats, int B, int Cx, int Cy, int Cout, int S, int centered, int precision, int fused, void* scratch,
                    void* stream);
+/* csd_input_conv for the first layer of a csd_unet_config.y_scale network: y, y_noise [B, Cy, S / y_scale, S / y_scale], the layer sees
+ * the bilinear upsample of y + y_sigma y_noise (perturbed at low resolution).  y_scale >= 2, Cx + Cy <= 8; fused: Cx <= 4, Cy <= 4.
+ * Scratch as csd_input_conv. */
+int csd_input_conv_kx(const float* x, const float* y, const float* y_noise, float y_sigma, const float* weight, const float* bias,
+                      float* out, double* stats, int B, int Cx, int Cy, int Cout, int S, int y_scale, int centered, int precision,
+                      int fused, void* scratch, void* stream);
 
 /* The ResnetBlock convolution with its prologue fused (csrc/conv_ff.hip; reference models/layers.py:632-675: Conv(act(GroupNorm(x)))
  * [+ Dense(temb)] [+ x]): 3x3, stride 1, pad 1 on NHWC fp32 tensors.  x0 [B,H,W,C0] (+ x1 [B,H,W,C1] or NULL: virtual concat),
