@@ -19,8 +19,6 @@ namespace {
 
 typedef float floatx16 __attribute__((ext_vector_type(16)));
 
-inline size_t al64(size_t v) { return (v + 63) / 64 * 64; }
-
 __device__ __forceinline__ float bw_act(float v, int act) {
   switch (act) {
     case CSD_ACT_SWISH: return v / (1.0f + expf(-v));
@@ -589,19 +587,30 @@ inline unsigned ew_grid(size_t n) { return (unsigned)std::min<size_t>((n + 255) 
 // ===============================================================================================================
 // C ABI
 // ===============================================================================================================
-extern "C" size_t csd_conv_wgrad_scratch_bytes(int B, int Cin, int Cout, int H, int W, int ksize, int stride, int up2) {
-  const int OH = (H << (up2 ? 1 : 0)) / stride, OW = (W << (up2 ? 1 : 0)) / stride;
-  int per;
-  const int S = wgrad_splits(B, OH, OW, Cin, Cout, ksize, &per);
-  size_t ext = 0, S2 = 0;
-  if (ksize == 3 && (stride == 2 || up2)) {      // resampling convs in the split-bf16 modes: operands rebuilt on the fine grid (wgrad_impl)
-    const int FH = H << (up2 ? 1 : 0), FW = W << (up2 ? 1 : 0);
-    int per2;
-    S2 = (size_t)wgrad_splits(B, FH, FW, Cin, Cout, 3, &per2);
-    ext = al64((size_t)B * FH * FW * (up2 ? Cin : Cout));
+// the resampling convolutions (Downsample, Upsample): in the split-bf16 modes one operand is rebuilt on the fine grid (wgrad_impl)
+static inline bool wgrad_resamples(int ksize, int stride, int up2) { return ksize == 3 && (stride == 2 || up2); }
+
+// scratch of csd_conv2d_wgrad*: x in NHWC | dy in NHWC | resampling convs: the operand rebuilt on the fine grid | the split-K partials of
+// whichever schedule runs (per / per_fine: pixels per split on the output grid / on the fine grid)
+struct WgradScratch { float *xh, *dyh, *ext, *partial; int S, per, S_fine, per_fine; size_t bytes; };
+static WgradScratch wgrad_scratch(void* base, int B, int Cin, int Cout, int H, int W, int ksize, int stride, int up2) {
+  WgradScratch L = {};
+  const int up = up2 ? 1 : 0, OH = (H << up) / stride, OW = (W << up) / stride, FH = H << up, FW = W << up;
+  L.S = wgrad_splits(B, OH, OW, Cin, Cout, ksize, &L.per);
+  ScratchCarver c(base);
+  L.xh = c.take<float>((size_t)B * H * W * Cin);
+  L.dyh = c.take<float>((size_t)B * OH * OW * Cout);
+  if (wgrad_resamples(ksize, stride, up2)) {
+    L.S_fine = wgrad_splits(B, FH, FW, Cin, Cout, 3, &L.per_fine);
+    L.ext = c.take<float>((size_t)B * FH * FW * (up ? Cin : Cout));
   }
-  return (al64((size_t)B * H * W * Cin) + al64((size_t)B * OH * OW * Cout) + ext +
-          al64(std::max((size_t)S, S2) * Cout * Cin * ksize * ksize)) * sizeof(float) + 1024;
+  L.partial = c.take<float>((size_t)std::max(L.S, L.S_fine) * Cout * Cin * ksize * ksize);
+  L.bytes = c.bytes(kScratchSlack);
+  return L;
+}
+
+extern "C" size_t csd_conv_wgrad_scratch_bytes(int B, int Cin, int Cout, int H, int W, int ksize, int stride, int up2) {
+  return wgrad_scratch(nullptr, B, Cin, Cout, H, W, ksize, stride, up2).bytes;
 }
 
 // layout bit 0: x is NHWC [B,H,W,Cin]; bit 1: dy is NHWC [B,OH,OW,Cout]; bit 2: split-bf16 arithmetic allowed (else exact fp32)
@@ -623,18 +632,15 @@ static int wgrad_impl(const float* x, const float* dy, float* dw, int B, int Cin
   const int up = up2 ? 1 : 0;
   const int OH = (H << up) / stride, OW = (W << up) / stride;
   CSD_REQUIRE((double)B * H * W * Cin < 4.0e9 && (double)B * OH * OW * Cout < 4.0e9, "conv2d_wgrad: tensor exceeds 32-bit indexing");
-  int per;
-  const int S = wgrad_splits(B, OH, OW, Cin, Cout, ksize, &per);
-  float* f = static_cast<float*>(scratch);
-  float* xh = f; f += al64((size_t)B * H * W * Cin);
-  float* dyh = f; f += al64((size_t)B * OH * OW * Cout);
-  float* partial = f;
+  const WgradScratch L = wgrad_scratch(scratch, B, Cin, Cout, H, W, ksize, stride, up2);
+  const int S = L.S, per = L.per;
+  float *xh = L.xh, *dyh = L.dyh, *const partial = L.partial;
   int rc;
   if (layout & 1) xh = const_cast<float*>(x);
   else if ((rc = nchw_to_nhwc_launch(x, xh, B, Cin, H * W, Cin, Cin, s))) return rc;
   if (layout & 2) dyh = const_cast<float*>(dy);
   else if ((rc = nchw_to_nhwc_launch(dy, dyh, B, Cout, OH * OW, Cout, Cout, s))) return rc;
-  if ((layout & 4) && ksize == 3 && (stride == 2 || up) && Cin % 4 == 0 && Cout % 4 == 0 && !wgrad_wide(Cin) && !getenv("CSD_WGRAD_FP32") &&
+  if ((layout & 4) && wgrad_resamples(ksize, stride, up2) && Cin % 4 == 0 && Cout % 4 == 0 && !wgrad_wide(Cin) && !getenv("CSD_WGRAD_FP32") &&
       !CSD_TUNE_ENV("CSD_WGRAD_RESAMPLE_FP32")) {
     // resampling convs on the bf16 kernel too (it knows stride 1 only): rebuild ONE operand on the fine grid.
     //   Upsample (nearest x2, then 3x3): x' = nearest_up2(x), the plain stride-1 gradient of (x', dy).
@@ -642,11 +648,8 @@ static int wgrad_impl(const float* x, const float* dy, float* dw, int B, int Cin
     //   zeros elsewhere: the stride-1, pad-1 gradient of (x, dy') (x[H] = 0 is that gradient's own padding).
     // 4x the matrix work of a direct kernel (3/4 zeros / repeats), still half the time of the fp32 one (322 us -> ~150 us per layer
     // of the 64 x 64 training net).
-    const int FH = H << up, FW = W << up;
-    int per2;
-    const int S2 = wgrad_splits(B, FH, FW, Cin, Cout, 3, &per2);
-    float* ext = partial;
-    float* partial2 = ext + al64((size_t)B * FH * FW * (up ? Cin : Cout));
+    const int FH = H << up, FW = W << up, S2 = L.S_fine, per2 = L.per_fine;
+    float *const ext = L.ext, *const partial2 = L.partial;
     if (up) { if ((rc = nearest_up2_nhwc_launch(xh, ext, B, H, W, Cin, s))) return rc; }
     else if ((rc = csd_zero_insert_odd_nhwc(dyh, ext, B, OH, OW, Cout, s))) return rc;
     if ((rc = wgrad_bf16_launch(up ? ext : xh, up ? dyh : ext, partial2, B, FH, FW, Cin, Cout, 3, S2, per2, s))) return rc;
@@ -722,9 +725,19 @@ extern "C" int csd_bgemm(const float* A, const float* Bm, float* Cm, int M, int 
   return bgemm_launch(A, Bm, Cm, d, batch, (hipStream_t)stream);
 }
 
+// scratch of the attention backward: the probabilities P [B, L, L] | their gradient dP
+struct AttnBwdScratch { float *P, *dP; size_t bytes; };
+static AttnBwdScratch attn_bwd_scratch(void* base, int B, size_t L) {
+  AttnBwdScratch S;
+  ScratchCarver c(base);
+  S.P = c.take<float>((size_t)B * L * L);
+  S.dP = c.take<float>((size_t)B * L * L);
+  S.bytes = c.bytes(kScratchSlack);
+  return S;
+}
+
 extern "C" size_t csd_attention_backward_scratch_bytes(int B, int C, int H, int W) {
-  const size_t L = (size_t)H * W;
-  return 2 * al64((size_t)B * L * L) * sizeof(float) + 1024;
+  return attn_bwd_scratch(nullptr, B, (size_t)H * W).bytes;
 }
 
 // q, k, v, dout, dq, dk, dv: [B, C, H, W]; the forward is csd_attention (models/layers.py:584-588)
@@ -735,8 +748,8 @@ extern "C" int csd_attention_backward(const float* q, const float* k, const floa
   const int L = H * W;
   const long long zq = (long long)C * L, zs = (long long)L * L;
   const float scale = 1.0f / sqrtf((float)C);
-  float* P = static_cast<float*>(scratch);
-  float* dP = P + al64((size_t)B * L * L);
+  const AttnBwdScratch sc = attn_bwd_scratch(scratch, B, (size_t)L);
+  float *const P = sc.P, *const dP = sc.dP;
   int rc;
   // S[i][j] = scale * sum_c q[c][i] k[c][j]
   if ((rc = bgemm_launch(q, k, P, GemmDesc{L, L, C, 1, L, L, 1, L, 1, zq, zq, zs, scale}, B, s))) return rc;
@@ -764,8 +777,8 @@ extern "C" int csd_attention_backward_nhwc(const float* qkv, const float* dout, 
   const float scale = 1.0f / sqrtf((float)C);
   const float *q = qkv, *k = qkv + C, *v = qkv + 2 * C;
   float *dq = dqkv, *dk = dqkv + C, *dv = dqkv + 2 * C;
-  float* P = static_cast<float*>(scratch);
-  float* dP = P + al64((size_t)B * L * L);
+  const AttnBwdScratch sc = attn_bwd_scratch(scratch, B, (size_t)L);
+  float *const P = sc.P, *const dP = sc.dP;
   int rc;
   if ((rc = bgemm_launch(q, k, P, GemmDesc{L, L, C, C3, 1, 1, C3, L, 1, zq, zq, zs, scale}, B, s))) return rc;
   hipLaunchKernelGGL(softmax_rows_kernel, dim3((unsigned)cdiv64((long long)B * L, 4)), dim3(256), 0, s, P, (long long)B * L, L);

@@ -171,6 +171,45 @@ __device__ __forceinline__ void wg_copy_to_lds(char* __restrict__ dst, const cha
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 // ---------------------------------------------------------------------------------------
+// Caller-owned scratch buffers are described ONCE, by a layout function that asks a ScratchCarver for the buffer's regions in order and
+// returns them in a struct together with bytes().  On a null base the carver only measures: that call is the csd_*_scratch_bytes
+// entry.  On the caller's pointer the same calls hand out the regions: that is the operator.  A region is added, resized or moved in
+// its layout function and nowhere else.
+// ---------------------------------------------------------------------------------------
+constexpr size_t kScratchSlack = 1024;           // trailing bytes no region owns, part of the declared size of most operator buffers ...
+constexpr size_t kScratchPrefetchSlack = 4096;   // ... and of the buffers that hold a packed convolution weight (csd_conv2d, the block convolutions)
+constexpr size_t kScratchGranule = 64 * sizeof(float);      // take(): a region is whole 64-float granules, so every region stays 256-byte aligned
+static inline size_t scratch_floats(size_t floats) { return align_up(floats * sizeof(float), kScratchGranule) / sizeof(float); }
+struct ScratchCarver {
+  char* base;
+  size_t off = 0, high = 0, pad = 0;
+  // align_base: the caller's pointer may have any alignment - the first region starts at the next 256-byte boundary, and bytes() counts
+  // the 256 bytes that can cost
+  explicit ScratchCarver(void* scratch, bool align_base = false) : base(static_cast<char*>(scratch)) {
+    if (align_base) {
+      base = reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(scratch) + 255) & ~(uintptr_t)255);
+      pad = 256;
+    }
+  }
+  template <class T> T* take_exact(size_t count) {              // count elements, no rounding (partials and weights with sizes of their own)
+    T* p = base ? reinterpret_cast<T*>(base + off) : nullptr;
+    off += count * sizeof(T);
+    return p;
+  }
+  template <class T> T* take(size_t count) { return take_exact<T>(align_up(count * sizeof(T), kScratchGranule) / sizeof(T)); }
+  // regions that share bytes (two operators, one buffer): take one set, rewind(mark) to where it began, take the other
+  void rewind(size_t mark) { high = off > high ? off : high; off = mark; }
+  size_t bytes(size_t slack = 0) const { return (off > high ? off : high) + pad + slack; }
+};
+// a buffer of ONE region behind an aligned base: its declared size, and the region
+static inline size_t scratch_aligned_bytes(size_t region_bytes, size_t slack = 0) {
+  ScratchCarver c(nullptr, true);
+  c.take_exact<char>(region_bytes);
+  return c.bytes(slack);
+}
+template <class T> static inline T* scratch_aligned(void* scratch) { return reinterpret_cast<T*>(ScratchCarver(scratch, true).base); }
+
+// ---------------------------------------------------------------------------------------
 // Convolution as implicit GEMM on the fp32 matrix cores (conv_f32.hip)
 //   M = output pixels (B*OH*OW), N = Cout, K = taps*Cin.  Activations NHWC fp32.
 // ---------------------------------------------------------------------------------------

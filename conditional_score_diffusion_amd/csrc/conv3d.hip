@@ -522,7 +522,7 @@ using namespace csd;
 
 extern "C" size_t csd_conv3d_block_scratch_bytes(int Cin, int Cout) {
   if (Cin <= 0 || Cout <= 0) return 0;
-  return std::max(mfma_pack_bytes(Cin, Cout), (size_t)C3_TAPS * Cin * Cout * sizeof(float)) + 4096 + 256;
+  return scratch_aligned_bytes(std::max(mfma_pack_bytes(Cin, Cout), (size_t)C3_TAPS * Cin * Cout * sizeof(float)), kScratchPrefetchSlack);
 }
 
 extern "C" int csd_conv3d_block(const float* x0, const float* x1, const float* weight, const float* bias, const float* nscale,
@@ -545,7 +545,7 @@ extern "C" int csd_conv3d_block(const float* x0, const float* x1, const float* w
   CSD_REQUIRE(vox * (size_t)std::max(Cin, Cout) * sizeof(float) < ((size_t)1 << 31) && vox < ((size_t)1 << 28),
               "conv3d_block: one sample (%dx%dx%d voxels, %d channels) exceeds the kernel's 2 GiB per-sample addressing", D, H, W, std::max(Cin, Cout));
   hipStream_t s = (hipStream_t)stream;
-  void* wpack = reinterpret_cast<void*>((reinterpret_cast<uintptr_t>(scratch) + 255) & ~(uintptr_t)255);
+  void* wpack = scratch_aligned<void>(scratch);
   Conv3dCall c;
   c.x0 = x0; c.x1 = x1; c.wpack = wpack; c.bias = bias; c.nscale = nscale; c.nshift = nshift; c.temb = temb; c.res = res; c.out = y;
   c.temb_stride = temb_stride; c.act = act; c.out_scale = out_scale;
@@ -578,7 +578,7 @@ extern "C" int csd_nearest_up2_3d_ndhwc(const float* x, float* out, int B, int D
 extern "C" size_t csd_groupnorm_scale_shift_scratch_bytes(int B, int C, int S, int groups) {
   GNPlan g;
   if (B < 1 || S < 1 || gn_plan(&g, B, S, C, 0, groups)) return 0;
-  return gn_partial_bytes(g) + 256;
+  return scratch_aligned_bytes(gn_partial_bytes(g));
 }
 
 extern "C" int csd_groupnorm_scale_shift(const float* x0, const float* x1, const float* gamma, const float* beta, float* nscale,
@@ -588,7 +588,7 @@ extern "C" int csd_groupnorm_scale_shift(const float* x0, const float* x1, const
   GNPlan g;
   int rc = gn_plan(&g, B, S, C0, C1, groups);
   if (rc) return rc;
-  double* partial = reinterpret_cast<double*>((reinterpret_cast<uintptr_t>(scratch) + 255) & ~(uintptr_t)255);
+  double* partial = scratch_aligned<double>(scratch);
   if ((rc = gn_stats_launch(g, x0, x1, partial, (hipStream_t)stream))) return rc;
   return gn_finalize_launch(g, partial, gamma, beta, eps, nscale, nshift, (hipStream_t)stream);
 }

@@ -353,7 +353,7 @@ extern "C" size_t csd_conv3d_wgrad_scratch_bytes(int B, int Cin, int Cout, int D
   memset(&a, 0, sizeof(a));
   a.B = B; a.D = D; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout;
   wgrad3d_plan(&a, precision);
-  return (size_t)B * a.nsplit * W3_TAPS * Cin * Cout * sizeof(float) + 256;
+  return scratch_aligned_bytes((size_t)B * a.nsplit * W3_TAPS * Cin * Cout * sizeof(float));
 }
 
 extern "C" int csd_conv3d_wgrad(const float* a_in, const float* dy, float* dw, int B, int Cin, int Cout, int D, int H, int W, int precision,
@@ -366,7 +366,7 @@ extern "C" int csd_conv3d_wgrad(const float* a_in, const float* dy, float* dw, i
   Wgrad3dArgs a;
   memset(&a, 0, sizeof(a));
   a.a = a_in; a.dy = dy;
-  a.partial = reinterpret_cast<float*>((reinterpret_cast<uintptr_t>(scratch) + 255) & ~(uintptr_t)255);
+  a.partial = scratch_aligned<float>(scratch);
   a.B = B; a.D = D; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout;
   wgrad3d_plan(&a, precision);
   const size_t nsplits = (size_t)B * a.nsplit;
@@ -390,7 +390,9 @@ extern "C" int csd_conv3d_wgrad(const float* a_in, const float* dy, float* dw, i
   return CSD_OK;
 }
 
-extern "C" size_t csd_conv3d_dgrad_scale_scratch_bytes(int B) { return B < 1 ? 0 : (size_t)B * DG_CHUNKS * sizeof(float) + 256; }
+extern "C" size_t csd_conv3d_dgrad_scale_scratch_bytes(int B) {
+  return B < 1 ? 0 : scratch_aligned_bytes((size_t)B * DG_CHUNKS * sizeof(float));
+}
 
 extern "C" int csd_conv3d_dgrad_scale(const float* dy, float* rowscale, float* nscale, float* nshift, int B, int64_t per_sample, int C,
                                       void* scratch, void* stream) {
@@ -398,7 +400,7 @@ extern "C" int csd_conv3d_dgrad_scale(const float* dy, float* rowscale, float* n
   CSD_REQUIRE(B >= 1 && B < 65536 && per_sample >= 1 && C >= 1, "conv3d_dgrad_scale: bad shape B=%d per_sample=%lld C=%d", B,
               (long long)per_sample, C);
   hipStream_t s = (hipStream_t)stream;
-  float* part = reinterpret_cast<float*>((reinterpret_cast<uintptr_t>(scratch) + 255) & ~(uintptr_t)255);
+  float* part = scratch_aligned<float>(scratch);
   const int nchunk = (int)std::min<int64_t>(DG_CHUNKS, cdiv64(per_sample, 256 * 8));
   hipLaunchKernelGGL(absmax_partial_kernel, dim3((unsigned)nchunk, (unsigned)B), dim3(256), 0, s, dy, part, per_sample);
   CSD_LAUNCH_CHECK();

@@ -13,36 +13,44 @@ using namespace csd;
 namespace {
 inline int ceil8(int v) { return (v + 7) / 8 * 8; }
 inline int ceil16(int v) { return (v + 15) / 16 * 16; }
-inline size_t al64(size_t v) { return (v + 63) / 64 * 64; }
 }  // namespace
 
 // ---- GroupNorm (+activation) ---------------------------------------------------------------------
-extern "C" size_t csd_groupnorm_scratch_bytes(int B, int C, int H, int W) {
+// scratch of csd_groupnorm_act: x and y in NHWC | scale, shift [B, C] | the statistics partials.  The size query does not know `groups`:
+// the partials are those of CSD_GN_SCRATCH_MAX_GROUPS groups, and the operator refuses more.
+struct GnScratch { float *xh, *yh, *sc, *sh; double* partial; size_t bytes; };
+static GnScratch gn_scratch(void* base, int B, int C, int HW) {
+  GnScratch L = {};
   GNPlan g;
-  if (gn_plan(&g, B, H * W, C, 0, 1)) return 0;
-  const size_t t = (size_t)B * H * W * C;
-  return (2 * al64(t) + 2 * al64((size_t)B * C)) * sizeof(float) + gn_partial_bytes(g) * 64 + 1024;
+  if (gn_plan(&g, B, HW, C, 0, 1)) return L;
+  g.G = CSD_GN_SCRATCH_MAX_GROUPS;
+  ScratchCarver c(base);
+  L.xh = c.take<float>((size_t)B * HW * C);
+  L.yh = c.take<float>((size_t)B * HW * C);
+  L.sc = c.take<float>((size_t)B * C);
+  L.sh = c.take<float>((size_t)B * C);
+  L.partial = c.take_exact<double>(gn_partial_bytes(g) / sizeof(double));
+  L.bytes = c.bytes(kScratchSlack);
+  return L;
 }
+
+extern "C" size_t csd_groupnorm_scratch_bytes(int B, int C, int H, int W) { return gn_scratch(nullptr, B, C, H * W).bytes; }
 
 extern "C" int csd_groupnorm_act(const float* x, const float* gamma, const float* beta, float* y, int B, int C,
                                  int H, int W, int groups, float eps, int act, void* scratch, void* stream) {
+  CSD_REQUIRE(groups <= CSD_GN_SCRATCH_MAX_GROUPS, "groupnorm: %d groups, csd_groupnorm_scratch_bytes covers up to %d", groups,
+              CSD_GN_SCRATCH_MAX_GROUPS);
   CSD_REQUIRE(x && gamma && beta && y && scratch, "groupnorm: null argument");
   hipStream_t s = (hipStream_t)stream;
   GNPlan g;
   int rc = gn_plan(&g, B, H * W, C, 0, groups);
   if (rc) return rc;
-  const size_t t = (size_t)B * H * W * C;
-  float* f = static_cast<float*>(scratch);
-  float* xh = f; f += al64(t);
-  float* yh = f; f += al64(t);
-  float* sc = f; f += al64((size_t)B * C);
-  float* sh = f; f += al64((size_t)B * C);
-  double* partial = reinterpret_cast<double*>(f);
-  if ((rc = nchw_to_nhwc_launch(x, xh, B, C, H * W, C, C, s))) return rc;
-  if ((rc = gn_stats_launch(g, xh, nullptr, partial, s))) return rc;
-  if ((rc = gn_finalize_launch(g, partial, gamma, beta, eps, sc, sh, s))) return rc;
-  if ((rc = gn_apply_launch(xh, sc, sh, yh, B, H * W, C, act, s))) return rc;
-  return nhwc_to_nchw_launch(yh, y, B, C, H * W, C, s);
+  const GnScratch L = gn_scratch(scratch, B, C, H * W);
+  if ((rc = nchw_to_nhwc_launch(x, L.xh, B, C, H * W, C, C, s))) return rc;
+  if ((rc = gn_stats_launch(g, L.xh, nullptr, L.partial, s))) return rc;
+  if ((rc = gn_finalize_launch(g, L.partial, gamma, beta, eps, L.sc, L.sh, s))) return rc;
+  if ((rc = gn_apply_launch(L.xh, L.sc, L.sh, L.yh, B, H * W, C, act, s))) return rc;
+  return nhwc_to_nchw_launch(L.yh, y, B, C, H * W, C, s);
 }
 
 // ---- convolution ------------------------------------------------------------------------------------
@@ -70,38 +78,52 @@ static int conv_api_plan(ConvPlan* p, int B, int Cin, int Cout, int H, int W, in
 
 static int ceil32(int c) { return (c + 31) / 32 * 32; }
 static size_t api_packed_floats(const ConvPlan& p, int Cin) {
-  size_t n = al64(conv_packed_floats(p)) * 2;
+  size_t n = scratch_floats(conv_packed_floats(p)) * 2;
   {
     ConvPlan q = p;
     q.C0 = Cin; q.C1 = 0;
     if (Cin % 32 == 0 && conv16q_supported(q, 2)) {
-      const size_t m = al64(conv16q_packed_bytes(q, 2) / sizeof(float) + 1);
+      const size_t m = scratch_floats(conv16q_packed_bytes(q, 2) / sizeof(float) + 1);
       if (m > n) n = m;
     }
   }
   if (p.taps == 1) {
     ConvPlan q = p;
     q.C0 = ceil32(Cin);
-    const size_t m = al64(pw16_packed_bytes(q, 2) / sizeof(float) + 1);
+    const size_t m = scratch_floats(pw16_packed_bytes(q, 2) / sizeof(float) + 1);
     if (m > n) n = m;
   }
   {
     ConvPlan q = p;
     q.C0 = Cin; q.C1 = 0;
     if (Cin % 16 == 0 && convff_pipelined(q, 2)) {
-      const size_t m = al64(convff_packed_bytes(q, 2) / sizeof(float) + 1);
+      const size_t m = scratch_floats(convff_packed_bytes(q, 2) / sizeof(float) + 1);
       if (m > n) n = m;
     }
   }
   return n;
 }
 
-extern "C" size_t csd_conv_scratch_bytes(int B, int Cin, int Cout, int H, int W, int ksize, int up2) {
+// scratch of csd_conv2d*: the NHWC source at ceil32(Cin) channels (or its fp16 operand planes) | the packed weight, sized for the
+// largest packed layout (fp32 fragments; the fp16 hi+lo layout is the same size; pointwise fp16) | the padded bias | the NHWC output.
+// The size query knows neither stride nor precision: the layout is that of the stride-1 fp32 plan for every call (a stride-2 output
+// is smaller, no stride-2 weight is larger).
+struct ConvScratch { float *xh, *wp, *bp, *yh; size_t bytes; };
+static ConvScratch conv_scratch(void* base, int B, int Cin, int Cout, int H, int W, int ksize, int up2) {
+  ConvScratch L = {};
   ConvPlan p;
-  if (conv_api_plan(&p, B, Cin, Cout, H, W, ksize, 1, 0, up2)) return 0;
-  // sized for the largest packed layout (fp32 fragments; the fp16 hi+lo layout is the same size; pointwise fp16)
-  return (al64((size_t)B * H * W * ceil32(Cin)) + api_packed_floats(p, Cin) + al64((size_t)p.CoutPad) +
-          al64((size_t)B * p.OH * p.OW * Cout)) * sizeof(float) + 4096;
+  if (conv_api_plan(&p, B, Cin, Cout, H, W, ksize, 1, 0, up2)) return L;
+  ScratchCarver c(base);
+  L.xh = c.take<float>((size_t)B * H * W * ceil32(Cin));
+  L.wp = c.take<float>(api_packed_floats(p, Cin));
+  L.bp = c.take<float>((size_t)p.CoutPad);
+  L.yh = c.take<float>((size_t)B * p.OH * p.OW * Cout);
+  L.bytes = c.bytes(kScratchPrefetchSlack);
+  return L;
+}
+
+extern "C" size_t csd_conv_scratch_bytes(int B, int Cin, int Cout, int H, int W, int ksize, int up2) {
+  return conv_scratch(nullptr, B, Cin, Cout, H, W, ksize, up2).bytes;
 }
 
 // layout bit 0: x is NHWC [B,H,W,Cin] (Cin must already be a multiple of the kernel's channel granule); bit 1: y is NHWC;
@@ -132,8 +154,8 @@ int csd::conv2d_impl(const float* x, const float* weight, const float* bias, con
   int rc = conv_api_plan(&p, B, Cin, Cout, H, W, ksize, stride, pad_mode, up2);
   if (rc) return rc;
   CSD_REQUIRE(!in_nhwc || Cin % 8 == 0, "conv2d: an NHWC input needs Cin %% 8 == 0 (got %d)", Cin);
-  const size_t packed_fl = api_packed_floats(p, Cin);      // (sized from the fp32 plan, exactly as csd_conv_scratch_bytes does)
-  const size_t bias_fl = al64((size_t)p.CoutPad);
+  const ConvScratch L = conv_scratch(scratch, B, Cin, Cout, H, W, ksize, up2);
+  if (!L.bytes) return CSD_ERR_INVALID;
   int ns = precision_ns(precision);
   bool pw = false, quad = false;
   if (ns == 2 && in_nhwc && out_nhwc && Cin % 16 == 0) {
@@ -145,11 +167,10 @@ int csd::conv2d_impl(const float* x, const float* weight, const float* bias, con
     if (convff_pipelined(q, ns)) {
       CSD_REQUIRE(!planes, "conv2d: pre-split operand planes on a layer that does not take them");
       if ((rc = convff_plan_tiles(&q, ns))) return rc;
-      float* const wpk = static_cast<float*>(scratch) + al64((size_t)B * H * W * ceil32(Cin));
-      if ((rc = convff_pack_weight(q, ns, weight, (layout & 4) ? 2 : 0, Cin, Cout, 0, wpk, s))) return rc;
+      if ((rc = convff_pack_weight(q, ns, weight, (layout & 4) ? 2 : 0, Cin, Cout, 0, L.wp, s))) return rc;
       ConvArgs a;
       memset(&a, 0, sizeof(a));
-      a.src0 = x; a.wpack = wpk; a.bias = bias; a.res = res; a.temb = temb; a.temb_stride = Cout;
+      a.src0 = x; a.wpack = L.wp; a.bias = bias; a.res = res; a.temb = temb; a.temb_stride = Cout;
       a.out = y; a.out_stride = Cout; a.out_nchw = 0; a.out_scale = 1.f;
       return convff_launch(q, ns, a, s);
     }
@@ -170,12 +191,8 @@ int csd::conv2d_impl(const float* x, const float* weight, const float* bias, con
     else if ((!in_nhwc || Cin % 32 == 0) && pw16_supported(q1, ns)) { p = q1; pw = true; }
     else ns = 0;
   }
-  float* f = static_cast<float*>(scratch);
-  float* xh = f; f += al64((size_t)B * H * W * ceil32(Cin));
-  float* const xh_scratch = xh;
-  float* wp = f; f += packed_fl;
-  float* bp = f; f += bias_fl;
-  float* yh = f;
+  float* xh = L.xh;
+  float* const xh_scratch = L.xh, *const wp = L.wp, *const bp = L.bp, *const yh = L.yh;
   if (in_nhwc) xh = const_cast<float*>(x);
   else if ((rc = nchw_to_nhwc_launch(x, xh, B, Cin, H * W, p.C0, p.C0, s))) return rc;
   const int wl = (layout & 4) ? 2 : 0;
@@ -236,8 +253,8 @@ extern "C" int csd_conv2d_ex(const float* x, const float* weight, const float* b
 // where the fused layer does not apply - assemble_input at the padded width, then the generic convolution.  The padded width follows
 // the network's rule (unet_layout.h): up to 8 channels 8 (fp32) / 16 (fp16 modes), above 8 the next multiple of 16.
 static int input_conv_cpad(int cin, int ns) { return cin > 8 ? wide_cpad(cin) : (ns ? 16 : 8); }
-// scratch: that of a 32-input-channel 3x3 convolution, csd_conv_scratch_bytes(B, 32, Cout, S, S, 3, 0): the assembled input at up to 32
-// channels | the packed weight of whichever kernel takes it (none is larger than the 32-channel layouts api_packed_floats covers) | the padded bias
+// scratch: that of a 32-input-channel 3x3 convolution, conv_scratch(B, 32, Cout, S, S, 3, 0): the assembled input at up to 32 channels
+// | the packed weight of whichever kernel takes it (none is larger than the 32-channel layouts api_packed_floats covers) | the padded bias
 // (y_scale = K >= 2: y and y_noise are [B, Cy, S / K, S / K] and the layer sees the bilinear upsample of y + y_sigma y_noise -
 // csd_input_conv_kx, the first layer of a csd_unet_config.y_scale network)
 static int input_conv_impl(const float* x, const float* y, const float* y_noise, float y_sigma, const float* weight, const float* bias,
@@ -254,12 +271,10 @@ static int input_conv_impl(const float* x, const float* y, const float* y_noise,
   hipStream_t s = (hipStream_t)stream;
   int ns = precision_ns(precision);
   const int cin = Cx + Cy, cpad = input_conv_cpad(cin, ns);
-  float* f = static_cast<float*>(scratch);
-  float* xh = f; f += al64((size_t)B * S * S * 32);
-  float* wp = f;
+  const ConvScratch L = conv_scratch(scratch, B, 32, Cout, S, S, 3, 0);
+  if (!L.bytes) return CSD_ERR_INVALID;
+  float *const xh = L.xh, *const wp = L.wp, *const bp = L.bp;
   int rc;
-  ConvPlan p32;
-  if ((rc = conv_api_plan(&p32, B, 32, Cout, S, S, 3, 1, 0, 0))) return rc;
   if (fused) {
     CSD_REQUIRE(ns && stem_supported(Cx, Cy, Cout, S, ns), "input_conv: the fused first layer does not cover %d+%d -> %d channels at %dx%d in this precision",
                 Cx, Cy, Cout, S, S);
@@ -271,7 +286,6 @@ static int input_conv_impl(const float* x, const float* y, const float* y_noise,
   CSD_REQUIRE(!stats, "input_conv: tile statistics come from the fused layer only");
   ConvPlan p;
   if ((rc = conv_api_plan(&p, B, cpad, Cout, S, S, 3, 1, 0, 0))) return rc;
-  float* bp = wp + api_packed_floats(p32, 32);
   if (ns) {
     CSD_REQUIRE(conv16_supported(p), "input_conv: no fp16 kernel for %d padded channels", cpad);
     if ((rc = conv16_plan_tiles(&p, ns))) return rc;
@@ -308,7 +322,7 @@ extern "C" size_t csd_conv3x3_block_scratch_bytes(int Cin, int Cout) {
   memset(&p, 0, sizeof(p));
   p.C0 = Cin; p.Cout = Cout;
   // (the shape is not known here: sized for the Winograd pack of conv_xk.hip - 12 instead of 9 fragment sets per 16 channels)
-  return convff_packed_bytes(p, 2) / 3 * 4 + 4096 + 256;
+  return scratch_aligned_bytes(convff_packed_bytes(p, 2) / 3 * 4, kScratchPrefetchSlack);
 }
 
 extern "C" int csd_conv3x3_block(const float* x0, const float* x1, const float* weight, const float* bias, const float* nscale,
@@ -326,7 +340,7 @@ extern "C" int csd_conv3x3_block(const float* x0, const float* x1, const float* 
   CSD_REQUIRE(convff_supported(p, ns), "conv3x3_block: unsupported shape (C %d+%d -> %d, %dx%d)", C0, C1, Cout, H, W);
   int rc = convff_plan_tiles(&p, ns);
   if (rc) return rc;
-  void* wpack = reinterpret_cast<void*>((reinterpret_cast<uintptr_t>(scratch) + 255) & ~(uintptr_t)255);
+  void* wpack = scratch_aligned<void>(scratch);
   if ((rc = convff_pack_weight(p, ns, weight, 0, C0 + C1, Cout, 0, wpack, s))) return rc;
   ConvArgs a;
   memset(&a, 0, sizeof(a));
@@ -337,19 +351,26 @@ extern "C" int csd_conv3x3_block(const float* x0, const float* x1, const float* 
 }
 
 // ---- attention ------------------------------------------------------------------------------------------
-extern "C" size_t csd_attention_scratch_bytes(int B, int C, int H, int W) {
-  const size_t L = (size_t)H * W;
-  return (al64((size_t)B * L * 3 * C) + al64((size_t)B * L * C)) * sizeof(float) + 1024;
+// scratch of csd_attention: q | k | v interleaved per pixel, NHWC [B, L, 3C] | the NHWC output
+struct AttnScratch { float *qkv, *oh; size_t bytes; };
+static AttnScratch attn_scratch(void* base, int B, int C, size_t L) {
+  AttnScratch S;
+  ScratchCarver c(base);
+  S.qkv = c.take<float>((size_t)B * L * 3 * C);
+  S.oh = c.take<float>((size_t)B * L * C);
+  S.bytes = c.bytes(kScratchSlack);
+  return S;
 }
+
+extern "C" size_t csd_attention_scratch_bytes(int B, int C, int H, int W) { return attn_scratch(nullptr, B, C, (size_t)H * W).bytes; }
 
 extern "C" int csd_attention(const float* q, const float* k, const float* v, float* out, int B, int C, int H, int W,
                              void* scratch, void* stream) {
   CSD_REQUIRE(q && k && v && out && scratch, "attention: null argument");
   hipStream_t s = (hipStream_t)stream;
   const int L = H * W;
-  float* f = static_cast<float*>(scratch);
-  float* qkv = f; f += al64((size_t)B * L * 3 * C);
-  float* oh = f;
+  const AttnScratch S = attn_scratch(scratch, B, C, (size_t)L);
+  float *const qkv = S.qkv, *const oh = S.oh;
   int rc;
   if ((rc = nchw_to_nhwc_launch(q, qkv, B, C, L, C, 3 * C, s))) return rc;
   if ((rc = nchw_to_nhwc_launch(k, qkv + C, B, C, L, C, 3 * C, s))) return rc;

@@ -10,8 +10,6 @@ using namespace csd;
 
 namespace {
 
-inline size_t al64(size_t v) { return (v + 63) / 64 * 64; }
-
 __device__ __forceinline__ float t_act(float v, int act) {
   switch (act) {
     case CSD_ACT_SWISH: return v / (1.0f + expf(-v));
@@ -277,13 +275,28 @@ int tn_chunks(int B, int HW, int C) {
 
 }  // namespace
 
-extern "C" size_t csd_groupnorm_nhwc_scratch_bytes(int B, int C, int HW) {
+// one scratch for the NHWC GroupNorm forward and backward (the training graph hands either the same size): scale, shift [B, C] of
+// the forward, then in the same bytes EITHER the forward's statistics partials (of up to CSD_GN_SCRATCH_MAX_GROUPS groups: the size
+// query does not know `groups`, the forward refuses more) OR the backward's per-chunk partials | per-sample coefficients
+struct GnNhwcScratch { float *sc, *sh; double* partial; double* bw_partial; float* bw_coef; size_t bytes; };
+static GnNhwcScratch gn_nhwc_scratch(void* base, int B, int C, int HW) {
+  GnNhwcScratch L = {};
   GNPlan g;
-  if (gn_plan(&g, B, HW, C, 0, 1)) return 0;
-  const size_t gn = gn_partial_bytes(g) * 64;
-  const size_t bw = (size_t)B * tn_chunks(B, HW, C) * C * 2 * sizeof(double) + (size_t)B * 3 * C * sizeof(float);
-  return std::max(gn, bw) + 2 * al64((size_t)B * C) * sizeof(float) + 1024;
+  if (gn_plan(&g, B, HW, C, 0, 1)) return L;
+  g.G = CSD_GN_SCRATCH_MAX_GROUPS;
+  ScratchCarver c(base);
+  L.sc = c.take<float>((size_t)B * C);
+  L.sh = c.take<float>((size_t)B * C);
+  const size_t shared = c.off;
+  L.partial = c.take_exact<double>(gn_partial_bytes(g) / sizeof(double));
+  c.rewind(shared);
+  L.bw_partial = c.take_exact<double>((size_t)B * tn_chunks(B, HW, C) * C * 2);
+  L.bw_coef = c.take_exact<float>((size_t)B * 3 * C);
+  L.bytes = c.bytes(kScratchSlack);
+  return L;
 }
+
+extern "C" size_t csd_groupnorm_nhwc_scratch_bytes(int B, int C, int HW) { return gn_nhwc_scratch(nullptr, B, C, HW).bytes; }
 
 // y = act(GroupNorm(x)); rs / ms [B, C] receive the statistics (rstd, -mean*rstd per channel) the backward needs
 extern "C" int csd_groupnorm_act_nhwc(const float* x, const float* gamma, const float* beta, float* y, float* rs, float* ms,
@@ -294,16 +307,17 @@ extern "C" int csd_groupnorm_act_nhwc(const float* x, const float* gamma, const 
 int csd::groupnorm_act_dropout_nhwc(const float* x, const float* gamma, const float* beta, float* y, float* rs, float* ms, float* mask,
                                     float p_drop, uint64_t seed, uint64_t stream_id, int B, int C, int HW, int groups, float eps,
                                     int act, void* scratch, void* stream, void* planes, int plane_count) {
+  CSD_REQUIRE(groups <= CSD_GN_SCRATCH_MAX_GROUPS, "groupnorm_act_nhwc: %d groups, csd_groupnorm_nhwc_scratch_bytes covers up to %d", groups,
+              CSD_GN_SCRATCH_MAX_GROUPS);
   CSD_REQUIRE(x && gamma && beta && y && rs && ms && scratch, "groupnorm_act_nhwc: null argument");
   CSD_REQUIRE(mask == nullptr || (p_drop > 0.f && p_drop < 1.f && ((size_t)B * HW * C) % 4 == 0), "groupnorm_act_nhwc: dropout p = %f", (double)p_drop);
   hipStream_t s = (hipStream_t)stream;
   GNPlan g;
   int rc = gn_plan(&g, B, HW, C, 0, groups);
   if (rc) return rc;
-  float* f = static_cast<float*>(scratch);
-  float* sc = f; f += al64((size_t)B * C);
-  float* sh = f; f += al64((size_t)B * C);
-  double* partial = reinterpret_cast<double*>(f);
+  const GnNhwcScratch L = gn_nhwc_scratch(scratch, B, C, HW);
+  float *const sc = L.sc, *const sh = L.sh;
+  double* const partial = L.partial;
   if ((rc = gn_stats_launch(g, x, nullptr, partial, s))) return rc;
   if ((rc = gn_finalize_launch(g, partial, gamma, beta, eps, sc, sh, s, rs, ms))) return rc;
   void* hi = plane_count > 0 ? planes : nullptr;
@@ -321,8 +335,10 @@ int csd::groupnorm_act_backward_nhwc_add(const float* x, const float* gamma, con
   hipStream_t s = (hipStream_t)stream;
   const int nchunk = tn_chunks(B, HW, C);
   const int rows = TN_THREADS / (C / 4);
-  double* partial = static_cast<double*>(scratch);
-  float* coef = reinterpret_cast<float*>(partial + (size_t)B * nchunk * C * 2);
+  const GnNhwcScratch L = gn_nhwc_scratch(scratch, B, C, HW);
+  if (!L.bytes) return CSD_ERR_INVALID;
+  double* const partial = L.bw_partial;
+  float* const coef = L.bw_coef;
   hipLaunchKernelGGL(gn_bwd_stats_nhwc_kernel, dim3(nchunk, B), dim3(TN_THREADS), (size_t)rows * C * 2 * sizeof(double), s, x, dy,
                      gamma, beta, rs, ms, partial, HW, C, act, nchunk);
   CSD_LAUNCH_CHECK();

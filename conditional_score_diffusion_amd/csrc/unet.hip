@@ -741,20 +741,27 @@ extern "C" int csd_unet_forward(csd_unet* net, const void* packed, void* workspa
 
 // ---- fused PC sampler -------------------------------------------------------------------------------
 // HW below is the per-sample element count of one channel (sample_elems): image_size^2, or D*H*W for the 3-D family.
-// scratch layout (floats): net_out [B*Co*HW] | x_mean [B*Cx*HW] | z [B*Cx*HW] | zy [B*Cy*HW] | labels [B]
-//                          | partial (double) [B*64*2]
-extern "C" size_t csd_pc_scratch_bytes(const csd_unet* net, int B) {
-  if (!net) return 0;
-  const csd_unet_config& c = net->net.cfg;
-  const size_t hw = sample_elems(c);
-  size_t fl = 0;
-  fl += align_up((size_t)B * c.out_channels * hw, 64);
-  fl += 2 * align_up((size_t)B * c.x_channels * hw, 64);
-  fl += align_up((size_t)B * std::max(c.y_channels, 1) * hw, 64);
-  fl += align_up((size_t)B, 64);
-  fl += align_up((size_t)B * std::max(c.y_channels, 1) * hw, 64);      // y_t of the use_path bridge
-  return fl * sizeof(float) + (size_t)B * 64 * 2 * sizeof(double) + 256;
+// scratch of csd_pc_* : net_out [B*Co*HW] | x_mean [B*Cx*HW] | z [B*Cx*HW] | zy [B*max(Cy,1)*HW] | labels [B] | ystate [B*max(Cy,1)*HW]
+// (y_t of the use_path bridge) | the norm partials (double) [B*64*2] | the device flag of the finiteness contract.  A y_scale network
+// needs less of net_out, zy and ystate (its y lives at S / K); the regions keep the full-resolution sizes.
+struct PCScratch { float *net_out, *x_mean, *z, *zy, *labels, *ystate; double* partial; int* nonfinite; size_t bytes; };
+static PCScratch pc_scratch(void* base, const csd_unet_config& cf, int B) {
+  PCScratch L;
+  const size_t hw = sample_elems(cf), ny = (size_t)B * std::max(cf.y_channels, 1) * hw;
+  ScratchCarver c(base);
+  L.net_out = c.take<float>((size_t)B * cf.out_channels * hw);
+  L.x_mean = c.take<float>((size_t)B * cf.x_channels * hw);
+  L.z = c.take<float>((size_t)B * cf.x_channels * hw);
+  L.zy = c.take<float>(ny);
+  L.labels = c.take<float>((size_t)B);
+  L.ystate = c.take<float>(ny);
+  L.partial = c.take<double>((size_t)B * 64 * 2);
+  L.nonfinite = c.take<int>(1);
+  L.bytes = c.bytes();
+  return L;
 }
+
+extern "C" size_t csd_pc_scratch_bytes(const csd_unet* net, int B) { return net ? pc_scratch(nullptr, net->net.cfg, B).bytes : 0; }
 
 __global__ void fill_labels_kernel(float* dst, float v, int B) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -762,11 +769,8 @@ __global__ void fill_labels_kernel(float* dst, float v, int B) {
 }
 
 // one validated view of a csd_pc_* call: scratch carved up, noise bookkeeping per step
-struct PCCtx {
+struct PCCtx : PCScratch {
   Evaluator ev; const float* pk; float* ws;
-  float *net_out, *x_mean, *z, *zy, *labels, *ystate;
-  double* partial;
-  int* nonfinite;                                    // device flag of the finiteness contract (behind the norm partials)
   bool path = false;                                 // use_path: y_t follows the bridge (csd_pc_params.path_coef)
   const csd_pc_params* p;
   const csd_pc_inpaint_params* ip = nullptr;         // inpainting: the known pixels are re-imposed after every phase (csd_pc_inpaint_*)
@@ -857,16 +861,7 @@ static int pc_setup(PCCtx* c, csd_unet* net, const void* packed, void* workspace
   // (y_scale = K: y, its noise and the bridge's y_t live at S / K; a sample of net_out is the x block, then the downsampled y block)
   const size_t hwy = cf.y_scale ? hw / ((size_t)cf.y_scale * cf.y_scale) : hw;
   c->nx = (size_t)B * cf.x_channels * hw; c->ny = (size_t)B * cf.y_channels * hwy;
-  const size_t no = (size_t)B * out_sample_elems(cf);
-  float* f = static_cast<float*>(scratch);
-  c->net_out = f; f += align_up(no, 64);
-  c->x_mean = f; f += align_up(c->nx, 64);
-  c->z = f; f += align_up(c->nx, 64);
-  c->zy = f; f += align_up(std::max(c->ny, (size_t)B * hw), 64);
-  c->labels = f; f += align_up((size_t)B, 64);
-  c->ystate = f; f += align_up(std::max(c->ny, (size_t)B * hw), 64);
-  c->partial = reinterpret_cast<double*>(f);
-  c->nonfinite = reinterpret_cast<int*>(c->partial + (size_t)B * 64 * 2);      // (csd_pc_scratch_bytes keeps 256 bytes behind the partials)
+  static_cast<PCScratch&>(*c) = pc_scratch(scratch, cf, B);
   c->path = p->path_coef != nullptr;
   CSD_REQUIRE(!c->path || (cf.y_channels > 0 && !p->std_y), "pc_sample: use_path needs a conditioning image and no marginal std_y");
   c->per = (int64_t)cf.x_channels * hw;

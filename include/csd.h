@@ -256,7 +256,10 @@ typedef struct csd_pc_params {
 } csd_pc_params;
 
 /* x: [B, x_channels, S, S] in: prior sample (VE: already scaled by sigma_max); out: result.
- * y: [B, y_channels, S, S] or NULL.  scratch: csd_pc_scratch_bytes() device bytes.  An arch-2 handle runs the same loop on volumes
+ * y: [B, y_channels, S, S] or NULL.  scratch: csd_pc_scratch_bytes() device bytes, 256-byte aligned: net_out [B, out_channels, HW] |
+ * x_mean, z [B, x_channels, HW] each | zy [B, max(y_channels, 1), HW] | labels [B] | y_t, the same size as zy, in 64-float granules,
+ * then the norm partials [B, 64, 2] doubles and 256 bytes for the finiteness flag (pc_scratch in csrc/unet.hip is the one description;
+ * a y_scale handle gets the same full-resolution regions).  An arch-2 handle runs the same loop on volumes
  * ([.., D, H, W] in place of [.., S, S]): same update kernels, noise order, tape layout, Philox stream numbering and contract.
  * Finiteness contract: the Langevin corrector's norms (which see every element of the score and of the noise) and one pass over the
  * returned state set a device flag; csd_pc_sample reads it back behind the stream before it returns - its ONE synchronisation - and
@@ -358,7 +361,10 @@ int csd_scale_rows(float* out, const float* in, const float* scale, int divide, 
  * for per-op parity tests and for callers that use the reference's functional ops directly.
  * ---------------------------------------------------------------------------------------- */
 /* y = act(GroupNorm(x; G groups, eps) * gamma + beta)  - nn.GroupNorm + get_act
- * (models/layers.py:571,638,646).  scratch: csd_groupnorm_scratch_bytes(B, C, H, W). */
+ * (models/layers.py:571,638,646).  scratch: csd_groupnorm_scratch_bytes(B, C, H, W).  The size queries of GroupNorm (this one and
+ * csd_groupnorm_nhwc_scratch_bytes) do not take `groups`: they cover up to CSD_GN_SCRATCH_MAX_GROUPS groups, and csd_groupnorm_act /
+ * csd_groupnorm_act_nhwc return CSD_ERR_INVALID for more. */
+#define CSD_GN_SCRATCH_MAX_GROUPS 64
 size_t csd_groupnorm_scratch_bytes(int B, int C, int H, int W);
 int csd_groupnorm_act(const float* x, const float* gamma, const float* beta, float* y, int B, int C,
                       int H, int W, int groups, float eps, int act, void* scratch, void* stream);
