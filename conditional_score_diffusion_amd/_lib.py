@@ -54,6 +54,13 @@ class PCInpaintParams(ctypes.Structure):
                 ('mean_scale', ctypes.POINTER(ctypes.c_float)), ('std', ctypes.POINTER(ctypes.c_float))]
 
 
+class CascadeStage(ctypes.Structure):
+    """csd_cascade_stage: one stage of csd_pc_cascade_sample; every pointer is an address (handle, device buffers) except ``pc`` /
+    ``inpaint``, which point at host structs"""
+    _fields_ = [('net', ctypes.c_void_p), ('packed', ctypes.c_void_p), ('pc', ctypes.POINTER(PCParams)),
+                ('inpaint', ctypes.POINTER(PCInpaintParams)), ('x', ctypes.c_void_p), ('link', ctypes.c_int32), ('out', ctypes.c_void_p)]
+
+
 class OdeCoef(ctypes.Structure):
     """csd_ode_coef: one Runge-Kutta tableau row, passed by value"""
     _fields_ = [('c', ctypes.c_double * 7)]
@@ -111,6 +118,10 @@ SIGNATURES = {
     'csd_pc_inpaint_step_end': (_i, [_vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _i, ctypes.POINTER(PCParams),
                                      ctypes.POINTER(PCInpaintParams), _i, _vp, _i, _vp]),
     'csd_inpaint_blend': (_i, [_vp, _vp, _vp, _vp, _vp, _f, _f, _i64, _u64, _u64, _vp]),
+    'csd_band_split': (_i, [_vp, _i64, _vp, _i64, _i, _i, _i, ctypes.POINTER(ctypes.c_float), _vp]),
+    'csd_band_merge': (_i, [_vp, _i64, _vp, _i64, _vp, _i64, _i, _i, _i, ctypes.POINTER(ctypes.c_float), _vp]),
+    'csd_pc_cascade_sample': (_i, [ctypes.POINTER(CascadeStage), _i, _i, _vp, _i, _vp, _sz, _vp, _sz, _vp, ctypes.POINTER(ctypes.c_float),
+                                   _vp]),
     'csd_unet_train_workspace_bytes': (_sz, [_vp, _i, _f]),
     'csd_unet_train_forward': (_i, [_vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _i, _f, ctypes.c_uint64, ctypes.c_uint64, _vp]),
     'csd_unet_backward': (_i, [_vp, _vp, _vp, _vp, _sz, _vp, _i, ctypes.c_uint64, _vp]),

@@ -490,6 +490,10 @@ int inpaint_blend_launch(float* x, float* x_mean, const float* data, const float
                          uint64_t seed, uint64_t stream_id, hipStream_t s);
 int scale_rows_launch(float* out, const float* in, const float* scale, int divide, int B, int64_t per,
                       hipStream_t s);
+// csrc/band.hip (csd_band_split / csd_band_merge; matrix: host 4 x 4 or NULL = Haar, strides in floats per sample)
+int band_split_launch(const float* x, int64_t x_ld, float* bands, int64_t bands_ld, int B, int C, int S, const float* matrix, hipStream_t s);
+int band_merge_launch(const float* lo, int64_t lo_ld, const float* hi, int64_t hi_ld, float* x, int64_t x_ld, int B, int C, int S,
+                      const float* matrix, hipStream_t s);
 int sumsq_nchunk(int64_t per);
 
 }  // namespace csd

@@ -19,6 +19,7 @@
 #include <map>
 #include <mutex>
 #include <memory>
+#include <string>
 #include <vector>
 
 #include "common.h"
@@ -956,9 +957,7 @@ static int pc_step_tail(const PCCtx& c, int i) {
 // The finiteness contract of the fused loop (BASELINE.json north_star: outputs within 1e-3 of the reference - a NaN image is not):
 // every Langevin step's norms and one pass over the returned state set a device flag; the loop's LAST call reads it back behind the
 // stream (the only synchronisation of the sampler) and fails with CSD_ERR_NONFINITE instead of returning NaN images silently.
-static int pc_finish(const PCCtx& c) {
-  int rc = finite_check_launch(c.x, c.nx, c.nonfinite, c.s);
-  if (rc) return rc;
+static int pc_read_flag(const PCCtx& c) {
   int flag = 0;
   CSD_CHECK_HIP(hipMemcpyAsync(&flag, c.nonfinite, sizeof(int), hipMemcpyDeviceToHost, c.s));
   CSD_CHECK_HIP(hipStreamSynchronize(c.s));
@@ -970,12 +969,18 @@ static int pc_finish(const PCCtx& c) {
   return CSD_OK;
 }
 
-static int pc_sample_run(csd_unet* net, const void* packed, void* workspace, size_t workspace_bytes, void* scratch,
-                         size_t scratch_bytes, float* x, const float* y, int B, const csd_pc_params* p,
-                         const csd_pc_inpaint_params* ip, bool inpaint, void* stream) {
-  PCCtx c;
-  int rc = pc_setup(&c, net, packed, workspace, workspace_bytes, scratch, scratch_bytes, x, y, B, p, stream, ip, inpaint);
+static int pc_finish(const PCCtx& c) {
+  int rc = finite_check_launch(c.x, c.nx, c.nonfinite, c.s);
   if (rc) return rc;
+  return pc_read_flag(c);
+}
+
+// The whole loop of a validated call, enqueued: the flag cleared, every step, the pass over the returned state.  Nothing here waits for
+// the device: csd_pc_sample / csd_pc_inpaint_sample read the flag back behind it (pc_read_flag), csd_pc_cascade_sample enqueues the
+// next stage first and reads every stage's flag behind the last one.
+static int pc_enqueue(const PCCtx& c) {
+  int rc;
+  const csd_pc_params* p = c.p;
   CSD_CHECK_HIP(hipMemsetAsync(c.nonfinite, 0, sizeof(int), c.s));
   if (c.path) {                                 // y_{T+tau} = y + sigma_y(T+tau) z (sampling/conditional.py:146-149)
     const float* z0 = c.noise_path(-1, 0, c.zy, c.ny);
@@ -998,7 +1003,17 @@ static int pc_sample_run(csd_unet* net, const void* packed, void* workspace, siz
     if ((rc = pc_step_tail(c, i))) return rc;
   }
   g_prof.step_on = true;
-  return pc_finish(c);
+  return finite_check_launch(c.x, c.nx, c.nonfinite, c.s);
+}
+
+static int pc_sample_run(csd_unet* net, const void* packed, void* workspace, size_t workspace_bytes, void* scratch,
+                         size_t scratch_bytes, float* x, const float* y, int B, const csd_pc_params* p,
+                         const csd_pc_inpaint_params* ip, bool inpaint, void* stream) {
+  PCCtx c;
+  int rc = pc_setup(&c, net, packed, workspace, workspace_bytes, scratch, scratch_bytes, x, y, B, p, stream, ip, inpaint);
+  if (rc) return rc;
+  if ((rc = pc_enqueue(c))) return rc;
+  return pc_read_flag(c);
 }
 
 static int pc_step_begin_run(csd_unet* net, const void* packed, void* workspace, size_t workspace_bytes, void* scratch,
@@ -1068,4 +1083,159 @@ extern "C" int csd_pc_inpaint_step_end(csd_unet* net, const void* packed, void* 
                                        void* stream) {
   return pc_step_end_run(net, packed, workspace, workspace_bytes, scratch, scratch_bytes, x, y, B, p, ip, true, step, norm_sums,
                          global_batch, stream);
+}
+
+// ---- sequential cascades (include/csd.h: csd_cascade_stage, csd_pc_cascade_sample) ----------------------------------------------------
+// Every stage is validated and set up (pc_setup) before the first kernel is enqueued; the stages then run pc_enqueue back to back on
+// the one stream, each with its flag of the finiteness contract in stage_flags[k], and the flags are read back once behind the last.
+static inline size_t round256(size_t n) { return (n + 255) & ~(size_t)255; }
+
+// a pc_setup / launch failure of stage k keeps its text, behind the stage's index
+static int cascade_fail(int rc, int k, int n) {
+  const std::string why = get_error();
+  set_error("pc_cascade: stage %d of %d (stages[%d]): %s", k + 1, n, k, why.c_str());
+  return rc;
+}
+
+extern "C" int csd_pc_cascade_sample(const csd_cascade_stage* st, int n, int final_link, const float* y0, int B, void* workspace,
+                                     size_t workspace_bytes, void* scratch, size_t scratch_bytes, int32_t* stage_flags,
+                                     const float* band_matrix, void* stream) {
+  CSD_REQUIRE(st && n >= 1 && n <= 64, "pc_cascade: null stages / bad n_stages %d", n);
+  CSD_REQUIRE(B >= 1 && workspace && scratch && stage_flags, "pc_cascade: B = %d / a null workspace, scratch or stage_flags", B);
+  CSD_REQUIRE(final_link >= 0 && final_link <= 2, "pc_cascade: bad final_link %d", final_link);
+  CSD_REQUIRE((reinterpret_cast<uintptr_t>(scratch) & 255) == 0, "pc_cascade: scratch must be 256-byte aligned");
+  hipStream_t s = (hipStream_t)stream;
+#define STAGE_REQUIRE(cond, fmt, ...) CSD_REQUIRE(cond, "pc_cascade: stage %d of %d (stages[%d]): " fmt, k + 1, n, k, ##__VA_ARGS__)
+  // 1. what each stage is, and the extents at every link
+  size_t pc_bytes = 0, hand_bytes = 0;
+  int pc_stage = 0;
+  for (int k = 0; k < n; ++k) {
+    const csd_cascade_stage& g = st[k];
+    STAGE_REQUIRE(g.net && g.packed && g.pc && g.x, "null handle, packed weights, pc params or x");
+    const csd_unet_config& cf = g.net->net.cfg;
+    STAGE_REQUIRE(!is3d(g.net->net), "3-D handles (arch 2) do not run in a cascade");
+    STAGE_REQUIRE(!cf.y_scale, "handles with y_scale (the Kx networks) do not run in a cascade");
+    STAGE_REQUIRE(!(cf.y_channels > 0 && g.inpaint), "a conditional stage (y_channels = %d) was given inpaint params", cf.y_channels);
+    STAGE_REQUIRE(!(cf.y_channels == 0 && !g.inpaint), "an unconditional stage needs inpaint params");
+    STAGE_REQUIRE(!g.inpaint || (g.inpaint->data && g.inpaint->mask), "inpaint params without data / mask");
+    STAGE_REQUIRE(g.link >= 0 && g.link <= 2 && (k > 0 || g.link == 0), "bad link %d%s", g.link, k == 0 ? " (stage 1 takes y0: link 0)" : "");
+    if (k == 0) {
+      STAGE_REQUIRE((cf.y_channels > 0) == (y0 != nullptr), "y0 must be given iff the stage has a condition (y_channels = %d)", cf.y_channels);
+    } else {
+      const csd_unet_config& pf = st[k - 1].net->net.cfg;
+      const int pS = pf.image_size, S = cf.image_size;
+      if (g.link == 0) {
+        const int ci = pf.x_squeeze ? pf.x_channels / 4 : pf.x_channels, side = pf.x_squeeze ? 2 * pS : pS;
+        STAGE_REQUIRE(cf.y_channels == ci && S == side, "link 0: the previous stage's x is %d x %d^2, this stage's y %d x %d^2", ci, side,
+                      cf.y_channels, S);
+      } else if (g.link == 1) {
+        const int C = pf.y_channels;
+        STAGE_REQUIRE(C > 0 && !pf.x_squeeze && pf.x_channels == 3 * C && cf.y_channels == C && S == 2 * pS,
+                      "link 1: needs previous y C x S^2, previous x 3C x S^2 and this y C x (2S)^2; got previous y %d, x %d at %d^2 "
+                      "(x_squeeze %d), this y %d at %d^2", pf.y_channels, pf.x_channels, pS, pf.x_squeeze, cf.y_channels, S);
+      } else {
+        STAGE_REQUIRE(st[k - 1].inpaint && g.inpaint, "link 2 joins two inpainting stages");
+        STAGE_REQUIRE(pf.x_channels % 4 == 0 && !pf.x_squeeze && !cf.x_squeeze && cf.x_channels == pf.x_channels && S == 2 * pS,
+                      "link 2: needs previous x 4C x S^2 and this x 4C x (2S)^2; got previous x %d at %d^2, this x %d at %d^2",
+                      pf.x_channels, pS, cf.x_channels, S);
+        STAGE_REQUIRE(!st[k - 1].out, "link 2 writes the merged image into this stage's data: the previous stage's out must be NULL");
+      }
+    }
+    if (k == n - 1 && final_link) {
+      if (final_link == 1)
+        STAGE_REQUIRE(cf.y_channels > 0 && !cf.x_squeeze && cf.x_channels == 3 * cf.y_channels, "final_link 1: needs y C, x 3C; got y %d, x %d",
+                      cf.y_channels, cf.x_channels);
+      else
+        STAGE_REQUIRE(g.inpaint && !cf.x_squeeze && cf.x_channels % 4 == 0, "final_link 2: needs an inpainting stage with x 4C; got x %d",
+                      cf.x_channels);
+      STAGE_REQUIRE(g.out, "final_link %d: the last stage's out is required", final_link);
+    }
+    const size_t pcb = round256(csd_pc_scratch_bytes(g.net, B));
+    if (pcb > pc_bytes) { pc_bytes = pcb; pc_stage = k; }
+    if (k + 1 < n && st[k + 1].link == 1 && !g.out)
+      hand_bytes += round256((size_t)B * std::max(cf.y_channels, 0) * 4 * sample_elems(cf) * sizeof(float));
+  }
+  // 2. the two shared buffers
+  for (int k = 0; k < n; ++k) {
+    const size_t need = csd_unet_workspace_bytes(st[k].net, B);
+    if (workspace_bytes < need) {
+      set_error("pc_cascade: stage %d of %d (stages[%d]): workspace too small: %zu bytes, the stage needs %zu", k + 1, n, k, workspace_bytes, need);
+      return CSD_ERR_WORKSPACE;
+    }
+  }
+  if (scratch_bytes < pc_bytes + hand_bytes) {
+    set_error("pc_cascade: stage %d of %d (stages[%d]): scratch too small: %zu bytes; the stage's loop needs %zu and the hand-over images "
+              "without a caller buffer %zu", pc_stage + 1, n, pc_stage, scratch_bytes, pc_bytes, hand_bytes);
+    return CSD_ERR_WORKSPACE;
+  }
+  // 3. every stage's condition pointer and validated loop, before anything is enqueued
+  std::vector<PCCtx> ctx(n);
+  std::vector<float*> handed(n, nullptr);              // stage k's merged image, where a link 1 / final link makes one
+  char* hand = static_cast<char*>(scratch) + pc_bytes;
+  for (int k = 0; k < n; ++k) {
+    const csd_cascade_stage& g = st[k];
+    const csd_unet_config& cf = g.net->net.cfg;
+    const float* y = nullptr;
+    if (k == 0) y = y0;
+    else if (g.link == 0) y = st[k - 1].x;
+    else if (g.link == 1) y = handed[k - 1];
+    if (k + 1 < n && st[k + 1].link == 1) {
+      handed[k] = g.out;
+      if (!g.out) {
+        handed[k] = reinterpret_cast<float*>(hand);
+        hand += round256((size_t)B * cf.y_channels * 4 * sample_elems(cf) * sizeof(float));
+      }
+    } else if (k == n - 1 && final_link) {
+      handed[k] = g.out;
+    }
+    int rc = pc_setup(&ctx[k], g.net, g.packed, workspace, workspace_bytes, scratch, pc_bytes, g.x, y, B, g.pc, stream, g.inpaint,
+                      g.inpaint != nullptr);
+    if (rc) return cascade_fail(rc, k, n);
+    STAGE_REQUIRE(!ctx[k].path, "use_path (pc->path_coef) does not run in a cascade");
+    ctx[k].nonfinite = stage_flags + k;
+  }
+#undef STAGE_REQUIRE
+  // 4. enqueue: [the link's merge] the stage's loop ... [the final merge]; then the one synchronisation
+  auto merge_of = [&](int k, float* dst, size_t dst_ld) -> int {      // stage k's bands -> the image of twice its side
+    const csd_unet_config& cf = st[k].net->net.cfg;
+    const size_t hw = sample_elems(cf);
+    ProfScope prof(CSD_PROF_OTHER, 0, 2.0 * B * (st[k].inpaint ? cf.x_channels : 4 * cf.y_channels) * hw * 4, s);
+    if (st[k].inpaint) {
+      const int C = cf.x_channels / 4;
+      const int64_t ld = (int64_t)cf.x_channels * hw;
+      return band_merge_launch(st[k].inpaint->data, ld, st[k].x + (size_t)C * hw, ld, dst, (int64_t)dst_ld, B, C, cf.image_size, band_matrix, s);
+    }
+    const int C = cf.y_channels;
+    return band_merge_launch(ctx[k].y, (int64_t)C * hw, st[k].x, (int64_t)3 * C * hw, dst, (int64_t)dst_ld, B, C, cf.image_size, band_matrix, s);
+  };
+  for (int k = 0; k < n; ++k) {
+    int rc = CSD_OK;
+    const csd_unet_config& cf = st[k].net->net.cfg;
+    if (k > 0 && st[k].link == 1) {
+      rc = merge_of(k - 1, handed[k - 1], (size_t)cf.y_channels * sample_elems(cf));
+    } else if (k > 0 && st[k].link == 2) {
+      float* data = const_cast<float*>(st[k].inpaint->data);
+      if (hipMemsetAsync(data, 0, ctx[k].nx * sizeof(float), s) != hipSuccess) {
+        set_error("hipMemsetAsync of the stage's data failed");
+        rc = CSD_ERR_HIP;
+      }
+      if (!rc) rc = merge_of(k - 1, data, (size_t)cf.x_channels * sample_elems(cf));
+      if (!rc) rc = inpaint_blend_launch(st[k].x, nullptr, data, st[k].inpaint->mask, nullptr, 1.f, 0.f, ctx[k].nx, 0, 0, s);
+    }
+    if (!rc) rc = pc_enqueue(ctx[k]);
+    if (!rc && k == n - 1 && final_link)
+      rc = merge_of(k, handed[k], (size_t)(st[k].inpaint ? cf.x_channels / 4 : cf.y_channels) * 4 * sample_elems(cf));
+    if (rc) return cascade_fail(rc, k, n);
+  }
+  std::vector<int32_t> flags(n, 0);
+  CSD_CHECK_HIP(hipMemcpyAsync(flags.data(), stage_flags, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  CSD_CHECK_HIP(hipStreamSynchronize(s));
+  for (int k = 0; k < n; ++k)
+    if (flags[k]) {
+      set_error("pc_cascade: stage %d of %d (stages[%d]): the sampler's state or a corrector norm is not finite (stage_flags[%d] = %d; the "
+                "stages before it stayed finite, the ones behind it ran on its result) - a non-finite condition or prior, or an operand of "
+                "an fp16-operand mode beyond 65504: run that network with csd_precision = 'fp32'", k + 1, n, k, k, (int)flags[k]);
+      return CSD_ERR_NONFINITE;
+    }
+  return CSD_OK;
 }

@@ -474,6 +474,65 @@ def inpaint_blend(x, data, mask, z=None, mean_scale=1.0, std=0.0, seed=0, stream
     return x, xm
 
 
+def _band_matrix(matrix):
+    """the host 4 x 4 fp32 array csd_band_split / csd_band_merge take (None: the library's orthonormal Haar matrix)"""
+    if matrix is None:
+        return None
+    m = torch.as_tensor(matrix, dtype=torch.float32).cpu().contiguous()
+    if tuple(m.shape) != (4, 4):
+        raise RuntimeError('band matrix must be 4 x 4 (rows = bands, columns = 2 dy + dx), got %s' % (tuple(m.shape),))
+    return (ctypes.c_float * 16)(*[float(v) for v in m.flatten()])
+
+
+def _sample_ld(t, name):
+    """floats between consecutive samples of a float32 GPU tensor [B, C, H, W] whose samples are dense (a channel slice of a wider
+    contiguous tensor qualifies: the library takes a per-sample stride)"""
+    _lib.require_gpu_tensor(t, name)
+    if t.dim() != 4:
+        raise RuntimeError('%s must be [B, C, H, W] (got %s)' % (name, tuple(t.shape)))
+    B, C, H, W = t.shape
+    if t.numel() == 0 or tuple(t.stride()[1:]) != (H * W, W, 1) or (B > 1 and t.stride(0) < C * H * W):
+        raise RuntimeError('%s must have dense samples: strides (ld, H*W, W, 1) with ld >= C*H*W (got %s for %s)'
+                           % (name, tuple(t.stride()), tuple(t.shape)))
+    return int(t.stride(0)) if B > 1 else C * H * W
+
+
+def band_split(x, matrix=None):
+    """Image [B, C, 2S, 2S] -> its four bands [B, 4C, S, S], band-major (channel C*k + c is band k of image channel c): the 2x2-block,
+    stride-2 orthogonal transform of the Haar multi-scale models, ``band_k = sum_{dy,dx} matrix[k][2dy + dx] * x[2i + dy, 2j + dx]``.
+    ``matrix=None`` is the orthonormal Haar matrix (include/csd.h, csd_band_split, spells it out and says why it is an argument: the
+    order and signs of the reference layer's bands 1 - 3 could not be checked against iunets).  A matrix with max |M M^T - I| > 1e-6 and
+    an odd image side are refused."""
+    ld = _sample_ld(x, 'x')
+    B, C, H, W = x.shape
+    if H != W or H % 2:
+        raise RuntimeError('band_split: the image side must be even and the image square (got %d x %d)' % (H, W))
+    S = H // 2
+    out = _out((B, 4 * C, S, S), torch.float32, x.device)
+    check(lib().csd_band_split(ctypes.c_void_p(x.data_ptr()), ld, ptr(out), 4 * C * S * S, B, C, S, _band_matrix(matrix),
+                               current_stream(x.device)), 'band_split')
+    return out
+
+
+def band_merge(lo, hi, matrix=None, out=None):
+    """The transpose (= inverse) of ``band_split``: low band ``lo`` [B, C, S, S] and detail bands ``hi`` [B, 3C, S, S] -> the image
+    [B, C, 2S, 2S].  ``lo`` / ``hi`` may be channel slices of wider tensors (no cat is needed), and ``out`` may be given: a float32
+    tensor or channel slice [B, C, 2S, 2S] with dense samples, e.g. ``buf[:, :C]`` of a [B, 4C, 2S, 2S] buffer, whose other channels
+    stay untouched."""
+    lo_ld, hi_ld = _sample_ld(lo, 'lo'), _sample_ld(hi, 'hi')
+    B, C, S, W = lo.shape
+    if S != W or tuple(hi.shape) != (B, 3 * C, S, S):
+        raise RuntimeError('band_merge: lo %s needs hi [B, 3C, S, S], got %s' % (tuple(lo.shape), tuple(hi.shape)))
+    if out is None:
+        out = _out((B, C, 2 * S, 2 * S), torch.float32, lo.device)
+    elif tuple(out.shape) != (B, C, 2 * S, 2 * S):
+        raise RuntimeError('band_merge: out has shape %s, the image is %s' % (tuple(out.shape), (B, C, 2 * S, 2 * S)))
+    x_ld = _sample_ld(out, 'out')
+    check(lib().csd_band_merge(ctypes.c_void_p(lo.data_ptr()), lo_ld, ctypes.c_void_p(hi.data_ptr()), hi_ld,
+                               ctypes.c_void_p(out.data_ptr()), x_ld, B, C, S, _band_matrix(matrix), current_stream(lo.device)), 'band_merge')
+    return out
+
+
 def scale_rows(x, scale, divide=False):
     """x[b] * scale[b] (or / scale[b]) - divide_by_sigmas (models/utils.py:50-74)."""
     x, scale = _c(x, 'x'), _c(scale, 'scale')

@@ -210,34 +210,23 @@ def path_tables(sy, ts):
     return torch.tensor(rows, dtype=torch.float32).contiguous(), std0
 
 
-def run(model, sde, shape, y, p_steps, snr, eps, denoise, noise_tape=None, seed=None, record=False,
-        unconditional_label=None, global_norm=None, predictor=None, corrector=None, probability_flow=False, use_path=False,
-        corr_alpha=None, continuous=True, inpaint=None):
-    """Run the fused loop; returns (samples, record_or_None, timesteps).  ``seed=None``: a fresh key per call (fresh_seed).
+class Prepared:
+    """One fused loop ready to be enqueued (``prepare``): the state ``x`` (prior in, result out), the condition ``y``, the filled
+    csd_pc_params ``p`` / csd_pc_inpaint_params ``ip`` (None: not an inpainting run), the record tensor ``rec`` and the timesteps
+    ``ts``.  ``keep`` holds every host array and device tensor the two structs point into: the object must stay alive until the
+    library call that reads them has returned."""
 
-    ``predictor`` / ``corrector``: the registered classes (default: the reverse-diffusion / Langevin pair); see ``fusable``.
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
 
-    ``corr_alpha``: optional [p_steps] fp32 factors of the Langevin step size (csd_pc_params.corr_alpha); None = alphas[timestep] for
-    the VP classes (sampling/correctors.py:63-65,94-96) and 1 for the VE SDEs.
 
-    ``continuous``: False selects the discrete-time std of the VP classes (sqrt_1m_alphas_cumprod at the truncated label,
-    models/utils.py:201-205,237-241); the VE SDEs run continuous only.
-
-    Prior: N(0, sigma_max^2) (+ data mean) for the VE SDEs, N(0, I) for VP / sub-VP; ``noise_tape[0]`` is the standard-normal draw.
-
-    ``inpaint``: ``(data, mask)`` - inpainting with an unconditional network (csd_pc_inpaint_sample; sampling/unconditional.py:230-345):
-    the loop starts from prior*(1 - mask) + data*mask and re-imposes the known pixels (mask = 1) at every step's noise level after
-    each phase.  ``mask`` broadcasts to ``data`` (the Haar multi-scale model passes [1, C, 1, 1]).  Draw order / tape layout: prior,
-    then per step [z_corrector] z_blend [z_predictor] z_blend (``inpaint_tape_length``); without a tape the prior is ``ops.randn``
-    stream 0 and draw k of step i is Philox stream 1 + i*draws_per_step + k.  ``record`` then returns [p_steps + 1, ...]: the
-    initial state followed by every step.
-
-    ``global_norm``: None = the Langevin step size uses the batch means of THIS call's batch (the reference run on this batch;
-    one library call enqueues the whole loop).  Otherwise ``(reduce_fn, global_batch)``: the batch is one shard of a larger one
-    and the step size must use the means over the GLOBAL batch (identical to one reference process holding all of it,
-    sampling/correctors.py:100-106): every PC step is enqueued as csd_pc_step_begin -> ``reduce_fn(sums)`` -> csd_pc_step_end,
-    where ``sums`` is a 2-float device tensor and ``reduce_fn`` adds the other shards' sums into it in place (an 8-byte
-    ``torch.distributed.all_reduce``) - no host synchronisation anywhere."""
+def prepare(model, sde, shape, y, p_steps, snr, eps, denoise, noise_tape=None, seed=None, record=False,
+            unconditional_label=None, global_norm=None, predictor=None, corrector=None, probability_flow=False, use_path=False,
+            corr_alpha=None, continuous=True, inpaint=None, blend=True):
+    """Everything ``run`` does before it calls the library - argument checks, per-step tables, prior, tape, record buffer, the two
+    parameter structs - as a ``Prepared``; ``run`` is ``launch(prepare(...))``.  sampling/cascade.py prepares every stage this way and
+    hands them to ONE csd_pc_cascade_sample.  ``blend=False`` (inpainting): the initial state stays the bare prior and ``data`` is
+    used as it is - the cascade's link writes the data and blends on the device."""
     if seed is None:
         seed = fresh_seed()
     if inpaint is not None and len(shape) == 5:
@@ -322,15 +311,15 @@ def run(model, sde, shape, y, p_steps, snr, eps, denoise, noise_tape=None, seed=
         flat = None
     model.eval()
     model._ensure_packed()
-    ws = model._workspace(B)
-    scratch_bytes = lib().csd_pc_inpaint_scratch_bytes if inpaint is not None else lib().csd_pc_scratch_bytes
-    scratch = ops._scratch(scratch_bytes(model._h, B), dev)
     n_rec = p_steps + (1 if inpaint is not None else 0)
     rec = ops._out((n_rec,) + tuple(x.shape), torch.float32, dev) if record else None
     rec_steps = rec
     ip = None
     if inpaint is not None:
-        ops.inpaint_blend(x, data, mask, x_mean=False)                # prior*(1 - mask) + data*mask
+        if blend:
+            ops.inpaint_blend(x, data, mask, x_mean=False)            # prior*(1 - mask) + data*mask
+        elif record:
+            raise NotImplementedError('record needs the initial state, which blend=False leaves to the caller')
         if record:
             rec[0].copy_(x)
             rec_steps = rec[1:]
@@ -362,6 +351,21 @@ def run(model, sde, shape, y, p_steps, snr, eps, denoise, noise_tape=None, seed=
     if global_norm is not None and cid != 0:
         global_norm = None                      # only the Langevin corrector couples the samples of a batch
     yy = y.contiguous() if y is not None else None
+    keep = (labels, std_x, G, std_y, pred_tab, corr_tab, path_tab, corr_alpha, rd_tab, flat, rec)
+    if inpaint is not None:
+        keep += (ip_mean, ip_std, data, mask)
+    return Prepared(model=model, dev=dev, B=B, x=x, y=yy, p=p, ip=ip, rec=rec, ts=ts, p_steps=p_steps, global_norm=global_norm,
+                    data=data if inpaint is not None else None, mask=mask if inpaint is not None else None, keep=keep)
+
+
+def launch(prep):
+    """Enqueue a ``Prepared`` loop through its single-stage entry (csd_pc_sample / csd_pc_inpaint_sample, or the two step calls per
+    PC step under ``global_norm``); returns ``(samples, record_or_None, timesteps)``."""
+    model, dev, B, x, yy, p, ip, p_steps = prep.model, prep.dev, prep.B, prep.x, prep.y, prep.p, prep.ip, prep.p_steps
+    global_norm = prep.global_norm
+    ws = model._workspace(B)
+    scratch_bytes = lib().csd_pc_inpaint_scratch_bytes if ip is not None else lib().csd_pc_scratch_bytes
+    scratch = ops._scratch(scratch_bytes(model._h, B), dev)
     if ip is not None:
         args = (model._h, ptr(model._packed), ptr(ws), ws.numel(), ptr(scratch), scratch.numel(), ptr(x), None, B, ctypes.byref(p),
                 ctypes.byref(ip))
@@ -374,7 +378,6 @@ def run(model, sde, shape, y, p_steps, snr, eps, denoise, noise_tape=None, seed=
                 check(lib().csd_pc_inpaint_step_begin(*args, i, ptr(sums), current_stream(dev)), 'pc_inpaint_step_begin')
                 reduce_fn(sums)
                 check(lib().csd_pc_inpaint_step_end(*args, i, ptr(sums), int(global_batch), current_stream(dev)), 'pc_inpaint_step_end')
-        del ip_mean, ip_std, data, mask         # (alive until the enqueue returned; the last call synchronised)
     elif global_norm is None:
         check(lib().csd_pc_sample(model._h, ptr(model._packed), ptr(ws), ws.numel(), ptr(scratch), scratch.numel(),
                                   ptr(x), ptr(yy) if yy is not None else None, B, ctypes.byref(p),
@@ -388,6 +391,39 @@ def run(model, sde, shape, y, p_steps, snr, eps, denoise, noise_tape=None, seed=
             check(lib().csd_pc_step_begin(*args, i, ptr(sums), current_stream(dev)), 'pc_step_begin')
             reduce_fn(sums)
             check(lib().csd_pc_step_end(*args, i, ptr(sums), int(global_batch), current_stream(dev)), 'pc_step_end')
-    # keep the host arrays alive until the enqueue returned (they are read at enqueue time only)
-    del labels, std_x, G, std_y, pred_tab, corr_tab, path_tab, corr_alpha, rd_tab
-    return x, rec, ts
+    # (prep.keep held the host arrays until the enqueue returned: they are read at enqueue time only)
+    return x, prep.rec, prep.ts
+
+
+def run(model, sde, shape, y, p_steps, snr, eps, denoise, noise_tape=None, seed=None, record=False,
+        unconditional_label=None, global_norm=None, predictor=None, corrector=None, probability_flow=False, use_path=False,
+        corr_alpha=None, continuous=True, inpaint=None):
+    """Run the fused loop; returns (samples, record_or_None, timesteps).  ``seed=None``: a fresh key per call (fresh_seed).
+
+    ``predictor`` / ``corrector``: the registered classes (default: the reverse-diffusion / Langevin pair); see ``fusable``.
+
+    ``corr_alpha``: optional [p_steps] fp32 factors of the Langevin step size (csd_pc_params.corr_alpha); None = alphas[timestep] for
+    the VP classes (sampling/correctors.py:63-65,94-96) and 1 for the VE SDEs.
+
+    ``continuous``: False selects the discrete-time std of the VP classes (sqrt_1m_alphas_cumprod at the truncated label,
+    models/utils.py:201-205,237-241); the VE SDEs run continuous only.
+
+    Prior: N(0, sigma_max^2) (+ data mean) for the VE SDEs, N(0, I) for VP / sub-VP; ``noise_tape[0]`` is the standard-normal draw.
+
+    ``inpaint``: ``(data, mask)`` - inpainting with an unconditional network (csd_pc_inpaint_sample; sampling/unconditional.py:230-345):
+    the loop starts from prior*(1 - mask) + data*mask and re-imposes the known pixels (mask = 1) at every step's noise level after
+    each phase.  ``mask`` broadcasts to ``data`` (the Haar multi-scale model passes [1, C, 1, 1]).  Draw order / tape layout: prior,
+    then per step [z_corrector] z_blend [z_predictor] z_blend (``inpaint_tape_length``); without a tape the prior is ``ops.randn``
+    stream 0 and draw k of step i is Philox stream 1 + i*draws_per_step + k.  ``record`` then returns [p_steps + 1, ...]: the
+    initial state followed by every step.
+
+    ``global_norm``: None = the Langevin step size uses the batch means of THIS call's batch (the reference run on this batch;
+    one library call enqueues the whole loop).  Otherwise ``(reduce_fn, global_batch)``: the batch is one shard of a larger one
+    and the step size must use the means over the GLOBAL batch (identical to one reference process holding all of it,
+    sampling/correctors.py:100-106): every PC step is enqueued as csd_pc_step_begin -> ``reduce_fn(sums)`` -> csd_pc_step_end,
+    where ``sums`` is a 2-float device tensor and ``reduce_fn`` adds the other shards' sums into it in place (an 8-byte
+    ``torch.distributed.all_reduce``) - no host synchronisation anywhere."""
+    return launch(prepare(model, sde, shape, y, p_steps, snr, eps, denoise, noise_tape=noise_tape, seed=seed, record=record,
+                          unconditional_label=unconditional_label, global_norm=global_norm, predictor=predictor, corrector=corrector,
+                          probability_flow=probability_flow, use_path=use_path, corr_alpha=corr_alpha, continuous=continuous,
+                          inpaint=inpaint))

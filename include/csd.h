@@ -325,6 +325,71 @@ int csd_pc_inpaint_step_end(csd_unet* net, const void* packed, void* workspace, 
 int csd_inpaint_blend(float* x, float* x_mean, const float* data, const float* mask, const float* z, float mean_scale,
                       float std, int64_t n, uint64_t seed, uint64_t stream_id, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Band split / merge (csrc/band.hip): the 2x2-block, stride-2 orthogonal transform of the Haar multi-scale models, per image channel,
+ * NCHW fp32 - what the reference does with iunets.layers.InvertibleDownsampling2D(init='haar') followed by permute_channels
+ * (lightning_modules/HaarMultiScaleSdeGenerativeModel.py:15-39, ConditionalSdeGenerativeModel.py:207-247).  With a_dydx = x[b, c, 2i+dy, 2j+dx]:
+ *   csd_band_split: x [B, C, 2S, 2S] -> bands [B, 4C, S, S], band-major: bands[b, C*k + c, i, j] = sum_{dy,dx} M[k][2dy+dx] * a_dydx
+ *   csd_band_merge: the transpose; lo [B, C, S, S] (band 0) and hi [B, 3C, S, S] (bands 1 - 3) through two pointers (no cat) ->
+ *                   x[b, c, 2i+dy, 2j+dx] = sum_k M[k][2dy+dx] * band_k[b, c, i, j]
+ * matrix: HOST 4 x 4 row-major M, or NULL = the orthonormal Haar matrix
+ *   b0 = (a00 + a01 + a10 + a11) / 2    b1 = (a00 - a01 + a10 - a11) / 2    b2 = (a00 + a01 - a10 - a11) / 2    b3 = (a00 - a01 - a10 + a11) / 2
+ * A matrix with max |M M^T - I| > 1e-6 is refused (CSD_ERR_INVALID, the message gives the figure).  The matrix is an argument because
+ * the ORDER AND SIGNS OF BANDS 1 - 3 of the reference's layer could not be checked: iunets was not available when this was written.
+ * Band 0 (the low band, all +1/2) is fixed by init='haar'; a caller who has that library passes its 4 x 4 kernel here.
+ * x_ld, bands_ld, lo_ld, hi_ld: floats between consecutive samples of that tensor (>= its dense per-sample size), so the merge can write
+ * the first C channels of a wider [B, 4C, 2S, 2S] buffer and either call can address a channel slice.  S >= 1 is the side of the bands
+ * (the image side 2S is even by construction; the Python operators refuse an odd image side).  Every output element is a fixed-order
+ * four-term fp32 fma chain: bitwise repeatable.  8-byte accesses on the image, coalesced 4-byte accesses on the bands; 16-byte accesses on
+ * both when S % 4 == 0 and every pointer is 16-byte aligned and every stride a multiple of 4 (else: the image pointer 8-byte aligned and
+ * x_ld even are REQUIRED).  No LDS, no scratch. */
+int csd_band_split(const float* x, int64_t x_ld, float* bands, int64_t bands_ld, int B, int C, int S, const float* matrix, void* stream);
+int csd_band_merge(const float* lo, int64_t lo_ld, const float* hi, int64_t hi_ld, float* x, int64_t x_ld, int B, int C, int S,
+                   const float* matrix, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Sequential super-resolution cascades (run_lib.py:113-222 multi_scale_test: bicubic_autoregressive_sampler,
+ * haar_autoregressive_sampler; the inpainting form of lightning_modules/HaarMultiScaleSdeGenerativeModel.py:62-89): n_stages fused PC
+ * loops enqueued back to back on one stream, each stage's condition made on the device from the stage before, ONE synchronisation
+ * behind the last stage.  A stage is what csd_pc_sample (inpaint == NULL) or csd_pc_inpaint_sample (inpaint != NULL) takes:
+ *   x: in = the caller's prior for this stage (an inpainting stage 0: already blended with its data), out = the stage's result.
+ *   link (stage k >= 1; stage 0 takes the call's y0 - NULL iff it has no condition - and must have link 0):
+ *     0  bicubic: the previous stage's x IS this stage's y (the pointer is handed over, no copy).  Previous x_channels / 4 (a 2x
+ *        network, x_squeeze) or x_channels image channels at side 2S or S must be this stage's y_channels at its side.
+ *     1  Haar, conditional: y = csd_band_merge(previous y, previous x).  Previous y_channels = C, x_channels = 3C at side S; this stage
+ *        y_channels = C at side 2S.  The merged image is written to the PREVIOUS stage's `out`, or, out == NULL, to a region of the scratch.
+ *     2  Haar, inpainting (both stages have inpaint): this stage's inpaint->data buffer [B, 4C, 2S, 2S] - which the stage owns; the
+ *        library writes it - is zeroed, csd_band_merge(previous data[:, :C], previous x[:, C:]) is written into its first C channels,
+ *        and the state is started as x = x * (1 - mask) + data * mask (csd_inpaint_blend with std = 0).  Previous x_channels = 4C at
+ *        side S; this stage x_channels = 4C at side 2S.  The previous stage's `out` must be NULL.
+ *   final_link: what becomes of the LAST stage's result: 0 nothing (x is the result); 1 / 2: the last stage's `out` (required)
+ *     [B, C, 2S, 2S] = the merge of link 1 / 2 applied to the last stage.
+ *   band_matrix: csd_band_merge's matrix for every link (host, NULL = Haar).
+ * Buffers, shared by the stages one after the other (results do not depend on what they held):
+ *   workspace_bytes >= max over stages of csd_unet_workspace_bytes(net, B)
+ *   scratch_bytes   >= max over stages of csd_pc_scratch_bytes(net, B), rounded up to 256, + for every stage that is followed by a
+ *                      link-1 stage and has out == NULL: B * C * 2S * 2S * 4 bytes rounded up to 256      (scratch 256-byte aligned)
+ * A short buffer is CSD_ERR_WORKSPACE naming the stage that needs more.
+ * stage_flags: device int32_t [n_stages], written by the call: stage k's flag of the finiteness contract of csd_pc_sample.  The call
+ * reads them back behind the last stage - its one synchronisation - and fails with CSD_ERR_NONFINITE naming the FIRST stage whose flag
+ * is set (the later stages then ran on garbage: wasted work, nothing else).
+ * Refused with CSD_ERR_INVALID naming the stage: extents that do not match at a link, 3-D handles, handles with y_scale, a
+ * conditional stage with inpaint or an unconditional one without, a NULL handle / packed / pc / x; B < 1 and a NULL stage_flags are
+ * refused too.  pc->record is honoured.  Each stage keeps the noise numbering and the bits of its single-stage entry.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct csd_cascade_stage {
+  csd_unet* net;
+  const void* packed;                    /* the handle's packed weights (csd_unet_pack)                                    */
+  const csd_pc_params* pc;
+  const csd_pc_inpaint_params* inpaint;  /* NULL: a conditional stage; else an inpainting stage (link 2 writes inpaint->data) */
+  float* x;                              /* the stage's state: prior in, result out                                        */
+  int32_t link;                          /* 0, 1, 2: how this stage's condition comes from the stage before (see above)    */
+  float* out;                            /* the image this stage hands on through a merge, or NULL                         */
+} csd_cascade_stage;
+int csd_pc_cascade_sample(const csd_cascade_stage* stages, int n_stages, int final_link, const float* y0, int B, void* workspace,
+                          size_t workspace_bytes, void* scratch, size_t scratch_bytes, int32_t* stage_flags, const float* band_matrix,
+                          void* stream);
+
 /* Stand-alone update kernels (the "noise-add" steps), usable with any score source:
  *   csd_langevin_step: sampling/correctors.py:51-78,88-108: step = (snr * mean||z|| / mean||score||)^2 * 2 * alpha with
  *                      alpha = sde.alphas[timestep] for the VP / subVP SDEs (:63-65,94-96) and 1 for the VE SDEs
