@@ -2,6 +2,10 @@
 // like csd_debug_timing: not part of include/csd.h).  tests/test_host_logic.py pins them to tests/golden/plan_digests.json, so a change
 // that is meant to leave every packed offset, launch and workspace address alone can prove it without a GPU.  Hashed field by field
 // (never raw struct bytes: padding, and Op::cp / Op::gp are only filled for the kinds that use them).
+//
+// The pinned values date from an Op of lettered slots (offsets a .. e, ints i0 .. i4) and a PackedConv of one flag per kernel.  The hash
+// still takes its values in THAT order; legacy_slots / legacy_flags below are the only place that knows it - and the record of what the
+// letters used to mean.
 #pragma once
 
 namespace csd {
@@ -22,6 +26,84 @@ struct Fnv {
   }
 };
 
+// ---- the pinned order ---------------------------------------------------------------------------------
+// PackedConv: ns, then the flags pw, q, ff, tap_cout, stem, up4
+struct LegacyFlags { int pw = 0, q = 0, ff = 0, stem = 0, up4 = 0; };
+static LegacyFlags legacy_flags(ConvKernel k) {
+  LegacyFlags f;
+  switch (k) {
+    case ConvKernel::F32: case ConvKernel::F16_LC: break;      // (told apart by ns == 0)
+    case ConvKernel::PW16: case ConvKernel::PW16_TAPS: f.pw = 1; break;      // (PW16_TAPS: tap_cout != 0)
+    case ConvKernel::QUAD: f.q = 1; break;
+    case ConvKernel::QUAD_UP4: f.q = 1; f.up4 = 1; break;
+    case ConvKernel::FUSED: f.ff = 1; break;
+    case ConvKernel::STEM: f.stem = 1; break;
+  }
+  return f;
+}
+
+// Op: the offsets a, b, c, d, e, out, stats, pk0, pk1 and the ints i0 .. i4 of every kind (an unused slot: NONE / 0)
+struct LegacySlots {
+  size_t a = NONE, b = NONE, c = NONE, d = NONE, e = NONE, out = NONE, stats = NONE, pk0 = NONE, pk1 = NONE;
+  int i0 = 0, i1 = 0, i2 = 0, i3 = 0, i4 = 0;
+};
+static void legacy_stem(const Op& o, LegacySlots& l) {
+  l.i0 = o.Cout; l.i4 = o.ns; l.stats = o.stats; l.c = o.out2;
+}
+static void legacy_embedding(const Op& o, LegacySlots& l) { l.i0 = o.C0; }      // OP_TEMB, OP_FOURIER (pk0 = W)
+static void legacy_fir(const Op& o, LegacySlots& l) {      // OP_FIR, OP_FIR2 (d / e: the GroupNorm it applies, c: FIR(x))
+  l.a = o.src0; l.d = o.nscale; l.e = o.nshift; l.c = o.out2; l.i0 = o.H; l.i1 = o.C0; l.i2 = o.up;
+}
+static void legacy_gn_apply32(const Op& o, LegacySlots& l) { l.a = o.src0; l.d = o.nscale; l.e = o.nshift; l.i0 = o.C0; l.i1 = o.hw; }
+static void legacy_linear(const Op& o, LegacySlots& l) { l.a = o.src0; l.i0 = o.C0; l.i1 = o.Cout; l.i2 = o.out_act; }
+static void legacy_gn_stats(const Op& o, LegacySlots& l) { l.a = o.src0; l.b = o.src1; l.out = o.stats; l.i0 = o.per_channel; }
+static void legacy_gn_final(const Op& o, LegacySlots& l) { l.a = o.stats; l.out = o.nscale; l.b = o.nshift; }      // (nshift in b ...)
+static void legacy_gn_final_tiles(const Op& o, LegacySlots& l) {                                                     // (... but in c here ...)
+  l.a = o.stats; l.i0 = o.tiles0; l.i1 = o.C0; l.b = o.stats1; l.i2 = o.tiles1; l.i3 = o.C1; l.i4 = o.hw; l.out = o.nscale; l.c = o.nshift;
+}
+static void legacy_gn_statfin(const Op& o, LegacySlots& l) { l.a = o.src0; l.b = o.src1; l.out = o.nscale; l.c = o.nshift; }      // (... and here)
+static void legacy_gn_planes16(const Op& o, LegacySlots& l) {      // OP_GN_APPLY16, OP_GN_FUSED16: out / c = the hi / lo plane
+  l.a = o.src0; l.b = o.src1; l.i0 = o.C0; l.i1 = o.C1; l.i2 = o.hw; l.d = o.nscale; l.e = o.nshift; l.c = o.out2; l.i3 = o.fp8_lo;
+}
+static void legacy_conv(const Op& o, LegacySlots& l) {
+  l.a = o.src0; l.b = o.src1; l.c = o.res; l.d = o.nscale; l.e = o.nshift; l.stats = o.stats;
+  const LegacyFlags f = legacy_flags(o.kernel);
+  l.i2 = f.ff ? 3 : (f.pw ? 1 : (f.q ? 2 : 0));      // "kernel id"
+  l.i3 = o.src_form == ConvSrc::SPLIT_STAGING ? 2 : (o.src_form == ConvSrc::PLANES16 ? 1 : 0);
+  l.i4 = o.ns;
+}
+static void legacy_attn(const Op& o, LegacySlots& l) { l.a = o.src0; l.i0 = o.hw; l.i1 = o.C0; }
+static void legacy_resample_plain(const Op& o, LegacySlots& l) { l.a = o.src0; l.i0 = o.H; l.i1 = o.C0; }      // OP_AVGPOOL, OP_UPNEAR
+static void legacy_pyrconv(const Op& o, LegacySlots& l) {
+  l.a = o.src0; l.c = o.res; l.i0 = o.H; l.i1 = o.C0; l.i2 = o.Cout; l.i3 = o.pix; l.i4 = o.fir;
+}
+static void legacy_tapsum(const Op& o, LegacySlots& l) { l.a = o.src0; l.c = o.res; l.i0 = o.H; l.i1 = o.W; l.i2 = o.Cout; }
+static LegacySlots legacy_slots(const Op& o) {
+  LegacySlots l;
+  l.out = o.out;      // (the kinds that write partial sums or scale / shift have no `out`: theirs went into this slot)
+  l.pk0 = o.pk_w; l.pk1 = o.pk_b;
+  switch (o.kind) {
+    case OP_ASSEMBLE: case OP_TO_NCHW: break;
+    case OP_STEM: legacy_stem(o, l); break;
+    case OP_TEMB: case OP_FOURIER: legacy_embedding(o, l); break;
+    case OP_FIR: case OP_FIR2: legacy_fir(o, l); break;
+    case OP_GN_APPLY32: legacy_gn_apply32(o, l); break;
+    case OP_LINEAR: legacy_linear(o, l); break;
+    case OP_GN_STATS: legacy_gn_stats(o, l); break;
+    case OP_GN_FINAL: legacy_gn_final(o, l); break;
+    case OP_GN_FINAL_TILES: legacy_gn_final_tiles(o, l); break;
+    case OP_GN_STATFIN: legacy_gn_statfin(o, l); break;
+    case OP_GN_APPLY16: case OP_GN_FUSED16: legacy_gn_planes16(o, l); break;
+    case OP_CONV: legacy_conv(o, l); break;
+    case OP_ATTN: legacy_attn(o, l); break;
+    case OP_AVGPOOL: case OP_UPNEAR: legacy_resample_plain(o, l); break;
+    case OP_PYRCONV: legacy_pyrconv(o, l); break;
+    case OP_TAPSUM: legacy_tapsum(o, l); break;
+    case OP_FORK: case OP_JOIN: l.i0 = o.n_chunks; break;
+  }
+  return l;
+}
+
 static uint64_t digest_params(const Net& n) {
   Fnv h;
   for (const Param& p : n.params) { h.s(p.name); h.i(p.ndim); for (int j = 0; j < 4; ++j) h.i(p.shape[j]); }      // (4: arch 0 / 1 have no 5-D parameter)
@@ -33,7 +115,8 @@ static uint64_t digest_layout(const Net& n) {
   for (const auto& kv : n.pconv_by_name) {
     const PackedConv& pc = n.pconvs[kv.second];
     h.s(kv.first); h.i(kv.second); h.z(pc.w_off); h.z(pc.b_off);
-    for (int v : {pc.ns, (int)pc.pw, (int)pc.q, (int)pc.ff, pc.tap_cout, (int)pc.stem, (int)pc.up4, pc.proto.C0, pc.proto.C1, pc.proto.Cout,
+    const LegacyFlags f = legacy_flags(pc.kernel);
+    for (int v : {pc.ns, f.pw, f.q, f.ff, pc.tap_cout, f.stem, f.up4, pc.proto.C0, pc.proto.C1, pc.proto.Cout,
                   pc.proto.taps, pc.proto.KC, pc.proto.NT, pc.proto.CoutPad, pc.proto.qnt}) h.i(v);
     for (const auto& sr : pc.srcs) for (int v : {sr.param_w, sr.param_b, sr.layout, sr.cout_src, sr.cout_off, sr.cin_src}) h.i(v);
   }
@@ -49,9 +132,10 @@ static uint64_t digest_plan(const Plan& pl) {
   Fnv h;
   for (const Op& o : pl.ops) {
     h.i(o.kind);
-    for (size_t v : {o.a, o.b, o.c, o.d, o.e, o.out, o.stats, o.temb_base, o.pk0, o.pk1, o.temb_col}) h.z(v);
-    for (int v : {o.i0, o.i1, o.i2, o.i3, o.i4, o.act, o.out_external, o.side, o.nb, o.stream, o.chunk, o.temb_stride, o.cls}) h.i(v);
-    for (double v : {(double)o.fscale, o.flops, o.bytes, o.abytes}) h.f(v);
+    const LegacySlots l = legacy_slots(o);
+    for (size_t v : {l.a, l.b, l.c, l.d, l.e, l.out, l.stats, o.temb_base, l.pk0, l.pk1, o.temb_col}) h.z(v);
+    for (int v : {l.i0, l.i1, l.i2, l.i3, l.i4, o.act, o.out_external, o.side, o.nb, o.stream, o.chunk, o.temb_stride, o.cls}) h.i(v);
+    for (double v : {(double)o.out_scale, o.flops, o.bytes, o.abytes}) h.f(v);
     if (o.kind == OP_CONV) h.cp(o.cp);
     if (o.kind == OP_GN_FINAL_TILES) h.i(o.gp.G);
     if (o.kind == OP_GN_STATS || o.kind == OP_GN_FINAL || o.kind == OP_GN_STATFIN || o.kind == OP_GN_FUSED16)

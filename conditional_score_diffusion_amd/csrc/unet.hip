@@ -9,7 +9,7 @@
 // launches on ONE stream: no per-step host objects, no allocation, no synchronisation.
 //
 // One translation unit in pieces: this file (structs, the topology = build_modules, the parameter table, the C ABI, the PC sampler),
-// unet_layout.h (packed-weight layout + pack_all), unet_plan.h (Builder + build_plan), unet_run.h (run_plan), unet3d.h (the 3-D DDPM
+// unet_layout.h (ConvKernel per layer, packed-weight layout + pack_all), unet_plan.h (Builder + build_plan), unet_run.h (run_plan), unet3d.h (the 3-D DDPM
 // family, arch 2: topology, packed layout, plan and executor on conv3d.hip's kernels), train_graph.h (training forward / backward),
 // plan_digest.h (csd_unet_debug_digest).
 #include <stdarg.h>
@@ -111,18 +111,29 @@ struct Module {
   bool last_up = false;    // the last module of its level on the up path, in front of the level's output pyramid / upsample / the head
 };
 
+// the schedule a packed convolution runs on: chosen ONCE, in build_packed_layout (unet_layout.h); pack_all, the Builder, run_plan,
+// split_conv3x3_classes and digest_layout switch on it
+enum class ConvKernel {
+  F32,             // conv_f32.hip: fp32 operands (the fp32 precision, and the layers no fp16 kernel takes)
+  F16_LC,          // conv_f16*.hip: the fp16 kernel with its loader / consumer variant
+  PW16,            // conv_pw16.hip: the pointwise fp16 kernel
+  PW16_TAPS,       // ... on a 3x3 convolution with tap_cout (<= 6) output channels in its tap-partial form: proto is the POINTWISE
+                   // contraction to 9 * tap_cout partial channels, a 9-tap gather (OP_TAPSUM) finishes it
+  QUAD,            // conv_f16_q.hip: the quad-wave fp16 kernel
+  QUAD_UP4,        // ... on the nearest-x2 Upsample conv in its phase-decomposed form (4 x 2x2 taps; UP4)
+  FUSED,           // conv_ff.hip / conv_fx.hip / conv_xk.hip: the fused-prologue family - fp32 sources, no gn_apply16 pass
+  STEM             // stem.hip: the first layer fused with the input assembly: x, y (NCHW) -> nf channels NHWC
+};
+static inline bool is_quad(ConvKernel k) { return k == ConvKernel::QUAD || k == ConvKernel::QUAD_UP4; }
+static inline bool is_pw16(ConvKernel k) { return k == ConvKernel::PW16 || k == ConvKernel::PW16_TAPS; }
+
 // one packed convolution weight (+bias): where it lives inside the packed buffer
 struct PackedConv {
   ConvPlan proto;          // channel-level fields only (C0,C1,Cout,taps,KC,NT,CoutPad)
   size_t w_off = 0, b_off = 0;   // float offsets in the packed buffer
-  int ns = 0;                    // 0: fp32 kernel layout; 1/2: fp16 kernel layout with ns planes
-  bool pw = false;               // ns != 0 and the layer runs on the pointwise fp16 kernel (conv_pw16.hip)
-  bool q = false;                // ns != 0 and the layer runs on the quad-wave fp16 kernel (conv_f16_q.hip)
-  bool ff = false;               // ns != 0 and the layer runs on the fused-prologue kernel (conv_ff.hip): fp32 sources, no gn_apply16
-  int tap_cout = 0;              // pw and the layer is a 3x3 convolution with tap_cout (<= 6) output channels in its tap-partial form (conv_pw16.hip):
-                                 // proto is the POINTWISE contraction to 9 * tap_cout partial channels, a 9-tap gather finishes it
-  bool stem = false;             // the DDPM-family first layer fused with the input assembly (stem.hip): x, y (NCHW) -> nf channels NHWC
-  bool up4 = false;              // q and the layer is the nearest-x2 Upsample conv in its phase-decomposed form (4 x 2x2 taps; conv_f16_q.hip UP4)
+  ConvKernel kernel = ConvKernel::F32;
+  int ns = 0;                    // operand planes of the fp16 kernels' layout: 1 / 2, 3: fp16 hi*hi + fp8 corrections (0: ConvKernel::F32)
+  int tap_cout = 0;              // ConvKernel::PW16_TAPS: the layer's own output channels
   struct Src { int param_w, param_b, layout, cout_src, cout_off, cin_src; };
   std::vector<Src> srcs;
 };
@@ -138,28 +149,61 @@ enum OpKind { OP_ASSEMBLE, OP_STEM, OP_TEMB, OP_FOURIER, OP_FIR, OP_FIR2, OP_GN_
 
 static const size_t NONE = (size_t)-1;
 
+// what the sources of an OP_CONV hold
+enum class ConvSrc {
+  F32,             // fp32 tensors (src0 | src1)
+  PLANES16,        // the fp16 planes an OP_GN_APPLY16 / OP_GN_FUSED16 wrote: src0 = hi, src1 = lo (ns >= 2)
+  SPLIT_STAGING    // one fp32 tensor that the quad kernel splits into fp16 operands while it stages it
+};
+
+// one launch of the plan.  Every field is named for what it is; a kind fills the ones its launch takes (the comment behind a field
+// says which), run_plan (unet_run.h) reads them by name.  Offsets are floats into the workspace unless stated; NONE: absent
 struct Op {
+  // ---- shared by every kind (all that fold_small_gn_pairs, interleave_chunks and the chunk stamping of build_plan touch) ----
   OpKind kind;
-  // generic offsets (floats) into workspace unless stated
-  size_t a = NONE, b = NONE, c = NONE, d = NONE, e = NONE, out = NONE;
-  size_t stats = NONE;                // conv: per-tile GroupNorm partials it writes; GN_FINAL_TILES: a = source 0's, b = source 1's
-  size_t temb_base = NONE;            // offset of dense_all (conv epilogue time-embedding source)
-  size_t pk0 = NONE, pk1 = NONE;      // offsets into the packed buffer
-  int i0 = 0, i1 = 0, i2 = 0, i3 = 0, i4 = 0;
-  ConvPlan cp;
-  GNPlan gp;
-  int act = 0;
-  int out_external = 0;               // conv writes to the caller's NCHW output
-  int side = 0;                       // 1: launched on the side stream (after the main stream's work so far); 2: the main stream waits for it first
-  int nb = 0;                         // batch of THIS launch (0: the plan's) - the ops of a batch chunk carry the chunk's size
-  int stream = 0;                     // 0: the caller's stream; k > 0: chunk stream k - 1 (between an OP_FORK and its OP_JOIN)
-  int chunk = 0;                      // k + 1 for the ops of batch chunk k (chunk 0 runs on the caller's stream)
-  float fscale = 1.f;                 // conv: epilogue out_scale
-  size_t temb_col = NONE;             // column offset inside dense_all
-  int temb_stride = 0;
   int cls = CSD_PROF_OTHER;           // profiling class
   double flops = 0, bytes = 0;        // algorithmic flops of this launch; bytes THIS kernel has to move
   double abytes = -1;                 // SURVEY 8(d) bytes of the layer (input + output tensor, fp32) where they differ from `bytes`
+  int nb = 0;                         // batch of THIS launch (0: the plan's) - the ops of a batch chunk carry the chunk's size
+  int stream = 0;                     // 0: the caller's stream; k > 0: chunk stream k - 1 (between an OP_FORK and its OP_JOIN)
+  int chunk = 0;                      // k + 1 for the ops of batch chunk k (chunk 0 runs on the caller's stream)
+  int side = 0;                       // 1: launched on the side stream (after the main stream's work so far); 2: the main stream waits for it first
+  // ---- tensors ----
+  size_t src0 = NONE, src1 = NONE;    // sources (src1: the second of a virtual concat; OP_CONV from ConvSrc::PLANES16: the hi / lo planes)
+  size_t out = NONE;                  // destination (OP_GN_APPLY16 / OP_GN_FUSED16: the hi plane; OP_FIR2: FIR(act(GroupNorm(x))))
+  size_t out2 = NONE;                 // OP_GN_APPLY16 / OP_GN_FUSED16: the lo plane; OP_FIR2: FIR(x); OP_STEM: room for the perturbed y of a y_scale network
+  size_t res = NONE;                  // OP_CONV / OP_TAPSUM / OP_PYRCONV: the tensor the epilogue adds
+  size_t nscale = NONE, nshift = NONE;      // GroupNorm scale / shift per (sample, channel): OP_GN_FINAL / OP_GN_FINAL_TILES / OP_GN_STATFIN write
+                                            // them; OP_CONV, OP_GN_APPLY16, OP_GN_APPLY32 and OP_FIR2 read them
+  size_t stats = NONE, stats1 = NONE; // GroupNorm partial sums (doubles): OP_CONV / OP_STEM (per tile) and OP_GN_STATS write `stats`,
+                                      // OP_GN_FINAL reads it; OP_GN_FINAL_TILES reads source 0's and source 1's
+  size_t temb_base = NONE;            // OP_CONV: offset of dense_all (the epilogue's time-embedding source) ...
+  size_t temb_col = NONE;             // ... the layer's first column inside it (NONE: no time embedding) ...
+  int temb_stride = 0;                // ... and its row length
+  size_t pk_w = NONE, pk_b = NONE;    // float offsets in the PACKED buffer: weight / bias (the GroupNorm kinds: gamma / beta; OP_FOURIER: W)
+  // ---- OP_CONV (cp: also its geometry) / OP_STEM ----
+  ConvPlan cp;
+  ConvKernel kernel = ConvKernel::F32;
+  ConvSrc src_form = ConvSrc::F32;
+  int ns = 0;                         // PackedConv::ns of the layer
+  int out_external = 0;               // OP_CONV / OP_TAPSUM: writes the caller's NCHW output
+  float out_scale = 1.f;              // OP_CONV / OP_TAPSUM / OP_PYRCONV: the epilogue's factor
+  int act = 0;                        // activation the launch applies (behind the GroupNorm where there is one)
+  int out_act = 0;                    // OP_LINEAR: the activation every consumer would apply to this output, applied ONCE by the producer (the
+                                      // consumers used to recompute it per workgroup: 396 x 24.6 k SiLUs in the Dense_0 launch)
+  // ---- the other kinds' extents ----
+  GNPlan gp;                          // OP_GN_STATS / OP_GN_FINAL / OP_GN_STATFIN / OP_GN_FUSED16 (OP_GN_FINAL_TILES: G only)
+  int C0 = 0, C1 = 0;                 // channels of src0 / src1 (OP_LINEAR: input features; OP_TEMB / OP_FOURIER: nf)
+  int Cout = 0;                       // OP_STEM / OP_TAPSUM / OP_PYRCONV: output channels; OP_LINEAR: output features
+  int H = 0, W = 0;                   // extent of the SOURCE map (OP_FIR*, OP_AVGPOOL, OP_UPNEAR, OP_PYRCONV, OP_TAPSUM)
+  int hw = 0;                         // pixels per sample (the GroupNorm kinds; OP_ATTN: tokens)
+  int tiles0 = 0, tiles1 = 0;         // OP_GN_FINAL_TILES: partials per sample in stats / stats1
+  int pix = 0;                        // OP_PYRCONV: floats per source pixel (>= C0: the padded input)
+  bool up = false;                    // OP_FIR / OP_FIR2: upsample (else downsample)
+  bool fir = false;                   // OP_PYRCONV: the FIR-folded 6x6 weight (else the plain stride-2 3x3)
+  bool per_channel = false;           // OP_GN_STATS: per-channel partials in the tile-partial layout (G = 1) for OP_GN_FINAL_TILES
+  bool fp8_lo = false;                // OP_GN_APPLY16 / OP_GN_FUSED16: the lo plane holds e4m3 byte pairs (ns == 3)
+  int n_chunks = 0;                   // OP_FORK / OP_JOIN
 };
 
 struct Plan {

@@ -36,9 +36,19 @@ static int build_packed_layout(Net& n) {
   int cur_res = n.cfg.image_size;    // resolution of the layer being laid out
   // opt-in experiment (measured slower: one loader wave cannot convert a patch as fast as three waves consume it)
   const bool fused_norm = CSD_TUNE_ENV("CSD_FUSED_NORM") != nullptr;
-  auto add_conv = [&](const std::string& key, int c0, int c1, int cout, int taps,
-                      std::vector<PackedConv::Src> srcs, bool stride1 = true, bool normed = false,
-                      bool resample = false, bool upsample = false, bool last = false) -> int {
+  // what build_packed_layout knows about a convolution when it picks the kernel
+  struct ConvSpec {
+    int c0 = 0, c1 = 0, cout = 0, taps = 9;        // reads (c0 | c1) channels
+    std::vector<PackedConv::Src> srcs;
+    bool normed = false;         // a GroupNorm in front (or, in an NCSN++ up / down block, its FIR-resampled activation): quad-eligible
+    bool resample = false;       // reads a resampled map: Downsample / Upsample, Conv_0 of an NCSN++ up / down block
+    bool upsample = false;       // the nearest-x2 Upsample conv
+    bool last = false;           // the network's last layer / an output-pyramid conv: a handful of couts
+  };
+  auto add_conv = [&](const std::string& key, const ConvSpec& sp) -> int {
+    const int c0 = sp.c0, c1 = sp.c1, cout = sp.cout, taps = sp.taps;
+    const std::vector<PackedConv::Src>& srcs = sp.srcs;
+    const bool normed = sp.normed, resample = sp.resample, upsample = sp.upsample, last = sp.last;
     PackedConv pc;
     int rc;
     if (last && net_ns && taps == 9 && c1 == 0 && srcs.size() == 1 && srcs[0].layout == 0 && srcs[0].cout_off == 0 &&
@@ -47,7 +57,7 @@ static int build_packed_layout(Net& n) {
       // SiLU networks only: it is the one activation pw16_kernel's prologue applies; any other head takes the ordinary 3x3 path below
       if ((rc = proto_conv(&pc.proto, c0, 0, pw16_taps_cout(cout), 1))) return rc;
       pc.ns = net_ns;
-      pc.pw = true;
+      pc.kernel = ConvKernel::PW16_TAPS;
       pc.tap_cout = cout;
       pc.w_off = take(pw16_packed_bytes(pc.proto, pc.ns) / sizeof(float) + 1);
       pc.b_off = take((size_t)pc.proto.CoutPad + 96);
@@ -60,7 +70,7 @@ static int build_packed_layout(Net& n) {
     if (rc) return rc;
     // the 5 x 5 level on the quad schedule: 32-cout groups (conv_f16_q.hip: q_ntq)
     static const int nt1_res = CSD_TUNE_ENV("CSD_Q_NT1_RES") ? atoi(CSD_TUNE_ENV("CSD_Q_NT1_RES")) : 5;      // tuning aid (0 disables)
-    if (net_ns == 2 && normed && stride1 && !resample && cur_res <= nt1_res) pc.proto.qnt = 1;
+    if (net_ns == 2 && normed && !resample && cur_res <= nt1_res) pc.proto.qnt = 1;
     ConvPlan one = pc.proto;       // a GroupNorm-ed conv reads ONE fp16 tensor of c0 + c1 channels
     one.C0 = c0 + c1; one.C1 = 0;
     // high-resolution GroupNorm-ed convs run the loader/consumer schedule with the norm fused into its loader
@@ -76,32 +86,33 @@ static int build_packed_layout(Net& n) {
     // kernel takes it with its NORM = false prologue (plain split; the values stay far inside e4m3): no split pass, no fp16 planes)
     const bool fir_act_input = resample && !upsample && normed && n.cfg.arch == 1;
     const int ff_ns = n.cfg.precision == CSD_PREC_F16F8 ? 3 : net_ns;      // 3: fp16 hi*hi + fp8 corrections (conv_ff.hip)
-    if (net_ns && normed && stride1 && (!resample || fir_act_input) && n.cfg.act == CSD_ACT_SWISH && convff_supported(ffp, ff_ns)) {
+    if (net_ns && normed && (!resample || fir_act_input) && n.cfg.act == CSD_ACT_SWISH && convff_supported(ffp, ff_ns)) {
       pc.ns = ff_ns;
-      pc.ff = true;
+      pc.kernel = ConvKernel::FUSED;
       pc.proto.KC = 16;
       pc.w_off = take(convff_packed_bytes(pc.proto, pc.ns) / sizeof(float) + 1);
-    } else if (q_here && normed && stride1 && !(fused_norm && cur_res >= 64) && conv16q_supported(one, net_ns)) {
+    } else if (q_here && normed && !(fused_norm && cur_res >= 64) && conv16q_supported(one, net_ns)) {
       // 3: fp16 hi*hi + fp8 corrections - for GroupNorm-ed operands only: e4m3 saturates at 448, which activated, normalised values never
       // reach, while the raw residual stream that the resampling convs read does at the large-sigma end of a sampling run (measured: the
       // 1000-step trajectory error went from 6e-7 to 1e-4 with them included)
       pc.ns = (n.cfg.precision == CSD_PREC_F16F8 && net_ns == 2 && !resample && conv16q_supported(one, 3)) ? 3 : net_ns;
-      pc.q = true;
       pc.proto.KC = 16;
-      pc.up4 = upsample && srcs.size() == 1 && conv16q_up4_supported(one, pc.ns);
-      pc.w_off = take((pc.up4 ? conv16q_up4_packed_bytes(one, pc.ns) : conv16q_packed_bytes(one, pc.ns)) / sizeof(float) + 1);
-    } else if (net_ns && stride1 && conv16_supported(pc.proto)) {
+      const bool up4 = upsample && srcs.size() == 1 && conv16q_up4_supported(one, pc.ns);
+      pc.kernel = up4 ? ConvKernel::QUAD_UP4 : ConvKernel::QUAD;
+      pc.w_off = take((up4 ? conv16q_up4_packed_bytes(one, pc.ns) : conv16q_packed_bytes(one, pc.ns)) / sizeof(float) + 1);
+    } else if (net_ns && conv16_supported(pc.proto)) {
       pc.ns = net_ns;
+      pc.kernel = ConvKernel::F16_LC;
       if ((rc = conv16_plan_tiles(&pc.proto, pc.ns))) return rc;
       pc.w_off = take(conv16_packed_bytes(pc.proto, pc.ns) / sizeof(float) + 1);
-    } else if (net_ns && stride1 && pw16_supported(pc.proto, net_ns)) {
+    } else if (net_ns && pw16_supported(pc.proto, net_ns)) {
       bool aligned = true;
       for (const auto& sr : srcs) aligned = aligned && (sr.cout_off % 16 == 0);
       if (aligned) {
         pc.ns = net_ns;
-        pc.pw = true;
+        pc.kernel = ConvKernel::PW16;
         pc.w_off = take(pw16_packed_bytes(pc.proto, pc.ns) / sizeof(float) + 1);
-      } else {
+      } else {      // (a source at an unaligned cout_off: the fp32 kernel)
         pc.w_off = take(conv_packed_floats(pc.proto));
       }
     } else {
@@ -128,7 +139,7 @@ static int build_packed_layout(Net& n) {
     PackedConv pc;
     if (proto_conv(&pc.proto, n.in_cpad, 0, m.cout, 9)) return false;
     pc.ns = net_ns;
-    pc.stem = true;
+    pc.kernel = ConvKernel::STEM;
     pc.w_off = take(stem_packed_bytes(m.cin, m.cout, net_ns) / sizeof(float) + 1);
     pc.b_off = take((size_t)pc.proto.CoutPad + 96);
     pc.srcs = {{n.P(mname(m.idx, "weight")), n.P(mname(m.idx, "bias")), 0, m.cout, 0, m.cin}};
@@ -144,18 +155,22 @@ static int build_packed_layout(Net& n) {
     add_copy(mname(m.idx, "GroupNorm_0.bias"));
     // Conv_0 reads the GroupNorm-ed input directly only in plain blocks; up/down blocks feed it the FIR-resampled
     // activation (an fp32 tensor without a norm)
-    int r = add_conv(k + ".Conv_0", c0, c1, m.cout, 9,
-                     {{n.P(mname(m.idx, "Conv_0.weight")), n.P(mname(m.idx, "Conv_0.bias")), 0, m.cout, 0}}, true,
-                     /*quad-eligible (plain split of the resampled tensor in up/down blocks)=*/true, /*resample=*/!plain);
+    int r = add_conv(k + ".Conv_0", {.c0 = c0, .c1 = c1, .cout = m.cout,
+                                     .srcs = {{n.P(mname(m.idx, "Conv_0.weight")), n.P(mname(m.idx, "Conv_0.bias")), 0, m.cout, 0}},
+                                     .normed = true,      // (up/down blocks: quad-eligible, a plain split of the resampled tensor)
+                                     .resample = !plain});
     if (r) return r;
     add_copy(mname(m.idx, "GroupNorm_1.weight"));
     add_copy(mname(m.idx, "GroupNorm_1.bias"));
-    r = add_conv(k + ".Conv_1", m.cout, 0, m.cout, 9,
-                 {{n.P(mname(m.idx, "Conv_1.weight")), n.P(mname(m.idx, "Conv_1.bias")), 0, m.cout, 0}}, true, true);
+    r = add_conv(k + ".Conv_1", {.c0 = m.cout, .cout = m.cout,
+                                 .srcs = {{n.P(mname(m.idx, "Conv_1.weight")), n.P(mname(m.idx, "Conv_1.bias")), 0, m.cout, 0}},
+                                 .normed = true});
     if (r) return r;
     if (m.cin != m.cout || !plain) {      // shortcut: NIN_0 (W [in, out]) / NCSN++ Conv_2 (1x1, OIHW)
-      r = pp ? add_conv(k + ".Conv_2", c0, c1, m.cout, 1, {{n.P(mname(m.idx, "Conv_2.weight")), n.P(mname(m.idx, "Conv_2.bias")), 0, m.cout, 0}})
-             : add_conv(k + ".NIN_0", c0, c1, m.cout, 1, {{n.P(mname(m.idx, "NIN_0.W")), n.P(mname(m.idx, "NIN_0.b")), 1, m.cout, 0}});
+      r = pp ? add_conv(k + ".Conv_2", {.c0 = c0, .c1 = c1, .cout = m.cout, .taps = 1,
+                                        .srcs = {{n.P(mname(m.idx, "Conv_2.weight")), n.P(mname(m.idx, "Conv_2.bias")), 0, m.cout, 0}}})
+             : add_conv(k + ".NIN_0", {.c0 = c0, .c1 = c1, .cout = m.cout, .taps = 1,
+                                       .srcs = {{n.P(mname(m.idx, "NIN_0.W")), n.P(mname(m.idx, "NIN_0.b")), 1, m.cout, 0}}});
       if (r) return r;
     }
     if (c.conditional) {
@@ -169,21 +184,21 @@ static int build_packed_layout(Net& n) {
     const int C = m.cin;
     add_copy(mname(m.idx, "GroupNorm_0.weight"));
     add_copy(mname(m.idx, "GroupNorm_0.bias"));
-    int r = add_conv(k + ".qkv", C, 0, 3 * C, 1,
-                     {{n.P(mname(m.idx, "NIN_0.W")), n.P(mname(m.idx, "NIN_0.b")), 1, C, 0},
-                      {n.P(mname(m.idx, "NIN_1.W")), n.P(mname(m.idx, "NIN_1.b")), 1, C, C},
-                      {n.P(mname(m.idx, "NIN_2.W")), n.P(mname(m.idx, "NIN_2.b")), 1, C, 2 * C}});
+    int r = add_conv(k + ".qkv", {.c0 = C, .cout = 3 * C, .taps = 1,
+                                  .srcs = {{n.P(mname(m.idx, "NIN_0.W")), n.P(mname(m.idx, "NIN_0.b")), 1, C, 0},
+                                           {n.P(mname(m.idx, "NIN_1.W")), n.P(mname(m.idx, "NIN_1.b")), 1, C, C},
+                                           {n.P(mname(m.idx, "NIN_2.W")), n.P(mname(m.idx, "NIN_2.b")), 1, C, 2 * C}}});
     if (r) return r;
-    return add_conv(k + ".NIN_3", C, 0, C, 1,
-                    {{n.P(mname(m.idx, "NIN_3.W")), n.P(mname(m.idx, "NIN_3.b")), 1, C, 0}});
+    return add_conv(k + ".NIN_3", {.c0 = C, .cout = C, .taps = 1,
+                                   .srcs = {{n.P(mname(m.idx, "NIN_3.W")), n.P(mname(m.idx, "NIN_3.b")), 1, C, 0}}});
   };
   auto resample_layout = [&](Module& m) -> int {
     if (!c.resamp_with_conv) return CSD_OK;
-    return add_conv(std::to_string(m.idx) + ".Conv_0", m.cin, 0, m.cin, 9,
-                    {{n.P(mname(m.idx, "Conv_0.weight")), n.P(mname(m.idx, "Conv_0.bias")), 0, m.cin, 0}},
-                    /*stride1=*/true,    // (the fp16 kernel also covers the stride-2 Downsample)
-                    /*quad-eligible=*/true, /*resample=*/true,    // plain fp16 split of the source tensor + quad schedule (x2 addressing / stride 2)
-                    /*upsample=*/m.kind == M_UP);
+    // quad-eligible: plain fp16 split of the source tensor + quad schedule (x2 addressing / stride 2: the fp16 kernels also cover the
+    // stride-2 Downsample)
+    return add_conv(std::to_string(m.idx) + ".Conv_0",
+                    {.c0 = m.cin, .cout = m.cin, .srcs = {{n.P(mname(m.idx, "Conv_0.weight")), n.P(mname(m.idx, "Conv_0.bias")), 0, m.cin, 0}},
+                     .normed = true, .resample = true, .upsample = m.kind == M_UP});
   };
   for (Module& m : n.mods) {
     cur_res = (m.up || m.down) ? m.out_side : m.side;      // (a BigGAN up / down block convolves the resampled map)
@@ -199,7 +214,7 @@ static int build_packed_layout(Net& n) {
         break;
       case R_STEM:      // Cin padded to in_cpad (zero weights for the padding channels)
         if (!stem_layout(m))
-          rc = add_conv(k, n.in_cpad, 0, m.cout, 9, {{n.P(mname(m.idx, "weight")), n.P(mname(m.idx, "bias")), 0, m.cout, 0, m.cin}});
+          rc = add_conv(k, {.c0 = n.in_cpad, .cout = m.cout, .srcs = {{n.P(mname(m.idx, "weight")), n.P(mname(m.idx, "bias")), 0, m.cout, 0, m.cin}}});
         break;
       case R_DOWN_BLOCK: case R_MID_RES_IN: case R_MID_RES_OUT: case R_UP_BLOCK:
         rc = res_layout(m, m.cin - m.skip, m.skip);
@@ -211,8 +226,8 @@ static int build_packed_layout(Net& n) {
         rc = m.kind == M_RES ? res_layout(m, m.cin, 0) : resample_layout(m);
         break;
       case R_COMBINE:      // 1x1 conv of the (in_cpad-channel padded) input pyramid
-        rc = add_conv(k + ".Conv_0", n.in_cpad, 0, m.cout, 1,
-                      {{n.P(mname(m.idx, "Conv_0.weight")), n.P(mname(m.idx, "Conv_0.bias")), 0, m.cout, 0, m.cin}});
+        rc = add_conv(k + ".Conv_0", {.c0 = n.in_cpad, .cout = m.cout, .taps = 1,
+                                      .srcs = {{n.P(mname(m.idx, "Conv_0.weight")), n.P(mname(m.idx, "Conv_0.bias")), 0, m.cout, 0, m.cin}}});
         break;
       case R_PYR_DOWN:     // the FIR-folded 6x6 stride-2 weight (pack_all folds it) + the raw bias
         n.pyr_fold_off[m.idx] = take((size_t)36 * m.cin * m.cout);
@@ -221,8 +236,8 @@ static int build_packed_layout(Net& n) {
       case R_PYR_CONV: case R_HEAD_CONV:
         // the network's last layer and the output pyramid's convs: a handful of couts each.  (The DDPM family's head is laid out as a conv
         // without a norm in front and leaves cin_src to its default: where the tap-partial form does not apply, that selects its kernel)
-        rc = add_conv(k, m.cin, 0, m.cout, 9, {{n.P(mname(m.idx, "weight")), n.P(mname(m.idx, "bias")), 0, m.cout, 0, pp ? m.cin : 0}}, true,
-                      /*normed=*/pp, false, false, /*last=*/true);
+        rc = add_conv(k, {.c0 = m.cin, .cout = m.cout, .srcs = {{n.P(mname(m.idx, "weight")), n.P(mname(m.idx, "bias")), 0, m.cout, 0, pp ? m.cin : 0}},
+                          .normed = pp, .last = true});
         break;
     }
     if (rc) return rc;
@@ -286,19 +301,18 @@ static int pack_all(Net& n, float* pk, hipStream_t s) {
       const int cin_src = src.cin_src > 0 ? src.cin_src : pc.proto.C0 + pc.proto.C1;
       ConvPlan one = pc.proto;
       one.C0 = pc.proto.C0 + pc.proto.C1; one.C1 = 0;
-      rc = pc.stem ? stem_pack_weight(n.params[src.param_w].ptr, cin_src, pc.proto.Cout, pc.ns, pk + pc.w_off, s)
-         : pc.ff ? convff_pack_weight(pc.proto, pc.ns, n.params[src.param_w].ptr, src.layout, cin_src, src.cout_src,
-                                      src.cout_off, pk + pc.w_off, s)
-         : pc.up4 ? conv16q_pack_weight_up4(one, pc.ns, n.params[src.param_w].ptr, pk + pc.w_off, s)
-         : pc.q ? conv16q_pack_weight(one, pc.ns, n.params[src.param_w].ptr, src.layout, cin_src, src.cout_src,
-                                      src.cout_off, pk + pc.w_off, s)
-         : pc.tap_cout ? pw16_pack_weight_taps(pc.proto, pc.ns, n.params[src.param_w].ptr, pc.tap_cout, pk + pc.w_off, s)
-         : pc.pw ? pw16_pack_weight(pc.proto, pc.ns, n.params[src.param_w].ptr, src.layout, cin_src, src.cout_src,
-                                    src.cout_off, pk + pc.w_off, s)
-         : pc.ns ? conv16_pack_weight(pc.proto, pc.ns, n.params[src.param_w].ptr, src.layout, cin_src, src.cout_src,
-                                      src.cout_off, pk + pc.w_off, s)
-                 : conv_pack_weight(pc.proto, n.params[src.param_w].ptr, src.layout, cin_src, src.cout_src,
-                                    src.cout_off, pk + pc.w_off, s);
+      const float* w = n.params[src.param_w].ptr;
+      float* dst = pk + pc.w_off;
+      switch (pc.kernel) {
+        case ConvKernel::STEM: rc = stem_pack_weight(w, cin_src, pc.proto.Cout, pc.ns, dst, s); break;
+        case ConvKernel::FUSED: rc = convff_pack_weight(pc.proto, pc.ns, w, src.layout, cin_src, src.cout_src, src.cout_off, dst, s); break;
+        case ConvKernel::QUAD_UP4: rc = conv16q_pack_weight_up4(one, pc.ns, w, dst, s); break;
+        case ConvKernel::QUAD: rc = conv16q_pack_weight(one, pc.ns, w, src.layout, cin_src, src.cout_src, src.cout_off, dst, s); break;
+        case ConvKernel::PW16_TAPS: rc = pw16_pack_weight_taps(pc.proto, pc.ns, w, pc.tap_cout, dst, s); break;
+        case ConvKernel::PW16: rc = pw16_pack_weight(pc.proto, pc.ns, w, src.layout, cin_src, src.cout_src, src.cout_off, dst, s); break;
+        case ConvKernel::F16_LC: rc = conv16_pack_weight(pc.proto, pc.ns, w, src.layout, cin_src, src.cout_src, src.cout_off, dst, s); break;
+        case ConvKernel::F32: rc = conv_pack_weight(pc.proto, w, src.layout, cin_src, src.cout_src, src.cout_off, dst, s); break;
+      }
       if (rc) return rc;
       batch.add(n.params[src.param_b].ptr, pk + pc.b_off + src.cout_off, (size_t)src.cout_src);      // (behind the fill above: same stream)
     }

@@ -45,12 +45,12 @@ struct Builder {
       Op s;
       s.kind = OP_GN_STATS;
       if (gn_plan(&s.gp, B, hw, cs, 0, 1)) { rc = CSD_ERR_INVALID; return; }
-      s.a = src; s.b = NONE; s.i0 = 1;      // per-channel partials
-      s.out = alloc_((size_t)B * s.gp.nchunk * cs * 2 * 2);      // doubles; never released (small)
+      s.src0 = src; s.per_channel = true;
+      s.stats = alloc_((size_t)B * s.gp.nchunk * cs * 2 * 2);      // doubles; never released (small)
       s.cls = CSD_PROF_GN_STATS; s.bytes = (double)B * hw * cs * 4;
       pl.ops.push_back(s);
       pl.launches += 1;
-      tile_stats[src] = TileStats{s.out, s.gp.nchunk};
+      tile_stats[src] = TileStats{s.stats, s.gp.nchunk};
     }
     const auto t0 = tile_stats.find(src0);
     const auto t1 = src1 == NONE ? tile_stats.end() : tile_stats.find(src1);
@@ -58,12 +58,12 @@ struct Builder {
       // both sources were written by convs that accumulated the statistics in their epilogue: no pass over the tensor
       Op f;
       f.kind = OP_GN_FINAL_TILES;
-      f.a = t0->second.off; f.i0 = t0->second.tpi; f.i1 = c0;
-      f.b = src1 == NONE ? NONE : t1->second.off; f.i2 = src1 == NONE ? 0 : t1->second.tpi; f.i3 = c1;
-      f.i4 = hw;
+      f.stats = t0->second.off; f.tiles0 = t0->second.tpi; f.C0 = c0;
+      f.stats1 = src1 == NONE ? NONE : t1->second.off; f.tiles1 = src1 == NONE ? 0 : t1->second.tpi; f.C1 = c1;
+      f.hw = hw;
       f.gp.G = G;
-      f.pk0 = n.copy_off.at(gname); f.pk1 = n.copy_off.at(bname);
-      f.out = nscale; f.c = nshift;
+      f.pk_w = n.copy_off.at(gname); f.pk_b = n.copy_off.at(bname);
+      f.nscale = nscale; f.nshift = nshift;
       f.cls = CSD_PROF_GN_FINAL;
       pl.ops.push_back(f);
       pl.launches += 1;
@@ -73,164 +73,198 @@ struct Builder {
     Op s;
     s.kind = OP_GN_STATS;
     if (gn_plan(&s.gp, B, hw, c0, c1, G)) { rc = CSD_ERR_INVALID; return; }
-    s.a = src0; s.b = src1; s.out = gn_partial;
+    s.src0 = src0; s.src1 = src1; s.stats = gn_partial;
     s.cls = CSD_PROF_GN_STATS; s.bytes = (double)B * hw * (c0 + c1) * 4;
     pl.ops.push_back(s);
     Op f;
     f.kind = OP_GN_FINAL;
     f.gp = s.gp;
-    f.a = gn_partial; f.pk0 = n.copy_off.at(gname); f.pk1 = n.copy_off.at(bname);
-    f.out = nscale; f.b = nshift;
+    f.stats = gn_partial; f.pk_w = n.copy_off.at(gname); f.pk_b = n.copy_off.at(bname);
+    f.nscale = nscale; f.nshift = nshift;
     f.cls = CSD_PROF_GN_FINAL;
     pl.ops.push_back(f);
     pl.launches += 2;
     pl.bytes += 2.0 * B * hw * (c0 + c1) * 4;   // GroupNorm reads + writes its tensor
   }
 
-  // convolution; returns output offset (allocated here unless external)
-  size_t conv(const std::string& key, size_t src0, size_t src1, int ih, int iw, int stride, int pad, int up,
-              bool norm, int act, size_t res, size_t temb_col, bool external_nchw, int real_cin = -1) {
-    const PackedConv& pc = n.pconvs[n.pconv_by_name.at(key)];
-    if (pc.tap_cout) {
-      // tap-partial form (conv_pw16.hip): pointwise contraction of act(GN(x)) to 9 * cout partial channels, then the 9-tap gather
-      if (!norm || src1 != NONE || stride != 1 || up || pad != 1 || temb_col != NONE) {
-        set_error("tap-partial conv on an unsupported layer"); rc = CSD_ERR_INVALID; return NONE;
-      }
-      if (act != CSD_ACT_SWISH) {      // (pw16_kernel's prologue knows SiLU only: build_packed_layout keeps every other head off this form)
-        set_error("tap-partial conv: activation %d is not supported (SiLU only)", act); rc = CSD_ERR_INVALID; return NONE;
-      }
-      Op o;
-      o.kind = OP_CONV;
-      o.cp = pc.proto;
-      o.cp.B = B; o.cp.IH = o.cp.OH = ih; o.cp.IW = o.cp.OW = iw;
-      o.cp.stride = 1; o.cp.pad = 0; o.cp.up = 0;
-      o.i4 = pc.ns; o.i2 = 1;
-      o.a = src0; o.b = NONE; o.pk0 = pc.w_off; o.pk1 = NONE;          // (the bias joins in the gather)
-      o.d = nscale; o.e = nshift;
-      o.act = act;
-      o.temb_base = dense_all; o.temb_stride = n.dense_total;
-      const size_t part = alloc_((size_t)B * ih * iw * o.cp.Cout);
-      o.out = part;
-      o.cls = CSD_PROF_CONV1X1;                  // (profiler classes follow the kernels: a pointwise contraction + a small gather)
-      pl.ops.push_back(o);
-      const size_t out_elems = (size_t)B * ih * iw * pc.tap_cout;
-      count(2.0 * out_elems * o.cp.C0 * 9, ((double)B * ih * iw * o.cp.C0 + (double)out_elems) * 4);
-      pl.ops.back().bytes = (double)B * ih * iw * (o.cp.C0 + o.cp.Cout) * 4.0;
-      Op g;
-      g.kind = OP_TAPSUM;
-      g.a = part; g.pk1 = pc.b_off; g.c = res;
-      g.i0 = ih; g.i1 = iw; g.i2 = pc.tap_cout;
-      g.fscale = pending_scale;
-      pending_scale = 1.f;
-      g.out_external = external_nchw ? 1 : 0;
-      g.out = external_nchw ? NONE : alloc_(out_elems);
-      g.cls = CSD_PROF_OTHER;
-      g.bytes = (double)B * ih * iw * (o.cp.Cout + pc.tap_cout) * 4.0;
-      pl.ops.push_back(g);
-      pl.launches += 1;
-      ar.release(part);
-      return g.out;
+  // the arguments of conv() beside the layer's key
+  struct ConvIn {
+    size_t src0 = NONE, src1 = NONE;      // sources (src1: the second of a virtual concat)
+    int ih = 0, iw = 0;                   // extent of the source map
+    int stride = 1, pad = 0, up = 0;
+    bool norm = false;                    // reads act(GroupNorm(sources)): scale / shift are the ones gn() has just planned
+    int act = CSD_ACT_NONE;
+    size_t residual = NONE;               // added by the epilogue
+    size_t temb_col = NONE;               // first column of the block's Dense_0 rows inside dense_all
+    bool external_nchw = false;           // writes the caller's NCHW output
+    int real_cin = -1;                    // input channels the flop count takes (a zero-padded input)
+  };
+
+  int fail(const char* what) { set_error("%s", what); rc = CSD_ERR_INVALID; return rc; }
+
+  // tap-partial form (conv_pw16.hip): pointwise contraction of act(GN(x)) to 9 * cout partial channels, then the 9-tap gather
+  size_t conv_taps(const PackedConv& pc, const ConvIn& in) {
+    const int ih = in.ih, iw = in.iw;
+    if (!in.norm || in.src1 != NONE || in.stride != 1 || in.up || in.pad != 1 || in.temb_col != NONE) {
+      fail("tap-partial conv on an unsupported layer"); return NONE;
+    }
+    if (in.act != CSD_ACT_SWISH) {      // (pw16_kernel's prologue knows SiLU only: build_packed_layout keeps every other head off this form)
+      set_error("tap-partial conv: activation %d is not supported (SiLU only)", in.act); rc = CSD_ERR_INVALID; return NONE;
     }
     Op o;
     o.kind = OP_CONV;
     o.cp = pc.proto;
+    o.cp.B = B; o.cp.IH = o.cp.OH = ih; o.cp.IW = o.cp.OW = iw;
+    o.cp.stride = 1; o.cp.pad = 0; o.cp.up = 0;
+    o.ns = pc.ns; o.kernel = pc.kernel;
+    o.src0 = in.src0; o.pk_w = pc.w_off;          // (the bias joins in the gather)
+    o.nscale = nscale; o.nshift = nshift;
+    o.act = in.act;
+    o.temb_base = dense_all; o.temb_stride = n.dense_total;
+    const size_t part = alloc_((size_t)B * ih * iw * o.cp.Cout);
+    o.out = part;
+    o.cls = CSD_PROF_CONV1X1;                  // (profiler classes follow the kernels: a pointwise contraction + a small gather)
+    pl.ops.push_back(o);
+    const size_t out_elems = (size_t)B * ih * iw * pc.tap_cout;
+    count(2.0 * out_elems * o.cp.C0 * 9, ((double)B * ih * iw * o.cp.C0 + (double)out_elems) * 4);
+    pl.ops.back().bytes = (double)B * ih * iw * (o.cp.C0 + o.cp.Cout) * 4.0;
+    Op g;
+    g.kind = OP_TAPSUM;
+    g.src0 = part; g.pk_b = pc.b_off; g.res = in.residual;
+    g.H = ih; g.W = iw; g.Cout = pc.tap_cout;
+    g.out_scale = pending_scale;
+    pending_scale = 1.f;
+    g.out_external = in.external_nchw ? 1 : 0;
+    g.out = in.external_nchw ? NONE : alloc_(out_elems);
+    g.cls = CSD_PROF_OTHER;
+    g.bytes = (double)B * ih * iw * (o.cp.Cout + pc.tap_cout) * 4.0;
+    pl.ops.push_back(g);
+    pl.launches += 1;
+    ar.release(part);
+    return g.out;
+  }
+
+  // convolution; returns output offset (allocated here unless external)
+  size_t conv(const std::string& key, const ConvIn& in) {
+    const PackedConv& pc = n.pconvs[n.pconv_by_name.at(key)];
+    if (pc.kernel == ConvKernel::PW16_TAPS) return conv_taps(pc, in);
+    const int ih = in.ih, iw = in.iw, stride = in.stride, up = in.up;
+    const bool norm = in.norm, external_nchw = in.external_nchw, quad = is_quad(pc.kernel);
+    Op o;
+    o.kind = OP_CONV;
+    o.cp = pc.proto;
     o.cp.B = B; o.cp.IH = ih; o.cp.IW = iw;
-    o.cp.stride = stride; o.cp.pad = pad; o.cp.up = up;
+    o.cp.stride = stride; o.cp.pad = in.pad; o.cp.up = up;
     o.cp.OH = (ih << up) / stride; o.cp.OW = (iw << up) / stride;
-    o.i4 = pc.ns;
-    o.i2 = pc.ff ? 3 : (pc.pw ? 1 : (pc.q ? 2 : 0));
-    const int kcs = (pc.ns && !pc.pw && norm) ? conv16_kcs(pc.ns, o.cp.C0 + o.cp.C1) : 1;    // fp16-source convs stage in bursts
-    bool fused = false;     // GroupNorm affine + activation applied by the conv's loader wave (no gn_apply16 pass)
-    if (pc.ns && !pc.pw && !pc.q && norm && stride == 1 && !up && o.cp.C0 % 32 == 0 && o.cp.C1 % 32 == 0 &&
-        !CSD_TUNE_ENV("CSD_NO_LC") && CSD_TUNE_ENV("CSD_FUSED_NORM")) {
+    o.ns = pc.ns; o.kernel = pc.kernel;
+    // tuning only (CSD_FUSED_NORM): GroupNorm affine + activation applied by the loader / consumer kernel's loader wave (no gn_apply16
+    // pass).  (The switch also reaches a layer packed for ConvKernel::FUSED, as it always has: an experiment, not a product path)
+    bool fused = false;
+    if ((pc.kernel == ConvKernel::F16_LC || pc.kernel == ConvKernel::FUSED) && norm && stride == 1 && !up && o.cp.C0 % 32 == 0 &&
+        o.cp.C1 % 32 == 0 && !CSD_TUNE_ENV("CSD_NO_LC") && CSD_TUNE_ENV("CSD_FUSED_NORM")) {
       ConvPlan trial = o.cp;
       if (conv16_plan_tiles(&trial, pc.ns, 2, true) == CSD_OK && trial.LC && trial.OH % trial.TH == 0) {
         fused = true;
         o.cp = trial;
       }
     }
-    if (fused) {
-    } else if (pc.ff) {
-      if (external_nchw || stride != 1 || up) { set_error("fused-prologue conv on an unsupported layer"); rc = CSD_ERR_INVALID; return NONE; }
-      if (convff_plan_tiles(&o.cp, pc.ns)) { rc = CSD_ERR_INVALID; return NONE; }
-    } else if (pc.q) {
-      if (external_nchw || (!norm && o.cp.C1 != 0) || (stride == 2 && (norm || up))) { set_error("quad fp16 conv on an unsupported layer"); rc = CSD_ERR_INVALID; return NONE; }
-      o.cp.C0 = o.cp.C0 + o.cp.C1; o.cp.C1 = 0;
-      if (pc.up4) {
-        if (!up || stride != 1) { set_error("phase-decomposed Upsample packed for a layer that is not one"); rc = CSD_ERR_INVALID; return NONE; }
-        o.cp.up = 2;
+    if (!fused) switch (pc.kernel) {
+      case ConvKernel::FUSED:
+        if (external_nchw || stride != 1 || up) { fail("fused-prologue conv on an unsupported layer"); return NONE; }
+        if (convff_plan_tiles(&o.cp, pc.ns)) { rc = CSD_ERR_INVALID; return NONE; }
+        break;
+      case ConvKernel::QUAD: case ConvKernel::QUAD_UP4:
+        if (external_nchw || (!norm && o.cp.C1 != 0) || (stride == 2 && (norm || up))) { fail("quad fp16 conv on an unsupported layer"); return NONE; }
+        o.cp.C0 = o.cp.C0 + o.cp.C1; o.cp.C1 = 0;
+        if (pc.kernel == ConvKernel::QUAD_UP4) {
+          if (!up || stride != 1) { fail("phase-decomposed Upsample packed for a layer that is not one"); return NONE; }
+          o.cp.up = 2;
+        }
+        if (conv16q_plan_tiles(&o.cp, pc.ns)) { rc = CSD_ERR_INVALID; return NONE; }
+        break;
+      case ConvKernel::PW16:
+        if (in.act != CSD_ACT_NONE || in.temb_col != NONE || external_nchw) { fail("pointwise fp16 layer with act/temb/NCHW"); return NONE; }
+        break;
+      case ConvKernel::F16_LC: {
+        const int kcs = norm ? conv16_kcs(pc.ns, o.cp.C0 + o.cp.C1) : 1;    // fp16-source convs stage in bursts
+        // (x_squeeze: the head's scattered NCHW store lives in conv_f16_kernel.h / conv_f32.hip; the loader / consumer schedule keeps its code)
+        if (conv16_plan_tiles(&o.cp, pc.ns, kcs, kcs > 1 && !CSD_TUNE_ENV("CSD_NO_LC") && !(external_nchw && n.cfg.x_squeeze))) {
+          rc = CSD_ERR_INVALID; return NONE;
+        }
+        break;
       }
-      if (conv16q_plan_tiles(&o.cp, pc.ns)) { rc = CSD_ERR_INVALID; return NONE; }
-    } else if (pc.pw) {
-      if (act != CSD_ACT_NONE || temb_col != NONE || external_nchw) { set_error("pointwise fp16 layer with act/temb/NCHW"); rc = CSD_ERR_INVALID; return NONE; }
-    // (x_squeeze: the head's scattered NCHW store lives in conv_f16_kernel.h / conv_f32.hip; the loader / consumer schedule keeps its code)
-    } else if (pc.ns ? conv16_plan_tiles(&o.cp, pc.ns, kcs, kcs > 1 && !CSD_TUNE_ENV("CSD_NO_LC") && !(external_nchw && n.cfg.x_squeeze))
-                     : conv_plan_tiles(&o.cp)) { rc = CSD_ERR_INVALID; return NONE; }
+      case ConvKernel::F32:
+        if (conv_plan_tiles(&o.cp)) { rc = CSD_ERR_INVALID; return NONE; }
+        break;
+      case ConvKernel::PW16_TAPS: case ConvKernel::STEM:      // (conv_taps above / Builder::stem)
+        fail("conv: a layer packed for another builder"); return NONE;
+    }
     // the packed layout depends on KC only (not on NT / tile shape)
-    if (o.cp.KC != pc.proto.KC) { set_error("conv plan/pack mismatch"); rc = CSD_ERR_INVALID; return NONE; }
-    o.a = src0; o.b = src1; o.pk0 = pc.w_off; o.pk1 = pc.b_off;
-    o.c = res;
-    o.d = norm ? nscale : NONE;
-    o.e = norm ? nshift : NONE;
+    if (o.cp.KC != pc.proto.KC) { fail("conv plan/pack mismatch"); return NONE; }
+    o.src0 = in.src0; o.src1 = in.src1; o.pk_w = pc.w_off; o.pk_b = pc.b_off;
+    o.res = in.residual;
+    o.nscale = norm ? nscale : NONE;
+    o.nshift = norm ? nshift : NONE;
     size_t hi16 = NONE, lo16 = NONE;
     // a quad-schedule conv WITHOUT a GroupNorm in front (Downsample / Upsample, the FIR-resampled Conv_0 of NCSN++) in the full split reads
     // its fp32 source directly: the split happens in the kernel's staging burst (no plane write / read)
-    const bool q_raw = pc.q && !norm && pc.ns == 2 && o.cp.C1 == 0 && (o.cp.NT == 3 || o.cp.NT == 4) && !CSD_TUNE_ENV("CSD_NO_Q_RAW");
+    const bool q_raw = quad && !norm && pc.ns == 2 && o.cp.C1 == 0 && (o.cp.NT == 3 || o.cp.NT == 4) && !CSD_TUNE_ENV("CSD_NO_Q_RAW");
     if (q_raw) {
-      o.i3 = 2;
-    } else if (pc.ns && !pc.pw && !pc.ff && (norm || pc.q) && !fused) {
+      o.src_form = ConvSrc::SPLIT_STAGING;
+    } else if (((pc.kernel == ConvKernel::F16_LC && norm) || quad) && !fused) {
       // fp16 kernel: normalise + activate + split ONCE per element into fp16 planes, conv copies them
       // (a quad-schedule conv without a GroupNorm - Upsample, the FIR-resampled Conv_0 of NCSN++ - gets a plain split)
       const size_t nh = ((size_t)B * ih * iw * (o.cp.C0 + o.cp.C1) + 1) / 2;      // halves -> floats
       Op ap;
       ap.kind = OP_GN_APPLY16;
-      ap.a = src0; ap.b = src1; ap.i0 = pc.proto.C0; ap.i1 = pc.proto.C1; ap.i2 = ih * iw;
-      ap.d = norm ? nscale : NONE; ap.e = norm ? nshift : NONE; ap.act = norm ? act : (int)CSD_ACT_NONE;
+      ap.src0 = in.src0; ap.src1 = in.src1; ap.C0 = pc.proto.C0; ap.C1 = pc.proto.C1; ap.hw = ih * iw;
+      ap.nscale = norm ? nscale : NONE; ap.nshift = norm ? nshift : NONE; ap.act = norm ? in.act : (int)CSD_ACT_NONE;
       hi16 = alloc_(nh);
       if (pc.ns >= 2) lo16 = alloc_(nh);
-      ap.out = hi16; ap.c = lo16;
+      ap.out = hi16; ap.out2 = lo16;
       // small maps: the GroupNorm's statistics + finalize launches (the two ops gn() has just pushed) and this pass become ONE launch
       const size_t nops = pl.ops.size();
       if (norm && nops >= 2 && pl.ops[nops - 2].kind == OP_GN_STATS && pl.ops[nops - 1].kind == OP_GN_FINAL &&
-          pl.ops[nops - 2].a == src0 && pl.ops[nops - 2].b == src1 && !CSD_TUNE_ENV("CSD_NO_GN_FUSED") &&
+          pl.ops[nops - 2].src0 == in.src0 && pl.ops[nops - 2].src1 == in.src1 && !CSD_TUNE_ENV("CSD_NO_GN_FUSED") &&
           gn_fused16_groups(ih * iw, pc.proto.C0, pc.proto.C1, pl.ops[nops - 2].gp.G) > 0) {
         ap.kind = OP_GN_FUSED16;
         ap.gp = pl.ops[nops - 2].gp;
-        ap.pk0 = pl.ops[nops - 1].pk0; ap.pk1 = pl.ops[nops - 1].pk1;      // gamma, beta
-        ap.d = NONE; ap.e = NONE;
+        ap.pk_w = pl.ops[nops - 1].pk_w; ap.pk_b = pl.ops[nops - 1].pk_b;      // gamma, beta
+        ap.nscale = NONE; ap.nshift = NONE;
         pl.ops.pop_back();
         pl.ops.pop_back();
         pl.launches -= 2;
       }
       ap.cls = CSD_PROF_GN_APPLY;
       ap.bytes = (double)B * ih * iw * (o.cp.C0 + o.cp.C1) * (4 + 2 * (pc.ns >= 2 ? 2 : 1));
-      ap.i3 = pc.ns == 3;                       // second plane = e4m3 byte pairs
+      ap.fp8_lo = pc.ns == 3;
       pl.ops.push_back(ap);
       pl.launches += 1;
-      o.a = hi16; o.b = lo16;
+      o.src0 = hi16; o.src1 = lo16;
       o.cp.C0 = o.cp.C0 + o.cp.C1; o.cp.C1 = 0;
-      o.d = NONE; o.e = NONE;
-      o.i3 = 1;                                   // in16
+      o.nscale = NONE; o.nshift = NONE;
+      o.src_form = ConvSrc::PLANES16;
     }
     o.temb_base = dense_all;
-    o.fscale = pending_scale;
+    o.out_scale = pending_scale;
     pending_scale = 1.f;
-    o.act = act;
-    o.temb_col = temb_col;
+    o.act = in.act;
+    o.temb_col = in.temb_col;
     o.temb_stride = n.dense_total;
     o.out_external = external_nchw ? 1 : 0;
     const size_t out_elems = (size_t)B * o.cp.OH * o.cp.OW * o.cp.Cout;
     o.out = external_nchw ? NONE : (next_out != NONE ? next_out : alloc_(out_elems));
     next_out = NONE;
     const int oh_tiled = o.cp.up == 2 ? o.cp.IH : o.cp.OH;         // (the phase form tiles the SOURCE image, four workgroups per tile)
-    // (pc.ff: the fused-prologue kernels tile every sample on its own - ragged tiles, where they run at all, mask their statistics)
-    if (!pc.pw && !external_nchw && o.cp.taps == 9 && (pc.ff || oh_tiled % o.cp.TH == 0) && !CSD_TUNE_ENV("CSD_NO_FUSED_STATS") &&
-        (o.cp.up != 2 || (conv16q_up4_stats_ok(o.cp) && !CSD_TUNE_ENV("CSD_NO_UP4_STATS")))) {
+    // (ConvKernel::FUSED: the fused-prologue kernels tile every sample on its own - ragged tiles, where they run at all, mask their statistics)
+    if (pc.kernel != ConvKernel::PW16 && !external_nchw && o.cp.taps == 9 && (pc.kernel == ConvKernel::FUSED || oh_tiled % o.cp.TH == 0) &&
+        !CSD_TUNE_ENV("CSD_NO_FUSED_STATS") && (o.cp.up != 2 || (conv16q_up4_stats_ok(o.cp) && !CSD_TUNE_ENV("CSD_NO_UP4_STATS")))) {
       // (phase-decomposed Upsample: fp32 partials per (tile, M half, phase) - in fp64 they cost the kernel more than the streaming pass
       // over its output that they replace - and only where its tile shape does not depend on the batch: conv16q_plan_tiles)
       // every tile lies inside one sample: the epilogue also leaves (sum, sumsq) per (tile, cout) for the next
-      // GroupNorm (the fp32 kernel: per (tile, wave, cout))
-      const int tpi = cdiv(oh_tiled, o.cp.TH) * o.cp.tiles_x * (pc.q ? 2 : (pc.ns ? 1 : 4)) * (o.cp.up == 2 ? 4 : 1);
+      // GroupNorm (the quad kernel: per (tile, M half, cout); the fp32 kernel: per (tile, wave, cout))
+      const int per_tile = quad ? 2 : (pc.kernel == ConvKernel::F32 ? 4 : 1);
+      const int tpi = cdiv(oh_tiled, o.cp.TH) * o.cp.tiles_x * per_tile * (o.cp.up == 2 ? 4 : 1);
       o.stats = alloc_((size_t)B * tpi * o.cp.Cout * 2 * 2);      // doubles; never released (small)
       tile_stats[o.out] = TileStats{o.stats, tpi};
     }
@@ -238,13 +272,13 @@ struct Builder {
     pl.ops.push_back(o);
     ar.release(hi16);      // (plan-time lifetimes: the planes die right after this conv)
     ar.release(lo16);
-    const int cin = real_cin > 0 ? real_cin : (o.cp.C0 + o.cp.C1);
+    const int cin = in.real_cin > 0 ? in.real_cin : (o.cp.C0 + o.cp.C1);
     count(2.0 * out_elems * cin * o.cp.taps, ((double)B * ih * iw * cin + (double)out_elems) * 4);
     // the profiler's per-launch bytes are what THIS kernel has to move (fp16 planes in, fp32 out, residual in);
     // the plan totals above stay the SURVEY 8(d) algorithmic figures
     pl.ops.back().abytes = pl.ops.back().bytes;
-    pl.ops.back().bytes = (double)B * ih * iw * (o.cp.C0 + o.cp.C1) * (o.i3 ? 2.0 * pc.ns : 4.0) +
-                          (double)out_elems * 4 * (res != NONE ? 2 : 1);
+    pl.ops.back().bytes = (double)B * ih * iw * (o.cp.C0 + o.cp.C1) * (o.src_form != ConvSrc::F32 ? 2.0 * pc.ns : 4.0) +
+                          (double)out_elems * 4 * (in.residual != NONE ? 2 : 1);
     return o.out;
   }
 
@@ -253,15 +287,15 @@ struct Builder {
     const csd_unet_config& c = n.cfg;
     Op o;
     o.kind = OP_STEM;
-    o.pk0 = pc.w_off; o.pk1 = pc.b_off;
-    o.i0 = m.cout; o.i4 = pc.ns;
+    o.pk_w = pc.w_off; o.pk_b = pc.b_off;
+    o.Cout = m.cout; o.ns = pc.ns; o.kernel = pc.kernel;
     const size_t out_elems = (size_t)B * S * S * m.cout;
     o.out = alloc_(out_elems);
     const int tpi = stem_tiles_per_image(S);
     o.stats = alloc_((size_t)B * tpi * m.cout * 2 * 2);      // doubles; never released (small)
     tile_stats[o.out] = TileStats{o.stats, tpi};
     // y_scale: room for the perturbed low-resolution y + sigma z of a sampling step (never released: a few KB per sample)
-    if (c.y_scale) o.c = alloc_((size_t)B * c.y_channels * (S / c.y_scale) * (S / c.y_scale));
+    if (c.y_scale) o.out2 = alloc_((size_t)B * c.y_channels * (S / c.y_scale) * (S / c.y_scale));
     o.cls = CSD_PROF_CONV3X3;
     pl.ops.push_back(o);
     const int cin = c.x_channels + c.y_channels;
@@ -279,7 +313,7 @@ struct Builder {
     size_t shortcut = x0, sc_buf = NONE;
     if (m.cin != m.cout) {
       const size_t op0 = pl.ops.size();
-      sc_buf = conv(k + (n.cfg.arch == 1 ? ".Conv_2" : ".NIN_0"), x0, x1, hw_side, hw_side, 1, 0, 0, false, 0, NONE, NONE, false);
+      sc_buf = conv(k + (n.cfg.arch == 1 ? ".Conv_2" : ".NIN_0"), {.src0 = x0, .src1 = x1, .ih = hw_side, .iw = hw_side});
       shortcut = sc_buf;
       if (side_on)
         for (size_t i = op0; i < pl.ops.size(); ++i) pl.ops[i].side = 1;
@@ -289,11 +323,11 @@ struct Builder {
     }
     gn(x0, x1, c0, c1, hw, mname(m.idx, "GroupNorm_0.weight"), mname(m.idx, "GroupNorm_0.bias"));
     const size_t tcol = n.cfg.conditional ? (size_t)n.dense_col.at(m.idx) : NONE;
-    const size_t h1 = conv(k + ".Conv_0", x0, x1, hw_side, hw_side, 1, 1, 0, true, n.cfg.act, NONE, tcol, false);
+    const size_t h1 = conv(k + ".Conv_0", {.src0 = x0, .src1 = x1, .ih = hw_side, .iw = hw_side, .pad = 1, .norm = true, .act = n.cfg.act, .temb_col = tcol});
     gn(h1, NONE, m.cout, 0, hw, mname(m.idx, "GroupNorm_1.weight"), mname(m.idx, "GroupNorm_1.bias"));
     pending_scale = skip_scale();
     next_out = out_to;
-    const size_t out = conv(k + ".Conv_1", h1, NONE, hw_side, hw_side, 1, 1, 0, true, n.cfg.act, shortcut, NONE, false);
+    const size_t out = conv(k + ".Conv_1", {.src0 = h1, .ih = hw_side, .iw = hw_side, .pad = 1, .norm = true, .act = n.cfg.act, .residual = shortcut});
     if (side_on && sc_buf != NONE && rc == CSD_OK && out != NONE) pl.ops.back().side = 2;
     ar.release(h1);
     ar.release(sc_buf);
@@ -307,7 +341,7 @@ struct Builder {
   size_t fir(size_t src, int side, int C, bool up) {
     Op o;
     o.kind = OP_FIR;
-    o.a = src; o.i0 = side; o.i1 = C; o.i2 = up ? 1 : 0;
+    o.src0 = src; o.H = o.W = side; o.C0 = C; o.up = up;
     const int os = up ? side * 2 : side / 2;
     o.out = alloc_((size_t)B * os * os * C);
     o.cls = CSD_PROF_OTHER;
@@ -322,16 +356,16 @@ struct Builder {
     const csd_unet_config& c = n.cfg;
     Op o;
     o.kind = OP_PYRCONV;
-    o.a = src; o.c = h;
-    o.pk0 = n.pyr_fold_off.at(m.idx); o.pk1 = n.copy_off.at(mname(m.idx, pyr_sub(c, true)));
-    o.i0 = side; o.i1 = m.cin; o.i2 = m.cout; o.i3 = pix; o.i4 = c.progressive_input == 2 ? 1 : 0;
-    o.fscale = c.skip_rescale ? 0.70710678118654752440f : 1.f;
+    o.src0 = src; o.res = h;
+    o.pk_w = n.pyr_fold_off.at(m.idx); o.pk_b = n.copy_off.at(mname(m.idx, pyr_sub(c, true)));
+    o.H = o.W = side; o.C0 = m.cin; o.Cout = m.cout; o.pix = pix; o.fir = c.progressive_input == 2;
+    o.out_scale = c.skip_rescale ? 0.70710678118654752440f : 1.f;
     const size_t out_elems = (size_t)B * (side / 2) * (side / 2) * m.cout;
     o.out = alloc_(out_elems);
     o.cls = CSD_PROF_CONV3X3_RESAMPLE;
     pl.ops.push_back(o);
     // algorithmic flops: FIR + VALID stride-2 3x3 (fir) or the stride-2 3x3 (fir = False), as the reference computes them
-    count(2.0 * out_elems * m.cin * 9 + (o.i4 ? 2.0 * B * (side + 1) * (side + 1) * m.cin * 16 : 0.0),
+    count(2.0 * out_elems * m.cin * 9 + (o.fir ? 2.0 * B * (side + 1) * (side + 1) * m.cin * 16 : 0.0),
           ((double)B * side * side * m.cin + 2.0 * out_elems) * 4);
     return o.out;
   }
@@ -340,7 +374,7 @@ struct Builder {
   size_t gn_apply32(size_t src, int C, int hw, int act) {
     Op o;
     o.kind = OP_GN_APPLY32;
-    o.a = src; o.d = nscale; o.e = nshift; o.i0 = C; o.i1 = hw; o.act = act;
+    o.src0 = src; o.nscale = nscale; o.nshift = nshift; o.C0 = C; o.hw = hw; o.act = act;
     o.out = alloc_((size_t)B * hw * C);
     o.cls = CSD_PROF_GN_APPLY;
     o.bytes = (double)B * hw * C * 8;
@@ -359,14 +393,14 @@ struct Builder {
     if (m.cin % 4 == 0) {      // FIR(act(GroupNorm(x))) and FIR(x) in one pass over x (elementwise.hip: fir_resample2)
       Op o;
       o.kind = OP_FIR2;
-      o.a = x; o.d = nscale; o.e = nshift; o.i0 = side; o.i1 = m.cin; o.i2 = m.up ? 1 : 0; o.act = n.cfg.act;
+      o.src0 = x; o.nscale = nscale; o.nshift = nshift; o.H = o.W = side; o.C0 = m.cin; o.up = m.up != 0; o.act = n.cfg.act;
       o.out = alloc_((size_t)B * os * os * m.cin);       // FIR(h)
-      o.c = alloc_((size_t)B * os * os * m.cin);         // FIR(x)
+      o.out2 = alloc_((size_t)B * os * os * m.cin);      // FIR(x)
       o.cls = CSD_PROF_OTHER;
       o.bytes = (double)B * (hw + 2.0 * os * os) * m.cin * 4;
       pl.ops.push_back(o);
       pl.launches += 1;
-      hr = o.out; xr = o.c;
+      hr = o.out; xr = o.out2;
     } else {
       const size_t ha = gn_apply32(x, m.cin, hw, n.cfg.act);
       hr = fir(ha, side, m.cin, m.up != 0);
@@ -374,13 +408,13 @@ struct Builder {
       xr = fir(x, side, m.cin, m.up != 0);
     }
     const size_t tcol = (size_t)n.dense_col.at(m.idx);
-    const size_t h1 = conv(k + ".Conv_0", hr, NONE, os, os, 1, 1, 0, false, 0, NONE, tcol, false);
+    const size_t h1 = conv(k + ".Conv_0", {.src0 = hr, .ih = os, .iw = os, .pad = 1, .temb_col = tcol});
     ar.release(hr);
     gn(h1, NONE, m.cout, 0, os * os, mname(m.idx, "GroupNorm_1.weight"), mname(m.idx, "GroupNorm_1.bias"));
-    const size_t sc = conv(k + ".Conv_2", xr, NONE, os, os, 1, 0, 0, false, 0, NONE, NONE, false);
+    const size_t sc = conv(k + ".Conv_2", {.src0 = xr, .ih = os, .iw = os});
     ar.release(xr);
     pending_scale = skip_scale();
-    const size_t out = conv(k + ".Conv_1", h1, NONE, os, os, 1, 1, 0, true, n.cfg.act, sc, NONE, false);
+    const size_t out = conv(k + ".Conv_1", {.src0 = h1, .ih = os, .iw = os, .pad = 1, .norm = true, .act = n.cfg.act, .residual = sc});
     ar.release(h1);
     ar.release(sc);
     return out;
@@ -390,17 +424,17 @@ struct Builder {
     const std::string k = std::to_string(m.idx);
     const int C = m.cin, L = hw_side * hw_side;
     gn(x, NONE, C, 0, L, mname(m.idx, "GroupNorm_0.weight"), mname(m.idx, "GroupNorm_0.bias"));
-    const size_t qkv = conv(k + ".qkv", x, NONE, hw_side, hw_side, 1, 0, 0, true, CSD_ACT_NONE, NONE, NONE, false);
+    const size_t qkv = conv(k + ".qkv", {.src0 = x, .ih = hw_side, .iw = hw_side, .norm = true});
     Op a;
     a.kind = OP_ATTN;
-    a.a = qkv; a.i0 = L; a.i1 = C;
+    a.src0 = qkv; a.hw = L; a.C0 = C;
     a.out = alloc_((size_t)B * L * C);
     a.cls = CSD_PROF_ATTENTION;
     pl.ops.push_back(a);
     count(4.0 * B * (double)L * L * C, 0);
     pending_scale = skip_scale();
     next_out = out_to;
-    const size_t o = conv(k + ".NIN_3", a.out, NONE, hw_side, hw_side, 1, 0, 0, false, 0, x, NONE, false);
+    const size_t o = conv(k + ".NIN_3", {.src0 = a.out, .ih = hw_side, .iw = hw_side, .residual = x});
     ar.release(qkv);
     ar.release(a.out);
     return o;
@@ -415,29 +449,27 @@ struct Builder {
     const bool fourier = l0.idx > 0 && n.mods[l0.idx - 1].role == R_EMB_FOURIER;
     Op e;
     e.kind = fourier ? OP_FOURIER : OP_TEMB;
-    if (fourier) e.pk0 = n.copy_off.at(mname(l0.idx - 1, "W"));
-    e.i0 = nf;
+    if (fourier) e.pk_w = n.copy_off.at(mname(l0.idx - 1, "W"));
+    e.C0 = nf;
     e.out = alloc_((size_t)B * l0.cin);
     pl.ops.push_back(e);
     Op a;
     a.kind = OP_LINEAR;
-    a.a = e.out; a.out = alloc_((size_t)B * 4 * nf);
-    a.pk0 = n.copy_off.at(mname(l0.idx, "weight")); a.pk1 = n.copy_off.at(mname(l0.idx, "bias"));
-    a.i0 = l0.cin; a.i1 = 4 * nf; a.act = CSD_ACT_NONE;
-    a.i2 = c.act;          // the activation every consumer applies to this output, applied ONCE by the producer (the consumers used
-                           // to recompute it per workgroup: 396 x 24.6 k SiLUs in the Dense_0 launch)
+    a.src0 = e.out; a.out = alloc_((size_t)B * 4 * nf);
+    a.pk_w = n.copy_off.at(mname(l0.idx, "weight")); a.pk_b = n.copy_off.at(mname(l0.idx, "bias"));
+    a.C0 = l0.cin; a.Cout = 4 * nf; a.act = CSD_ACT_NONE; a.out_act = c.act;
     pl.ops.push_back(a);
     Op b2;
     b2.kind = OP_LINEAR;
-    b2.a = a.out; b2.out = alloc_((size_t)B * 4 * nf);
-    b2.pk0 = n.copy_off.at(mname(l1.idx, "weight")); b2.pk1 = n.copy_off.at(mname(l1.idx, "bias"));
-    b2.i0 = 4 * nf; b2.i1 = 4 * nf; b2.act = CSD_ACT_NONE; b2.i2 = c.act;
+    b2.src0 = a.out; b2.out = alloc_((size_t)B * 4 * nf);
+    b2.pk_w = n.copy_off.at(mname(l1.idx, "weight")); b2.pk_b = n.copy_off.at(mname(l1.idx, "bias"));
+    b2.C0 = 4 * nf; b2.Cout = 4 * nf; b2.act = CSD_ACT_NONE; b2.out_act = c.act;
     pl.ops.push_back(b2);
     Op d;
     d.kind = OP_LINEAR;   // every block's Dense_0(act(temb)) in one launch
-    d.a = b2.out; d.out = alloc_((size_t)B * n.dense_total);
-    d.pk0 = n.dense_all_off; d.pk1 = n.dense_all_bias_off;
-    d.i0 = 4 * nf; d.i1 = n.dense_total; d.act = CSD_ACT_NONE;
+    d.src0 = b2.out; d.out = alloc_((size_t)B * n.dense_total);
+    d.pk_w = n.dense_all_off; d.pk_b = n.dense_all_bias_off;
+    d.C0 = 4 * nf; d.Cout = n.dense_total; d.act = CSD_ACT_NONE;
     pl.ops.push_back(d);
     dense_all = d.out;
     pl.launches += 4;
@@ -450,7 +482,7 @@ struct Builder {
   size_t resample_plain(OpKind kind, size_t src, int side, int C, int out_side) {
     Op p;
     p.kind = kind;
-    p.a = src; p.i0 = side; p.i1 = C;
+    p.src0 = src; p.H = p.W = side; p.C0 = C;
     p.out = alloc_((size_t)B * out_side * out_side * C);
     pl.ops.push_back(p);
     pl.launches += 1;
@@ -486,9 +518,9 @@ static void fold_small_gn_pairs(Plan& pl) {
       const Op& f = pl.ops[i + 1];
       Op o;
       o.kind = OP_GN_STATFIN;
-      o.a = a.a; o.b = a.b; o.gp = a.gp;
-      o.pk0 = f.pk0; o.pk1 = f.pk1;
-      o.out = f.out; o.c = f.b;                       // nscale, nshift
+      o.src0 = a.src0; o.src1 = a.src1; o.gp = a.gp;
+      o.pk_w = f.pk_w; o.pk_b = f.pk_b;
+      o.nscale = f.nscale; o.nshift = f.nshift;
       o.cls = CSD_PROF_GN_STATS; o.bytes = a.bytes;
       o.nb = a.nb; o.stream = a.stream; o.chunk = a.chunk;
       out.push_back(o);
@@ -501,15 +533,14 @@ static void fold_small_gn_pairs(Plan& pl) {
   pl.ops.swap(out);
 }
 
-// profiling classes: when the plan runs its big 3x3 stride-1 layers on the fused-prologue kernel (conv_xk / conv_ff: OP_CONV with i2 == 3),
+// profiling classes: when the plan runs its big 3x3 stride-1 layers on the fused-prologue kernel (conv_xk / conv_ff: ConvKernel::FUSED),
 // class CSD_PROF_CONV3X3 is THAT kernel's launches - the bench's roofline object prices the dominant kernel, SURVEY 8(d) - and the
 // other 3x3 stride-1 launches (the first layer, the quad kernel on the small maps) report as CSD_PROF_CONV3X3_OTHER
 static void split_conv3x3_classes(Plan& pl) {
-  bool any_ff = false;
-  for (const Op& o : pl.ops) any_ff = any_ff || (o.kind == OP_CONV && o.i2 == 3);
-  if (!any_ff) return;
+  auto is_ff = [](const Op& o) { return o.kind == OP_CONV && o.kernel == ConvKernel::FUSED; };
+  if (std::none_of(pl.ops.begin(), pl.ops.end(), is_ff)) return;
   for (Op& o : pl.ops)
-    if (o.cls == CSD_PROF_CONV3X3 && !(o.kind == OP_CONV && o.i2 == 3)) o.cls = CSD_PROF_CONV3X3_OTHER;
+    if (o.cls == CSD_PROF_CONV3X3 && !is_ff(o)) o.cls = CSD_PROF_CONV3X3_OTHER;
 }
 
 // the ops of a chunk region are enqueued round robin over the chunks (op j of every chunk, then op j + 1): when the host is the slower
@@ -556,7 +587,8 @@ static int build_plan(Net& n, int B, Plan** out) {
   const Module& stem_m = *std::find_if(n.mods.begin(), n.mods.end(), [](const Module& m) { return m.role == R_STEM; });
   const PackedConv& stem_pc = n.pconvs[n.pconv_by_name.at(std::to_string(stem_m.idx))];
   size_t as_out = NONE;
-  if (!stem_pc.stem || pin != 0) {
+  const bool fused_stem = stem_pc.kernel == ConvKernel::STEM;
+  if (!fused_stem || pin != 0) {
     Op as;
     as.kind = OP_ASSEMBLE;
     as.out = as_out = bd.alloc_((size_t)B * S * S * n.in_cpad);
@@ -582,7 +614,7 @@ static int build_plan(Net& n, int B, Plan** out) {
         bd.time_embedding(m);
         return;
       case R_STEM:
-        o = stem_pc.stem ? bd.stem(stem_pc, m, S) : bd.conv(k, as_out, NONE, S, S, 1, 1, 0, false, 0, NONE, NONE, false, channels);
+        o = fused_stem ? bd.stem(stem_pc, m, S) : bd.conv(k, {.src0 = as_out, .ih = S, .iw = S, .pad = 1, .real_cin = channels});
         if (!pp) { bd.ar.release(as_out); as_out = NONE; }      // (NCSN++ keeps it for the input pyramid: released behind the down path)
         break;
       case R_MID_RES_IN:                         // the down path is done: the input pyramid and the assembled input die here
@@ -598,12 +630,12 @@ static int build_plan(Net& n, int B, Plan** out) {
         break;
       case R_DOWNSAMPLE:
         o = m.kind == M_RES ? bd.res_block_updown(m, h, m.side)
-          : c.resamp_with_conv ? bd.conv(k + ".Conv_0", h, NONE, m.side, m.side, 2, 0, 0, false, 0, NONE, NONE, false)
+          : c.resamp_with_conv ? bd.conv(k + ".Conv_0", {.src0 = h, .ih = m.side, .iw = m.side, .stride = 2})
                                : bd.resample_plain(OP_AVGPOOL, h, m.side, m.cin, m.out_side);
         break;
       case R_UPSAMPLE:
         o = m.kind == M_RES ? bd.res_block_updown(m, h, m.side)
-          : c.resamp_with_conv ? bd.conv(k + ".Conv_0", h, NONE, m.side, m.side, 1, 1, 1, false, 0, NONE, NONE, false)
+          : c.resamp_with_conv ? bd.conv(k + ".Conv_0", {.src0 = h, .ih = m.side, .iw = m.side, .pad = 1, .up = 1})
                                : bd.resample_plain(OP_UPNEAR, h, m.side, m.cin, m.out_side);
         break;
       case R_COMBINE: {                          // pyramid_downsample (FIR, no conv), then Combine 'sum' (layerspp.py:53-57): Conv_0(input_pyramid) + h
@@ -611,7 +643,7 @@ static int build_plan(Net& n, int B, Plan** out) {
         if (pyr_in != as_out) bd.ar.release(pyr_in);
         pyr_in = pn;
         pyr_side /= 2;
-        o = bd.conv(k + ".Conv_0", pyr_in, NONE, m.side, m.side, 1, 0, 0, false, 0, h, NONE, false, channels);
+        o = bd.conv(k + ".Conv_0", {.src0 = pyr_in, .ih = m.side, .iw = m.side, .residual = h, .real_cin = channels});
         break;
       }
       case R_PYR_DOWN:
@@ -628,7 +660,8 @@ static int build_plan(Net& n, int B, Plan** out) {
         bd.gn(h, NONE, m.cin, 0, m.side * m.side, mname(m.idx, "weight"), mname(m.idx, "bias"));
         return;
       case R_PYR_CONV: case R_HEAD_CONV:         // (level 0: straight to the caller's NCHW output, pyr = NONE)
-        pyr = bd.conv(k, h, NONE, m.side, m.side, 1, 1, 0, true, c.act, pyr_up, NONE, m.level == 0);
+        pyr = bd.conv(k, {.src0 = h, .ih = m.side, .iw = m.side, .pad = 1, .norm = true, .act = c.act, .residual = pyr_up,
+                          .external_nchw = m.level == 0});
         bd.ar.release(pyr_up);
         pyr_up = NONE;
         return;
@@ -705,7 +738,7 @@ static int build_plan(Net& n, int B, Plan** out) {
     {
       Op f;
       f.kind = OP_FORK;
-      f.i0 = K;
+      f.n_chunks = K;
       pl.ops.push_back(f);
     }
     for (int k = 0; k < K; ++k) {
@@ -721,7 +754,7 @@ static int build_plan(Net& n, int B, Plan** out) {
     {
       Op j;
       j.kind = OP_JOIN;
-      j.i0 = K;
+      j.n_chunks = K;
       pl.ops.push_back(j);
     }
     // back in the full batch
