@@ -108,6 +108,7 @@ SIGNATURES = {
                             ctypes.POINTER(ctypes.c_double)]),
     'csd_pc_scratch_bytes': (_sz, [_vp, _i]),
     'csd_pc_sample': (_i, [_vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _i, ctypes.POINTER(PCParams), _vp]),
+    'csd_pc_noise_draws': (_i64, [_vp, _i, _i, _i, _i, _i, _i, _i, ctypes.POINTER(_i64), _i]),
     'csd_pc_step_begin': (_i, [_vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _i, ctypes.POINTER(PCParams), _i, _vp, _vp]),
     'csd_pc_step_end': (_i, [_vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _i, ctypes.POINTER(PCParams), _i, _vp, _i, _vp]),
     'csd_pc_inpaint_scratch_bytes': (_sz, [_vp, _i]),

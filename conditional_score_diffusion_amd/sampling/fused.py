@@ -179,6 +179,35 @@ def inpaint_tables(sde, ts):
     return mean_scale.contiguous(), std.contiguous()
 
 
+DRAW_KINDS = ('z_y0', 'z_y', 'zy', 'z', 'z_blend')      # csd_pc_noise_draws (include/csd.h): kind ids
+DRAW_PHASES = ('corrector', 'predictor', 'none')        # ... and phase ids
+
+
+def noise_draws(handle, B, predictor, corrector, std_y=False, use_path=False, inpaint=False, n_steps=1):
+    """The draws behind the prior of a fused loop, in the order it consumes them, as the library lists them (csd_pc_noise_draws; no
+    GPU): rows ``(step, kind, phase, elems, tape_offset, philox_stream)`` with step -1 in front of the loop, kind / phase indexing
+    DRAW_KINDS / DRAW_PHASES.  ``predictor`` / ``corrector``: the rule ids of csd_pc_params.  A combination the loop refuses raises
+    RuntimeError with the library's message."""
+    args = (handle, int(B), int(predictor), int(corrector), int(bool(std_y)), int(bool(use_path)), int(bool(inpaint)), int(n_steps))
+    n = lib().csd_pc_noise_draws(*args, None, 0)
+    if n < 0:
+        check(int(n), 'pc_noise_draws')
+    rows = (ctypes.c_int64 * (6 * n))()
+    lib().csd_pc_noise_draws(*args, rows, n)
+    return [tuple(rows[6 * k:6 * k + 6]) for k in range(n)]
+
+
+def check_tape(draws, tape, nx, ny):
+    """``tape``: the tensors after the prior; ``draws``: the rows of ``noise_draws``.  The loop finds each draw by the sizes of the ones
+    before it, so the tape must hold that many draws and that many elements."""
+    if len(tape) != len(draws):
+        raise RuntimeError('noise tape holds %d draws after the prior, the loop needs %d' % (len(tape), len(draws)))
+    have, floats = sum(int(t.numel()) for t in tape), sum(r[3] for r in draws)
+    if have != floats:
+        raise RuntimeError('noise tape holds %d elements after the prior, the loop needs %d (x draws of %d, y draws of %d)'
+                           % (have, floats, nx, ny))
+
+
 def inpaint_tape_length(p_steps, has_corrector, has_predictor):
     """draws of an inpainting run in the order of the step-by-step inpainter's randn_like calls: the prior, then per step
     [z_corrector] z_blend [z_predictor] z_blend - a 'none' phase draws no update noise but its blend does draw"""
@@ -255,7 +284,6 @@ def prepare(model, sde, shape, y, p_steps, snr, eps, denoise, noise_tape=None, s
     rd_tab, rd_sub_x = reverse_diffusion_table(c_sde, ts) if pid == 0 else (None, 0)
     if cid == 0 and corr_alpha is None:
         corr_alpha = langevin_alphas(c_sde, ts)
-    n_phases = (pid != 2) + (cid != 2)
     path_tab, path_std0 = None, 0.0
     if inpaint is not None:
         if getattr(model, 'y_scale', 0):
@@ -284,24 +312,9 @@ def prepare(model, sde, shape, y, p_steps, snr, eps, denoise, noise_tape=None, s
             x = x + c_sde.diffused_mean.unsqueeze(0)
         x = x.to(dev).contiguous()
         flat = torch.cat([t.reshape(-1) for t in tape[1:]]).to(dev).contiguous() if len(tape) > 1 else None
-        expected = n_phases * p_steps * (2 if std_y is not None else 1)
-        if use_path:                            # z_y0 | per step: z_y, z_predictor, z_corrector
-            expected = 1 + p_steps * (1 + n_phases)
-        if inpaint is not None:
-            expected = inpaint_tape_length(p_steps, cid != 2, pid != 2) - 1
-        if len(tape) - 1 != expected:
-            raise RuntimeError('noise tape holds %d draws after the prior, the loop needs %d' % (len(tape) - 1, expected))
-        if inpaint is None and flat is not None and getattr(model, 'y_scale', 0):
-            # y_scale networks (every other network keeps the check by draws above): elements, not only draws - an x draw has the
-            # state's size, a y draw that of the low-resolution y; the device loop finds each draw by these sizes
-            nx, ny = int(x.numel()), (int(y.numel()) if y is not None else 0)
-            if use_path:
-                floats = ny + p_steps * (ny + n_phases * nx)
-            else:
-                floats = n_phases * p_steps * (nx + (ny if std_y is not None else 0))
-            if flat.numel() != floats:
-                raise RuntimeError('noise tape holds %d elements after the prior, the loop needs %d (x draws of %d, y draws of %d)'
-                                   % (flat.numel(), floats, nx, ny))
+        # draws and elements: an x draw has the state's size, a y draw that of y (the low-resolution y of a y_scale network)
+        check_tape(noise_draws(model._h, B, pid, cid, std_y is not None, use_path, inpaint is not None, p_steps), tape[1:],
+                   int(x.numel()), int(y.numel()) if y is not None else 0)
     else:
         x = ops.randn(tuple(shape), seed, 0, dev)
         if ve:
@@ -413,9 +426,8 @@ def run(model, sde, shape, y, p_steps, snr, eps, denoise, noise_tape=None, seed=
     ``inpaint``: ``(data, mask)`` - inpainting with an unconditional network (csd_pc_inpaint_sample; sampling/unconditional.py:230-345):
     the loop starts from prior*(1 - mask) + data*mask and re-imposes the known pixels (mask = 1) at every step's noise level after
     each phase.  ``mask`` broadcasts to ``data`` (the Haar multi-scale model passes [1, C, 1, 1]).  Draw order / tape layout: prior,
-    then per step [z_corrector] z_blend [z_predictor] z_blend (``inpaint_tape_length``); without a tape the prior is ``ops.randn``
-    stream 0 and draw k of step i is Philox stream 1 + i*draws_per_step + k.  ``record`` then returns [p_steps + 1, ...]: the
-    initial state followed by every step.
+    then the rows of ``noise_draws`` (per step [z_corrector] z_blend [z_predictor] z_blend); without a tape the prior is
+    ``ops.randn`` stream 0.  ``record`` then returns [p_steps + 1, ...]: the initial state followed by every step.
 
     ``global_norm``: None = the Langevin step size uses the batch means of THIS call's batch (the reference run on this batch;
     one library call enqueues the whole loop).  Otherwise ``(reduce_fn, global_batch)``: the batch is one shard of a larger one

@@ -146,8 +146,7 @@ size_t csd_unet_config_size(void);
  * y_channels == 0, image_size % K != 0, x_channels + y_channels > 8 and out_channels < x_channels).  With s = S / K:
  *   y, y_noise (csd_unet_forward, csd_unet_train_forward, csd_pc_sample / csd_pc_step_begin / _end, the use_path bridge)
  *                                                                              [B, y_channels, s, s]
- *   the perturbation y + y_sigma y_noise / y + std_y z happens at s x s, then the upsample; every y draw of the noise tape / Philox
- *   stream has y_channels * s * s elements per sample, the order of the draws is unchanged
+ *   the perturbation y + y_sigma y_noise / y + std_y z happens at s x s, then the upsample; a y draw of the sampler has this size
  *   out, d_out: per sample x_channels * S * S floats - the x block [x_channels, S, S] - then (out_channels - x_channels) * s * s
  *   floats, the other channels downsampled: the mean of the 2 x 2 block at rows / columns K i + K / 2 - 1, K i + K / 2 (K even) or the
  *   pixel K i + (K - 1) / 2 (K odd), which is what the bilinear formula gives for an integer K
@@ -242,7 +241,7 @@ typedef struct csd_pc_params {
   /* `use_path` of the two-SDE samplers (sampling/conditional.py:85-100,124-178; sde_lib.py:323-339): y_t is not redrawn from the
    * marginal for every evaluation but follows the bridge p(y_t | y_0, y_{t+tau}): once per step y_t = w0*y + w1*y_{t+tau} + s*z,
    * the PREDICTOR runs first, then the corrector, both on that y_t.  path_coef != NULL selects it (std_y must be NULL);
-   * y_{T+tau} = y + path_std0 * z.  Draw order: prior | z_y0 | per step: z_y, z_predictor, z_corrector (existing phases only). */
+   * y_{T+tau} = y + path_std0 * z (the draw z_y0 of csd_pc_noise_draws). */
   const float* path_coef;       /* [n_steps][3] = (w0, w1, s), or NULL                                                */
   float path_std0;              /* sigma_y(T + tau)                                                                    */
   /* Langevin corrector of the VP / subVP SDEs (sampling/correctors.py:63-65,94-96): step size times alphas[timestep_i]     */
@@ -258,9 +257,9 @@ typedef struct csd_pc_params {
 /* x: [B, x_channels, S, S] in: prior sample (VE: already scaled by sigma_max); out: result.
  * y: [B, y_channels, S, S] or NULL.  scratch: csd_pc_scratch_bytes() device bytes, 256-byte aligned: net_out [B, out_channels, HW] |
  * x_mean, z [B, x_channels, HW] each | zy [B, max(y_channels, 1), HW] | labels [B] | y_t, the same size as zy, in 64-float granules,
- * then the norm partials [B, 64, 2] doubles and 256 bytes for the finiteness flag (pc_scratch in csrc/unet.hip is the one description;
+ * then the norm partials [B, 64, 2] doubles and 256 bytes for the finiteness flag (pc_scratch in csrc/pc_loop.h is the one description;
  * a y_scale handle gets the same full-resolution regions).  An arch-2 handle runs the same loop on volumes
- * ([.., D, H, W] in place of [.., S, S]): same update kernels, noise order, tape layout, Philox stream numbering and contract.
+ * ([.., D, H, W] in place of [.., S, S]): same update kernels, noise draws and contract.
  * Finiteness contract: the Langevin corrector's norms (which see every element of the score and of the noise) and one pass over the
  * returned state set a device flag; csd_pc_sample reads it back behind the stream before it returns - its ONE synchronisation - and
  * fails with CSD_ERR_NONFINITE rather than hand back NaN images (csd_pc_step_end does the same after the last step). */
@@ -268,6 +267,22 @@ size_t csd_pc_scratch_bytes(const csd_unet* net, int B);
 int csd_pc_sample(csd_unet* net, const void* packed, void* workspace, size_t workspace_bytes,
                   void* scratch, size_t scratch_bytes, float* x, const float* y, int B,
                   const csd_pc_params* p, void* stream);
+/* The noise draws of the loop.  ONE rule: the draws behind the prior form one sequence in the order the loop consumes them; draw j
+ * of it is Philox stream 1 + j of p->seed (stream 0 is the caller's prior) and lies on p->noise_tape behind the draws before it.  An x
+ * draw (z, z_blend) has the state's size, a y draw (z_y0, z_y, zy) that of y (at S / K for a y_scale handle).  A phase whose rule is
+ * `none` has no zy / z; a probability-flow predictor still consumes its z.  Per step, by mode:
+ *   plain                  [z corrector] [z predictor]
+ *   std_y                  [zy z corrector] [zy z predictor]        (zy: the y_t of that phase's evaluation)
+ *   path_coef (use_path)   z_y0 in front of the loop | z_y of the bridge, [z predictor], [z corrector]
+ *   inpainting             [z corrector] z_blend [z predictor] z_blend       (a `none` phase draws its z_blend)
+ * csd_pc_noise_draws lists them for a handle, a batch size and the fields of csd_pc_params the schedule depends on (has_std_y,
+ * has_path_coef: the pointer is given; inpaint: a csd_pc_inpaint_* call).  It returns the number of draws behind the prior and fills
+ * up to `cap` rows of 6: {step (-1: in front of the loop), kind (0 z_y0, 1 z_y, 2 zy, 3 z, 4 z_blend), phase (0 corrector,
+ * 1 predictor, 2 none), elements, tape offset in floats, Philox stream}.  It needs no GPU.  It refuses, with CSD_ERR_INVALID and the
+ * message of the sampling entries (which make the same check): both rules `none`; std_y or path_coef with y_channels == 0; std_y and
+ * path_coef together; inpainting with y_channels > 0, std_y, path_coef, x_squeeze, y_scale or an arch-2 handle. */
+int64_t csd_pc_noise_draws(const csd_unet* net, int B, int predictor, int corrector, int has_std_y, int has_path_coef, int inpaint,
+                           int n_steps, int64_t* rows, int cap);
 /* The same loop one PC step at a time, for the GLOBAL-NORM exactness mode of batch-sharded sampling (identical to
  * ONE reference process holding the global batch; the Langevin step size uses batch-mean norms, sampling/correctors.py:100-106).
  *   csd_pc_step_begin(step): corrector network evaluation + its noise draw; norm_sums[0] = sum_b ||score_b||_2 and
@@ -292,12 +307,8 @@ int csd_pc_step_end(csd_unet* net, const void* packed, void* workspace, size_t w
  *     x = x*(1 - mask) + masked*mask ; x_mean = x*(1 - mask) + masked_mean*mask        (x_mean from the NEW x)
  * x (in): the initial state prior*(1 - mask) + data*mask.  mask is 1 on known pixels; any value in [0, 1] is blended as written.
  * Unconditional networks only: y_channels > 0, std_y or path_coef are refused with CSD_ERR_INVALID.
- * Draw order = the order of the step-by-step inpainter's randn_like calls: prior | per step: z_corrector (if a corrector exists),
- * z_blend, z_predictor (if a predictor exists; a probability-flow predictor still consumes it), z_blend.  A `none` phase evaluates
- * no network and draws no update noise, but it does draw its blend noise.  p->noise_tape holds the draws after the prior in that
- * layout, draws_per_step = 2 + (existing phases) tensors of x's size per step.  With p->noise_tape == NULL the Philox stream id of
- * draw k of step i is 1 + i*draws_per_step + k in the same order (stream 0 is the caller's prior); the blend makes its normals in
- * registers, bit-identical to a csd_randn fill of that stream id.
+ * The draws are those of the step-by-step inpainter's randn_like calls (csd_pc_noise_draws above lists them); the blend makes its
+ * normals in registers, bit-identical to a csd_randn fill of the draw's stream id.
  * denoise returns the re-imposed x_mean of the last predictor phase; record, the finiteness contract and the single final
  * synchronisation are those of the loop above, and the two step calls with global_batch == B and no all-reduce reproduce the one
  * call.  The entry points without an inpainting struct keep their noise numbering and results bit for bit.
