@@ -15,8 +15,8 @@
 //   D                    : lane l holds couts (l >> 4)*4 .. +4 of pixel (l & 15): one 16-byte store
 //
 // A wave owns MTP x 16 pixels x 96 couts; a workgroup (4 waves) loops over pixel tiles (persistent), with
-// the raw fp32 rows of the next TWO K steps always in flight (register ring of 2, re-issued right after the
-// fp32 -> fp16 conversion), across tile boundaries.
+// the raw fp32 rows of the next TWO K steps always in flight (register ring of 2 on the big maps, 4 on the small
+// ones, re-issued right after the fp32 -> fp16 conversion), across tile boundaries.
 #include <stdlib.h>
 #include <string.h>
 
@@ -33,7 +33,7 @@ typedef unsigned int uint4_t __attribute__((ext_vector_type(4)));
 #define PW_NTL 6                 // 16-cout tiles per workgroup pass (96 couts)
 #define PW_WSCALE 256.0f         // weights are packed * 2^8 (keeps the lo half of F16X3 out of the subnormals)
 #ifndef PW_DEPTH
-#define PW_DEPTH 2          // K steps of raw rows in flight per wave on the big maps (4: no faster, measured)
+#define PW_DEPTH 2          // K steps of raw rows in flight per wave on the big maps (3 and 4: no faster, measured again with counted waits)
 #endif
 
 struct PwKArgs {
@@ -50,16 +50,30 @@ __device__ __forceinline__ float4 pw_gload4(const float* p) {
   return make_float4(v.x, v.y, v.z, v.w);
 }
 
-template <int NS, int MTP, int OCC>
+// The forms of a layer are template flags, chosen by the host (pw16_launch_form), so that every instantiation's K loop is one
+// straight instruction stream with a FIXED number of memory requests per K step:
+//   FULL : all 96 couts of every group exist (Cout % 96 == 0) - a straight block of 6 x MTP x (NS == 2 ? 3 : 1) MFMAs per K step and no
+//          cout test in the epilogue; else the group's tile count ntl is a scalar and tiles that do not exist are neither
+//          multiplied nor stored (the tap-partial head: 2 tiles; the last group of a 200-cout layer: 1)
+//   RES  : a residual is added - requested in the tile's LAST K step, before that step re-issues the ring, so the epilogue's wait for it
+//          (vmcnt retires in order) leaves the next tile's prefetch in flight; without RES no residual load exists
+//   NORM : GroupNorm scale / shift rows (+ SiLU when k.a.act says so) - their loads ride with the ring
+// hipcc counts the s_waitcnt of a load from the requests issued after it, and where two paths join it takes the path with FEWER of them:
+// a request under a run-time condition (a ring slot skipped past the end, a row load under has_norm) makes every wait of the loop
+// assume that nothing was issued behind it, i.e. drain the ring.  So the ring is re-issued unconditionally (past the workgroup's last
+// K step it reads a valid row nobody consumes) and the loop runs whole rounds of the ring.
+template <int NS, int MTP, int OCC, bool FULL, bool RES, bool NORM>
 __global__ __launch_bounds__(PW_THREADS, OCC) void pw16_kernel(const float* __restrict__ g_src0,
                                                           const float* __restrict__ g_src1,
                                                           const char* __restrict__ g_wpack, const PwKArgs k) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int WPIX = MTP * 16;          // pixels per wave
   constexpr int TPIX = 4 * WPIX;          // pixels per workgroup tile
+  constexpr unsigned OOB = 0x80000000u;   // buffer range = offset of a lane that must not access
+  constexpr int RSRC_FLAGS = 0x00020000;
   const int tid = threadIdx.x;
   const int lane = tid & 63;
-  const int wave = tid >> 6;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);      // a scalar the compiler can see: the buffer descriptors below are built from it
   const int l16 = lane & 15;
   const int kq = lane >> 4;
   const int ng = blockIdx.y;
@@ -71,17 +85,15 @@ __global__ __launch_bounds__(PW_THREADS, OCC) void pw16_kernel(const float* __re
 
   const int nt_mine = (k.ntiles - (int)blockIdx.x + (int)gridDim.x - 1) / (int)gridDim.x;
   const int total = nt_mine * k.ks;
-  const bool has_norm = k.a.nscale != nullptr;
-  const bool has_res = k.a.res != nullptr;
-  const bool has_act = k.a.act == CSD_ACT_SWISH;          // (only next to a GroupNorm: the tap-partial form of a tiny-Cout 3x3, below)
-  const int ntl = min(PW_NTL, (k.Cout - (int)blockIdx.y * (PW_NTL * 16) + 15) / 16);     // 16-cout tiles of this group that exist
+  const bool has_act = NORM && k.a.act == CSD_ACT_SWISH;          // (only next to a GroupNorm: the tap-partial form of a tiny-Cout 3x3, below)
+  const int ntl = FULL ? PW_NTL : min(PW_NTL, (k.Cout - ng * (PW_NTL * 16) + 15) / 16);     // 16-cout tiles of this group that exist
 
   // load-side pipeline depth in K steps: small maps (one or two tiles per workgroup, MTP = 1) have nothing but their own K loop to
-  // cover a global load with - four steps in flight, GroupNorm scale / shift rows included; big ones keep two (registers)
+  // cover a global load with - four steps in flight; big ones keep PW_DEPTH.  GroupNorm scale / shift rows included.
   constexpr int D = MTP == 1 ? 4 : PW_DEPTH;
   float4 raw[D][MTP][2];
-  constexpr bool PFN = MTP == 1;          // the scale / shift rows ride with the prefetch (else: loaded at their use, as ever)
-  float4 nsc[PFN ? D : 1][MTP][2], nsh[PFN ? D : 1][MTP][2];
+  float4 nsc[NORM ? D : 1][MTP][2], nsh[NORM ? D : 1][MTP][2];
+  uint4_t rv[RES ? MTP : 1][PW_NTL];      // the tile's residual, requested one K step ahead of its epilogue
   floatx4 acc[MTP][PW_NTL];
 #pragma unroll
   for (int j = 0; j < MTP; ++j)
@@ -89,36 +101,33 @@ __global__ __launch_bounds__(PW_THREADS, OCC) void pw16_kernel(const float* __re
     for (int nt = 0; nt < PW_NTL; ++nt) acc[j][nt] = floatx4{0.f, 0.f, 0.f, 0.f};
 
   // (tile, K step) counters of the load side and of the MFMA side of the pipeline
-  int l_tile = blockIdx.x, l_kk = 0, l_it = 0;
+  int l_tile = blockIdx.x, l_kk = 0;
   int c_tile = blockIdx.x, c_kk = 0;
 
   auto issue = [&](float4 (&dst)[MTP][2], float4 (&dsc)[MTP][2], float4 (&dsh)[MTP][2]) {
-    if (l_it < total) {
-      const int kb = l_kk * 32;
-      const bool s1 = kb >= k.C0;
-      const float* src = s1 ? g_src1 : g_src0;
-      const int C = s1 ? k.C1 : k.C0;
-      const int ch = (s1 ? kb - k.C0 : kb) + kq * 8;
+    const int kb = l_kk * 32;
+    const bool s1 = kb >= k.C0;
+    const float* src = s1 ? g_src1 : g_src0;
+    const int C = s1 ? k.C1 : k.C0;
+    const int ch = (s1 ? kb - k.C0 : kb) + kq * 8;
 #pragma unroll
-      for (int j = 0; j < MTP; ++j) {
-        int p = l_tile * TPIX + wave * WPIX + j * 16 + l16;
-        p = p < k.npix ? p : k.npix - 1;                   // tail pixels: any valid row, never stored
-        const float* q = src + (size_t)p * C + ch;
-        dst[j][0] = pw_gload4(q);
-        dst[j][1] = pw_gload4(q + 4);
-        if (PFN && has_norm) {
-          const size_t row = (size_t)(p / k.hw) * Cin + l_kk * 32 + kq * 8;
-          dsc[j][0] = pw_gload4(k.a.nscale + row); dsc[j][1] = pw_gload4(k.a.nscale + row + 4);
-          dsh[j][0] = pw_gload4(k.a.nshift + row); dsh[j][1] = pw_gload4(k.a.nshift + row + 4);
-        }
+    for (int j = 0; j < MTP; ++j) {
+      int p = l_tile * TPIX + wave * WPIX + j * 16 + l16;
+      p = p < k.npix ? p : k.npix - 1;                   // tail pixels and tiles past the last: any valid row, never stored
+      const float* q = src + (size_t)p * C + ch;
+      dst[j][0] = pw_gload4(q);
+      dst[j][1] = pw_gload4(q + 4);
+      if constexpr (NORM) {
+        const size_t row = (size_t)(p / k.hw) * Cin + l_kk * 32 + kq * 8;
+        dsc[j][0] = pw_gload4(k.a.nscale + row); dsc[j][1] = pw_gload4(k.a.nscale + row + 4);
+        dsh[j][0] = pw_gload4(k.a.nshift + row); dsh[j][1] = pw_gload4(k.a.nshift + row + 4);
       }
-      ++l_it;
-      if (++l_kk == k.ks) { l_kk = 0; l_tile += gridDim.x; }
     }
+    if (++l_kk == k.ks) { l_kk = 0; l_tile += gridDim.x; }
   };
 
 #pragma unroll
-  for (int u = 0; u < D; ++u) issue(raw[u], nsc[PFN ? u : 0], nsh[PFN ? u : 0]);
+  for (int u = 0; u < D; ++u) issue(raw[u], nsc[NORM ? u : 0], nsh[NORM ? u : 0]);
 
   // ---- this cout group's weights -> LDS, once per workgroup (behind the first activation requests: their latency overlaps the copy) ----
   wg_copy_to_lds<PW_THREADS, 9>(smem, g_wpack + (size_t)ng * wbytes, wbytes, tid);      // (9 x 4 KiB per round: a 288-channel layer's 108 KiB in three)
@@ -128,102 +137,125 @@ __global__ __launch_bounds__(PW_THREADS, OCC) void pw16_kernel(const float* __re
   }
   __syncthreads();
 
+  // ---- fp32 rows -> fp16 B fragments (GroupNorm affine applied here when the layer has one) ----
+  half8_t bh[MTP], bl[MTP];
+  auto convert = [&](const float4 (&src)[MTP][2], const float4 (&ssc)[MTP][2], const float4 (&ssh)[MTP][2]) {
+#pragma unroll
+    for (int j = 0; j < MTP; ++j) {
+      float v[8] = {src[j][0].x, src[j][0].y, src[j][0].z, src[j][0].w, src[j][1].x, src[j][1].y, src[j][1].z, src[j][1].w};
+      if constexpr (NORM) {
+        const float4 s0 = ssc[j][0], s1 = ssc[j][1], h0 = ssh[j][0], h1 = ssh[j][1];
+        const float sc[8] = {s0.x, s0.y, s0.z, s0.w, s1.x, s1.y, s1.z, s1.w};
+        const float sh[8] = {h0.x, h0.y, h0.z, h0.w, h1.x, h1.y, h1.z, h1.w};
+#pragma unroll
+        for (int q = 0; q < 8; ++q) v[q] = fmaf(v[q], sc[q], sh[q]);     // same fma as the fp32 staging
+        if (has_act) {
+#pragma unroll
+          for (int q = 0; q < 8; ++q) v[q] = v[q] * __builtin_amdgcn_rcpf(1.0f + __expf(-v[q]));     // SiLU as conv_ff / gn_apply16
+        }
+      }
+#pragma unroll
+      for (int q = 0; q < 8; ++q) {
+        const _Float16 hi = (_Float16)v[q];
+        bh[j][q] = hi;
+        if (NS == 2) bl[j][q] = (_Float16)(v[q] - (float)hi);
+      }
+    }
+  };
+
+  // ---- MFMAs of K step c_kk: 6 cout tiles x MTP pixel tiles ----
+  auto mfmas = [&]() {
+    const char* wk = smem + (size_t)c_kk * PW_NTL * NS * 1024 + lane * 16;
+#pragma unroll
+    for (int nt = 0; nt < PW_NTL; ++nt) {
+      if (!FULL && nt >= ntl) break;       // (uniform: a 28-cout layer runs 2 of the 6 tiles)
+      const half8_t wh = *reinterpret_cast<const half8_t*>(wk + (nt * NS) * 1024);
+      half8_t wl;
+      if (NS == 2) wl = *reinterpret_cast<const half8_t*>(wk + (nt * NS + 1) * 1024);
+#pragma unroll
+      for (int j = 0; j < MTP; ++j) {
+        if (NS == 2) {
+          acc[j][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl, bh[j], acc[j][nt], 0, 0, 0);
+          acc[j][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh, bl[j], acc[j][nt], 0, 0, 0);
+        }
+        acc[j][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh, bh[j], acc[j][nt], 0, 0, 0);
+      }
+    }
+  };
+
+  // ---- tile c_tile's residual -> rv (tail lanes and couts that do not exist: out of range) ----
+  auto request_res = [&]() {
+    const size_t p_base = (size_t)c_tile * TPIX + wave * WPIX;
+    const int left = k.npix - (int)p_base;            // valid pixels from p_base on (may be <= 0)
+    const __amdgpu_buffer_rsrc_t res_r =
+        __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(k.a.res + p_base * k.Cout), 0, OOB, RSRC_FLAGS);
+#pragma unroll
+    for (int j = 0; j < (RES ? MTP : 0); ++j) {
+      const int pl = j * 16 + l16;
+#pragma unroll
+      for (int nt = 0; nt < PW_NTL; ++nt) {
+        if (!FULL && nt >= ntl) break;
+        const int col0 = col_base + nt * 16;
+        const unsigned off = (pl < left && (FULL || col0 < k.Cout)) ? (unsigned)(pl * k.Cout + col0) * 4u : OOB;
+        rv[j][nt] = __builtin_amdgcn_raw_buffer_load_b128(res_r, off, 0, 0);
+      }
+    }
+  };
+
+  // ---- end of tile c_tile: bias + residual, 16-byte buffer stores (tail lanes out of range); on to the next tile ----
+  auto epilogue = [&]() {
+    const size_t p_base = (size_t)c_tile * TPIX + wave * WPIX;      // scalar: the per-lane part of an address is the offset operand only
+    const int left = k.npix - (int)p_base;              // valid pixels from p_base on (may be <= 0)
+    const __amdgpu_buffer_rsrc_t out_r =
+        __builtin_amdgcn_make_buffer_rsrc(k.a.out + p_base * k.a.out_stride + k.a.out_coff, 0, OOB, RSRC_FLAGS);
+    const float unscale = 1.0f / PW_WSCALE;
+#pragma unroll
+    for (int j = 0; j < MTP; ++j) {
+      const int pl = j * 16 + l16;
+      const bool pv = pl < left;
+#pragma unroll
+      for (int nt = 0; nt < PW_NTL; ++nt) {
+        if (!FULL && nt >= ntl) break;
+        const int col0 = col_base + nt * 16;
+        const float4 b = *reinterpret_cast<const float4*>(lds_bias + nt * 16 + kq * 4);
+        uint4_t ov;
+        // (acc*2^-8 + bias) + residual, then the skip_rescale factor: association of the reference.  Without a residual the sum is
+        // taken as it is: it can only be -0 where acc is, and acc (+0 at the start of a tile, then sums) never is - adding the +0
+        // an absent residual used to read as changes no bit.
+        if constexpr (RES) {
+          ov.x = __float_as_uint(((acc[j][nt][0] * unscale + b.x) + __uint_as_float(rv[j][nt].x)) * k.a.out_scale);
+          ov.y = __float_as_uint(((acc[j][nt][1] * unscale + b.y) + __uint_as_float(rv[j][nt].y)) * k.a.out_scale);
+          ov.z = __float_as_uint(((acc[j][nt][2] * unscale + b.z) + __uint_as_float(rv[j][nt].z)) * k.a.out_scale);
+          ov.w = __float_as_uint(((acc[j][nt][3] * unscale + b.w) + __uint_as_float(rv[j][nt].w)) * k.a.out_scale);
+        } else {
+          ov.x = __float_as_uint((acc[j][nt][0] * unscale + b.x) * k.a.out_scale);
+          ov.y = __float_as_uint((acc[j][nt][1] * unscale + b.y) * k.a.out_scale);
+          ov.z = __float_as_uint((acc[j][nt][2] * unscale + b.z) * k.a.out_scale);
+          ov.w = __float_as_uint((acc[j][nt][3] * unscale + b.w) * k.a.out_scale);
+        }
+        const unsigned off = (pv && (FULL || col0 < k.Cout)) ? (unsigned)(pl * k.a.out_stride + col0) * 4u : OOB;
+        __builtin_amdgcn_raw_buffer_store_b128(ov, out_r, off, 0, 0);
+        acc[j][nt] = floatx4{0.f, 0.f, 0.f, 0.f};
+      }
+    }
+    c_kk = 0;
+    c_tile += gridDim.x;
+  };
+
+  // whole rounds of the ring: up to D - 1 K steps past the workgroup's last belong to a tile past the last one, whose every pixel is out
+  // of range (left <= 0 above) - a test per step would be one more join in front of every wait
   for (int it = 0; it < total; it += D) {
 #pragma unroll
     for (int u = 0; u < D; ++u) {
-      if (it + u < total) {
-        // ---- fp32 rows -> fp16 B fragments (GroupNorm affine applied here when the layer has one) ----
-        half8_t bh[MTP], bl[MTP];
-#pragma unroll
-        for (int j = 0; j < MTP; ++j) {
-          float v[8] = {raw[u][j][0].x, raw[u][j][0].y, raw[u][j][0].z, raw[u][j][0].w,
-                        raw[u][j][1].x, raw[u][j][1].y, raw[u][j][1].z, raw[u][j][1].w};
-          if (has_norm) {
-            float4 s0, s1, h0, h1;
-            if constexpr (PFN) {
-              s0 = nsc[u][j][0]; s1 = nsc[u][j][1]; h0 = nsh[u][j][0]; h1 = nsh[u][j][1];
-            } else {
-              int p = c_tile * TPIX + wave * WPIX + j * 16 + l16;
-              p = p < k.npix ? p : k.npix - 1;
-              const size_t row = (size_t)(p / k.hw) * Cin + c_kk * 32 + kq * 8;
-              s0 = pw_gload4(k.a.nscale + row); s1 = pw_gload4(k.a.nscale + row + 4);
-              h0 = pw_gload4(k.a.nshift + row); h1 = pw_gload4(k.a.nshift + row + 4);
-            }
-            const float sc[8] = {s0.x, s0.y, s0.z, s0.w, s1.x, s1.y, s1.z, s1.w};
-            const float sh[8] = {h0.x, h0.y, h0.z, h0.w, h1.x, h1.y, h1.z, h1.w};
-#pragma unroll
-            for (int q = 0; q < 8; ++q) v[q] = fmaf(v[q], sc[q], sh[q]);     // same fma as the fp32 staging
-            if (has_act) {
-#pragma unroll
-              for (int q = 0; q < 8; ++q) v[q] = v[q] * __builtin_amdgcn_rcpf(1.0f + __expf(-v[q]));     // SiLU as conv_ff / gn_apply16
-            }
-          }
-#pragma unroll
-          for (int q = 0; q < 8; ++q) {
-            const _Float16 hi = (_Float16)v[q];
-            bh[j][q] = hi;
-            if (NS == 2) bl[j][q] = (_Float16)(v[q] - (float)hi);
-          }
-        }
-        issue(raw[u], nsc[PFN ? u : 0], nsh[PFN ? u : 0]);       // this slot is free again: request K step it + u + D
-        // ---- MFMAs: 6 cout tiles x MTP pixel tiles ----
-        const char* wk = smem + (size_t)c_kk * PW_NTL * NS * 1024 + lane * 16;
-#pragma unroll
-        for (int nt = 0; nt < PW_NTL; ++nt) {
-          if (nt >= ntl) continue;             // (uniform: a 28-cout layer runs 2 of the 6 tiles)
-          const half8_t wh = *reinterpret_cast<const half8_t*>(wk + (nt * NS) * 1024);
-          half8_t wl;
-          if (NS == 2) wl = *reinterpret_cast<const half8_t*>(wk + (nt * NS + 1) * 1024);
-#pragma unroll
-          for (int j = 0; j < MTP; ++j) {
-            if (NS == 2) {
-              acc[j][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl, bh[j], acc[j][nt], 0, 0, 0);
-              acc[j][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh, bl[j], acc[j][nt], 0, 0, 0);
-            }
-            acc[j][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh, bh[j], acc[j][nt], 0, 0, 0);
-          }
-        }
-        // ---- end of a tile: epilogue (bias + residual, 16-byte buffer stores; tail lanes out of range) ----
-        if (++c_kk == k.ks) {
-          constexpr unsigned OOB = 0x80000000u;
-          constexpr int RSRC_FLAGS = 0x00020000;
-          const size_t p_base = (size_t)c_tile * TPIX + wave * WPIX;
-          const int left = k.npix - (int)p_base;            // valid pixels from p_base on (may be <= 0)
-          const __amdgpu_buffer_rsrc_t out_r = __builtin_amdgcn_make_buffer_rsrc(
-              k.a.out + p_base * k.a.out_stride + k.a.out_coff, 0, OOB, RSRC_FLAGS);
-          const __amdgpu_buffer_rsrc_t res_r = __builtin_amdgcn_make_buffer_rsrc(
-              const_cast<float*>(has_res ? k.a.res + p_base * k.Cout : k.a.out), 0, OOB, RSRC_FLAGS);
-          const float unscale = 1.0f / PW_WSCALE;
-#pragma unroll
-          for (int j = 0; j < MTP; ++j) {
-            const int pl = j * 16 + l16;
-            const bool pv = pl < left;
-            uint4_t rv[PW_NTL];
-#pragma unroll
-            for (int nt = 0; nt < PW_NTL; ++nt) {
-              const int col0 = col_base + nt * 16;
-              const unsigned off = (pv && has_res && col0 < k.Cout) ? (unsigned)(pl * k.Cout + col0) * 4u : OOB;
-              rv[nt] = __builtin_amdgcn_raw_buffer_load_b128(res_r, off, 0, 0);
-            }
-#pragma unroll
-            for (int nt = 0; nt < PW_NTL; ++nt) {
-              const int col0 = col_base + nt * 16;
-              const float4 b = *reinterpret_cast<const float4*>(lds_bias + nt * 16 + kq * 4);
-              uint4_t ov;
-              // (acc*2^-8 + bias) + residual, then the skip_rescale factor: association of the reference
-              ov.x = __float_as_uint(((acc[j][nt][0] * unscale + b.x) + __uint_as_float(rv[nt].x)) * k.a.out_scale);
-              ov.y = __float_as_uint(((acc[j][nt][1] * unscale + b.y) + __uint_as_float(rv[nt].y)) * k.a.out_scale);
-              ov.z = __float_as_uint(((acc[j][nt][2] * unscale + b.z) + __uint_as_float(rv[nt].z)) * k.a.out_scale);
-              ov.w = __float_as_uint(((acc[j][nt][3] * unscale + b.w) + __uint_as_float(rv[nt].w)) * k.a.out_scale);
-              const unsigned off = (pv && col0 < k.Cout) ? (unsigned)(pl * k.a.out_stride + col0) * 4u : OOB;
-              __builtin_amdgcn_raw_buffer_store_b128(ov, out_r, off, 0, 0);
-              acc[j][nt] = floatx4{0.f, 0.f, 0.f, 0.f};
-            }
-          }
-          c_kk = 0;
-          c_tile += gridDim.x;
-        }
+      convert(raw[u], nsc[NORM ? u : 0], nsh[NORM ? u : 0]);
+      const bool last = c_kk == k.ks - 1;
+      if constexpr (RES) {
+        if (last) request_res();       // BEFORE the ring's request for the next tile
       }
+      issue(raw[u], nsc[NORM ? u : 0], nsh[NORM ? u : 0]);       // this slot is free again: request K step it + u + D
+      mfmas();
+      if (last) epilogue();
+      else ++c_kk;
     }
   }
 }
@@ -414,9 +446,15 @@ bool pw16_taps_supported(int cin, int cout, int ns) {
   return cout >= 1 && cout <= 6 && pw16_supported(p, ns) && !CSD_TUNE_ENV("CSD_NO_TAPSUM");
 }
 
-template <int NS, int MTP, int OCC>
+// workgroups per CU an instantiation is built for (register bound): two; the fp16 big-map kernel fits three (168 registers) as long as
+// it holds neither GroupNorm rows nor a residual
+template <int NS, int MTP, bool RES, bool NORM>
+constexpr int pw16_occ() { return (NS == 1 && MTP == 2 && !RES && !NORM) ? 3 : 2; }
+
+template <int NS, int MTP, bool FULL, bool RES, bool NORM>
 static int pw16_launch_t(const PwKArgs& k, const ConvPlan& p, hipStream_t s) {
-  auto kern = pw16_kernel<NS, MTP, OCC>;
+  constexpr int OCC = pw16_occ<NS, MTP, RES, NORM>();
+  auto kern = pw16_kernel<NS, MTP, OCC, FULL, RES, NORM>;
   const size_t lds = pw16_lds_bytes(p, NS);
   static size_t attr_lds = 0;
   if (lds > attr_lds) {
@@ -428,7 +466,7 @@ static int pw16_launch_t(const PwKArgs& k, const ConvPlan& p, hipStream_t s) {
     attr_lds = 160 * 1024;
   }
   const int n_groups = cdiv(p.Cout, PW_NTL * 16);
-  // persistent: two workgroups per CU (register bound) share the tiles of one cout group
+  // persistent: OCC workgroups per CU (register bound) share the tiles of one cout group
   int gx = (OCC * 256) / n_groups;
   if (gx < 1) gx = 1;
   if (gx > k.ntiles) gx = k.ntiles;
@@ -436,6 +474,22 @@ static int pw16_launch_t(const PwKArgs& k, const ConvPlan& p, hipStream_t s) {
                      reinterpret_cast<const char*>(k.a.wpack), k);
   CSD_LAUNCH_CHECK();
   return CSD_OK;
+}
+
+// the layer's form (the kernel's FULL / RES / NORM flags) is known here: one instantiation per form
+template <int NS, int MTP>
+static int pw16_launch_form(const PwKArgs& k, const ConvPlan& p, hipStream_t s) {
+  const int form = (p.Cout % (PW_NTL * 16) == 0 ? 4 : 0) | (k.a.res ? 2 : 0) | (k.a.nscale ? 1 : 0);
+  switch (form) {
+    case 0: return pw16_launch_t<NS, MTP, false, false, false>(k, p, s);
+    case 1: return pw16_launch_t<NS, MTP, false, false, true>(k, p, s);
+    case 2: return pw16_launch_t<NS, MTP, false, true, false>(k, p, s);
+    case 3: return pw16_launch_t<NS, MTP, false, true, true>(k, p, s);
+    case 4: return pw16_launch_t<NS, MTP, true, false, false>(k, p, s);
+    case 5: return pw16_launch_t<NS, MTP, true, false, true>(k, p, s);
+    case 6: return pw16_launch_t<NS, MTP, true, true, false>(k, p, s);
+    default: return pw16_launch_t<NS, MTP, true, true, true>(k, p, s);
+  }
 }
 
 int pw16_launch(const ConvPlan& p, int ns, const ConvArgs& a, hipStream_t s) {
@@ -452,8 +506,8 @@ int pw16_launch(const ConvPlan& p, int ns, const ConvArgs& a, hipStream_t s) {
   // fastest (more waves in flight beat more bytes per wave); small layers: 64-pixel tiles to fill the chip
   const bool big = cdiv(k.npix, 128) >= 768;
   k.ntiles = cdiv(k.npix, big ? 128 : 64);
-  if (ns == 2) return big ? pw16_launch_t<2, 2, 2>(k, p, s) : pw16_launch_t<2, 1, 2>(k, p, s);
-  return big ? pw16_launch_t<1, 2, 3>(k, p, s) : pw16_launch_t<1, 1, 2>(k, p, s);
+  if (ns == 2) return big ? pw16_launch_form<2, 2>(k, p, s) : pw16_launch_form<2, 1>(k, p, s);
+  return big ? pw16_launch_form<1, 2>(k, p, s) : pw16_launch_form<1, 1>(k, p, s);
 }
 
 }  // namespace csd
