@@ -613,7 +613,7 @@ extern "C" size_t csd_conv_wgrad_scratch_bytes(int B, int Cin, int Cout, int H, 
   return wgrad_scratch(nullptr, B, Cin, Cout, H, W, ksize, stride, up2).bytes;
 }
 
-// layout bit 0: x is NHWC [B,H,W,Cin]; bit 1: dy is NHWC [B,OH,OW,Cout]; bit 2: split-bf16 arithmetic allowed (else exact fp32)
+// layout CSD_IN_NHWC: x is NHWC [B,H,W,Cin]; CSD_OUT_NHWC: dy is NHWC [B,OH,OW,Cout]; CSD_SPLIT_BF16: split-bf16 arithmetic allowed (else exact fp32)
 static int wgrad_impl(const float* x, const float* dy, float* dw, int B, int Cin, int Cout, int H, int W, int ksize, int stride,
                       int pad_mode, int up2, int layout, void* scratch, void* stream) {
   CSD_REQUIRE(x && dy && dw && scratch, "conv2d_wgrad: null argument");
@@ -636,11 +636,11 @@ static int wgrad_impl(const float* x, const float* dy, float* dw, int B, int Cin
   const int S = L.S, per = L.per;
   float *xh = L.xh, *dyh = L.dyh, *const partial = L.partial;
   int rc;
-  if (layout & 1) xh = const_cast<float*>(x);
+  if (layout & CSD_IN_NHWC) xh = const_cast<float*>(x);
   else if ((rc = nchw_to_nhwc_launch(x, xh, B, Cin, H * W, Cin, Cin, s))) return rc;
-  if (layout & 2) dyh = const_cast<float*>(dy);
+  if (layout & CSD_OUT_NHWC) dyh = const_cast<float*>(dy);
   else if ((rc = nchw_to_nhwc_launch(dy, dyh, B, Cout, OH * OW, Cout, Cout, s))) return rc;
-  if ((layout & 4) && wgrad_resamples(ksize, stride, up2) && Cin % 4 == 0 && Cout % 4 == 0 && !wgrad_wide(Cin) && !getenv("CSD_WGRAD_FP32") &&
+  if ((layout & CSD_SPLIT_BF16) && wgrad_resamples(ksize, stride, up2) && Cin % 4 == 0 && Cout % 4 == 0 && !wgrad_wide(Cin) && !getenv("CSD_WGRAD_FP32") &&
       !CSD_TUNE_ENV("CSD_WGRAD_RESAMPLE_FP32")) {
     // resampling convs on the bf16 kernel too (it knows stride 1 only): rebuild ONE operand on the fine grid.
     //   Upsample (nearest x2, then 3x3): x' = nearest_up2(x), the plain stride-1 gradient of (x', dy).
@@ -658,7 +658,7 @@ static int wgrad_impl(const float* x, const float* dy, float* dw, int B, int Cin
     CSD_LAUNCH_CHECK();
     return CSD_OK;
   }
-  if ((layout & 4) && stride == 1 && !up && !wgrad_wide(Cin) && !getenv("CSD_WGRAD_FP32")) {
+  if ((layout & CSD_SPLIT_BF16) && stride == 1 && !up && !wgrad_wide(Cin) && !getenv("CSD_WGRAD_FP32")) {
     // split-bf16 operands on the bf16 matrix cores (wgrad_bf16.hip): the fp16 precision modes of the training step
     if ((rc = wgrad_bf16_launch(xh, dyh, partial, B, H, W, Cin, Cout, ksize, S, per, s))) return rc;
     const size_t n = (size_t)Cout * Cin * ksize * ksize;

@@ -126,8 +126,8 @@ extern "C" size_t csd_conv_scratch_bytes(int B, int Cin, int Cout, int H, int W,
   return conv_scratch(nullptr, B, Cin, Cout, H, W, ksize, up2).bytes;
 }
 
-// layout bit 0: x is NHWC [B,H,W,Cin] (Cin must already be a multiple of the kernel's channel granule); bit 1: y is NHWC;
-// bit 2: `weight` is the OIHW weight [Cin][Cout][k][k] of the transposed convolution - it is used transposed and spatially flipped
+// layout CSD_IN_NHWC: x is NHWC [B,H,W,Cin] (Cin must already be a multiple of the kernel's channel granule); CSD_OUT_NHWC: y is NHWC;
+// CSD_WEIGHT_T: `weight` is the OIHW weight [Cin][Cout][k][k] of the transposed convolution - it is used transposed and spatially flipped
 // (the data gradient of a convolution, without materialising the flipped weight)
 // res: optional NHWC tensor of the output's shape added in the epilogue (y NHWC only) - the block's shortcut, the attention input;
 // temb: optional [B, Cout] row added per sample (Dense_0(act(temb))[:, :, None, None])
@@ -147,7 +147,7 @@ int csd::conv2d_impl(const float* x, const float* weight, const float* bias, con
                      const void* planes) {
   CSD_REQUIRE(x && weight && y && scratch, "conv2d: null argument");
   CSD_REQUIRE(precision >= CSD_PREC_F32 && precision <= CSD_PREC_F16F8, "conv2d: bad precision id %d", precision);
-  const bool in_nhwc = layout & 1, out_nhwc = layout & 2;
+  const bool in_nhwc = layout & CSD_IN_NHWC, out_nhwc = layout & CSD_OUT_NHWC;
   CSD_REQUIRE(!res || out_nhwc, "conv2d: a residual needs an NHWC output");
   hipStream_t s = (hipStream_t)stream;
   ConvPlan p;
@@ -167,7 +167,7 @@ int csd::conv2d_impl(const float* x, const float* weight, const float* bias, con
     if (convff_pipelined(q, ns)) {
       CSD_REQUIRE(!planes, "conv2d: pre-split operand planes on a layer that does not take them");
       if ((rc = convff_plan_tiles(&q, ns))) return rc;
-      if ((rc = convff_pack_weight(q, ns, weight, (layout & 4) ? 2 : 0, Cin, Cout, 0, L.wp, s))) return rc;
+      if ((rc = convff_pack_weight(q, ns, weight, (layout & CSD_WEIGHT_T) ? 2 : 0, Cin, Cout, 0, L.wp, s))) return rc;
       ConvArgs a;
       memset(&a, 0, sizeof(a));
       a.src0 = x; a.wpack = L.wp; a.bias = bias; a.res = res; a.temb = temb; a.temb_stride = Cout;
@@ -195,7 +195,7 @@ int csd::conv2d_impl(const float* x, const float* weight, const float* bias, con
   float* const xh_scratch = L.xh, *const wp = L.wp, *const bp = L.bp, *const yh = L.yh;
   if (in_nhwc) xh = const_cast<float*>(x);
   else if ((rc = nchw_to_nhwc_launch(x, xh, B, Cin, H * W, p.C0, p.C0, s))) return rc;
-  const int wl = (layout & 4) ? 2 : 0;
+  const int wl = (layout & CSD_WEIGHT_T) ? 2 : 0;
   CSD_REQUIRE(!planes || quad, "conv2d: pre-split operand planes on a layer that does not take them");
   if (quad) {
     void* hi = planes ? const_cast<void*>(planes) : static_cast<void*>(xh_scratch);

@@ -5,7 +5,7 @@
 //
 // The pinned values date from an Op of lettered slots (offsets a .. e, ints i0 .. i4) and a PackedConv of one flag per kernel.  The hash
 // still takes its values in THAT order; legacy_slots / legacy_flags below are the only place that knows it - and the record of what the
-// letters used to mean.
+// letters used to mean.  The training digest likewise dates from a TStep of ten positional saved-tensor slots: legacy_saved.
 #pragma once
 
 namespace csd {
@@ -145,6 +145,17 @@ static uint64_t digest_plan(const Plan& pl) {
   return h.h;
 }
 
+// TStep: its saved tensors were ten positional slots sv[0 .. 9]; the pinned hash takes all ten in this order (an unused slot: null)
+static std::array<const float*, 10> legacy_saved(const TStep& sp) {
+  switch (sp.kind) {
+    case TS_RES: return {sp.op0, sp.rs0, sp.ms0, sp.c0, sp.a1, sp.rs1, sp.ms1, sp.mask, sp.xr};
+    case TS_ATTN: return {sp.op0, sp.rs0, sp.ms0, sp.qkv, sp.attn};
+    case TS_HEAD: case TS_PYR: return {sp.op0, sp.rs0, sp.ms0};
+    case TS_COMBINE: return {sp.pyr};
+    default: return {};
+  }
+}
+
 // the training graph's dry run (the one csd_unet_train_workspace_bytes sizes the workspace with); 0: no planned training graph
 static uint64_t digest_train(csd_unet* net, int B, float dropout_p) {
   if (train_check(net)) return 0;
@@ -158,7 +169,7 @@ static uint64_t digest_train(csd_unet* net, int B, float dropout_p) {
   auto off = [&](const float* p) { h.i(p ? (int64_t)(p - base) : -1); };
   for (const TStep& sp : st.steps) {
     for (int64_t v : {(int64_t)sp.kind, (int64_t)sp.mod, (int64_t)sp.in0, (int64_t)sp.in1, (int64_t)sp.out, (int64_t)sp.drop_id, (int64_t)sp.flag}) h.i(v);
-    for (const float* p : sp.sv) off(p);
+    for (const float* p : legacy_saved(sp)) off(p);
   }
   for (const TT& t : st.t) { off(t.p); h.i(t.H); h.i(t.C); }
   h.z(st.fwd_top); h.z(g.peak);

@@ -23,12 +23,34 @@ struct TT { float* p = nullptr; int H = 0, C = 0; float* g = nullptr; };        
 enum TSKind { TS_STEM, TS_RES, TS_ATTN, TS_DOWN, TS_UP, TS_CAT, TS_HEAD, TS_COMBINE, TS_PYR, TS_RPYR };
 struct TStep {
   TSKind kind;
-  int mod = -1, in0 = -1, in1 = -1, out = -1;
-  float* sv[10] = {};
+  int mod = -1, in0 = -1, in1 = -1, out = -1;      // (TS_RPYR: in0 = the down block's h, in1 = the pyramid source tensor, -1 = the network input)
+  // the saved tensors the backward reads; a step sets and reads only the ones its kind has
+  float* op0 = nullptr;         // the step's first conv operand: TS_RES act(GroupNorm_0(x)) (FIR-resampled in an up / down block), TS_ATTN
+                                // GroupNorm_0(x), TS_HEAD / TS_PYR act(GroupNorm(h)); rs0 / ms0: that GroupNorm's (rstd, -mean * rstd) [B, C]
+  float *rs0 = nullptr, *ms0 = nullptr;
+  float *c0 = nullptr, *a1 = nullptr, *rs1 = nullptr, *ms1 = nullptr;      // TS_RES: Conv_0(.) + Dense_0 row; dropout(act(GroupNorm_1(c0)))
+  float *mask = nullptr, *xr = nullptr;      // TS_RES: the dropout mask (p > 0); the FIR-resampled block input (the shortcut's operand)
+  float *qkv = nullptr, *attn = nullptr;     // TS_ATTN: q | k | v [B, H, H, 3C]; the attention core's output (NIN_3's operand)
+  float* pyr = nullptr;         // TS_COMBINE: the input pyramid's level (NCHW), Conv_0's operand
   uint64_t drop_id = 0;
-  int flag = 0;                 // TS_PYR: 1 = the pyramid level above adds FIR-up of the previous level (in1)
-                                // (TS_RPYR: in0 = the down block's h, in1 = the pyramid source tensor, -1 = the network input)
+  int flag = 0;                 // TS_PYR: PYR_* bits
 };
+enum {
+  PYR_ADDS_COARSER = 1,         // the level adds FIR-up of the coarser level (in1)
+  PYR_CALLER_OUT = 2            // the finest level: the forward writes the caller's `out`, the backward reads d_out
+};
+
+// what a convolution (TG::conv) or a weight gradient (TG::wgrad) sets beside its operands and extents; a call names what differs
+static constexpr int NHWC = CSD_IN_NHWC | CSD_OUT_NHWC;
+struct TConv {
+  int k = 3, stride = 1;
+  int dpad = 0, up2 = 0;        // the Downsample's (0, 1, 0, 1) padding; nearest x2 in front of the convolution
+  int layout = NHWC;            // conv: | CSD_WEIGHT_T for a data gradient (wgrad adds CSD_SPLIT_BF16 by the precision)
+  const float *res = nullptr, *temb = nullptr;      // conv: NHWC tensor / per-sample [B, Cout] row added in the epilogue
+  const void* planes = nullptr; // conv: the operand's fp16 planes (conv2d_operand_planes)
+};
+static const char* const QKV_W[3] = {"NIN_0.W", "NIN_1.W", "NIN_2.W"};      // the attention block's q, k, v projections
+static const char* const QKV_B[3] = {"NIN_0.b", "NIN_1.b", "NIN_2.b"};
 
 struct TrainState {
   bool valid = false;
@@ -186,19 +208,19 @@ struct TG {
   } while (0)
 
   // ---- operator wrappers (scratch is a temporary above `top`) ---------------------------------------------------------
-  int conv(const float* x, const float* w, const float* b, float* y, int Cin, int Cout, int H, int k, int stride, int dpad,
-           int up2, int layout, const float* res = nullptr, const float* temb = nullptr, const void* planes = nullptr) {
+  int conv(const float* x, const float* w, const float* b, float* y, int Cin, int Cout, int H, const TConv& a = {}) {
     const size_t m = top;
-    float* sc = alloc_bytes(csd_conv_scratch_bytes(B, Cin, Cout, H, H, k, up2));
-    TG_RUN(conv2d_impl(x, w, b, res, temb, y, B, Cin, Cout, H, H, k, stride, dpad, up2, prec, layout, sc, s, planes));
+    float* sc = alloc_bytes(csd_conv_scratch_bytes(B, Cin, Cout, H, H, a.k, a.up2));
+    TG_RUN(conv2d_impl(x, w, b, a.res, a.temb, y, B, Cin, Cout, H, H, a.k, a.stride, a.dpad, a.up2, prec, a.layout, sc, s, a.planes));
     top = m;
     return CSD_OK;
   }
-  int wgrad(const float* x, const float* dy, float* dw, int Cin, int Cout, int H, int k, int stride, int dpad, int up2, int layout) {
+  int wgrad(const float* x, const float* dy, float* dw, int Cin, int Cout, int H, const TConv& a = {}) {
     if (!pg) return CSD_OK;
     const size_t m = top;
-    float* sc = alloc_bytes(csd_conv_wgrad_scratch_bytes(B, Cin, Cout, H, H, k, stride, up2));
-    TG_RUN(csd_conv2d_wgrad_ex(x, dy, dw, B, Cin, Cout, H, H, k, stride, dpad, up2, layout | (prec == CSD_PREC_F32 ? 0 : 4), sc, s));
+    float* sc = alloc_bytes(csd_conv_wgrad_scratch_bytes(B, Cin, Cout, H, H, a.k, a.stride, a.up2));
+    TG_RUN(csd_conv2d_wgrad_ex(x, dy, dw, B, Cin, Cout, H, H, a.k, a.stride, a.dpad, a.up2,
+                               a.layout | (prec == CSD_PREC_F32 ? 0 : CSD_SPLIT_BF16), sc, s));
     top = m;
     return CSD_OK;
   }
@@ -284,104 +306,72 @@ struct TG {
   // =====================================================================================================================
   // forward (models/ddpm.py:149-213 with model.train())
   // =====================================================================================================================
+  // The residual block of both families is one block: ResnetBlockDDPM (models/layers.py:632-675) is ResnetBlockBigGANpp
+  // (models/layerspp.py:242-274) with no resampling, the NIN shortcut and scale 1.  What differs, from the module and the config:
+  struct ResForm {
+    bool up = false, down = false;                   // FIR resampling of both branches in front of Conv_0 / the shortcut
+    // the 1x1 shortcut on the (resampled) block input; sc_w == null: the identity.  NIN_0.W is [cin, cout]: applied through the
+    // transposed-weight flag, its data gradient is the plain OIHW conv of dout (W read as [O = cin, I = cout]) and its weight gradient
+    // dW[i, o] = sum_p x[p, i] dout[p, o] the 1x1 weight gradient with the operands swapped.  Conv_2.weight is OIHW.
+    const char *sc_w = nullptr, *sc_b = nullptr;
+    int sc_layout = NHWC, sc_dgrad_layout = NHWC;
+    bool sc_swap = false;
+    float scale = 1.f;                               // out = (shortcut + h) * scale
+    bool dense = false;                              // Dense_0(act(temb)) rides in Conv_0's epilogue (time-conditional networks)
+    bool resample() const { return up || down; }
+    int out_side(int H) const { return up ? 2 * H : (down ? H / 2 : H); }
+  };
+  ResForm res_form(const Module& m) const {
+    ResForm f;
+    f.up = m.up != 0; f.down = m.down != 0;
+    f.scale = skip_scale();
+    f.dense = n.cfg.conditional != 0;
+    if (m.cin == m.cout && !f.resample()) return f;
+    if (n.cfg.arch == 1) { f.sc_w = "Conv_2.weight"; f.sc_b = "Conv_2.bias"; f.sc_dgrad_layout = NHWC | CSD_WEIGHT_T; }
+    else { f.sc_w = "NIN_0.W"; f.sc_b = "NIN_0.b"; f.sc_layout = NHWC | CSD_WEIGHT_T; f.sc_swap = true; }
+    return f;
+  }
+
+  // h = act(GroupNorm_0(x)); up / down: h, x = FIR(h), FIR(x); h = Conv_0(h) + Dense_0(act(temb)); h = Conv_1(dropout(act(GroupNorm_1(h))));
+  // x = shortcut(x) if the shape changes; (x + h) * scale
   int res_fwd(const Module& m, int in, int* out_tid) {
-    const csd_unet_config& c = n.cfg;
-    const int H = st.t[in].H, cin = m.cin, cout = m.cout;
+    const ResForm f = res_form(m);
+    const int H = st.t[in].H, cin = m.cin, cout = m.cout, Ho = f.out_side(H);
     const float* h = st.t[in].p;
     TStep sp;
     sp.kind = TS_RES; sp.mod = m.idx; sp.in0 = in;
     // persistent tensors first (the backward reads them), temporaries - the convs' operand planes, the shortcut - above them
-    float* a0 = alloc(act_n(H, cin));                // act(GroupNorm_0(h)): Conv_0's operand
-    float* rs0 = alloc((size_t)B * cin); float* ms0 = alloc((size_t)B * cin);
-    float* c0 = alloc(act_n(H, cout));               // Conv_0(.) + Dense_0(act(temb))[:, None, None, :]: GroupNorm_1's input
-    float* a1 = alloc(act_n(H, cout));               // dropout(act(GroupNorm_1(.))): Conv_1's operand
-    float* rs1 = alloc((size_t)B * cout); float* ms1 = alloc((size_t)B * cout);
-    float* mask = nullptr;
+    float* a0 = sp.op0 = alloc(act_n(H, cin));       // act(GroupNorm_0(x))
+    sp.rs0 = alloc((size_t)B * cin); sp.ms0 = alloc((size_t)B * cin);
+    if (f.resample()) { sp.op0 = alloc(act_n(Ho, cin)); sp.xr = alloc(act_n(Ho, cin)); }
+    sp.c0 = alloc(act_n(Ho, cout));
+    sp.a1 = alloc(act_n(Ho, cout));
+    sp.rs1 = alloc((size_t)B * cout); sp.ms1 = alloc((size_t)B * cout);
     ++drop_count;
     sp.drop_id = (call << 16) + (uint64_t)drop_count;
-    if (p_drop > 0.f) mask = alloc(act_n(H, cout));
-    const int out = new_tensor(H, cout);
-    float* o = st.t[out].p;
+    if (p_drop > 0.f) sp.mask = alloc(act_n(Ho, cout));
+    sp.out = new_tensor(Ho, cout);
+    float* o = st.t[sp.out].p;
+    const float* xs = f.resample() ? sp.xr : h;      // the shortcut's operand
     int rc;
     {
       const size_t mk = top;
       // the GroupNorm's apply pass also writes the fp16 operand planes Conv_0 would otherwise split a0 into in a pass of its own
-      const int np0 = conv2d_operand_planes(B, cin, cout, H, H, 3, 1, 0, 0, prec);
+      const int np0 = f.resample() ? 0 : conv2d_operand_planes(B, cin, cout, H, H, 3, 1, 0, 0, prec);
       float* pl0 = np0 ? alloc_bytes((size_t)np0 * B * H * H * cin * 2) : nullptr;
-      rc = gn(h, W(m.idx, "GroupNorm_0.weight"), W(m.idx, "GroupNorm_0.bias"), a0, rs0, ms0, cin, H, act, nullptr, 0, pl0, np0);
+      rc = gn(h, W(m.idx, "GroupNorm_0.weight"), W(m.idx, "GroupNorm_0.bias"), a0, sp.rs0, sp.ms0, cin, H, act, nullptr, 0, pl0, np0);
       if (rc) return rc;
+      if (f.resample()) {
+        rc = fir(a0, sp.op0, B, H, cin, f.up, false); if (rc) return rc;
+        rc = fir(h, sp.xr, B, H, cin, f.up, false); if (rc) return rc;
+      }
       float* d = nullptr;
-      if (c.conditional) {                           // the time-embedding row rides in Conv_0's epilogue
+      if (f.dense) {                                 // the time-embedding row rides in Conv_0's epilogue
         d = alloc((size_t)B * cout);
         // (act(temb) is computed once per forward: every block's Dense_0 used to redo it inside its own latency-bound launch)
-        TG_RUN(csd_linear(st.temb2_act, W(m.idx, "Dense_0.weight"), W(m.idx, "Dense_0.bias"), d, B, 4 * c.nf, cout, CSD_ACT_NONE, s));
+        TG_RUN(csd_linear(st.temb2_act, W(m.idx, "Dense_0.weight"), W(m.idx, "Dense_0.bias"), d, B, 4 * n.cfg.nf, cout, CSD_ACT_NONE, s));
       }
-      rc = conv(a0, W(m.idx, "Conv_0.weight"), W(m.idx, "Conv_0.bias"), c0, cin, cout, H, 3, 1, 0, 0, 3, nullptr, d, pl0);
-      if (rc) return rc;
-      top = mk;
-    }
-    {
-      const size_t mk = top;
-      const int np1 = conv2d_operand_planes(B, cout, cout, H, H, 3, 1, 0, 0, prec);
-      float* pl1 = np1 ? alloc_bytes((size_t)np1 * B * H * H * cout * 2) : nullptr;
-      rc = gn(c0, W(m.idx, "GroupNorm_1.weight"), W(m.idx, "GroupNorm_1.bias"), a1, rs1, ms1, cout, H, act, mask, sp.drop_id, pl1, np1);   // (dropout in the apply pass)
-      if (rc) return rc;
-      if (cin != cout) {                             // NIN shortcut: h . W + b through the transposed-weight flag (no W^T copy)
-        float* sc = alloc(act_n(H, cout));
-        rc = conv(h, W(m.idx, "NIN_0.W"), W(m.idx, "NIN_0.b"), sc, cin, cout, H, 1, 1, 0, 0, 3 | 4);
-        if (rc) return rc;
-        rc = conv(a1, W(m.idx, "Conv_1.weight"), W(m.idx, "Conv_1.bias"), o, cout, cout, H, 3, 1, 0, 0, 3, sc, nullptr, pl1);   // + shortcut in the epilogue
-        if (rc) return rc;
-      } else {
-        rc = conv(a1, W(m.idx, "Conv_1.weight"), W(m.idx, "Conv_1.bias"), o, cout, cout, H, 3, 1, 0, 0, 3, h, nullptr, pl1);
-        if (rc) return rc;
-      }
-      top = mk;
-    }
-    sp.out = out;
-    sp.sv[0] = a0; sp.sv[1] = rs0; sp.sv[2] = ms0; sp.sv[3] = c0; sp.sv[4] = a1; sp.sv[5] = rs1; sp.sv[6] = ms1; sp.sv[7] = mask;
-    st.steps.push_back(sp);
-    *out_tid = out;
-    return CSD_OK;
-  }
-
-  // ResnetBlockBigGANpp.forward (models/layerspp.py:242-274): h = act(GroupNorm_0(x)); up / down: h, x = FIR(h), FIR(x); h = Conv_0(h)
-  // + Dense_0(act(temb)); h = Conv_1(dropout(act(GroupNorm_1(h)))); x = Conv_2(x) if the shape changes; (x + h) / sqrt(2)
-  int respp_fwd(const Module& m, int in, int* out_tid) {
-    const csd_unet_config& c = n.cfg;
-    const int H = st.t[in].H, cin = m.cin, cout = m.cout;
-    const int Ho = m.up ? 2 * H : (m.down ? H / 2 : H);
-    const bool resample = m.up || m.down, has_sc = cin != cout || resample;
-    const float* h = st.t[in].p;
-    TStep sp;
-    sp.kind = TS_RES; sp.mod = m.idx; sp.in0 = in;
-    float* a0 = alloc(act_n(H, cin));                // act(GroupNorm_0(x))
-    float* rs0 = alloc((size_t)B * cin); float* ms0 = alloc((size_t)B * cin);
-    float *hr = a0, *xr = nullptr;
-    if (resample) { hr = alloc(act_n(Ho, cin)); xr = alloc(act_n(Ho, cin)); }
-    float* c0 = alloc(act_n(Ho, cout));
-    float* a1 = alloc(act_n(Ho, cout));
-    float* rs1 = alloc((size_t)B * cout); float* ms1 = alloc((size_t)B * cout);
-    float* mask = nullptr;
-    ++drop_count;
-    sp.drop_id = (call << 16) + (uint64_t)drop_count;
-    if (p_drop > 0.f) mask = alloc(act_n(Ho, cout));
-    const int out = new_tensor(Ho, cout);
-    float* o = st.t[out].p;
-    int rc;
-    {
-      const size_t mk = top;
-      const int np0 = resample ? 0 : conv2d_operand_planes(B, cin, cout, H, H, 3, 1, 0, 0, prec);
-      float* pl0 = np0 ? alloc_bytes((size_t)np0 * B * H * H * cin * 2) : nullptr;
-      rc = gn(h, W(m.idx, "GroupNorm_0.weight"), W(m.idx, "GroupNorm_0.bias"), a0, rs0, ms0, cin, H, act, nullptr, 0, pl0, np0);
-      if (rc) return rc;
-      if (resample) {
-        rc = fir(a0, hr, B, H, cin, m.up != 0, false); if (rc) return rc;
-        rc = fir(h, xr, B, H, cin, m.up != 0, false); if (rc) return rc;
-      }
-      float* d = alloc((size_t)B * cout);            // (time-conditional networks only: build_modules)
-      TG_RUN(csd_linear(st.temb2_act, W(m.idx, "Dense_0.weight"), W(m.idx, "Dense_0.bias"), d, B, 4 * c.nf, cout, CSD_ACT_NONE, s));
-      rc = conv(hr, W(m.idx, "Conv_0.weight"), W(m.idx, "Conv_0.bias"), c0, cin, cout, Ho, 3, 1, 0, 0, 3, nullptr, d, pl0);
+      rc = conv(sp.op0, W(m.idx, "Conv_0.weight"), W(m.idx, "Conv_0.bias"), sp.c0, cin, cout, Ho, {.temb = d, .planes = pl0});
       if (rc) return rc;
       top = mk;
     }
@@ -389,24 +379,33 @@ struct TG {
       const size_t mk = top;
       const int np1 = conv2d_operand_planes(B, cout, cout, Ho, Ho, 3, 1, 0, 0, prec);
       float* pl1 = np1 ? alloc_bytes((size_t)np1 * B * Ho * Ho * cout * 2) : nullptr;
-      rc = gn(c0, W(m.idx, "GroupNorm_1.weight"), W(m.idx, "GroupNorm_1.bias"), a1, rs1, ms1, cout, Ho, act, mask, sp.drop_id, pl1, np1);
+      rc = gn(sp.c0, W(m.idx, "GroupNorm_1.weight"), W(m.idx, "GroupNorm_1.bias"), sp.a1, sp.rs1, sp.ms1, cout, Ho, act, sp.mask, sp.drop_id,
+              pl1, np1);                             // (dropout in the apply pass)
       if (rc) return rc;
       const float* shortcut = h;
-      if (has_sc) {                                  // Conv_2: 1x1 on the (resampled) block input
+      if (f.sc_w) {
         float* sc = alloc(act_n(Ho, cout));
-        rc = conv(resample ? xr : h, W(m.idx, "Conv_2.weight"), W(m.idx, "Conv_2.bias"), sc, cin, cout, Ho, 1, 1, 0, 0, 3);
+        rc = conv(xs, W(m.idx, f.sc_w), W(m.idx, f.sc_b), sc, cin, cout, Ho, {.k = 1, .layout = f.sc_layout});
         if (rc) return rc;
         shortcut = sc;
       }
-      rc = conv(a1, W(m.idx, "Conv_1.weight"), W(m.idx, "Conv_1.bias"), o, cout, cout, Ho, 3, 1, 0, 0, 3, shortcut, nullptr, pl1);
+      rc = conv(sp.a1, W(m.idx, "Conv_1.weight"), W(m.idx, "Conv_1.bias"), o, cout, cout, Ho, {.res = shortcut, .planes = pl1});   // + shortcut in the epilogue
       if (rc) return rc;
-      if (skip_scale() != 1.f) { rc = scale_into(o, o, skip_scale(), act_n(Ho, cout)); if (rc) return rc; }
+      if (f.scale != 1.f) { rc = scale_into(o, o, f.scale, act_n(Ho, cout)); if (rc) return rc; }
       top = mk;
     }
-    sp.out = out;
-    sp.sv[0] = hr; sp.sv[1] = rs0; sp.sv[2] = ms0; sp.sv[3] = c0; sp.sv[4] = a1; sp.sv[5] = rs1; sp.sv[6] = ms1; sp.sv[7] = mask; sp.sv[8] = xr;
     st.steps.push_back(sp);
-    *out_tid = out;
+    *out_tid = sp.out;
+    return CSD_OK;
+  }
+
+  // the q | k | v weight of ONE contraction, [NIN_0.W | NIN_1.W | NIN_2.W] ([C, 3C]) into wc, and (bc != null) its bias [3C] into bc
+  int qkv_weight(int mod, int C, float* wc, float* bc) {
+    for (int j = 0; j < 3 && !dry; ++j) {
+      hipLaunchKernelGGL(copy2d_kernel, dim3(launch_blocks((size_t)C * C)), dim3(256), 0, s, W(mod, QKV_W[j]), C, wc + j * C, 3 * C, C, C);
+      CSD_LAUNCH_CHECK();
+      if (bc) TG_RUN(copy(W(mod, QKV_B[j]), bc + j * C, C));
+    }
     return CSD_OK;
   }
 
@@ -415,37 +414,29 @@ struct TG {
     const float* h = st.t[in].p;
     TStep sp;
     sp.kind = TS_ATTN; sp.mod = m.idx; sp.in0 = in;
-    float* t = alloc(act_n(H, C));
-    float* rs = alloc((size_t)B * C); float* ms = alloc((size_t)B * C);
-    int rc = gn(h, W(m.idx, "GroupNorm_0.weight"), W(m.idx, "GroupNorm_0.bias"), t, rs, ms, C, H, CSD_ACT_NONE);
+    sp.op0 = alloc(act_n(H, C));
+    sp.rs0 = alloc((size_t)B * C); sp.ms0 = alloc((size_t)B * C);
+    int rc = gn(h, W(m.idx, "GroupNorm_0.weight"), W(m.idx, "GroupNorm_0.bias"), sp.op0, sp.rs0, sp.ms0, C, H, CSD_ACT_NONE);
     if (rc) return rc;
-    float* qkv = alloc(act_n(H, 3 * C));
-    {                                                // q | k | v from ONE contraction: W = [NIN_0.W | NIN_1.W | NIN_2.W] ([C, 3C])
+    sp.qkv = alloc(act_n(H, 3 * C));
+    {
       const size_t mk = top;
       float* wc = alloc((size_t)C * 3 * C);
       float* bc = alloc(3 * C);
-      for (int j = 0; j < 3 && !dry; ++j) {
-        char wn[16], bn[16];
-        snprintf(wn, sizeof(wn), "NIN_%d.W", j); snprintf(bn, sizeof(bn), "NIN_%d.b", j);
-        hipLaunchKernelGGL(copy2d_kernel, dim3(launch_blocks((size_t)C * C)), dim3(256), 0, s, W(m.idx, wn), C, wc + j * C, 3 * C, C, C);
-        CSD_LAUNCH_CHECK();
-        TG_RUN(copy(W(m.idx, bn), bc + j * C, C));
-      }
-      rc = conv(t, wc, bc, qkv, C, 3 * C, H, 1, 1, 0, 0, 3 | 4);
+      rc = qkv_weight(m.idx, C, wc, bc); if (rc) return rc;
+      rc = conv(sp.op0, wc, bc, sp.qkv, C, 3 * C, H, {.k = 1, .layout = NHWC | CSD_WEIGHT_T});
       if (rc) return rc;
       top = mk;
     }
-    float* a = alloc(act_n(H, C));
-    TG_RUN(csd_attention_nhwc_prec(qkv, a, B, H * H, C, prec, s));      // (the arithmetic of the mode, as csd_unet_forward)
-    const int out = new_tensor(H, C);
-    float* o = st.t[out].p;
-    rc = conv(a, W(m.idx, "NIN_3.W"), W(m.idx, "NIN_3.b"), o, C, C, H, 1, 1, 0, 0, 3 | 4, h);      // + h in the epilogue
+    sp.attn = alloc(act_n(H, C));
+    TG_RUN(csd_attention_nhwc_prec(sp.qkv, sp.attn, B, H * H, C, prec, s));      // (the arithmetic of the mode, as csd_unet_forward)
+    sp.out = new_tensor(H, C);
+    float* o = st.t[sp.out].p;
+    rc = conv(sp.attn, W(m.idx, "NIN_3.W"), W(m.idx, "NIN_3.b"), o, C, C, H, {.k = 1, .layout = NHWC | CSD_WEIGHT_T, .res = h});      // + h in the epilogue
     if (rc) return rc;
     if (skip_scale() != 1.f) { rc = scale_into(o, o, skip_scale(), act_n(H, C)); if (rc) return rc; }      // AttnBlockpp: (x + h) / sqrt(2)
-    sp.out = out;
-    sp.sv[0] = t; sp.sv[1] = rs; sp.sv[2] = ms; sp.sv[3] = qkv; sp.sv[4] = a;
     st.steps.push_back(sp);
-    *out_tid = out;
+    *out_tid = sp.out;
     return CSD_OK;
   }
 
@@ -471,19 +462,18 @@ struct TG {
   int out_fwd(const Module& mg, int h, float* out, int* pyr) {
     const Module& mc = n.mods[mg.idx + 1];
     const int H = st.t[h].H, C = mg.cin, co = n.cfg.out_channels;
-    float* g = alloc(act_n(H, C));
-    float* rs = alloc((size_t)B * C); float* ms = alloc((size_t)B * C);
-    int rc = gn(st.t[h].p, W(mg.idx, "weight"), W(mg.idx, "bias"), g, rs, ms, C, H, act); if (rc) return rc;
     TStep sp;
     sp.kind = pyr ? TS_PYR : TS_HEAD; sp.mod = mg.idx; sp.in0 = h;
-    sp.sv[0] = g; sp.sv[1] = rs; sp.sv[2] = ms;
+    sp.op0 = alloc(act_n(H, C));
+    sp.rs0 = alloc((size_t)B * C); sp.ms0 = alloc((size_t)B * C);
+    int rc = gn(st.t[h].p, W(mg.idx, "weight"), W(mg.idx, "bias"), sp.op0, sp.rs0, sp.ms0, C, H, act); if (rc) return rc;
     if (pyr) {
       sp.out = new_tensor(H, co, false);
       st.t[sp.out].p = out = mg.level == 0 ? out : alloc((size_t)B * co * H * H);
       sp.in1 = *pyr;
-      sp.flag = (*pyr >= 0 ? 1 : 0) | (mg.level == 0 ? 2 : 0);
+      sp.flag = (*pyr >= 0 ? PYR_ADDS_COARSER : 0) | (mg.level == 0 ? PYR_CALLER_OUT : 0);
     }
-    rc = conv(g, W(mc.idx, "weight"), W(mc.idx, "bias"), out, C, co, H, 3, 1, 0, 0, 1); if (rc) return rc;
+    rc = conv(sp.op0, W(mc.idx, "weight"), W(mc.idx, "bias"), out, C, co, H, {.layout = CSD_IN_NHWC}); if (rc) return rc;      // NCHW out
     if (pyr && *pyr >= 0) {
       const size_t mk = top;
       float* up = alloc((size_t)B * co * H * H);
@@ -553,7 +543,7 @@ struct TG {
           break;
         case R_STEM: {                               // NCHW in, NHWC out
           h = new_tensor(S, nf);
-          rc = conv(st.xin, W(m.idx, "weight"), W(m.idx, "bias"), st.t[h].p, cio, nf, S, 3, 1, 0, 0, 2);
+          rc = conv(st.xin, W(m.idx, "weight"), W(m.idx, "bias"), st.t[h].p, cio, nf, S, {.layout = CSD_OUT_NHWC});
           if (rc) return rc;
           TStep sp;
           sp.kind = TS_STEM; sp.mod = m.idx; sp.out = h;
@@ -565,18 +555,19 @@ struct TG {
           hs.pop_back();
           [[fallthrough]];
         case R_DOWN_BLOCK: case R_MID_RES_IN: case R_MID_RES_OUT:
-          rc = pp ? respp_fwd(m, h, &h) : res_fwd(m, h, &h);
+          rc = res_fwd(m, h, &h);
           break;
         case R_ATTN: case R_MID_ATTN:
           rc = attn_fwd(m, h, &h);
           break;
         case R_DOWNSAMPLE: case R_UPSAMPLE: {
-          if (pp) { rc = respp_fwd(m, h, &h); break; }      // the BigGAN down / up block
+          if (pp) { rc = res_fwd(m, h, &h); break; }      // the BigGAN down / up block
           // Downsample: pad (0,1,0,1) + stride-2 conv (models/layers.py:619-625); Upsample: nearest x2 + conv (:600-604)
           const bool down = m.role == R_DOWNSAMPLE;
           const int H = st.t[h].H, C = m.cin;
           const int o = new_tensor(m.out_side, C);
-          rc = conv(st.t[h].p, W(m.idx, "Conv_0.weight"), W(m.idx, "Conv_0.bias"), st.t[o].p, C, C, H, 3, down ? 2 : 1, down ? 1 : 0, down ? 0 : 1, 3);
+          rc = conv(st.t[h].p, W(m.idx, "Conv_0.weight"), W(m.idx, "Conv_0.bias"), st.t[o].p, C, C, H,
+                    down ? TConv{.stride = 2, .dpad = 1} : TConv{.up2 = 1});
           if (rc) return rc;
           TStep sp;
           sp.kind = down ? TS_DOWN : TS_UP; sp.mod = m.idx; sp.in0 = h; sp.out = o;
@@ -590,10 +581,10 @@ struct TG {
           rc = fir(pyr_in, pn, B * cio, pyr_side, 1, false, false); if (rc) return rc;
           pyr_in = pn; pyr_side = side;
           const int o = new_tensor(side, C);
-          rc = conv(pn, W(m.idx, "Conv_0.weight"), W(m.idx, "Conv_0.bias"), st.t[o].p, cio, C, side, 1, 1, 0, 0, 2); if (rc) return rc;
+          rc = conv(pn, W(m.idx, "Conv_0.weight"), W(m.idx, "Conv_0.bias"), st.t[o].p, cio, C, side, {.k = 1, .layout = CSD_OUT_NHWC}); if (rc) return rc;
           rc = add_into(st.t[o].p, st.t[h].p, act_n(side, C)); if (rc) return rc;
           TStep sp;
-          sp.kind = TS_COMBINE; sp.mod = m.idx; sp.in0 = h; sp.out = o; sp.sv[0] = pn;
+          sp.kind = TS_COMBINE; sp.mod = m.idx; sp.in0 = h; sp.out = o; sp.pyr = pn;
           st.steps.push_back(sp);
           h = o;
           break;
@@ -671,126 +662,99 @@ struct TG {
   }
 
   int res_bwd(const TStep& sp, float* dtemb_act) {
-    const csd_unet_config& c = n.cfg;
     const Module& m = n.mods[sp.mod];
+    const ResForm f = res_form(m);
     const TT& tin = st.t[sp.in0];
-    const int H = tin.H, cin = m.cin, cout = m.cout;
+    const int H = tin.H, cin = m.cin, cout = m.cout, Ho = f.out_side(H);
     const float* h = tin.p;
-    float* dout = st.t[sp.out].g;
-    float *a0 = sp.sv[0], *rs0 = sp.sv[1], *ms0 = sp.sv[2], *c0 = sp.sv[3], *a1 = sp.sv[4], *rs1 = sp.sv[5], *ms1 = sp.sv[6], *mask = sp.sv[7];
+    const float* xs = f.resample() ? sp.xr : h;      // the shortcut's operand
     float* dh = alloc(act_n(H, cin));                // gradient w.r.t. the block input (kept until its producer has consumed it)
     const size_t mk = top;
     int rc;
+    float* dout = st.t[sp.out].g;
+    if (f.scale != 1.f) {                            // out = (x + h) / sqrt(2)
+      float* ds = alloc(act_n(Ho, cout));
+      rc = scale_into(dout, ds, f.scale, act_n(Ho, cout)); if (rc) return rc;
+      dout = ds;
+    }
     // Conv_1
-    rc = wgrad(a1, dout, DW(m.idx, "Conv_1.weight"), cout, cout, H, 3, 1, 0, 0, 3); if (rc) return rc;
-    rc = bias_grad(dout, DW(m.idx, "Conv_1.bias"), cout, H); if (rc) return rc;
-    float* d1 = alloc(act_n(H, cout));
-    rc = conv(dout, W(m.idx, "Conv_1.weight"), nullptr, d1, cout, cout, H, 3, 1, 0, 0, 3 | 4); if (rc) return rc;
-    if (mask) TG_RUN(csd_mul(d1, mask, d1, (int64_t)act_n(H, cout), s));
+    rc = wgrad(sp.a1, dout, DW(m.idx, "Conv_1.weight"), cout, cout, Ho); if (rc) return rc;
+    rc = bias_grad(dout, DW(m.idx, "Conv_1.bias"), cout, Ho); if (rc) return rc;
+    float* d1 = alloc(act_n(Ho, cout));
+    rc = conv(dout, W(m.idx, "Conv_1.weight"), nullptr, d1, cout, cout, Ho, {.layout = NHWC | CSD_WEIGHT_T}); if (rc) return rc;
+    if (sp.mask) TG_RUN(csd_mul(d1, sp.mask, d1, (int64_t)act_n(Ho, cout), s));
     // GroupNorm_1 + act
-    float* d1b = alloc(act_n(H, cout));
-    rc = gn_bwd(c0, W(m.idx, "GroupNorm_1.weight"), W(m.idx, "GroupNorm_1.bias"), rs1, ms1, d1, d1b, DW(m.idx, "GroupNorm_1.weight"),
-                DW(m.idx, "GroupNorm_1.bias"), cout, H, act);
+    float* d1b = alloc(act_n(Ho, cout));
+    rc = gn_bwd(sp.c0, W(m.idx, "GroupNorm_1.weight"), W(m.idx, "GroupNorm_1.bias"), sp.rs1, sp.ms1, d1, d1b, DW(m.idx, "GroupNorm_1.weight"),
+                DW(m.idx, "GroupNorm_1.bias"), cout, Ho, act);
     if (rc) return rc;
     d1 = d1b;
     // Conv_0 bias and the time-embedding row share the per-(sample, channel) pixel sums of d1
     if (pg) {
       float* dd = alloc((size_t)B * cout);
-      rc = sum_pixels(d1, dd, cout, H); if (rc) return rc;
+      rc = sum_pixels(d1, dd, cout, Ho); if (rc) return rc;
       TG_RUN(csd_sum_rows(dd, DW(m.idx, "Conv_0.bias"), B, cout, s));
-      if (c.conditional) {
+      if (f.dense) {
         rc = linear_bwd(st.temb2_act, CSD_ACT_NONE, W(m.idx, "Dense_0.weight"), dd, DW(m.idx, "Dense_0.weight"), DW(m.idx, "Dense_0.bias"), dtemb_act,
-                        4 * c.nf, cout);
+                        4 * n.cfg.nf, cout);
         if (rc) return rc;
       }
     }
-    rc = wgrad(a0, d1, DW(m.idx, "Conv_0.weight"), cin, cout, H, 3, 1, 0, 0, 3); if (rc) return rc;
-    float* d0 = alloc(act_n(H, cin));
-    rc = conv(d1, W(m.idx, "Conv_0.weight"), nullptr, d0, cout, cin, H, 3, 1, 0, 0, 3 | 4); if (rc) return rc;
-    if (cin != cout) {
-      // NIN_0: y = h.W + b, W [cin, cout]: dW[i,o] = sum_p h[p,i] dout[p,o] = the 1x1 weight gradient with the operands swapped;
-      // the shortcut's data gradient dout . W^T = the OIHW 1x1 conv of dout with W read as [O = cin, I = cout]; it joins dh inside
-      // the GroupNorm_0 backward
-      rc = wgrad(dout, h, DW(m.idx, "NIN_0.W"), cout, cin, H, 1, 1, 0, 0, 3); if (rc) return rc;
-      rc = bias_grad(dout, DW(m.idx, "NIN_0.b"), cout, H); if (rc) return rc;
-      float* dsc = alloc(act_n(H, cin));
-      rc = conv(dout, W(m.idx, "NIN_0.W"), nullptr, dsc, cout, cin, H, 1, 1, 0, 0, 3); if (rc) return rc;
-      rc = gn_bwd(h, W(m.idx, "GroupNorm_0.weight"), W(m.idx, "GroupNorm_0.bias"), rs0, ms0, d0, dh, DW(m.idx, "GroupNorm_0.weight"),
-                  DW(m.idx, "GroupNorm_0.bias"), cin, H, act, dsc);
-      if (rc) return rc;
-    } else {
-      rc = gn_bwd(h, W(m.idx, "GroupNorm_0.weight"), W(m.idx, "GroupNorm_0.bias"), rs0, ms0, d0, dh, DW(m.idx, "GroupNorm_0.weight"),
-                  DW(m.idx, "GroupNorm_0.bias"), cin, H, act, dout);
-      if (rc) return rc;
-    }
-    top = mk;
-    return contribute(sp.in0, dh);
-  }
-
-  int respp_bwd(const TStep& sp, float* dtemb_act) {
-    const csd_unet_config& c = n.cfg;
-    const Module& m = n.mods[sp.mod];
-    const TT& tin = st.t[sp.in0];
-    const int H = tin.H, cin = m.cin, cout = m.cout;
-    const int Ho = m.up ? 2 * H : (m.down ? H / 2 : H);
-    const bool resample = m.up || m.down, has_sc = cin != cout || resample;
-    const float* h = tin.p;
-    float *op0 = sp.sv[0], *rs0 = sp.sv[1], *ms0 = sp.sv[2], *c0 = sp.sv[3], *a1 = sp.sv[4], *rs1 = sp.sv[5], *ms1 = sp.sv[6], *mask = sp.sv[7],
-          *xr = sp.sv[8];
-    float* dh = alloc(act_n(H, cin));
-    const size_t mk = top;
-    int rc;
-    float* dout = st.t[sp.out].g;
-    if (skip_scale() != 1.f) {                       // out = (x + h) / sqrt(2)
-      float* ds = alloc(act_n(Ho, cout));
-      rc = scale_into(dout, ds, skip_scale(), act_n(Ho, cout)); if (rc) return rc;
-      dout = ds;
-    }
-    // Conv_1
-    rc = wgrad(a1, dout, DW(m.idx, "Conv_1.weight"), cout, cout, Ho, 3, 1, 0, 0, 3); if (rc) return rc;
-    rc = bias_grad(dout, DW(m.idx, "Conv_1.bias"), cout, Ho); if (rc) return rc;
-    float* d1 = alloc(act_n(Ho, cout));
-    rc = conv(dout, W(m.idx, "Conv_1.weight"), nullptr, d1, cout, cout, Ho, 3, 1, 0, 0, 3 | 4); if (rc) return rc;
-    if (mask) TG_RUN(csd_mul(d1, mask, d1, (int64_t)act_n(Ho, cout), s));
-    float* d1b = alloc(act_n(Ho, cout));
-    rc = gn_bwd(c0, W(m.idx, "GroupNorm_1.weight"), W(m.idx, "GroupNorm_1.bias"), rs1, ms1, d1, d1b, DW(m.idx, "GroupNorm_1.weight"),
-                DW(m.idx, "GroupNorm_1.bias"), cout, Ho, act);
-    if (rc) return rc;
-    d1 = d1b;
-    if (pg) {
-      float* dd = alloc((size_t)B * cout);
-      rc = sum_pixels(d1, dd, cout, Ho); if (rc) return rc;
-      TG_RUN(csd_sum_rows(dd, DW(m.idx, "Conv_0.bias"), B, cout, s));
-      rc = linear_bwd(st.temb2_act, CSD_ACT_NONE, W(m.idx, "Dense_0.weight"), dd, DW(m.idx, "Dense_0.weight"), DW(m.idx, "Dense_0.bias"), dtemb_act,
-                      4 * c.nf, cout);
-      if (rc) return rc;
-    }
-    rc = wgrad(op0, d1, DW(m.idx, "Conv_0.weight"), cin, cout, Ho, 3, 1, 0, 0, 3); if (rc) return rc;
+    rc = wgrad(sp.op0, d1, DW(m.idx, "Conv_0.weight"), cin, cout, Ho); if (rc) return rc;
     float* d0 = alloc(act_n(Ho, cin));
-    rc = conv(d1, W(m.idx, "Conv_0.weight"), nullptr, d0, cout, cin, Ho, 3, 1, 0, 0, 3 | 4); if (rc) return rc;
-    if (resample) {                                  // through the FIR of the h branch: the other direction's geometry, flipped taps
+    rc = conv(d1, W(m.idx, "Conv_0.weight"), nullptr, d0, cout, cin, Ho, {.layout = NHWC | CSD_WEIGHT_T}); if (rc) return rc;
+    if (f.resample()) {                              // through the FIR of the h branch: the other direction's geometry, flipped taps
       float* d0l = alloc(act_n(H, cin));
-      rc = fir(d0, d0l, B, Ho, cin, m.up == 0, true); if (rc) return rc;
+      rc = fir(d0, d0l, B, Ho, cin, !f.up, true); if (rc) return rc;
       d0 = d0l;
     }
-    const float* add = dout;                         // the identity shortcut's gradient
-    if (has_sc) {                                    // Conv_2 (1x1 OIHW) on the (resampled) block input
-      rc = wgrad(resample ? xr : h, dout, DW(m.idx, "Conv_2.weight"), cin, cout, Ho, 1, 1, 0, 0, 3); if (rc) return rc;
-      rc = bias_grad(dout, DW(m.idx, "Conv_2.bias"), cout, Ho); if (rc) return rc;
+    const float* add = dout;                         // the identity shortcut's gradient; it joins dh inside the GroupNorm_0 backward
+    if (f.sc_w) {
+      rc = f.sc_swap ? wgrad(dout, xs, DW(m.idx, f.sc_w), cout, cin, Ho, {.k = 1}) : wgrad(xs, dout, DW(m.idx, f.sc_w), cin, cout, Ho, {.k = 1});
+      if (rc) return rc;
+      rc = bias_grad(dout, DW(m.idx, f.sc_b), cout, Ho); if (rc) return rc;
       float* dsc = alloc(act_n(Ho, cin));
-      rc = conv(dout, W(m.idx, "Conv_2.weight"), nullptr, dsc, cout, cin, Ho, 1, 1, 0, 0, 3 | 4); if (rc) return rc;
-      if (resample) {
+      rc = conv(dout, W(m.idx, f.sc_w), nullptr, dsc, cout, cin, Ho, {.k = 1, .layout = f.sc_dgrad_layout}); if (rc) return rc;
+      if (f.resample()) {
         float* dscl = alloc(act_n(H, cin));
-        rc = fir(dsc, dscl, B, Ho, cin, m.up == 0, true); if (rc) return rc;
+        rc = fir(dsc, dscl, B, Ho, cin, !f.up, true); if (rc) return rc;
         dsc = dscl;
       }
       add = dsc;
     }
-    rc = gn_bwd(h, W(m.idx, "GroupNorm_0.weight"), W(m.idx, "GroupNorm_0.bias"), rs0, ms0, d0, dh, DW(m.idx, "GroupNorm_0.weight"),
+    rc = gn_bwd(h, W(m.idx, "GroupNorm_0.weight"), W(m.idx, "GroupNorm_0.bias"), sp.rs0, sp.ms0, d0, dh, DW(m.idx, "GroupNorm_0.weight"),
                 DW(m.idx, "GroupNorm_0.bias"), cin, H, act, add);
     if (rc) return rc;
     top = mk;
     return contribute(sp.in0, dh);
+  }
+
+  // the head or one level of the output pyramid (out_fwd): conv weight gradient, NCHW bias sum, transposed conv, GroupNorm backward;
+  // a pyramid level that added FIR-up of the coarser level hands that level its gradient
+  int out_bwd(const TStep& sp, const float* d_out) {
+    const Module& mg = n.mods[sp.mod];
+    const Module& mc = n.mods[sp.mod + 1];
+    const TT& tin = st.t[sp.in0];
+    const int H = tin.H, C = mg.cin, Co = n.cfg.out_channels;
+    const float* dP = (sp.kind == TS_HEAD || (sp.flag & PYR_CALLER_OUT)) ? d_out : st.t[sp.out].g;
+    float* dh = alloc(act_n(H, C));
+    float* dprev = (sp.flag & PYR_ADDS_COARSER) ? alloc((size_t)B * Co * (H / 2) * (H / 2)) : nullptr;
+    const size_t mk = top;
+    int rc = wgrad(sp.op0, dP, DW(mc.idx, "weight"), C, Co, H, {.layout = CSD_IN_NHWC}); if (rc) return rc;
+    if (pg) {                                        // bias: NCHW gradient -> per-(sample, channel) sums -> batch sum
+      float* bc = alloc((size_t)B * Co);
+      TG_RUN(csd_sum_inner(dP, bc, (int64_t)B * Co, (int64_t)H * H, s));
+      TG_RUN(csd_sum_rows(bc, DW(mc.idx, "bias"), B, Co, s));
+    }
+    float* dg = alloc(act_n(H, C));
+    rc = conv(dP, W(mc.idx, "weight"), nullptr, dg, Co, C, H, {.layout = CSD_OUT_NHWC | CSD_WEIGHT_T}); if (rc) return rc;      // NCHW in
+    rc = gn_bwd(tin.p, W(mg.idx, "weight"), W(mg.idx, "bias"), sp.rs0, sp.ms0, dg, dh, DW(mg.idx, "weight"), DW(mg.idx, "bias"), C, H, act);
+    if (rc) return rc;
+    if (dprev) { rc = fir(dP, dprev, B * Co, H, 1, false, true); if (rc) return rc; }      // d pyramid_upsample
+    top = mk;
+    rc = contribute(sp.in0, dh); if (rc) return rc;
+    if (dprev) st.t[sp.in1].g = dprev;               // (the coarser level's only consumer)
+    return CSD_OK;
   }
 
   int attn_bwd(const TStep& sp) {
@@ -799,7 +763,6 @@ struct TG {
     const int H = tin.H, C = m.cin;
     const float* h = tin.p;
     float* dout = st.t[sp.out].g;
-    float *t = sp.sv[0], *rs = sp.sv[1], *ms = sp.sv[2], *qkv = sp.sv[3], *a = sp.sv[4];
     float* dh = alloc(act_n(H, C));
     const size_t mk = top;
     int rc;
@@ -809,36 +772,32 @@ struct TG {
       dout = ds;
     }
     // NIN_3
-    rc = wgrad(dout, a, DW(m.idx, "NIN_3.W"), C, C, H, 1, 1, 0, 0, 3); if (rc) return rc;
+    rc = wgrad(dout, sp.attn, DW(m.idx, "NIN_3.W"), C, C, H, {.k = 1}); if (rc) return rc;
     rc = bias_grad(dout, DW(m.idx, "NIN_3.b"), C, H); if (rc) return rc;
     float* da = alloc(act_n(H, C));
-    rc = conv(dout, W(m.idx, "NIN_3.W"), nullptr, da, C, C, H, 1, 1, 0, 0, 3); if (rc) return rc;
+    rc = conv(dout, W(m.idx, "NIN_3.W"), nullptr, da, C, C, H, {.k = 1}); if (rc) return rc;
     // attention core
     float* dqkv = alloc(act_n(H, 3 * C));
     {
       const size_t m2 = top;
       float* sc = alloc_bytes(csd_attention_backward_scratch_bytes(B, C, H * H, 1));
-      TG_RUN(csd_attention_backward_nhwc(qkv, da, dqkv, B, H * H, C, sc, s));
+      TG_RUN(csd_attention_backward_nhwc(sp.qkv, da, dqkv, B, H * H, C, sc, s));
       top = m2;
     }
     // q | k | v contraction: gradients of the concatenated weight, scattered back to NIN_0..2
     float* wc = alloc((size_t)C * 3 * C);
     float* dwc = alloc((size_t)C * 3 * C);
     float* dbc = alloc(3 * C);
-    rc = wgrad(dqkv, t, dwc, 3 * C, C, H, 1, 1, 0, 0, 3); if (rc) return rc;           // dW[i, o] with o over 3C
+    rc = wgrad(dqkv, sp.op0, dwc, 3 * C, C, H, {.k = 1}); if (rc) return rc;           // dW[i, o] with o over 3C
     rc = bias_grad(dqkv, dbc, 3 * C, H); if (rc) return rc;
-    for (int j = 0; j < 3 && !dry; ++j) {
-      char wn[16], bn[16];
-      snprintf(wn, sizeof(wn), "NIN_%d.W", j); snprintf(bn, sizeof(bn), "NIN_%d.b", j);
-      hipLaunchKernelGGL(copy2d_kernel, dim3(launch_blocks((size_t)C * C)), dim3(256), 0, s, W(m.idx, wn), C, wc + j * C, 3 * C, C, C);
+    rc = qkv_weight(m.idx, C, wc, nullptr); if (rc) return rc;
+    for (int j = 0; j < 3 && !dry && pg; ++j) {
+      hipLaunchKernelGGL(copy2d_kernel, dim3(launch_blocks((size_t)C * C)), dim3(256), 0, s, dwc + j * C, 3 * C, DW(m.idx, QKV_W[j]), C, C, C);
       CSD_LAUNCH_CHECK();
-      if (!pg) continue;
-      hipLaunchKernelGGL(copy2d_kernel, dim3(launch_blocks((size_t)C * C)), dim3(256), 0, s, dwc + j * C, 3 * C, DW(m.idx, wn), C, C, C);
-      CSD_LAUNCH_CHECK();
-      TG_RUN(copy(dbc + j * C, DW(m.idx, bn), C));
+      TG_RUN(copy(dbc + j * C, DW(m.idx, QKV_B[j]), C));
     }
-    rc = conv(dqkv, wc, nullptr, da, 3 * C, C, H, 1, 1, 0, 0, 3); if (rc) return rc;    // dt = dqkv . Wcat^T (Wcat read as OIHW [C, 3C])
-    rc = gn_bwd(h, W(m.idx, "GroupNorm_0.weight"), W(m.idx, "GroupNorm_0.bias"), rs, ms, da, dh, DW(m.idx, "GroupNorm_0.weight"),
+    rc = conv(dqkv, wc, nullptr, da, 3 * C, C, H, {.k = 1}); if (rc) return rc;    // dt = dqkv . Wcat^T (Wcat read as OIHW [C, 3C])
+    rc = gn_bwd(h, W(m.idx, "GroupNorm_0.weight"), W(m.idx, "GroupNorm_0.bias"), sp.rs0, sp.ms0, da, dh, DW(m.idx, "GroupNorm_0.weight"),
                 DW(m.idx, "GroupNorm_0.bias"), C, H, CSD_ACT_NONE, dout);
     if (rc) return rc;
     top = mk;
@@ -868,7 +827,7 @@ struct TG {
     const size_t mk = top;
     float* w = nullptr;
     int rc = x_weight_slice(W(m.idx, "Conv_0.weight"), m.cout, 1, &w); if (rc) return rc;
-    rc = conv(to.g, w, nullptr, g, m.cout, cx, side, 1, 1, 0, 0, 1 | 4); if (rc) return rc;
+    rc = conv(to.g, w, nullptr, g, m.cout, cx, side, {.k = 1, .layout = CSD_IN_NHWC | CSD_WEIGHT_T}); if (rc) return rc;
     if (dpyr) {
       float* u = alloc(np);
       rc = fir(dpyr, u, B * cx, side / 2, 1, true, true); if (rc) return rc;
@@ -887,7 +846,7 @@ struct TG {
     if (n.cfg.x_squeeze) d_x = alloc(np);            // (the squeezed gradient; scattered into the caller's image below)
     float* w = nullptr;
     int rc = x_weight_slice(W(m.idx, "weight"), n.cfg.nf, 9, &w); if (rc) return rc;
-    rc = conv(to.g, w, nullptr, d_x, n.cfg.nf, cx, S, 3, 1, 0, 0, 1 | 4); if (rc) return rc;
+    rc = conv(to.g, w, nullptr, d_x, n.cfg.nf, cx, S, {.layout = CSD_IN_NHWC | CSD_WEIGHT_T}); if (rc) return rc;
     if (dpyr) {
       float* u = alloc(np);
       rc = fir(dpyr, u, B * cx, S / 2, 1, true, true); if (rc) return rc;
@@ -955,34 +914,13 @@ struct TG {
         rc = marks_reached(n.mods[st.steps[i + 1].mod].idx); if (rc) return rc;
       }
       switch (sp.kind) {
-        case TS_HEAD: {
-          const Module& mg = n.mods[sp.mod];
-          const Module& mc = n.mods[sp.mod + 1];
-          const TT& tin = st.t[sp.in0];
-          const int H = tin.H, C = mg.cin, Co = c.out_channels;
-          float* dh = alloc(act_n(H, C));
-          const size_t mk = top;
-          rc = wgrad(sp.sv[0], d_out, DW(mc.idx, "weight"), C, Co, H, 3, 1, 0, 0, 1); if (rc) return rc;
-          if (pg) {                                  // bias: NCHW gradient -> per-(sample, channel) sums -> batch sum
-            float* bc = alloc((size_t)B * Co);
-            TG_RUN(csd_sum_inner(d_out, bc, (int64_t)B * Co, (int64_t)H * H, s));
-            TG_RUN(csd_sum_rows(bc, DW(mc.idx, "bias"), B, Co, s));
-          }
-          float* dg = alloc(act_n(H, C));
-          rc = conv(d_out, W(mc.idx, "weight"), nullptr, dg, Co, C, H, 3, 1, 0, 0, 2 | 4); if (rc) return rc;
-          rc = gn_bwd(tin.p, W(mg.idx, "weight"), W(mg.idx, "bias"), sp.sv[1], sp.sv[2], dg, dh, DW(mg.idx, "weight"), DW(mg.idx, "bias"), C,
-                      H, act);
-          if (rc) return rc;
-          top = mk;
-          rc = contribute(sp.in0, dh); if (rc) return rc;
-          break;
-        }
-        case TS_RES: rc = (c.arch == 1 ? respp_bwd(sp, dtemb_act) : res_bwd(sp, dtemb_act)); if (rc) return rc; break;
+        case TS_HEAD: case TS_PYR: rc = out_bwd(sp, d_out); if (rc) return rc; break;
+        case TS_RES: rc = res_bwd(sp, dtemb_act); if (rc) return rc; break;
         case TS_COMBINE: {                           // out = Conv_0(pyramid) + h: h's gradient is dout; the pyramid's only when d_x is wanted
           const Module& m = n.mods[sp.mod];
           const TT& to = st.t[sp.out];
           const int cio = c.x_channels + c.y_channels;
-          rc = wgrad(sp.sv[0], to.g, DW(m.idx, "Conv_0.weight"), cio, m.cout, to.H, 1, 1, 0, 0, 2); if (rc) return rc;
+          rc = wgrad(sp.pyr, to.g, DW(m.idx, "Conv_0.weight"), cio, m.cout, to.H, {.k = 1, .layout = CSD_OUT_NHWC}); if (rc) return rc;
           rc = bias_grad(to.g, DW(m.idx, "Conv_0.bias"), m.cout, to.H); if (rc) return rc;
           if (want_dx) { rc = pyramid_dx(m, to); if (rc) return rc; }
           rc = contribute(sp.in0, to.g); if (rc) return rc;
@@ -1017,32 +955,6 @@ struct TG {
           if (dsrc) { rc = contribute(sp.in1, dsrc); if (rc) return rc; }
           break;
         }
-        case TS_PYR: {                               // pyramid level: Conv(act(GroupNorm(h))) (+ FIR-up of the coarser level), NCHW
-          const Module& mg = n.mods[sp.mod];
-          const Module& mc = n.mods[sp.mod + 1];
-          const TT& tin = st.t[sp.in0];
-          const int H = tin.H, C = mg.cin, Co = c.x_channels + c.y_channels;
-          const float* dP = (sp.flag & 2) ? d_out : st.t[sp.out].g;
-          float* dh = alloc(act_n(H, C));
-          float* dprev = (sp.flag & 1) ? alloc((size_t)B * Co * (H / 2) * (H / 2)) : nullptr;
-          const size_t mk = top;
-          rc = wgrad(sp.sv[0], dP, DW(mc.idx, "weight"), C, Co, H, 3, 1, 0, 0, 1); if (rc) return rc;
-          if (pg) {
-            float* bc = alloc((size_t)B * Co);
-            TG_RUN(csd_sum_inner(dP, bc, (int64_t)B * Co, (int64_t)H * H, s));
-            TG_RUN(csd_sum_rows(bc, DW(mc.idx, "bias"), B, Co, s));
-          }
-          float* dg = alloc(act_n(H, C));
-          rc = conv(dP, W(mc.idx, "weight"), nullptr, dg, Co, C, H, 3, 1, 0, 0, 2 | 4); if (rc) return rc;
-          rc = gn_bwd(tin.p, W(mg.idx, "weight"), W(mg.idx, "bias"), sp.sv[1], sp.sv[2], dg, dh, DW(mg.idx, "weight"), DW(mg.idx, "bias"), C,
-                      H, act);
-          if (rc) return rc;
-          if (dprev) { rc = fir(dP, dprev, B * Co, H, 1, false, true); if (rc) return rc; }      // d pyramid_upsample
-          top = mk;
-          rc = contribute(sp.in0, dh); if (rc) return rc;
-          if (dprev) st.t[sp.in1].g = dprev;         // (the coarser level's only consumer)
-          break;
-        }
         case TS_ATTN: rc = attn_bwd(sp); if (rc) return rc; break;
         case TS_CAT: {
           const TT& ta = st.t[sp.in0];
@@ -1067,10 +979,10 @@ struct TG {
           float* dout = st.t[sp.out].g;
           float* dh = alloc(act_n(H, C));
           const size_t mk = top;
-          rc = wgrad(tin.p, dout, DW(m.idx, "Conv_0.weight"), C, C, H, 3, 1, 0, 1, 3); if (rc) return rc;
+          rc = wgrad(tin.p, dout, DW(m.idx, "Conv_0.weight"), C, C, H, {.up2 = 1}); if (rc) return rc;
           rc = bias_grad(dout, DW(m.idx, "Conv_0.bias"), C, 2 * H); if (rc) return rc;
           float* full = alloc(act_n(2 * H, C));
-          rc = conv(dout, W(m.idx, "Conv_0.weight"), nullptr, full, C, C, 2 * H, 3, 1, 0, 0, 3 | 4); if (rc) return rc;
+          rc = conv(dout, W(m.idx, "Conv_0.weight"), nullptr, full, C, C, 2 * H, {.layout = NHWC | CSD_WEIGHT_T}); if (rc) return rc;
           TG_RUN(csd_sumpool2_nhwc(full, dh, B, H, H, C, s));
           top = mk;
           rc = contribute(sp.in0, dh); if (rc) return rc;
@@ -1083,11 +995,11 @@ struct TG {
           float* dout = st.t[sp.out].g;
           float* dh = alloc(act_n(H, C));
           const size_t mk = top;
-          rc = wgrad(tin.p, dout, DW(m.idx, "Conv_0.weight"), C, C, H, 3, 2, 1, 0, 3); if (rc) return rc;
+          rc = wgrad(tin.p, dout, DW(m.idx, "Conv_0.weight"), C, C, H, {.stride = 2, .dpad = 1}); if (rc) return rc;
           rc = bias_grad(dout, DW(m.idx, "Conv_0.bias"), C, H / 2); if (rc) return rc;
           float* z = alloc(act_n(H, C));
           TG_RUN(csd_zero_insert_odd_nhwc(dout, z, B, H / 2, H / 2, C, s));
-          rc = conv(z, W(m.idx, "Conv_0.weight"), nullptr, dh, C, C, H, 3, 1, 0, 0, 3 | 4); if (rc) return rc;
+          rc = conv(z, W(m.idx, "Conv_0.weight"), nullptr, dh, C, C, H, {.layout = NHWC | CSD_WEIGHT_T}); if (rc) return rc;
           top = mk;
           rc = contribute(sp.in0, dh); if (rc) return rc;
           break;
@@ -1096,7 +1008,7 @@ struct TG {
           const Module& m = n.mods[sp.mod];
           const TT& to = st.t[sp.out];
           const int cio = c.x_channels + c.y_channels;
-          rc = wgrad(st.xin, to.g, DW(m.idx, "weight"), cio, nf, to.H, 3, 1, 0, 0, 2); if (rc) return rc;
+          rc = wgrad(st.xin, to.g, DW(m.idx, "weight"), cio, nf, to.H, {.layout = CSD_OUT_NHWC}); if (rc) return rc;
           rc = bias_grad(to.g, DW(m.idx, "bias"), nf, to.H); if (rc) return rc;
           if (want_dx) { rc = stem_dx(m, to); if (rc) return rc; }
           break;

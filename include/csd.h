@@ -605,6 +605,12 @@ int csd_conv3x3_block(const float* x0, const float* x1, const float* weight, con
  * convolution and is applied transposed + spatially flipped (the data gradient, without materialising that weight).
  * csd_conv2d_wgrad_ex bit 2: the stride-1 weight gradient may run with split-bf16
  * operands on the bf16 matrix cores (hi*hi + hi*lo + lo*hi, ~2^-16 relative error per product) instead of exact fp32 MFMA. */
+enum {
+  CSD_IN_NHWC = 1,           /* bit 0 */
+  CSD_OUT_NHWC = 2,          /* bit 1 */
+  CSD_WEIGHT_T = 4,          /* bit 2 of csd_conv2d_ex */
+  CSD_SPLIT_BF16 = 4         /* bit 2 of csd_conv2d_wgrad_ex */
+};
 int csd_conv2d_ex(const float* x, const float* weight, const float* bias, float* y, int B, int Cin, int Cout, int H, int W,
                   int ksize, int stride, int pad_mode, int up2, int precision, int layout, void* scratch, void* stream);
 int csd_conv2d_wgrad_ex(const float* x, const float* dy, float* dw, int B, int Cin, int Cout, int H, int W, int ksize,

@@ -163,11 +163,13 @@ def test_dropout_mask_and_backward():
     assert torch.allclose(x.grad, g * y.detach())
 
 
-def _hip_loss_and_grads(case, precision='fp32', layout='nhwc', executor='planned', dropout=None):
+def _hip_loss_and_grads(case, precision='fp32', layout='nhwc', executor='planned', dropout=None, conditional=None):
     from conditional_score_diffusion_amd import losses
     cfg, B, x, y, u, tape = cases.grad_case(case)
     if dropout is not None:
         cfg.model.dropout = dropout
+    if conditional is not None:        # False: the time-unconditional network (no embedding MLP, no Dense_0 in the blocks)
+        cfg.model.conditional = conditional
     cfg, nc, p, model = build(cfg, precision)
     model.train_layout = layout
     model.train_executor = executor
@@ -209,12 +211,14 @@ def test_training_loss_and_grads_vs_reference(golden_dir, case, layout, executor
 
 
 @pytest.mark.parametrize('precision,tol', [('fp32', 2e-5), ('fp16x3', 2e-4)])
-@pytest.mark.parametrize('case', list(cases.CASES))
-def test_planned_graph_equals_operator_graph(case, precision, tol):
+@pytest.mark.parametrize('case,conditional', [(c, None) for c in cases.CASES] + [('uncond_tiny', False)],
+                         ids=list(cases.CASES) + ['uncond_tiny-timeless'])
+def test_planned_graph_equals_operator_graph(case, conditional, precision, tol):
     """csd_unet_train_forward / csd_unet_backward against autograd over the per-layer operators, dropout 0.1 ON (same Philox
-    stream ids in both): same loss, same gradient for every parameter (the two differ only in summation order)."""
-    la, ga, ma = _hip_loss_and_grads(case, precision, 'nhwc', 'planned', dropout=0.1)
-    lb, gb, mb = _hip_loss_and_grads(case, precision, 'nhwc', 'operators', dropout=0.1)
+    stream ids in both): same loss, same gradient for every parameter (the two differ only in summation order).  The last case is
+    uncond_tiny with model.conditional = False: blocks without Dense_0, no embedding MLP."""
+    la, ga, ma = _hip_loss_and_grads(case, precision, 'nhwc', 'planned', dropout=0.1, conditional=conditional)
+    lb, gb, mb = _hip_loss_and_grads(case, precision, 'nhwc', 'operators', dropout=0.1, conditional=conditional)
     assert ma._train_calls == mb._train_calls == 1
     assert abs(la - lb) <= 1e-5 * abs(lb)
     total = float(np.sqrt(sum(float((v.double() ** 2).sum()) for v in gb.values())))
