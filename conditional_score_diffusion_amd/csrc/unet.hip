@@ -9,7 +9,7 @@
 // launches on ONE stream: no per-step host objects, no allocation, no synchronisation.
 //
 // One translation unit in pieces: this file (structs, the topology = build_modules, the parameter table, the C ABI of the network),
-// pc_loop.h (the fused PC sampler: its noise-draw schedule, the loop, the csd_pc_* entries and the cascade), unet_layout.h (ConvKernel per layer, packed-weight layout + pack_all), unet_plan.h (Builder + build_plan), unet_run.h (run_plan), unet3d.h (the 3-D DDPM
+// pc_loop.h (the fused PC sampler: its noise-draw schedule, the loop, the csd_pc_* entries and the cascade), unet_layout.h (ConvKernel per layer, packed-weight layout + pack_all), unet_plan.h (Builder: the walk's state and one step() per module; build_plan; a batch chunk is planned by a Builder of its own), unet_run.h (run_plan), unet3d.h (the 3-D DDPM
 // family, arch 2: topology, packed layout, plan and executor on conv3d.hip's kernels), train_graph.h (training forward / backward),
 // plan_digest.h (csd_unet_debug_digest).
 #include <stdarg.h>

@@ -1,5 +1,6 @@
 // unet_plan.h - the inference plan of a network for one batch size: a flat list of kernel launches with every workspace offset fixed
-// (Builder: one method per module kind; build_plan: one walk over Net::mods).  Included by unet.hip.
+// (Builder: one method per module kind, step() for one module of Net::mods with the walk's state in Builder::w; build_plan: one walk
+// over Net::mods, a batch chunk through a Builder of its own).  Included by unet.hip.
 #pragma once
 
 namespace csd {
@@ -12,14 +13,30 @@ struct Builder {
   int B;
   size_t gn_partial = NONE, nscale = NONE, nshift = NONE;   // shared scratch
   size_t dense_all = NONE;
-  float pending_scale = 1.f;          // out_scale of the NEXT conv() (NCSN++ skip_rescale: (x + h)/sqrt(2))
-  size_t next_out = NONE;             // the NEXT conv() writes here instead of allocating (a batch chunk's slice of the region's output tensor)
   int rc = CSD_OK;
   // tensors whose producing conv left per-tile GroupNorm partials behind: workspace offset -> (partials, tiles per sample)
   struct TileStats { size_t off; int tpi; };
   std::map<size_t, TileStats> tile_stats;
+  // what gn() planned: nothing (no GroupNorm in front of the consumer), a finalize over tile partials, or the streaming statistics /
+  // finalize pair pl.ops[stats_op], pl.ops[stats_op + 1].  Either way the scale / shift are in nscale / nshift behind it
+  struct Norm {
+    enum Kind { ABSENT, TILES, STREAMED } kind = ABSENT;
+    size_t stats_op = NONE;
+    explicit operator bool() const { return kind != ABSENT; }
+  };
+  // what step() carries from one module of Net::mods to the next
+  struct Walk {
+    std::vector<size_t> hs;             // skip stack
+    size_t h = NONE;                    // the current tensor
+    bool h_on_stack = true;             // ... is hs.back(): its consumer must not release it
+    size_t as_out = NONE;               // the assembled input (NONE: the fused first layer reads x, y itself)
+    size_t pyr_in = NONE;               // NCSN++ input pyramid (level 0: the in_cpad-channel padded NHWC input)
+    int pyr_side = 0, pyr_pix = 0;
+    size_t pyr = NONE, pyr_up = NONE;   // NCSN++ output pyramid [B, side, side, channels] of the level below / its FIR upsampling
+    Norm out_norm;                      // the GroupNorm R_PYR_GN / R_HEAD_GN planned for the conv behind it
+  } w;
 
-  Builder(Net& n_, Plan& p_, int B_) : n(n_), pl(p_), B(B_) {}
+  Builder(Net& n_, Plan& p_, int B_, Arena ar_ = Arena()) : n(n_), pl(p_), ar(ar_), B(B_) {}
 
   // every workspace allocation goes through here: a new tensor at an offset invalidates what was known about the old one
   size_t alloc_(size_t nfloats) {
@@ -28,13 +45,16 @@ struct Builder {
     return off;
   }
 
+  // every op enters the plan here (OP_FORK / OP_JOIN: no launch of their own)
+  void emit(const Op& o, int launches = 1) { pl.ops.push_back(o); pl.launches += launches; }
+  // algorithmic flops / bytes of the op emit() has just taken
   void count(double flops, double bytes) {
-    pl.flops += flops; pl.bytes += bytes; pl.launches += 1;
+    pl.flops += flops; pl.bytes += bytes;
     pl.ops.back().flops = flops; pl.ops.back().bytes = bytes;
   }
 
   // GroupNorm statistics of (src0|src1) -> nscale/nshift
-  void gn(size_t src0, size_t src1, int c0, int c1, int hw, const std::string& gname, const std::string& bname) {
+  Norm gn(size_t src0, size_t src1, int c0, int c1, int hw, const std::string& gname, const std::string& bname) {
     const int G = n.cfg.arch == 1 ? ncsnpp_groups(c0 + c1) : 32;
     if (src1 != NONE && (tile_stats.count(src0) != 0) != (tile_stats.count(src1) != 0)) {
       // a concatenated input of which ONE half carries epilogue partials (the skip tensor next to an Upsample output): the streaming pass
@@ -44,12 +64,11 @@ struct Builder {
       const int cs = first ? c0 : c1;
       Op s;
       s.kind = OP_GN_STATS;
-      if (gn_plan(&s.gp, B, hw, cs, 0, 1)) { rc = CSD_ERR_INVALID; return; }
+      if (gn_plan(&s.gp, B, hw, cs, 0, 1)) { rc = CSD_ERR_INVALID; return Norm{Norm::TILES}; }
       s.src0 = src; s.per_channel = true;
       s.stats = alloc_((size_t)B * s.gp.nchunk * cs * 2 * 2);      // doubles; never released (small)
       s.cls = CSD_PROF_GN_STATS; s.bytes = (double)B * hw * cs * 4;
-      pl.ops.push_back(s);
-      pl.launches += 1;
+      emit(s);
       tile_stats[src] = TileStats{s.stats, s.gp.nchunk};
     }
     const auto t0 = tile_stats.find(src0);
@@ -65,26 +84,26 @@ struct Builder {
       f.pk_w = n.copy_off.at(gname); f.pk_b = n.copy_off.at(bname);
       f.nscale = nscale; f.nshift = nshift;
       f.cls = CSD_PROF_GN_FINAL;
-      pl.ops.push_back(f);
-      pl.launches += 1;
+      emit(f);
       pl.bytes += 2.0 * B * hw * (c0 + c1) * 4;   // SURVEY 8(d) algorithmic bytes are those of the unfused op
-      return;
+      return Norm{Norm::TILES};
     }
     Op s;
     s.kind = OP_GN_STATS;
-    if (gn_plan(&s.gp, B, hw, c0, c1, G)) { rc = CSD_ERR_INVALID; return; }
+    if (gn_plan(&s.gp, B, hw, c0, c1, G)) { rc = CSD_ERR_INVALID; return Norm{Norm::TILES}; }
     s.src0 = src0; s.src1 = src1; s.stats = gn_partial;
     s.cls = CSD_PROF_GN_STATS; s.bytes = (double)B * hw * (c0 + c1) * 4;
-    pl.ops.push_back(s);
+    const size_t stats_op = pl.ops.size();
+    emit(s);
     Op f;
     f.kind = OP_GN_FINAL;
     f.gp = s.gp;
     f.stats = gn_partial; f.pk_w = n.copy_off.at(gname); f.pk_b = n.copy_off.at(bname);
     f.nscale = nscale; f.nshift = nshift;
     f.cls = CSD_PROF_GN_FINAL;
-    pl.ops.push_back(f);
-    pl.launches += 2;
+    emit(f);
     pl.bytes += 2.0 * B * hw * (c0 + c1) * 4;   // GroupNorm reads + writes its tensor
+    return Norm{Norm::STREAMED, stats_op};
   }
 
   // the arguments of conv() beside the layer's key
@@ -92,12 +111,14 @@ struct Builder {
     size_t src0 = NONE, src1 = NONE;      // sources (src1: the second of a virtual concat)
     int ih = 0, iw = 0;                   // extent of the source map
     int stride = 1, pad = 0, up = 0;
-    bool norm = false;                    // reads act(GroupNorm(sources)): scale / shift are the ones gn() has just planned
+    Norm norm;                            // reads act(GroupNorm(sources)): what gn() returned for them
     int act = CSD_ACT_NONE;
     size_t residual = NONE;               // added by the epilogue
     size_t temb_col = NONE;               // first column of the block's Dense_0 rows inside dense_all
     bool external_nchw = false;           // writes the caller's NCHW output
     int real_cin = -1;                    // input channels the flop count takes (a zero-padded input)
+    float out_scale = 1.f;                // the epilogue's factor (NCSN++ skip_rescale: (x + h)/sqrt(2))
+    size_t out_to = NONE;                 // writes here instead of allocating (a batch chunk's slice of the region's output tensor)
   };
 
   int fail(const char* what) { set_error("%s", what); rc = CSD_ERR_INVALID; return rc; }
@@ -105,8 +126,8 @@ struct Builder {
   // tap-partial form (conv_pw16.hip): pointwise contraction of act(GN(x)) to 9 * cout partial channels, then the 9-tap gather
   size_t conv_taps(const PackedConv& pc, const ConvIn& in) {
     const int ih = in.ih, iw = in.iw;
-    if (!in.norm || in.src1 != NONE || in.stride != 1 || in.up || in.pad != 1 || in.temb_col != NONE) {
-      fail("tap-partial conv on an unsupported layer"); return NONE;
+    if (!in.norm || in.src1 != NONE || in.stride != 1 || in.up || in.pad != 1 || in.temb_col != NONE || in.out_to != NONE) {
+      fail("tap-partial conv on an unsupported layer"); return NONE;      // (out_to: the head is never inside a chunk region)
     }
     if (in.act != CSD_ACT_SWISH) {      // (pw16_kernel's prologue knows SiLU only: build_packed_layout keeps every other head off this form)
       set_error("tap-partial conv: activation %d is not supported (SiLU only)", in.act); rc = CSD_ERR_INVALID; return NONE;
@@ -124,7 +145,7 @@ struct Builder {
     const size_t part = alloc_((size_t)B * ih * iw * o.cp.Cout);
     o.out = part;
     o.cls = CSD_PROF_CONV1X1;                  // (profiler classes follow the kernels: a pointwise contraction + a small gather)
-    pl.ops.push_back(o);
+    emit(o);
     const size_t out_elems = (size_t)B * ih * iw * pc.tap_cout;
     count(2.0 * out_elems * o.cp.C0 * 9, ((double)B * ih * iw * o.cp.C0 + (double)out_elems) * 4);
     pl.ops.back().bytes = (double)B * ih * iw * (o.cp.C0 + o.cp.Cout) * 4.0;
@@ -132,146 +153,157 @@ struct Builder {
     g.kind = OP_TAPSUM;
     g.src0 = part; g.pk_b = pc.b_off; g.res = in.residual;
     g.H = ih; g.W = iw; g.Cout = pc.tap_cout;
-    g.out_scale = pending_scale;
-    pending_scale = 1.f;
+    g.out_scale = in.out_scale;
     g.out_external = in.external_nchw ? 1 : 0;
     g.out = in.external_nchw ? NONE : alloc_(out_elems);
     g.cls = CSD_PROF_OTHER;
     g.bytes = (double)B * ih * iw * (o.cp.Cout + pc.tap_cout) * 4.0;
-    pl.ops.push_back(g);
-    pl.launches += 1;
+    emit(g);
     ar.release(part);
     return g.out;
   }
 
-  // convolution; returns output offset (allocated here unless external)
-  size_t conv(const std::string& key, const ConvIn& in) {
-    const PackedConv& pc = n.pconvs[n.pconv_by_name.at(key)];
-    if (pc.kernel == ConvKernel::PW16_TAPS) return conv_taps(pc, in);
-    const int ih = in.ih, iw = in.iw, stride = in.stride, up = in.up;
-    const bool norm = in.norm, external_nchw = in.external_nchw, quad = is_quad(pc.kernel);
-    Op o;
-    o.kind = OP_CONV;
-    o.cp = pc.proto;
-    o.cp.B = B; o.cp.IH = ih; o.cp.IW = iw;
-    o.cp.stride = stride; o.cp.pad = in.pad; o.cp.up = up;
-    o.cp.OH = (ih << up) / stride; o.cp.OW = (iw << up) / stride;
-    o.ns = pc.ns; o.kernel = pc.kernel;
-    // tuning only (CSD_FUSED_NORM): GroupNorm affine + activation applied by the loader / consumer kernel's loader wave (no gn_apply16
-    // pass).  (The switch also reaches a layer packed for ConvKernel::FUSED, as it always has: an experiment, not a product path)
-    bool fused = false;
-    if ((pc.kernel == ConvKernel::F16_LC || pc.kernel == ConvKernel::FUSED) && norm && stride == 1 && !up && o.cp.C0 % 32 == 0 &&
-        o.cp.C1 % 32 == 0 && !CSD_TUNE_ENV("CSD_NO_LC") && CSD_TUNE_ENV("CSD_FUSED_NORM")) {
-      ConvPlan trial = o.cp;
+  // conv(), the geometry: the layer on its kernel, validated and tiled by that kernel's *_plan_tiles.  false: failed (rc is set).
+  // *loader_norm: the tuning-only CSD_FUSED_NORM form - GroupNorm affine + activation applied by the loader / consumer kernel's loader
+  // wave (no gn_apply16 pass).  (The switch also reaches a layer packed for ConvKernel::FUSED, as it always has: an experiment, not a
+  // product path)
+  bool conv_geometry(const PackedConv& pc, const ConvIn& in, ConvPlan& cp, bool* loader_norm) {
+    const int stride = in.stride, up = in.up;
+    const bool norm = (bool)in.norm, external_nchw = in.external_nchw;
+    cp = pc.proto;
+    cp.B = B; cp.IH = in.ih; cp.IW = in.iw;
+    cp.stride = stride; cp.pad = in.pad; cp.up = up;
+    cp.OH = (in.ih << up) / stride; cp.OW = (in.iw << up) / stride;
+    *loader_norm = false;
+    if ((pc.kernel == ConvKernel::F16_LC || pc.kernel == ConvKernel::FUSED) && norm && stride == 1 && !up && cp.C0 % 32 == 0 &&
+        cp.C1 % 32 == 0 && !CSD_TUNE_ENV("CSD_NO_LC") && CSD_TUNE_ENV("CSD_FUSED_NORM")) {
+      ConvPlan trial = cp;
       if (conv16_plan_tiles(&trial, pc.ns, 2, true) == CSD_OK && trial.LC && trial.OH % trial.TH == 0) {
-        fused = true;
-        o.cp = trial;
+        *loader_norm = true;
+        cp = trial;
       }
     }
-    if (!fused) switch (pc.kernel) {
+    if (!*loader_norm) switch (pc.kernel) {
       case ConvKernel::FUSED:
-        if (external_nchw || stride != 1 || up) { fail("fused-prologue conv on an unsupported layer"); return NONE; }
-        if (convff_plan_tiles(&o.cp, pc.ns)) { rc = CSD_ERR_INVALID; return NONE; }
+        if (external_nchw || stride != 1 || up) { fail("fused-prologue conv on an unsupported layer"); return false; }
+        if (convff_plan_tiles(&cp, pc.ns)) { rc = CSD_ERR_INVALID; return false; }
         break;
       case ConvKernel::QUAD: case ConvKernel::QUAD_UP4:
-        if (external_nchw || (!norm && o.cp.C1 != 0) || (stride == 2 && (norm || up))) { fail("quad fp16 conv on an unsupported layer"); return NONE; }
-        o.cp.C0 = o.cp.C0 + o.cp.C1; o.cp.C1 = 0;
+        if (external_nchw || (!norm && cp.C1 != 0) || (stride == 2 && (norm || up))) { fail("quad fp16 conv on an unsupported layer"); return false; }
+        cp.C0 = cp.C0 + cp.C1; cp.C1 = 0;
         if (pc.kernel == ConvKernel::QUAD_UP4) {
-          if (!up || stride != 1) { fail("phase-decomposed Upsample packed for a layer that is not one"); return NONE; }
-          o.cp.up = 2;
+          if (!up || stride != 1) { fail("phase-decomposed Upsample packed for a layer that is not one"); return false; }
+          cp.up = 2;
         }
-        if (conv16q_plan_tiles(&o.cp, pc.ns)) { rc = CSD_ERR_INVALID; return NONE; }
+        if (conv16q_plan_tiles(&cp, pc.ns)) { rc = CSD_ERR_INVALID; return false; }
         break;
       case ConvKernel::PW16:
-        if (in.act != CSD_ACT_NONE || in.temb_col != NONE || external_nchw) { fail("pointwise fp16 layer with act/temb/NCHW"); return NONE; }
+        if (in.act != CSD_ACT_NONE || in.temb_col != NONE || external_nchw) { fail("pointwise fp16 layer with act/temb/NCHW"); return false; }
         break;
       case ConvKernel::F16_LC: {
-        const int kcs = norm ? conv16_kcs(pc.ns, o.cp.C0 + o.cp.C1) : 1;    // fp16-source convs stage in bursts
+        const int kcs = norm ? conv16_kcs(pc.ns, cp.C0 + cp.C1) : 1;    // fp16-source convs stage in bursts
         // (x_squeeze: the head's scattered NCHW store lives in conv_f16_kernel.h / conv_f32.hip; the loader / consumer schedule keeps its code)
-        if (conv16_plan_tiles(&o.cp, pc.ns, kcs, kcs > 1 && !CSD_TUNE_ENV("CSD_NO_LC") && !(external_nchw && n.cfg.x_squeeze))) {
-          rc = CSD_ERR_INVALID; return NONE;
+        if (conv16_plan_tiles(&cp, pc.ns, kcs, kcs > 1 && !CSD_TUNE_ENV("CSD_NO_LC") && !(external_nchw && n.cfg.x_squeeze))) {
+          rc = CSD_ERR_INVALID; return false;
         }
         break;
       }
       case ConvKernel::F32:
-        if (conv_plan_tiles(&o.cp)) { rc = CSD_ERR_INVALID; return NONE; }
+        if (conv_plan_tiles(&cp)) { rc = CSD_ERR_INVALID; return false; }
         break;
-      case ConvKernel::PW16_TAPS: case ConvKernel::STEM:      // (conv_taps above / Builder::stem)
-        fail("conv: a layer packed for another builder"); return NONE;
+      case ConvKernel::PW16_TAPS: case ConvKernel::STEM:      // (conv_taps / Builder::stem)
+        fail("conv: a layer packed for another builder"); return false;
     }
     // the packed layout depends on KC only (not on NT / tile shape)
-    if (o.cp.KC != pc.proto.KC) { fail("conv plan/pack mismatch"); return NONE; }
-    o.src0 = in.src0; o.src1 = in.src1; o.pk_w = pc.w_off; o.pk_b = pc.b_off;
-    o.res = in.residual;
-    o.nscale = norm ? nscale : NONE;
-    o.nshift = norm ? nshift : NONE;
-    size_t hi16 = NONE, lo16 = NONE;
+    if (cp.KC != pc.proto.KC) { fail("conv plan/pack mismatch"); return false; }
+    return true;
+  }
+
+  // conv(), the operand form: o.src_form, o.src0 / src1 and, where the kernel itself normalises, o.nscale / nshift
+  void conv_operand(const PackedConv& pc, const ConvIn& in, bool loader_norm, Op& o) {
+    const bool norm = (bool)in.norm, quad = is_quad(pc.kernel);
+    o.src0 = in.src0; o.src1 = in.src1;
+    o.nscale = norm ? nscale : NONE; o.nshift = norm ? nshift : NONE;
     // a quad-schedule conv WITHOUT a GroupNorm in front (Downsample / Upsample, the FIR-resampled Conv_0 of NCSN++) in the full split reads
     // its fp32 source directly: the split happens in the kernel's staging burst (no plane write / read)
-    const bool q_raw = quad && !norm && pc.ns == 2 && o.cp.C1 == 0 && (o.cp.NT == 3 || o.cp.NT == 4) && !CSD_TUNE_ENV("CSD_NO_Q_RAW");
-    if (q_raw) {
+    if (quad && !norm && pc.ns == 2 && o.cp.C1 == 0 && (o.cp.NT == 3 || o.cp.NT == 4) && !CSD_TUNE_ENV("CSD_NO_Q_RAW")) {
       o.src_form = ConvSrc::SPLIT_STAGING;
-    } else if (((pc.kernel == ConvKernel::F16_LC && norm) || quad) && !fused) {
-      // fp16 kernel: normalise + activate + split ONCE per element into fp16 planes, conv copies them
-      // (a quad-schedule conv without a GroupNorm - Upsample, the FIR-resampled Conv_0 of NCSN++ - gets a plain split)
-      const size_t nh = ((size_t)B * ih * iw * (o.cp.C0 + o.cp.C1) + 1) / 2;      // halves -> floats
-      Op ap;
-      ap.kind = OP_GN_APPLY16;
-      ap.src0 = in.src0; ap.src1 = in.src1; ap.C0 = pc.proto.C0; ap.C1 = pc.proto.C1; ap.hw = ih * iw;
-      ap.nscale = norm ? nscale : NONE; ap.nshift = norm ? nshift : NONE; ap.act = norm ? in.act : (int)CSD_ACT_NONE;
-      hi16 = alloc_(nh);
-      if (pc.ns >= 2) lo16 = alloc_(nh);
-      ap.out = hi16; ap.out2 = lo16;
-      // small maps: the GroupNorm's statistics + finalize launches (the two ops gn() has just pushed) and this pass become ONE launch
-      const size_t nops = pl.ops.size();
-      if (norm && nops >= 2 && pl.ops[nops - 2].kind == OP_GN_STATS && pl.ops[nops - 1].kind == OP_GN_FINAL &&
-          pl.ops[nops - 2].src0 == in.src0 && pl.ops[nops - 2].src1 == in.src1 && !CSD_TUNE_ENV("CSD_NO_GN_FUSED") &&
-          gn_fused16_groups(ih * iw, pc.proto.C0, pc.proto.C1, pl.ops[nops - 2].gp.G) > 0) {
-        ap.kind = OP_GN_FUSED16;
-        ap.gp = pl.ops[nops - 2].gp;
-        ap.pk_w = pl.ops[nops - 1].pk_w; ap.pk_b = pl.ops[nops - 1].pk_b;      // gamma, beta
-        ap.nscale = NONE; ap.nshift = NONE;
-        pl.ops.pop_back();
-        pl.ops.pop_back();
-        pl.launches -= 2;
-      }
-      ap.cls = CSD_PROF_GN_APPLY;
-      ap.bytes = (double)B * ih * iw * (o.cp.C0 + o.cp.C1) * (4 + 2 * (pc.ns >= 2 ? 2 : 1));
-      ap.fp8_lo = pc.ns == 3;
-      pl.ops.push_back(ap);
-      pl.launches += 1;
-      o.src0 = hi16; o.src1 = lo16;
-      o.cp.C0 = o.cp.C0 + o.cp.C1; o.cp.C1 = 0;
-      o.nscale = NONE; o.nshift = NONE;
-      o.src_form = ConvSrc::PLANES16;
+      return;
     }
+    if (!((pc.kernel == ConvKernel::F16_LC && norm) || quad) || loader_norm) return;      // fp32 sources
+    // fp16 kernel: normalise + activate + split ONCE per element into fp16 planes, conv copies them
+    // (a quad-schedule conv without a GroupNorm - Upsample, the FIR-resampled Conv_0 of NCSN++ - gets a plain split)
+    const int hw = in.ih * in.iw;
+    const size_t nh = ((size_t)B * hw * (o.cp.C0 + o.cp.C1) + 1) / 2;      // halves -> floats
+    Op ap;
+    ap.kind = OP_GN_APPLY16;
+    ap.src0 = in.src0; ap.src1 = in.src1; ap.C0 = pc.proto.C0; ap.C1 = pc.proto.C1; ap.hw = hw;
+    ap.nscale = o.nscale; ap.nshift = o.nshift; ap.act = norm ? in.act : (int)CSD_ACT_NONE;
+    ap.out = alloc_(nh);
+    if (pc.ns >= 2) ap.out2 = alloc_(nh);
+    // small maps: the GroupNorm's statistics + finalize launches (the pair gn() planned, still the plan's last two ops) and this pass
+    // become ONE launch
+    if (in.norm.kind == Norm::STREAMED && in.norm.stats_op + 2 == pl.ops.size() && !CSD_TUNE_ENV("CSD_NO_GN_FUSED") &&
+        gn_fused16_groups(hw, pc.proto.C0, pc.proto.C1, pl.ops[in.norm.stats_op].gp.G) > 0) {
+      ap.kind = OP_GN_FUSED16;
+      ap.gp = pl.ops[in.norm.stats_op].gp;
+      ap.pk_w = pl.ops[in.norm.stats_op + 1].pk_w; ap.pk_b = pl.ops[in.norm.stats_op + 1].pk_b;      // gamma, beta
+      ap.nscale = NONE; ap.nshift = NONE;
+      pl.ops.pop_back();
+      pl.ops.pop_back();
+      pl.launches -= 2;
+    }
+    ap.cls = CSD_PROF_GN_APPLY;
+    ap.bytes = (double)B * hw * (o.cp.C0 + o.cp.C1) * (4 + 2 * (pc.ns >= 2 ? 2 : 1));
+    ap.fp8_lo = pc.ns == 3;
+    emit(ap);
+    o.src0 = ap.out; o.src1 = ap.out2;
+    o.cp.C0 = o.cp.C0 + o.cp.C1; o.cp.C1 = 0;
+    o.nscale = NONE; o.nshift = NONE;
+    o.src_form = ConvSrc::PLANES16;
+  }
+
+  // conv(), the epilogue's tile statistics: where every tile lies inside one sample the epilogue also leaves (sum, sumsq) per
+  // (tile, cout) for the next GroupNorm (the quad kernel: per (tile, M half, cout); the fp32 kernel: per (tile, wave, cout))
+  void conv_tile_stats(const PackedConv& pc, Op& o) {
+    const int oh_tiled = o.cp.up == 2 ? o.cp.IH : o.cp.OH;         // (the phase form tiles the SOURCE image, four workgroups per tile)
+    // (ConvKernel::FUSED: the fused-prologue kernels tile every sample on its own - ragged tiles, where they run at all, mask their statistics)
+    // (phase-decomposed Upsample: fp32 partials per (tile, M half, phase) - in fp64 they cost the kernel more than the streaming pass
+    // over its output that they replace - and only where its tile shape does not depend on the batch: conv16q_plan_tiles)
+    if (pc.kernel == ConvKernel::PW16 || o.out_external || o.cp.taps != 9 || !(pc.kernel == ConvKernel::FUSED || oh_tiled % o.cp.TH == 0) ||
+        CSD_TUNE_ENV("CSD_NO_FUSED_STATS") || (o.cp.up == 2 && !(conv16q_up4_stats_ok(o.cp) && !CSD_TUNE_ENV("CSD_NO_UP4_STATS"))))
+      return;
+    const int per_tile = is_quad(pc.kernel) ? 2 : (pc.kernel == ConvKernel::F32 ? 4 : 1);
+    const int tpi = cdiv(oh_tiled, o.cp.TH) * o.cp.tiles_x * per_tile * (o.cp.up == 2 ? 4 : 1);
+    o.stats = alloc_((size_t)B * tpi * o.cp.Cout * 2 * 2);      // doubles; never released (small)
+    tile_stats[o.out] = TileStats{o.stats, tpi};
+  }
+
+  // convolution; returns output offset (allocated here unless external or in.out_to names one)
+  size_t conv(const std::string& key, const ConvIn& in) {
+    const PackedConv& pc = n.pconvs[n.pconv_by_name.at(key)];
+    if (pc.kernel == ConvKernel::PW16_TAPS) return conv_taps(pc, in);
+    const int ih = in.ih, iw = in.iw;
+    Op o;
+    o.kind = OP_CONV;
+    o.ns = pc.ns; o.kernel = pc.kernel;
+    bool loader_norm = false;
+    if (!conv_geometry(pc, in, o.cp, &loader_norm)) return NONE;
+    conv_operand(pc, in, loader_norm, o);
+    o.pk_w = pc.w_off; o.pk_b = pc.b_off;
+    o.res = in.residual;
     o.temb_base = dense_all;
-    o.out_scale = pending_scale;
-    pending_scale = 1.f;
+    o.out_scale = in.out_scale;
     o.act = in.act;
     o.temb_col = in.temb_col;
     o.temb_stride = n.dense_total;
-    o.out_external = external_nchw ? 1 : 0;
+    o.out_external = in.external_nchw ? 1 : 0;
     const size_t out_elems = (size_t)B * o.cp.OH * o.cp.OW * o.cp.Cout;
-    o.out = external_nchw ? NONE : (next_out != NONE ? next_out : alloc_(out_elems));
-    next_out = NONE;
-    const int oh_tiled = o.cp.up == 2 ? o.cp.IH : o.cp.OH;         // (the phase form tiles the SOURCE image, four workgroups per tile)
-    // (ConvKernel::FUSED: the fused-prologue kernels tile every sample on its own - ragged tiles, where they run at all, mask their statistics)
-    if (pc.kernel != ConvKernel::PW16 && !external_nchw && o.cp.taps == 9 && (pc.kernel == ConvKernel::FUSED || oh_tiled % o.cp.TH == 0) &&
-        !CSD_TUNE_ENV("CSD_NO_FUSED_STATS") && (o.cp.up != 2 || (conv16q_up4_stats_ok(o.cp) && !CSD_TUNE_ENV("CSD_NO_UP4_STATS")))) {
-      // (phase-decomposed Upsample: fp32 partials per (tile, M half, phase) - in fp64 they cost the kernel more than the streaming pass
-      // over its output that they replace - and only where its tile shape does not depend on the batch: conv16q_plan_tiles)
-      // every tile lies inside one sample: the epilogue also leaves (sum, sumsq) per (tile, cout) for the next
-      // GroupNorm (the quad kernel: per (tile, M half, cout); the fp32 kernel: per (tile, wave, cout))
-      const int per_tile = quad ? 2 : (pc.kernel == ConvKernel::F32 ? 4 : 1);
-      const int tpi = cdiv(oh_tiled, o.cp.TH) * o.cp.tiles_x * per_tile * (o.cp.up == 2 ? 4 : 1);
-      o.stats = alloc_((size_t)B * tpi * o.cp.Cout * 2 * 2);      // doubles; never released (small)
-      tile_stats[o.out] = TileStats{o.stats, tpi};
-    }
-    o.cls = o.cp.taps == 1 ? CSD_PROF_CONV1X1 : ((stride == 1 && !up) ? CSD_PROF_CONV3X3 : CSD_PROF_CONV3X3_RESAMPLE);
-    pl.ops.push_back(o);
-    ar.release(hi16);      // (plan-time lifetimes: the planes die right after this conv)
-    ar.release(lo16);
+    o.out = in.external_nchw ? NONE : (in.out_to != NONE ? in.out_to : alloc_(out_elems));
+    conv_tile_stats(pc, o);
+    o.cls = o.cp.taps == 1 ? CSD_PROF_CONV1X1 : ((in.stride == 1 && !in.up) ? CSD_PROF_CONV3X3 : CSD_PROF_CONV3X3_RESAMPLE);
+    emit(o);
+    if (o.src_form == ConvSrc::PLANES16) { ar.release(o.src0); ar.release(o.src1); }      // (plan-time lifetimes: the planes die right after this conv)
     const int cin = in.real_cin > 0 ? in.real_cin : (o.cp.C0 + o.cp.C1);
     count(2.0 * out_elems * cin * o.cp.taps, ((double)B * ih * iw * cin + (double)out_elems) * 4);
     // the profiler's per-launch bytes are what THIS kernel has to move (fp16 planes in, fp32 out, residual in);
@@ -297,7 +329,7 @@ struct Builder {
     // y_scale: room for the perturbed low-resolution y + sigma z of a sampling step (never released: a few KB per sample)
     if (c.y_scale) o.out2 = alloc_((size_t)B * c.y_channels * (S / c.y_scale) * (S / c.y_scale));
     o.cls = CSD_PROF_CONV3X3;
-    pl.ops.push_back(o);
+    emit(o);
     const int cin = c.x_channels + c.y_channels;
     count(2.0 * out_elems * cin * 9, ((double)B * S * S * cin + (double)out_elems) * 4);
     return o.out;
@@ -321,13 +353,12 @@ struct Builder {
       set_error("res block %d: identity shortcut on a concatenated input is not supported", m.idx);
       rc = CSD_ERR_INVALID;
     }
-    gn(x0, x1, c0, c1, hw, mname(m.idx, "GroupNorm_0.weight"), mname(m.idx, "GroupNorm_0.bias"));
+    const Norm n0 = gn(x0, x1, c0, c1, hw, mname(m.idx, "GroupNorm_0.weight"), mname(m.idx, "GroupNorm_0.bias"));
     const size_t tcol = n.cfg.conditional ? (size_t)n.dense_col.at(m.idx) : NONE;
-    const size_t h1 = conv(k + ".Conv_0", {.src0 = x0, .src1 = x1, .ih = hw_side, .iw = hw_side, .pad = 1, .norm = true, .act = n.cfg.act, .temb_col = tcol});
-    gn(h1, NONE, m.cout, 0, hw, mname(m.idx, "GroupNorm_1.weight"), mname(m.idx, "GroupNorm_1.bias"));
-    pending_scale = skip_scale();
-    next_out = out_to;
-    const size_t out = conv(k + ".Conv_1", {.src0 = h1, .ih = hw_side, .iw = hw_side, .pad = 1, .norm = true, .act = n.cfg.act, .residual = shortcut});
+    const size_t h1 = conv(k + ".Conv_0", {.src0 = x0, .src1 = x1, .ih = hw_side, .iw = hw_side, .pad = 1, .norm = n0, .act = n.cfg.act, .temb_col = tcol});
+    const Norm n1 = gn(h1, NONE, m.cout, 0, hw, mname(m.idx, "GroupNorm_1.weight"), mname(m.idx, "GroupNorm_1.bias"));
+    const size_t out = conv(k + ".Conv_1", {.src0 = h1, .ih = hw_side, .iw = hw_side, .pad = 1, .norm = n1, .act = n.cfg.act, .residual = shortcut,
+                                            .out_scale = skip_scale(), .out_to = out_to});
     if (side_on && sc_buf != NONE && rc == CSD_OK && out != NONE) pl.ops.back().side = 2;
     ar.release(h1);
     ar.release(sc_buf);
@@ -345,8 +376,7 @@ struct Builder {
     const int os = up ? side * 2 : side / 2;
     o.out = alloc_((size_t)B * os * os * C);
     o.cls = CSD_PROF_OTHER;
-    pl.ops.push_back(o);
-    pl.launches += 1;
+    emit(o);
     return o.out;
   }
 
@@ -363,7 +393,7 @@ struct Builder {
     const size_t out_elems = (size_t)B * (side / 2) * (side / 2) * m.cout;
     o.out = alloc_(out_elems);
     o.cls = CSD_PROF_CONV3X3_RESAMPLE;
-    pl.ops.push_back(o);
+    emit(o);
     // algorithmic flops: FIR + VALID stride-2 3x3 (fir) or the stride-2 3x3 (fir = False), as the reference computes them
     count(2.0 * out_elems * m.cin * 9 + (o.fir ? 2.0 * B * (side + 1) * (side + 1) * m.cin * 16 : 0.0),
           ((double)B * side * side * m.cin + 2.0 * out_elems) * 4);
@@ -378,8 +408,7 @@ struct Builder {
     o.out = alloc_((size_t)B * hw * C);
     o.cls = CSD_PROF_GN_APPLY;
     o.bytes = (double)B * hw * C * 8;
-    pl.ops.push_back(o);
-    pl.launches += 1;
+    emit(o);
     return o.out;
   }
 
@@ -398,8 +427,7 @@ struct Builder {
       o.out2 = alloc_((size_t)B * os * os * m.cin);      // FIR(x)
       o.cls = CSD_PROF_OTHER;
       o.bytes = (double)B * (hw + 2.0 * os * os) * m.cin * 4;
-      pl.ops.push_back(o);
-      pl.launches += 1;
+      emit(o);
       hr = o.out; xr = o.out2;
     } else {
       const size_t ha = gn_apply32(x, m.cin, hw, n.cfg.act);
@@ -410,11 +438,11 @@ struct Builder {
     const size_t tcol = (size_t)n.dense_col.at(m.idx);
     const size_t h1 = conv(k + ".Conv_0", {.src0 = hr, .ih = os, .iw = os, .pad = 1, .temb_col = tcol});
     ar.release(hr);
-    gn(h1, NONE, m.cout, 0, os * os, mname(m.idx, "GroupNorm_1.weight"), mname(m.idx, "GroupNorm_1.bias"));
+    const Norm n1 = gn(h1, NONE, m.cout, 0, os * os, mname(m.idx, "GroupNorm_1.weight"), mname(m.idx, "GroupNorm_1.bias"));
     const size_t sc = conv(k + ".Conv_2", {.src0 = xr, .ih = os, .iw = os});
     ar.release(xr);
-    pending_scale = skip_scale();
-    const size_t out = conv(k + ".Conv_1", {.src0 = h1, .ih = os, .iw = os, .pad = 1, .norm = true, .act = n.cfg.act, .residual = sc});
+    const size_t out = conv(k + ".Conv_1", {.src0 = h1, .ih = os, .iw = os, .pad = 1, .norm = n1, .act = n.cfg.act, .residual = sc,
+                                            .out_scale = skip_scale()});
     ar.release(h1);
     ar.release(sc);
     return out;
@@ -423,18 +451,16 @@ struct Builder {
   size_t attn_block(const Module& m, size_t x, int hw_side, size_t out_to = NONE) {
     const std::string k = std::to_string(m.idx);
     const int C = m.cin, L = hw_side * hw_side;
-    gn(x, NONE, C, 0, L, mname(m.idx, "GroupNorm_0.weight"), mname(m.idx, "GroupNorm_0.bias"));
-    const size_t qkv = conv(k + ".qkv", {.src0 = x, .ih = hw_side, .iw = hw_side, .norm = true});
+    const Norm n0 = gn(x, NONE, C, 0, L, mname(m.idx, "GroupNorm_0.weight"), mname(m.idx, "GroupNorm_0.bias"));
+    const size_t qkv = conv(k + ".qkv", {.src0 = x, .ih = hw_side, .iw = hw_side, .norm = n0});
     Op a;
     a.kind = OP_ATTN;
     a.src0 = qkv; a.hw = L; a.C0 = C;
     a.out = alloc_((size_t)B * L * C);
     a.cls = CSD_PROF_ATTENTION;
-    pl.ops.push_back(a);
+    emit(a);
     count(4.0 * B * (double)L * L * C, 0);
-    pending_scale = skip_scale();
-    next_out = out_to;
-    const size_t o = conv(k + ".NIN_3", {.src0 = a.out, .ih = hw_side, .iw = hw_side, .residual = x});
+    const size_t o = conv(k + ".NIN_3", {.src0 = a.out, .ih = hw_side, .iw = hw_side, .residual = x, .out_scale = skip_scale(), .out_to = out_to});
     ar.release(qkv);
     ar.release(a.out);
     return o;
@@ -452,27 +478,19 @@ struct Builder {
     if (fourier) e.pk_w = n.copy_off.at(mname(l0.idx - 1, "W"));
     e.C0 = nf;
     e.out = alloc_((size_t)B * l0.cin);
-    pl.ops.push_back(e);
-    Op a;
-    a.kind = OP_LINEAR;
-    a.src0 = e.out; a.out = alloc_((size_t)B * 4 * nf);
-    a.pk_w = n.copy_off.at(mname(l0.idx, "weight")); a.pk_b = n.copy_off.at(mname(l0.idx, "bias"));
-    a.C0 = l0.cin; a.Cout = 4 * nf; a.act = CSD_ACT_NONE; a.out_act = c.act;
-    pl.ops.push_back(a);
-    Op b2;
-    b2.kind = OP_LINEAR;
-    b2.src0 = a.out; b2.out = alloc_((size_t)B * 4 * nf);
-    b2.pk_w = n.copy_off.at(mname(l1.idx, "weight")); b2.pk_b = n.copy_off.at(mname(l1.idx, "bias"));
-    b2.C0 = 4 * nf; b2.Cout = 4 * nf; b2.act = CSD_ACT_NONE; b2.out_act = c.act;
-    pl.ops.push_back(b2);
-    Op d;
-    d.kind = OP_LINEAR;   // every block's Dense_0(act(temb)) in one launch
-    d.src0 = b2.out; d.out = alloc_((size_t)B * n.dense_total);
-    d.pk_w = n.dense_all_off; d.pk_b = n.dense_all_bias_off;
-    d.C0 = 4 * nf; d.Cout = n.dense_total; d.act = CSD_ACT_NONE;
-    pl.ops.push_back(d);
-    dense_all = d.out;
-    pl.launches += 4;
+    emit(e);
+    auto linear = [&](size_t src, size_t pk_w, size_t pk_b, int cin, int cout, int out_act) {
+      Op a;
+      a.kind = OP_LINEAR;
+      a.src0 = src; a.out = alloc_((size_t)B * cout);
+      a.pk_w = pk_w; a.pk_b = pk_b;
+      a.C0 = cin; a.Cout = cout; a.act = CSD_ACT_NONE; a.out_act = out_act;
+      emit(a);
+      return a.out;
+    };
+    const size_t t0 = linear(e.out, n.copy_off.at(mname(l0.idx, "weight")), n.copy_off.at(mname(l0.idx, "bias")), l0.cin, 4 * nf, c.act);
+    const size_t t1 = linear(t0, n.copy_off.at(mname(l1.idx, "weight")), n.copy_off.at(mname(l1.idx, "bias")), 4 * nf, 4 * nf, c.act);
+    dense_all = linear(t1, n.dense_all_off, n.dense_all_bias_off, 4 * nf, n.dense_total, CSD_ACT_NONE);   // every block's Dense_0(act(temb)) in one launch
     pl.flops += 2.0 * B * ((double)l0.cin * 4 * nf + 16.0 * nf * nf + 4.0 * nf * n.dense_total);
     // (only the DDPM family's plans have ever counted the embedding's bytes; the totals are pinned, see tests/golden/plan_digests.json)
     if (c.arch == 0) pl.bytes += 4.0 * B * (nf + 4 * nf + 4 * nf + 4 * nf + (4.0 * nf + 1) * 0 + 2.0 * n.dense_total);
@@ -484,8 +502,7 @@ struct Builder {
     p.kind = kind;
     p.src0 = src; p.H = p.W = side; p.C0 = C;
     p.out = alloc_((size_t)B * out_side * out_side * C);
-    pl.ops.push_back(p);
-    pl.launches += 1;
+    emit(p);
     return p.out;
   }
 
@@ -502,8 +519,83 @@ struct Builder {
     nscale = alloc_((size_t)nb * cmax);
     nshift = alloc_((size_t)nb * cmax);
   }
-};
 
+  // ---- the walk (models/ddpm.py:149-213, models/ncsnpp.py:238-388): one module of Net::mods on this Builder's batch ----
+  // (out_to: the module writes there instead of into a tensor of its own - a batch chunk's slice of the region's output)
+  void step(const Module& m, size_t out_to = NONE) {
+    const csd_unet_config& c = n.cfg;
+    const bool pp = c.arch == 1;
+    const int S = c.image_size, channels = c.x_channels + c.y_channels;
+    const std::string k = std::to_string(m.idx);
+    size_t o = NONE, sk = NONE;
+    switch (m.role) {
+      case R_EMB_FOURIER: case R_EMB_LINEAR0:
+        return;                                  // (planned with the MLP's last module)
+      case R_EMB_LINEAR1:
+        time_embedding(m);
+        return;
+      case R_STEM: {
+        const PackedConv& pc = n.pconvs[n.pconv_by_name.at(k)];
+        o = pc.kernel == ConvKernel::STEM ? stem(pc, m, S) : conv(k, {.src0 = w.as_out, .ih = S, .iw = S, .pad = 1, .real_cin = channels});
+        if (!pp) { ar.release(w.as_out); w.as_out = NONE; }      // (NCSN++ keeps it for the input pyramid: released behind the down path)
+        break;
+      }
+      case R_MID_RES_IN:                         // the down path is done: the input pyramid and the assembled input die here
+        if (pp && c.progressive_input == 1 && w.pyr_in != w.as_out) ar.release(w.pyr_in);
+        ar.release(w.as_out);
+        [[fallthrough]];
+      case R_DOWN_BLOCK: case R_MID_RES_OUT: case R_UP_BLOCK:
+        if (m.skip) { sk = w.hs.back(); w.hs.pop_back(); }
+        o = res_block(m, w.h, sk, m.cin - m.skip, m.skip, m.side, out_to);
+        break;
+      case R_ATTN: case R_MID_ATTN:
+        o = attn_block(m, w.h, m.side, out_to);
+        break;
+      case R_DOWNSAMPLE:
+        o = m.kind == M_RES ? res_block_updown(m, w.h, m.side)
+          : c.resamp_with_conv ? conv(k + ".Conv_0", {.src0 = w.h, .ih = m.side, .iw = m.side, .stride = 2})
+                               : resample_plain(OP_AVGPOOL, w.h, m.side, m.cin, m.out_side);
+        break;
+      case R_UPSAMPLE:
+        o = m.kind == M_RES ? res_block_updown(m, w.h, m.side)
+          : c.resamp_with_conv ? conv(k + ".Conv_0", {.src0 = w.h, .ih = m.side, .iw = m.side, .pad = 1, .up = 1})
+                               : resample_plain(OP_UPNEAR, w.h, m.side, m.cin, m.out_side);
+        break;
+      case R_COMBINE: {                          // pyramid_downsample (FIR, no conv), then Combine 'sum' (layerspp.py:53-57): Conv_0(input_pyramid) + h
+        const size_t pn = fir(w.pyr_in, w.pyr_side, n.in_cpad, false);
+        if (w.pyr_in != w.as_out) ar.release(w.pyr_in);
+        w.pyr_in = pn;
+        w.pyr_side /= 2;
+        o = conv(k + ".Conv_0", {.src0 = w.pyr_in, .ih = m.side, .iw = m.side, .residual = w.h, .real_cin = channels});
+        break;
+      }
+      case R_PYR_DOWN:
+        // 'residual': input_pyramid = Downsample(input_pyramid); h = (input_pyramid + h) * skip scale; input_pyramid = h.  From level 1
+        // on the source is the previous level's combined h, a live skip-stack entry: the up path releases it, never this one
+        o = pyr_conv(m, w.pyr_in, w.pyr_pix, m.side, w.h);
+        w.pyr_in = o; w.pyr_pix = m.cout;
+        break;
+      case R_PYR_GN: case R_HEAD_GN:
+        if (w.pyr != NONE) {
+          w.pyr_up = fir(w.pyr, m.side / 2, channels, true);      // pyramid_upsample
+          ar.release(w.pyr);
+        }
+        w.out_norm = gn(w.h, NONE, m.cin, 0, m.side * m.side, mname(m.idx, "weight"), mname(m.idx, "bias"));
+        return;
+      case R_PYR_CONV: case R_HEAD_CONV:         // (level 0: straight to the caller's NCHW output, pyr = NONE)
+        w.pyr = conv(k, {.src0 = w.h, .ih = m.side, .iw = m.side, .pad = 1, .norm = w.out_norm, .act = c.act, .residual = w.pyr_up,
+                         .external_nchw = m.level == 0});
+        ar.release(w.pyr_up);
+        w.pyr_up = NONE;
+        return;
+    }
+    if (!w.h_on_stack) ar.release(w.h);
+    ar.release(sk);
+    w.h = o;
+    w.h_on_stack = m.push;
+    if (m.push) w.hs.push_back(w.h);
+  }
+};
 
 // after the walk: a GroupNorm whose statistics + finalize pair survived (its consumer applies scale / shift itself: the attention
 // blocks' q/k/v contraction, the last layer) becomes ONE launch when the map is small enough for the one-sweep kernel
@@ -577,101 +669,23 @@ static int build_plan(Net& n, int B, Plan** out) {
   Builder bd(n, pl, B);
   const csd_unet_config& c = n.cfg;
   const bool pp = c.arch == 1;
-  const int S = c.image_size, last = c.n_levels - 1, channels = c.x_channels + c.y_channels;
-  const int pin = pp ? c.progressive_input : 0;
+  const int S = c.image_size, last = c.n_levels - 1;
   int cmax = c.nf;
   for (auto& m : n.mods) cmax = std::max(cmax, std::max(m.cin, m.cout));
   bd.gn_scratch(B, 0, cmax);
 
   // ---- input assembly: a launch of its own unless the fused first layer reads x, y itself (the NCSN++ input pyramid reads the tensor) ----
   const Module& stem_m = *std::find_if(n.mods.begin(), n.mods.end(), [](const Module& m) { return m.role == R_STEM; });
-  const PackedConv& stem_pc = n.pconvs[n.pconv_by_name.at(std::to_string(stem_m.idx))];
-  size_t as_out = NONE;
-  const bool fused_stem = stem_pc.kernel == ConvKernel::STEM;
-  if (!fused_stem || pin != 0) {
+  const bool fused_stem = n.pconvs[n.pconv_by_name.at(std::to_string(stem_m.idx))].kernel == ConvKernel::STEM;
+  const bool pyramid_in = pp && c.progressive_input != 0;
+  if (!fused_stem || pyramid_in) {
     Op as;
     as.kind = OP_ASSEMBLE;
-    as.out = as_out = bd.alloc_((size_t)B * S * S * n.in_cpad);
-    pl.ops.push_back(as);
-    pl.launches += 1;
+    as.out = bd.w.as_out = bd.alloc_((size_t)B * S * S * n.in_cpad);
+    bd.emit(as);
   }
-
-  // ---- the walk (models/ddpm.py:149-213, models/ncsnpp.py:238-388): one module of Net::mods at a time on the Builder's CURRENT batch ----
-  std::vector<size_t> hs;                        // skip stack
-  size_t h = NONE;                               // the current tensor
-  bool h_on_stack = true;                        // ... is hs.back(): its consumer must not release it
-  size_t pyr_in = pin != 0 ? as_out : NONE;      // NCSN++ input pyramid (level 0: the in_cpad-channel padded NHWC input)
-  int pyr_side = S, pyr_pix = n.in_cpad;
-  size_t pyr = NONE, pyr_up = NONE;              // NCSN++ output pyramid [B, side, side, channels] of the level below / its FIR upsampling
-  // (out_to: the module writes there instead of into a tensor of its own - a batch chunk's slice of the region's output)
-  auto step = [&](const Module& m, size_t out_to) {
-    const std::string k = std::to_string(m.idx);
-    size_t o = NONE, sk = NONE;
-    switch (m.role) {
-      case R_EMB_FOURIER: case R_EMB_LINEAR0:
-        return;                                  // (planned with the MLP's last module)
-      case R_EMB_LINEAR1:
-        bd.time_embedding(m);
-        return;
-      case R_STEM:
-        o = fused_stem ? bd.stem(stem_pc, m, S) : bd.conv(k, {.src0 = as_out, .ih = S, .iw = S, .pad = 1, .real_cin = channels});
-        if (!pp) { bd.ar.release(as_out); as_out = NONE; }      // (NCSN++ keeps it for the input pyramid: released behind the down path)
-        break;
-      case R_MID_RES_IN:                         // the down path is done: the input pyramid and the assembled input die here
-        if (pin == 1 && pyr_in != as_out) bd.ar.release(pyr_in);
-        bd.ar.release(as_out);
-        [[fallthrough]];
-      case R_DOWN_BLOCK: case R_MID_RES_OUT: case R_UP_BLOCK:
-        if (m.skip) { sk = hs.back(); hs.pop_back(); }
-        o = bd.res_block(m, h, sk, m.cin - m.skip, m.skip, m.side, out_to);
-        break;
-      case R_ATTN: case R_MID_ATTN:
-        o = bd.attn_block(m, h, m.side, out_to);
-        break;
-      case R_DOWNSAMPLE:
-        o = m.kind == M_RES ? bd.res_block_updown(m, h, m.side)
-          : c.resamp_with_conv ? bd.conv(k + ".Conv_0", {.src0 = h, .ih = m.side, .iw = m.side, .stride = 2})
-                               : bd.resample_plain(OP_AVGPOOL, h, m.side, m.cin, m.out_side);
-        break;
-      case R_UPSAMPLE:
-        o = m.kind == M_RES ? bd.res_block_updown(m, h, m.side)
-          : c.resamp_with_conv ? bd.conv(k + ".Conv_0", {.src0 = h, .ih = m.side, .iw = m.side, .pad = 1, .up = 1})
-                               : bd.resample_plain(OP_UPNEAR, h, m.side, m.cin, m.out_side);
-        break;
-      case R_COMBINE: {                          // pyramid_downsample (FIR, no conv), then Combine 'sum' (layerspp.py:53-57): Conv_0(input_pyramid) + h
-        const size_t pn = bd.fir(pyr_in, pyr_side, n.in_cpad, false);
-        if (pyr_in != as_out) bd.ar.release(pyr_in);
-        pyr_in = pn;
-        pyr_side /= 2;
-        o = bd.conv(k + ".Conv_0", {.src0 = pyr_in, .ih = m.side, .iw = m.side, .residual = h, .real_cin = channels});
-        break;
-      }
-      case R_PYR_DOWN:
-        // 'residual': input_pyramid = Downsample(input_pyramid); h = (input_pyramid + h) * skip scale; input_pyramid = h.  From level 1
-        // on the source is the previous level's combined h, a live skip-stack entry: the up path releases it, never this one
-        o = bd.pyr_conv(m, pyr_in, pyr_pix, m.side, h);
-        pyr_in = o; pyr_pix = m.cout;
-        break;
-      case R_PYR_GN: case R_HEAD_GN:
-        if (pyr != NONE) {
-          pyr_up = bd.fir(pyr, m.side / 2, channels, true);      // pyramid_upsample
-          bd.ar.release(pyr);
-        }
-        bd.gn(h, NONE, m.cin, 0, m.side * m.side, mname(m.idx, "weight"), mname(m.idx, "bias"));
-        return;
-      case R_PYR_CONV: case R_HEAD_CONV:         // (level 0: straight to the caller's NCHW output, pyr = NONE)
-        pyr = bd.conv(k, {.src0 = h, .ih = m.side, .iw = m.side, .pad = 1, .norm = true, .act = c.act, .residual = pyr_up,
-                          .external_nchw = m.level == 0});
-        bd.ar.release(pyr_up);
-        pyr_up = NONE;
-        return;
-    }
-    if (!h_on_stack) bd.ar.release(h);
-    bd.ar.release(sk);
-    h = o;
-    h_on_stack = m.push;
-    if (m.push) hs.push_back(h);
-  };
+  if (pyramid_in) bd.w.pyr_in = bd.w.as_out;
+  bd.w.pyr_side = S; bd.w.pyr_pix = n.in_cpad;
 
   // Batch chunks: below CHUNK_SIDE^2 a launch is bound by its own dependent chain (weights -> LDS, K steps of global loads, epilogue), not by
   // throughput - at 5^2 / 10^2 a kernel takes the same ~20 us for 8 samples as for 64 (profiles/r06_*: timeline by batch).  The levels
@@ -697,82 +711,62 @@ static int build_plan(Net& n, int B, Plan** out) {
     if (K > 1 && m.level == l0 && m.last_up) i_hi = m.idx;
   }
   for (size_t i = 0; i < n.mods.size(); ++i) {
-    if (i != i_lo) { step(n.mods[i], NONE); continue; }
+    if (i != i_lo) { bd.step(n.mods[i]); continue; }
     const int side0 = S >> l0, Bc = cdiv(B, K);
-    const size_t in_full = hs.back();                   // [B, side0, side0, ch]: the Downsample output that enters level l0
+    const size_t in_full = bd.w.hs.back();              // [B, side0, side0, ch]: the Downsample output that enters level l0
     const size_t in_ps = (size_t)side0 * side0 * n.mods[i_lo].cin, out_ps = (size_t)side0 * side0 * n.mods[i_hi].cout;
-    const size_t dense_full = bd.dense_all, gp_full = bd.gn_partial, ns_full = bd.nscale, nh_full = bd.nshift;
-    std::vector<size_t> hs_main;
-    hs_main.swap(hs);
-    auto tile_stats_main = bd.tile_stats;
-    Arena ar_main = bd.ar;
-    // one chunk's walk in the Builder's current arena
-    auto chunk_walk = [&](int b0, int nb, size_t out_slice) {
-      bd.B = nb;
-      bd.tile_stats.clear();
-      hs.assign(1, in_full + (size_t)b0 * in_ps);
-      h = hs.back(); h_on_stack = true;
-      bd.dense_all = dense_full == NONE ? NONE : dense_full + (size_t)b0 * n.dense_total;
-      bd.gn_scratch(nb, l0, cmax);                      // the chunk's own GroupNorm scratch
-      for (size_t j = i_lo; j <= i_hi; ++j) step(n.mods[j], j == i_hi ? out_slice : NONE);
-      return bd.rc;
-    };
-    // dry run of one full-size chunk: the size of a chunk's private block
-    size_t chunk_floats = 0;
-    {
-      const size_t nops = pl.ops.size();
-      const int64_t launches = pl.launches;
-      const double flops = pl.flops, bytes = pl.bytes;
-      bd.ar = Arena(0);
-      const int rc = chunk_walk(0, Bc, 0);
-      chunk_floats = (bd.ar.peak() + 63) / 64 * 64;
-      pl.ops.resize(nops);
-      pl.launches = launches; pl.flops = flops; pl.bytes = bytes;
-      bd.next_out = NONE;
-      if (rc) return rc;
-    }
-    bd.ar = ar_main;
     const size_t out_full = bd.alloc_((size_t)B * out_ps);
-    const size_t block = bd.alloc_((size_t)K * chunk_floats);
-    ar_main = bd.ar;
-    {
-      Op f;
-      f.kind = OP_FORK;
-      f.n_chunks = K;
-      pl.ops.push_back(f);
+    // samples b0 .. b0 + nb - 1 planned as a batch of their own by a Builder of their own: its arena starts at `base`, it knows no
+    // tile statistics, has its own GroupNorm scratch, reads its rows of dense_all and starts from its slice of the region's input as
+    // the one entry of its skip stack.  The main Builder is only read.  *peak: what the chunk needed, in floats from `base`
+    auto plan_chunk = [&](Plan& sink, int b0, int nb, size_t base, size_t* peak) {
+      Builder cb(n, sink, nb, Arena(base));
+      cb.dense_all = bd.dense_all == NONE ? NONE : bd.dense_all + (size_t)b0 * n.dense_total;
+      cb.gn_scratch(nb, l0, cmax);
+      cb.w.hs.assign(1, in_full + (size_t)b0 * in_ps);
+      cb.w.h = cb.w.hs.back();
+      for (size_t j = i_lo; j <= i_hi; ++j) cb.step(n.mods[j], j == i_hi ? out_full + (size_t)b0 * out_ps : NONE);
+      *peak = cb.ar.peak();
+      return cb.rc;
+    };
+    // a chunk's private block: the largest peak over the region's chunk sizes - Bc and, for a ragged batch, the last chunk's (a peak is
+    // not monotone in the batch: which convs leave never-released tile statistics depends on their tiling, that is on nb * OH) - each
+    // from a dry run into a throwaway Plan, at a base no offset of the main arena reaches (Arena::release ignores what lies below it)
+    size_t chunk_floats = 0;
+    for (const int nb : {Bc, B % Bc}) {
+      if (nb == 0) continue;
+      Plan dry;
+      size_t peak = 0;
+      const int rc = plan_chunk(dry, 0, nb, (size_t)1 << 40, &peak);
+      if (rc) return rc;
+      chunk_floats = std::max(chunk_floats, (peak + 63) / 64 * 64);
     }
+    const size_t block = bd.alloc_((size_t)K * chunk_floats);
+    Op fork, join;
+    fork.kind = OP_FORK; join.kind = OP_JOIN;
+    fork.n_chunks = join.n_chunks = K;
+    bd.emit(fork, 0);
     for (int k = 0; k < K; ++k) {
       const int b0 = k * Bc, nb = std::min(Bc, B - b0);
       if (nb <= 0) break;
       const size_t i0 = pl.ops.size();
-      bd.ar = Arena(block + (size_t)k * chunk_floats);
-      const int rc = chunk_walk(b0, nb, out_full + (size_t)b0 * out_ps);
+      size_t peak = 0;
+      const int rc = plan_chunk(pl, b0, nb, block + (size_t)k * chunk_floats, &peak);
       if (rc) return rc;
-      CSD_REQUIRE(bd.ar.peak() <= chunk_floats, "unet: a chunk outgrew its block");
+      CSD_REQUIRE(peak <= chunk_floats, "unet: a chunk outgrew its block");
       for (size_t j = i0; j < pl.ops.size(); ++j) { pl.ops[j].nb = nb; pl.ops[j].stream = k; pl.ops[j].chunk = k + 1; }
     }
-    {
-      Op j;
-      j.kind = OP_JOIN;
-      j.n_chunks = K;
-      pl.ops.push_back(j);
-    }
-    // back in the full batch
-    bd.ar = ar_main;
-    bd.B = B;
-    bd.tile_stats = tile_stats_main;
-    bd.tile_stats.erase(out_full);
-    bd.dense_all = dense_full; bd.gn_partial = gp_full; bd.nscale = ns_full; bd.nshift = nh_full;
-    hs.swap(hs_main);
+    bd.emit(join, 0);
+    // back in the full batch: the block and the region's input (consumed by every chunk's last up block) die, the walk goes on behind i_hi
     bd.ar.release(block);
-    bd.ar.release(hs.back());      // the region's input: consumed by every chunk's last up block
-    hs.pop_back();
-    h = out_full; h_on_stack = false;
+    bd.ar.release(in_full);
+    bd.w.hs.pop_back();
+    bd.w.h = out_full; bd.w.h_on_stack = false;
     i = i_hi;
   }
-  bd.ar.release(h);
+  bd.ar.release(bd.w.h);
   if (bd.rc) return bd.rc;
-  CSD_REQUIRE(hs.empty(), "unet: the skip stack is not empty behind the last module");
+  CSD_REQUIRE(bd.w.hs.empty(), "unet: the skip stack is not empty behind the last module");
   // parameters are read once per forward (+ param_bytes per NFE)
   double pbytes = 0;
   for (auto& p : n.params) pbytes += 4.0 * p.numel;

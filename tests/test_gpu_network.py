@@ -459,13 +459,18 @@ def test_batch_independence_of_network():
     assert torch.equal(full[3:4], one)
 
 
-@pytest.mark.parametrize('case,B', [('sr3_tiny', 65), ('cmde_tiny', 64), ('uncond_tiny', 69)])
+# (a 40^2 network on four levels at 33 + 32: the ragged last chunk needs MORE room than the first - a plan that sized the chunks'
+# private blocks by the first alone was refused)
+_SR3_40 = dict(name='ddpm_paired_SR3', nf=32, ch_mult=(1, 1, 2, 2), num_res_blocks=2, attn_resolutions=(), image_size=40)
+
+
+@pytest.mark.parametrize('case,B', [('sr3_tiny', 65), ('cmde_tiny', 64), ('uncond_tiny', 69), (_SR3_40, 65)])
 def test_batch_chunk_plan_returns_the_bits_of_the_unchunked_plan(case, B):
     """from 64 images on the planned executor runs the levels of <= 20^2 pixels as two batch chunks on two streams (csrc/unet.hip
     build_plan: OP_FORK / OP_JOIN, a private workspace block per chunk, slices of the full-batch tensors at the region's boundary):
     ragged chunk sizes (33 + 32, 35 + 34) included, every sample's output must be bit-identical to the same sample evaluated in a
     batch below the threshold (the unchunked plan), and a second call must not be disturbed by the first one's streams"""
-    cfg, nc, p, model = build(case, precision='fp16x3')
+    cfg, nc, p, model = build(case if isinstance(case, str) else cases.make_config(**case), precision='fp16x3')
     shape_x = tuple(cfg.data.shape_x) if hasattr(cfg.data, 'shape_x') else (cfg.data.num_channels, cfg.data.image_size, cfg.data.image_size)
     g = torch.Generator().manual_seed(11)
     x = (torch.randn((B,) + shape_x, generator=g) * 20).to(dev())
@@ -473,7 +478,7 @@ def test_batch_chunk_plan_returns_the_bits_of_the_unchunked_plan(case, B):
     if cfg.model.name == 'ddpm':
         inp = lambda sl: x[sl].contiguous()      # noqa: E731
     else:
-        y = cases.case_y(case, B=B).to(dev())
+        y = (cases.case_y(case, B=B) if isinstance(case, str) else torch.rand((B,) + tuple(cfg.data.shape_y), generator=g)).to(dev())
         inp = lambda sl: {'x': x[sl].contiguous(), 'y': y[sl].contiguous()}      # noqa: E731
     flat = lambda r: torch.cat([r['x'], r['y']], 1) if isinstance(r, dict) else r      # noqa: E731
     with torch.no_grad():

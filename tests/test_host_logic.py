@@ -482,6 +482,70 @@ def test_plan_digests_equal_the_pinned_ones(golden_dir):
     assert not diff, '%d of %d digests differ, first: %s' % (len(diff), sum(len(v) for v in want.values()), diff[:8])
 
 
+# the four configurations of test_chunked_plans_of_ragged_batches_build and, per precision, the inference-plan digest of each at
+# B = 64 as the commit BEFORE the per-chunk-size block sizing computed it (equal chunks: that sizing leaves them alone)
+_RAGGED_CHUNK_CONFIGS = [
+    dict(name='ddpm', nf=32, ch_mult=(1, 1, 2, 2), num_res_blocks=2, attn_resolutions=(), image_size=40),
+    dict(name='ddpm', nf=96, ch_mult=(1, 1, 2, 2), num_res_blocks=2, attn_resolutions=(), image_size=40),
+    dict(name='ddpm_paired_SR3', nf=32, ch_mult=(1, 1, 2, 2), num_res_blocks=3, attn_resolutions=(16, 8), image_size=40),
+    dict(name='ddpm_paired_SR3', nf=96, ch_mult=(1, 1, 2, 2), num_res_blocks=3, attn_resolutions=(16, 8), image_size=40),
+]
+_RAGGED_CHUNK_B64_PLAN_DIGESTS = {
+    'fp32': ['d2355ef4eda15497', 'aea9fc5ec0b3f273', '3595f31bcb0a6d9e', 'a6bb53b074b0b7bb'],
+    'fp16x3': ['814d3b732d78f5a8', '8e1d015fff298408', 'e5010a65bed97f0d', 'c0ae75b2259dccf0'],
+}
+
+
+def test_chunked_plans_of_ragged_batches_build():
+    """From 64 samples on the small levels of a DDPM-family plan run as two batch chunks, each in a private block of the workspace
+    (csrc/unet_plan.h: build_plan).  The block is the maximum over the region's chunk sizes of what a dry run of that size needs: a
+    chunk's peak is not monotone in its batch (which convs leave never-released tile statistics depends on their tiling), so a block
+    sized by the full chunk of 33 alone was too small for the ragged last chunk of 32 in the four configurations below at B = 65 in
+    fp16x3, and the plan failed with 'unet: a chunk outgrew its block'.  They build, at B = 65 and B = 64 in fp32 and fp16x3, and so
+    does a sweep over widths, depths, image sizes and ragged batches; at B = 64 their plans hash to the values from before the fix."""
+    import itertools
+    from conditional_score_diffusion_amd import _lib
+    from conditional_score_diffusion_amd.models import utils as mutils
+    fn = ctypes.CDLL(_lib.LIB_PATH).csd_unet_debug_digest
+    fn.restype, fn.argtypes = ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.POINTER(ctypes.c_uint64)]
+
+    def meta_model(prec, **kw):
+        cfg = cases.make_config(**kw)
+        cfg.model.csd_precision = prec
+        with torch.device('meta'):                      # (the digests need the handle only: no parameter values)
+            model = mutils.create_model(cfg)
+        model.digest_dropout = float(cfg.model.dropout)
+        return model
+
+    def plan_digest(model, B):
+        d = (ctypes.c_uint64 * 4)()
+        rc = fn(model._h, B, model.digest_dropout, d)
+        return rc, '%016x' % d[2], _lib.lib().csd_last_error()
+
+    failed = []
+    for prec in ('fp32', 'fp16x3'):
+        for i, kw in enumerate(_RAGGED_CHUNK_CONFIGS):
+            model = meta_model(prec, **kw)
+            for B in (65, 64):
+                rc, dig, err = plan_digest(model, B)
+                if rc != 0:
+                    failed.append((kw, prec, B, err))
+                elif B == 64:
+                    assert dig == _RAGGED_CHUNK_B64_PLAN_DIGESTS[prec][i], (kw, prec, dig)
+    for nf, ch_mult, image_size in itertools.product((32, 96), ((1, 2, 2), (1, 1, 2, 2)), (20, 40, 80)):
+        kw = dict(name='ddpm_paired_SR3', nf=nf, ch_mult=ch_mult, num_res_blocks=2, attn_resolutions=(), image_size=image_size)
+        if image_size % (1 << (len(ch_mult) - 1)):      # (20^2 on four levels: there is no such network to plan)
+            with pytest.raises(RuntimeError, match='not divisible'):
+                meta_model('fp16x3', **kw)
+            continue
+        model = meta_model('fp16x3', **kw)
+        for B in (65, 67, 100, 127):
+            rc, _, err = plan_digest(model, B)
+            if rc != 0:
+                failed.append((dict(nf=nf, ch_mult=ch_mult, image_size=image_size), 'fp16x3', B, err))
+    assert not failed, failed
+
+
 def test_every_sizing_entry_has_a_guarded_buffer_test():
     """tests/guarded.py:SIZING names, for every csd_*_bytes entry of the ABI, the tests of tests/test_gpu_buffers.py that run in a
     buffer of exactly the size the entry declared (those tests assert from the seam's record that it really did): a new sizing entry
