@@ -27,6 +27,9 @@ struct ConvFFArgs {
   int tiles_x, tpi, n_groups, nblocks;
   int nstage;
   int abl;                   // tuning aid (CSD_FF_ABL): 1 no weight refills, 2 no patch conversion, 4 no patch prefetch, 8 no epilogue IO
+  // conv_xk.hip, layers with a half-height bottom tile row (set by its launcher): the first tpi_full tiles of a sample are full-height,
+  // nblocks_full = B * tpi_full * n_groups work items, walked by the first 8 * wg8_full workgroups; the other workgroups walk the rest
+  int tpi_full, nblocks_full, wg8_full;
 };
 
 // LDS hand-over: this wave's ds_writes / ds_reads have completed (lgkmcnt), then the workgroup barrier.  NOT a fence: with an

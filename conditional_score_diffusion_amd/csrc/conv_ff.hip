@@ -507,6 +507,8 @@ static inline int ff_nt(int cout) { return cout % 96 == 0 ? 3 : 2; }
 // Maps that 16 does not divide (the 40^2 level of the 160^2 nets) run on RAGGED tiles - in conv_xk.hip alone: its epilogue masks the lanes
 // whose 4 x 8-pixel block lies outside the image (8 | H, W), the patch geometry pads with zeros as at any image border.  Worth it while
 // the tiles are at least 65 % full (40^2: 9 tiles of which 6.25 are work; the alternative is the quad kernel behind a gn_apply16 pass).
+// A bottom tile row of 8 rows (H % 16 == 8) runs on half-height tiles, so of the 40^2 map's 9 tile slots 6 are full-height and 3 cost
+// XK_HALF_COST each (conv_xk.hip); the right-hand tile column is still half empty.  The accepted domain is what it was.
 static bool ff_ragged_ok(const ConvPlan& p, int ns) {
   const int nstage = (p.C0 + p.C1) / 16;
   if (CSD_TUNE_ENV("CSD_XP_OPS_OFF") || CSD_TUNE_ENV("CSD_NO_RAGGED")) return false;

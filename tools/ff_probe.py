@@ -17,6 +17,8 @@ SHAPES = [  # B, C0, C1, Cout, H, residual
     (64, 192, 0, 192, 80, True),
     (64, 128, 0, 128, 64, True),       # 6, 7: nf = 128 networks (64-cout groups)
     (64, 256, 128, 128, 64, False),
+    (64, 192, 0, 192, 40, True),       # 8, 9: the 40^2 level (ragged tiles, the bottom tile row on half-height tiles)
+    (64, 192, 192, 192, 40, False),
 ]
 
 

@@ -28,3 +28,9 @@ ghz = ((t[:, 27] - t[:, 26]) / ((t[:, 29] - t[:, 28]) * 10.0)).mean()
 print('one tile (%d stages, MFMA floor %d cycles): %.0f cycles in %.2f us -> shader clock %.3f GHz' % (
     Cin // 16, Cin // 16 * 3456, (t[:, 27] - t[:, 26]).mean(), (t[:, 29] - t[:, 28]).mean() * 0.01, ghz))
 print('kernel wall per workgroup %.1f us' % ((t[:, 31] - t[:, 30]).mean() * 10.0 / 1e3))
+if H % 16 == 8:      # a launch of two walks: the first workgroups walk full-height tiles, the others the half-height bottom row
+    cyc = (t[:, 27] - t[:, 26]).astype(np.float64)
+    full = cyc > 0.8 * cyc.max()
+    if full.any() and (~full).any():
+        print('full-height tile: %d workgroups, %.0f cycles; half-height tile: %d workgroups, %.0f cycles; ratio %.3f' % (
+            full.sum(), cyc[full].mean(), (~full).sum(), cyc[~full].mean(), cyc[~full].mean() / cyc[full].mean()))
