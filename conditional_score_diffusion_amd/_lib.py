@@ -54,6 +54,13 @@ class PCInpaintParams(ctypes.Structure):
                 ('mean_scale', ctypes.POINTER(ctypes.c_float)), ('std', ctypes.POINTER(ctypes.c_float))]
 
 
+class PCColorizeParams(ctypes.Structure):
+    """csd_pc_colorize_params: gray0 is a device address, mean_scale / std host arrays of n_steps floats, matrix / inv_matrix host 3 x 3
+    arrays or NULL"""
+    _fields_ = [('gray0', ctypes.c_void_p), ('mean_scale', ctypes.POINTER(ctypes.c_float)), ('std', ctypes.POINTER(ctypes.c_float)),
+                ('matrix', ctypes.POINTER(ctypes.c_float)), ('inv_matrix', ctypes.POINTER(ctypes.c_float))]
+
+
 class CascadeStage(ctypes.Structure):
     """csd_cascade_stage: one stage of csd_pc_cascade_sample; every pointer is an address (handle, device buffers) except ``pc`` /
     ``inpaint``, which point at host structs"""
@@ -119,6 +126,15 @@ SIGNATURES = {
     'csd_pc_inpaint_step_end': (_i, [_vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _i, ctypes.POINTER(PCParams),
                                      ctypes.POINTER(PCInpaintParams), _i, _vp, _i, _vp]),
     'csd_inpaint_blend': (_i, [_vp, _vp, _vp, _vp, _vp, _f, _f, _i64, _u64, _u64, _vp]),
+    'csd_pc_colorize_sample': (_i, [_vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _i, ctypes.POINTER(PCParams),
+                                    ctypes.POINTER(PCColorizeParams), _vp]),
+    'csd_pc_colorize_step_begin': (_i, [_vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _i, ctypes.POINTER(PCParams),
+                                        ctypes.POINTER(PCColorizeParams), _i, _vp, _vp]),
+    'csd_pc_colorize_step_end': (_i, [_vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _i, ctypes.POINTER(PCParams),
+                                      ctypes.POINTER(PCColorizeParams), _i, _vp, _i, _vp]),
+    'csd_colorize_blend': (_i, [_vp, _vp, _vp, _vp, _f, _f, _i, _i64, _i, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float),
+                                _u64, _u64, _vp]),
+    'csd_colorize_gray0': (_i, [_vp, _vp, _i, _i64, ctypes.POINTER(ctypes.c_float), _vp]),
     'csd_band_split': (_i, [_vp, _i64, _vp, _i64, _i, _i, _i, ctypes.POINTER(ctypes.c_float), _vp]),
     'csd_band_merge': (_i, [_vp, _i64, _vp, _i64, _vp, _i64, _i, _i, _i, ctypes.POINTER(ctypes.c_float), _vp]),
     'csd_pc_cascade_sample': (_i, [ctypes.POINTER(CascadeStage), _i, _i, _vp, _i, _vp, _sz, _vp, _sz, _vp, ctypes.POINTER(ctypes.c_float),

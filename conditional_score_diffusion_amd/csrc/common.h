@@ -488,6 +488,11 @@ int randn_launch(float* out, int64_t n, uint64_t seed, uint64_t stream_id, hipSt
 // z == nullptr: the normals of (seed, stream_id) in registers (std == 0: no draw); x_mean may be nullptr
 int inpaint_blend_launch(float* x, float* x_mean, const float* data, const float* mask, const float* z, float m, float std, size_t n,
                          uint64_t seed, uint64_t stream_id, hipStream_t s);
+// colorization (include/csd.h: csd_colorize_blend): x [B, 3, hw] in place, gray0 [B, 1, hw], z a full-size tape tensor or nullptr;
+// init: the initial state from the prior in x; matrix / inv_matrix: host 3 x 3 or nullptr = the default / the float64 inverse
+int colorize_blend_launch(float* x, float* x_mean, const float* gray0, const float* z, float m, float std, int B, size_t hw, int init,
+                          const float* matrix, const float* inv_matrix, uint64_t seed, uint64_t stream_id, hipStream_t s);
+int colorize_gray0_launch(const float* gray, float* gray0, int B, size_t hw, const float* matrix, hipStream_t s);
 int scale_rows_launch(float* out, const float* in, const float* scale, int divide, int B, int64_t per,
                       hipStream_t s);
 // csrc/band.hip (csd_band_split / csd_band_merge; matrix: host 4 x 4 or NULL = Haar, strides in floats per sample)

@@ -1,5 +1,5 @@
 // pc_loop.h - the fused predictor-corrector sampler: its scratch, the noise-draw schedule, the loop of csd_pc_sample and its step,
-// inpainting and cascade forms.  Host code only; the kernels are sampler.hip's.  Included by unet.hip behind Evaluator.
+// inpainting, colorization and cascade forms.  Host code only; the kernels are sampler.hip's.  Included by unet.hip behind Evaluator.
 #pragma once
 
 // ---- fused PC sampler -------------------------------------------------------------------------------
@@ -34,8 +34,11 @@ __global__ void fill_labels_kernel(float* dst, float v, int B) {
 // ---- the noise-draw schedule ------------------------------------------------------------------------------------------------------------
 // The draws behind the prior form ONE sequence in the order the loop consumes them: draw j of it is Philox stream 1 + j (stream 0 is
 // the caller's prior) and lies on the tape behind the draws before it.  A schedule is the optional draw in front of the loop plus the
-// draws of one step in that order; every mode (plain, std_y, use_path, inpainting) is one list, built by pc_schedule below.
-enum { DRAW_ZY0 = 0, DRAW_ZY_PATH = 1, DRAW_ZY = 2, DRAW_Z = 3, DRAW_BLEND = 4 };      // the kinds of csd_pc_noise_draws (include/csd.h)
+// draws of one step in that order; every mode (plain, std_y, use_path, inpainting, colorization) is one list, built by pc_schedule below.
+enum { DRAW_ZY0 = 0, DRAW_ZY_PATH = 1, DRAW_ZY = 2, DRAW_Z = 3, DRAW_BLEND = 4, DRAW_COLORIZE = 5 };      // the kinds of csd_pc_noise_draws (include/csd.h)
+enum { BLEND_NONE = 0, BLEND_INPAINT = 1, BLEND_COLORIZE = 2 };      // what is re-imposed behind every phase (the `inpaint` argument of csd_pc_noise_draws)
+// the re-imposition of a call: its mode and that mode's struct
+struct PCBlend { int mode = BLEND_NONE; const csd_pc_inpaint_params* ip = nullptr; const csd_pc_colorize_params* cp = nullptr; };
 enum { PHASE_CORRECTOR = 0, PHASE_PREDICTOR = 1, PHASE_NONE = 2 };
 struct PCDraw { int kind, phase; size_t elems, offset; };      // offset: floats of the step's draws in front of it
 struct PCDrawAt { size_t offset; uint64_t stream; size_t elems; };      // where one draw of one step is: tape offset and Philox stream
@@ -48,7 +51,7 @@ struct PCSchedule {
   bool has[2] = {false, false};
   int order[2] = {PHASE_CORRECTOR, PHASE_PREDICTOR}; // execution order of the step's phases: the predictor first under use_path
   int n_pre = 0; size_t pre_elems = 0;               // the draw in front of the loop: z_y0 of use_path, or none
-  PCDraw step[6]; int n_step = 0;                    // the draws of one step (at most [zy] z [z_blend] per phase)
+  PCDraw step[6]; int n_step = 0;                    // the draws of one step (at most [zy] z [z_blend | z_colorize] per phase)
   size_t step_elems = 0;
   void add(int kind, int phase, size_t elems) {
     step[n_step++] = PCDraw{kind, phase, elems, step_elems};
@@ -68,9 +71,18 @@ struct PCSchedule {
 };
 
 // The schedule of a call with these rules and modes, and the ONE check of what they exclude (csd_pc_* and csd_pc_noise_draws).  The
-// handle's refusals come first: an inpainting entry refuses the handle before it looks at another argument.
-static int pc_schedule(PCSchedule* sc, const csd_unet* net, int B, int predictor, int corrector, bool std_y, bool path, bool inpaint) {
+// handle's refusals come first: an inpainting or colorization entry refuses the handle before it looks at another argument.
+static int pc_schedule(PCSchedule* sc, const csd_unet* net, int B, int predictor, int corrector, bool std_y, bool path, int blend) {
   const csd_unet_config& cf = net->net.cfg;
+  CSD_REQUIRE(blend >= BLEND_NONE && blend <= BLEND_COLORIZE, "pc_sample: bad inpaint mode %d (0 none, 1 inpainting, 2 colorization)", blend);
+  const bool inpaint = blend == BLEND_INPAINT, colorize = blend == BLEND_COLORIZE;
+  CSD_REQUIRE(!(colorize && is3d(net->net)), "pc_colorize: colorization is not provided for the 3-D networks (arch 2) on the device loop");
+  CSD_REQUIRE(!(colorize && cf.x_squeeze), "pc_colorize: colorization is not provided for a handle with x_squeeze (the 2x "
+              "super-resolution networks are conditional)");
+  CSD_REQUIRE(!(colorize && cf.y_scale), "pc_colorize: colorization is not provided for a handle with y_scale (the Kx "
+              "super-resolution networks are conditional)");
+  CSD_REQUIRE(!(colorize && cf.y_channels != 0), "pc_colorize: colorization runs unconditional networks only (y_channels = %d)", cf.y_channels);
+  CSD_REQUIRE(!(colorize && cf.x_channels != 3), "pc_colorize: colorization needs a 3-channel state (x_channels = %d)", cf.x_channels);
   CSD_REQUIRE(!(inpaint && is3d(net->net)), "pc_inpaint: inpainting is not provided for the 3-D networks (arch 2) on the device loop");
   CSD_REQUIRE(!(inpaint && cf.x_squeeze), "pc_inpaint: inpainting is not provided for a handle with x_squeeze (the 2x "
               "super-resolution networks are conditional)");
@@ -81,6 +93,7 @@ static int pc_schedule(PCSchedule* sc, const csd_unet* net, int B, int predictor
   CSD_REQUIRE(!(std_y && cf.y_channels == 0), "pc_sample: std_y given for an unconditional network");
   CSD_REQUIRE(!inpaint || cf.y_channels == 0, "pc_inpaint: inpainting runs unconditional networks only (y_channels = %d)", cf.y_channels);
   CSD_REQUIRE(!inpaint || (!std_y && !path), "pc_inpaint: std_y / path_coef belong to the conditional samplers");
+  CSD_REQUIRE(!colorize || (!std_y && !path), "pc_colorize: std_y / path_coef belong to the conditional samplers");
   CSD_REQUIRE(!path || (cf.y_channels > 0 && !std_y), "pc_sample: use_path needs a conditioning image and no marginal std_y");
   *sc = PCSchedule();
   // (y_scale = K: y, its noise and the bridge's y_t live at S / K; a sample of net_out is the x block, then the downsampled y block)
@@ -99,6 +112,7 @@ static int pc_schedule(PCSchedule* sc, const csd_unet* net, int B, int predictor
       sc->add(DRAW_Z, phase, sc->nx);                // (a probability-flow predictor still consumes its draw)
     }
     if (inpaint) sc->add(DRAW_BLEND, phase, sc->nx); // behind every phase, a 'none' phase included
+    if (colorize) sc->add(DRAW_COLORIZE, phase, sc->nx);      // the same place; a full-size draw whose channel 0 is used
   }
   return CSD_OK;
 }
@@ -107,7 +121,7 @@ extern "C" int64_t csd_pc_noise_draws(const csd_unet* net, int B, int predictor,
                                       int inpaint, int n_steps, int64_t* rows, int cap) {
   CSD_REQUIRE(net && B >= 1 && n_steps >= 1 && cap >= 0 && (rows || cap == 0), "pc_noise_draws: null handle / rows, or bad B, n_steps, cap");
   PCSchedule sc;
-  int rc = pc_schedule(&sc, net, B, predictor, corrector, has_std_y != 0, has_path_coef != 0, inpaint != 0);
+  int rc = pc_schedule(&sc, net, B, predictor, corrector, has_std_y != 0, has_path_coef != 0, inpaint);
   if (rc) return rc;
   int64_t n = 0;
   auto row = [&](int i, const PCDraw& d) {
@@ -129,6 +143,8 @@ struct PCCtx : PCScratch, PCSchedule {
   Evaluator ev; const float* pk; float* ws;
   const csd_pc_params* p;
   const csd_pc_inpaint_params* ip = nullptr;         // inpainting: the known pixels are re-imposed after every phase (csd_pc_inpaint_*)
+  const csd_pc_colorize_params* cp = nullptr;        // colorization: the gray channel is re-imposed after every phase (csd_pc_colorize_*)
+  bool blends() const { return ip || cp; }
   float* x; const float* y;
   int B, nchunk;
   int64_t per, net_stride;
@@ -144,9 +160,9 @@ struct PCCtx : PCScratch, PCSchedule {
 
 static int pc_setup(PCCtx* c, csd_unet* net, const void* packed, void* workspace, size_t workspace_bytes, void* scratch,
                     size_t scratch_bytes, float* x, const float* y, int B, const csd_pc_params* p, void* stream,
-                    const csd_pc_inpaint_params* ip = nullptr, bool inpaint = false) {
+                    const PCBlend& bl = PCBlend()) {
   int rc = CSD_OK;
-  if (net && p && (rc = pc_schedule(c, net, B, p->predictor, p->corrector, p->std_y != nullptr, p->path_coef != nullptr, inpaint))) return rc;
+  if (net && p && (rc = pc_schedule(c, net, B, p->predictor, p->corrector, p->std_y != nullptr, p->path_coef != nullptr, bl.mode))) return rc;
   if ((rc = check_forward_args(net, packed, workspace, workspace_bytes, B, &c->ev))) return rc;
   CSD_REQUIRE(p && x && scratch, "pc_sample: null argument");
   CSD_REQUIRE(p->n_steps >= 1 && p->labels && p->std_x, "pc_sample: per-step scalar arrays missing");
@@ -167,9 +183,14 @@ static int pc_setup(PCCtx* c, csd_unet* net, const void* packed, void* workspace
   const size_t hw = sample_elems(cf);
   c->pk = static_cast<const float*>(packed); c->ws = static_cast<float*>(workspace);
   c->p = p; c->x = x; c->y = y; c->B = B; c->s = (hipStream_t)stream;
-  if (inpaint) {
+  if (bl.mode == BLEND_INPAINT) {
+    const csd_pc_inpaint_params* ip = bl.ip;
     CSD_REQUIRE(ip && ip->data && ip->mask && ip->mean_scale && ip->std, "pc_inpaint: data, mask, mean_scale and std are required");
     c->ip = ip;
+  } else if (bl.mode == BLEND_COLORIZE) {
+    const csd_pc_colorize_params* cp = bl.cp;
+    CSD_REQUIRE(cp && cp->gray0 && cp->mean_scale && cp->std, "pc_colorize: gray0, mean_scale and std are required");
+    c->cp = cp;
   }
   static_cast<PCScratch&>(*c) = pc_scratch(scratch, cf, B);
   c->per = (int64_t)cf.x_channels * hw;
@@ -181,10 +202,18 @@ static int pc_setup(PCCtx* c, csd_unet* net, const void* packed, void* workspace
 
 // inpainting: re-impose the known pixels behind the update of a phase (sampling/unconditional.py:268-271).  The blend's draw follows
 // the phase's own; without a tape the kernel makes it in registers.  x_mean is only ever read after the last predictor phase.
+// colorization: the gray channel instead, in the decoupled channel space (colorize_blend_kernel); its draw stands where the blend's does.
 static int pc_blend(const PCCtx& c, int i, int phase) {
   const csd_pc_params* p = c.p;
-  const PCDrawAt d = c.draw(i, DRAW_BLEND, phase);
   const bool want_mean = phase == 1 && i == p->n_steps - 1 && p->denoise;
+  if (c.cp) {
+    const PCDrawAt d = c.draw(i, DRAW_COLORIZE, phase);
+    const size_t hw = c.nx / ((size_t)c.B * 3);
+    ProfScope prof(CSD_PROF_SAMPLER, 0, ((p->noise_tape ? 7.0 : 6.0) + 1.0) * c.nx * 4 / 3, c.s);
+    return colorize_blend_launch(c.x, want_mean ? c.x_mean : nullptr, c.cp->gray0, p->noise_tape ? p->noise_tape + d.offset : nullptr,
+                                 c.cp->mean_scale[i], c.cp->std[i], c.B, hw, 0, c.cp->matrix, c.cp->inv_matrix, p->seed, d.stream, c.s);
+  }
+  const PCDrawAt d = c.draw(i, DRAW_BLEND, phase);
   ProfScope prof(CSD_PROF_SAMPLER, 0, (p->noise_tape ? 5.0 : 4.0) * c.nx * 4, c.s);
   return inpaint_blend_launch(c.x, want_mean ? c.x_mean : nullptr, c.ip->data, c.ip->mask,
                               p->noise_tape ? p->noise_tape + d.offset : nullptr, c.ip->mean_scale[i], c.ip->std[i], c.nx, p->seed,
@@ -197,7 +226,7 @@ static int pc_phase(const PCCtx& c, int i, int phase, int part, float* sums_out,
   int rc;
   const csd_pc_params* p = c.p;
   if (!c.has[phase]) {                       // 'none': x stays, x_mean = x (sampling/predictors.py:182-200, correctors.py:145-163)
-    if (c.ip) return (part & 2) ? pc_blend(c, i, phase) : CSD_OK;      // (the reference wraps the 'none' update functions as well)
+    if (c.blends()) return (part & 2) ? pc_blend(c, i, phase) : CSD_OK;      // (the reference wraps the 'none' update functions as well)
     if ((part & 2) && c.is_last(phase) && i == p->n_steps - 1 && p->denoise)
       CSD_CHECK_HIP(hipMemcpyAsync(c.x_mean, c.x, c.nx * sizeof(float), hipMemcpyDeviceToDevice, c.s));
     return CSD_OK;
@@ -243,7 +272,7 @@ static int pc_phase(const PCCtx& c, int i, int phase, int part, float* sums_out,
       rc = reverse_diffusion_update_launch(c.x, c.x_mean, c.net_out, c.net_stride, zp, p->std_x[i], p->G[i], c.B, c.per, c.s);
     }
     if (rc) return rc;
-    if (c.ip && (rc = pc_blend(c, i, phase))) return rc;
+    if (c.blends() && (rc = pc_blend(c, i, phase))) return rc;
   }
   return CSD_OK;
 }
@@ -308,9 +337,9 @@ static int pc_enqueue(const PCCtx& c) {
 
 static int pc_sample_run(csd_unet* net, const void* packed, void* workspace, size_t workspace_bytes, void* scratch,
                          size_t scratch_bytes, float* x, const float* y, int B, const csd_pc_params* p,
-                         const csd_pc_inpaint_params* ip, bool inpaint, void* stream) {
+                         const PCBlend& bl, void* stream) {
   PCCtx c;
-  int rc = pc_setup(&c, net, packed, workspace, workspace_bytes, scratch, scratch_bytes, x, y, B, p, stream, ip, inpaint);
+  int rc = pc_setup(&c, net, packed, workspace, workspace_bytes, scratch, scratch_bytes, x, y, B, p, stream, bl);
   if (rc) return rc;
   if ((rc = pc_enqueue(c))) return rc;
   return pc_read_flag(c);
@@ -318,9 +347,9 @@ static int pc_sample_run(csd_unet* net, const void* packed, void* workspace, siz
 
 static int pc_step_begin_run(csd_unet* net, const void* packed, void* workspace, size_t workspace_bytes, void* scratch,
                              size_t scratch_bytes, float* x, const float* y, int B, const csd_pc_params* p,
-                             const csd_pc_inpaint_params* ip, bool inpaint, int step, float* norm_sums, void* stream) {
+                             const PCBlend& bl, int step, float* norm_sums, void* stream) {
   PCCtx c;
-  int rc = pc_setup(&c, net, packed, workspace, workspace_bytes, scratch, scratch_bytes, x, y, B, p, stream, ip, inpaint);
+  int rc = pc_setup(&c, net, packed, workspace, workspace_bytes, scratch, scratch_bytes, x, y, B, p, stream, bl);
   if (rc) return rc;
   CSD_REQUIRE(norm_sums && step >= 0 && step < p->n_steps, "pc_step_begin: bad step %d / null norm_sums", step);
   CSD_REQUIRE(!c.path, "pc_step_begin: use_path runs through csd_pc_sample only");
@@ -330,10 +359,9 @@ static int pc_step_begin_run(csd_unet* net, const void* packed, void* workspace,
 
 static int pc_step_end_run(csd_unet* net, const void* packed, void* workspace, size_t workspace_bytes, void* scratch,
                            size_t scratch_bytes, float* x, const float* y, int B, const csd_pc_params* p,
-                           const csd_pc_inpaint_params* ip, bool inpaint, int step, const float* norm_sums, int global_batch,
-                           void* stream) {
+                           const PCBlend& bl, int step, const float* norm_sums, int global_batch, void* stream) {
   PCCtx c;
-  int rc = pc_setup(&c, net, packed, workspace, workspace_bytes, scratch, scratch_bytes, x, y, B, p, stream, ip, inpaint);
+  int rc = pc_setup(&c, net, packed, workspace, workspace_bytes, scratch, scratch_bytes, x, y, B, p, stream, bl);
   if (rc) return rc;
   CSD_REQUIRE(norm_sums && global_batch >= B && step >= 0 && step < p->n_steps, "pc_step_end: bad arguments");
   if ((rc = pc_phase(c, step, 0, 2, nullptr, norm_sums, global_batch))) return rc;
@@ -345,20 +373,20 @@ static int pc_step_end_run(csd_unet* net, const void* packed, void* workspace, s
 extern "C" int csd_pc_sample(csd_unet* net, const void* packed, void* workspace, size_t workspace_bytes,
                              void* scratch, size_t scratch_bytes, float* x, const float* y, int B,
                              const csd_pc_params* p, void* stream) {
-  return pc_sample_run(net, packed, workspace, workspace_bytes, scratch, scratch_bytes, x, y, B, p, nullptr, false, stream);
+  return pc_sample_run(net, packed, workspace, workspace_bytes, scratch, scratch_bytes, x, y, B, p, PCBlend(), stream);
 }
 
 extern "C" int csd_pc_step_begin(csd_unet* net, const void* packed, void* workspace, size_t workspace_bytes, void* scratch,
                                  size_t scratch_bytes, float* x, const float* y, int B, const csd_pc_params* p, int step,
                                  float* norm_sums, void* stream) {
-  return pc_step_begin_run(net, packed, workspace, workspace_bytes, scratch, scratch_bytes, x, y, B, p, nullptr, false, step, norm_sums,
+  return pc_step_begin_run(net, packed, workspace, workspace_bytes, scratch, scratch_bytes, x, y, B, p, PCBlend(), step, norm_sums,
                            stream);
 }
 
 extern "C" int csd_pc_step_end(csd_unet* net, const void* packed, void* workspace, size_t workspace_bytes, void* scratch,
                                size_t scratch_bytes, float* x, const float* y, int B, const csd_pc_params* p, int step,
                                const float* norm_sums, int global_batch, void* stream) {
-  return pc_step_end_run(net, packed, workspace, workspace_bytes, scratch, scratch_bytes, x, y, B, p, nullptr, false, step, norm_sums,
+  return pc_step_end_run(net, packed, workspace, workspace_bytes, scratch, scratch_bytes, x, y, B, p, PCBlend(), step, norm_sums,
                          global_batch, stream);
 }
 
@@ -368,21 +396,44 @@ extern "C" size_t csd_pc_inpaint_scratch_bytes(const csd_unet* net, int B) { ret
 extern "C" int csd_pc_inpaint_sample(csd_unet* net, const void* packed, void* workspace, size_t workspace_bytes, void* scratch,
                                      size_t scratch_bytes, float* x, const float* y, int B, const csd_pc_params* p,
                                      const csd_pc_inpaint_params* ip, void* stream) {
-  return pc_sample_run(net, packed, workspace, workspace_bytes, scratch, scratch_bytes, x, y, B, p, ip, true, stream);
+  return pc_sample_run(net, packed, workspace, workspace_bytes, scratch, scratch_bytes, x, y, B, p, PCBlend{BLEND_INPAINT, ip, nullptr}, stream);
 }
 
 extern "C" int csd_pc_inpaint_step_begin(csd_unet* net, const void* packed, void* workspace, size_t workspace_bytes, void* scratch,
                                          size_t scratch_bytes, float* x, const float* y, int B, const csd_pc_params* p,
                                          const csd_pc_inpaint_params* ip, int step, float* norm_sums, void* stream) {
-  return pc_step_begin_run(net, packed, workspace, workspace_bytes, scratch, scratch_bytes, x, y, B, p, ip, true, step, norm_sums, stream);
+  return pc_step_begin_run(net, packed, workspace, workspace_bytes, scratch, scratch_bytes, x, y, B, p, PCBlend{BLEND_INPAINT, ip, nullptr}, step,
+                           norm_sums, stream);
 }
 
 extern "C" int csd_pc_inpaint_step_end(csd_unet* net, const void* packed, void* workspace, size_t workspace_bytes, void* scratch,
                                        size_t scratch_bytes, float* x, const float* y, int B, const csd_pc_params* p,
                                        const csd_pc_inpaint_params* ip, int step, const float* norm_sums, int global_batch,
                                        void* stream) {
-  return pc_step_end_run(net, packed, workspace, workspace_bytes, scratch, scratch_bytes, x, y, B, p, ip, true, step, norm_sums,
-                         global_batch, stream);
+  return pc_step_end_run(net, packed, workspace, workspace_bytes, scratch, scratch_bytes, x, y, B, p, PCBlend{BLEND_INPAINT, ip, nullptr}, step,
+                         norm_sums, global_batch, stream);
+}
+
+// ---- colorization on the same loop (include/csd.h: csd_pc_colorize_params) ----------------------------------------------------------
+extern "C" int csd_pc_colorize_sample(csd_unet* net, const void* packed, void* workspace, size_t workspace_bytes, void* scratch,
+                                      size_t scratch_bytes, float* x, const float* y, int B, const csd_pc_params* p,
+                                      const csd_pc_colorize_params* cp, void* stream) {
+  return pc_sample_run(net, packed, workspace, workspace_bytes, scratch, scratch_bytes, x, y, B, p, PCBlend{BLEND_COLORIZE, nullptr, cp}, stream);
+}
+
+extern "C" int csd_pc_colorize_step_begin(csd_unet* net, const void* packed, void* workspace, size_t workspace_bytes, void* scratch,
+                                          size_t scratch_bytes, float* x, const float* y, int B, const csd_pc_params* p,
+                                          const csd_pc_colorize_params* cp, int step, float* norm_sums, void* stream) {
+  return pc_step_begin_run(net, packed, workspace, workspace_bytes, scratch, scratch_bytes, x, y, B, p, PCBlend{BLEND_COLORIZE, nullptr, cp},
+                           step, norm_sums, stream);
+}
+
+extern "C" int csd_pc_colorize_step_end(csd_unet* net, const void* packed, void* workspace, size_t workspace_bytes, void* scratch,
+                                        size_t scratch_bytes, float* x, const float* y, int B, const csd_pc_params* p,
+                                        const csd_pc_colorize_params* cp, int step, const float* norm_sums, int global_batch,
+                                        void* stream) {
+  return pc_step_end_run(net, packed, workspace, workspace_bytes, scratch, scratch_bytes, x, y, B, p, PCBlend{BLEND_COLORIZE, nullptr, cp},
+                         step, norm_sums, global_batch, stream);
 }
 
 // ---- sequential cascades (include/csd.h: csd_cascade_stage, csd_pc_cascade_sample) ----------------------------------------------------
@@ -488,8 +539,8 @@ extern "C" int csd_pc_cascade_sample(const csd_cascade_stage* st, int n, int fin
     } else if (k == n - 1 && final_link) {
       handed[k] = g.out;
     }
-    int rc = pc_setup(&ctx[k], g.net, g.packed, workspace, workspace_bytes, scratch, pc_bytes, g.x, y, B, g.pc, stream, g.inpaint,
-                      g.inpaint != nullptr);
+    int rc = pc_setup(&ctx[k], g.net, g.packed, workspace, workspace_bytes, scratch, pc_bytes, g.x, y, B, g.pc, stream,
+                      PCBlend{g.inpaint ? BLEND_INPAINT : BLEND_NONE, g.inpaint, nullptr});
     if (rc) return cascade_fail(rc, k, n);
     STAGE_REQUIRE(!ctx[k].path, "use_path (pc->path_coef) does not run in a cascade");
     ctx[k].nonfinite = stage_flags + k;

@@ -319,6 +319,101 @@ __global__ __launch_bounds__(256) void inpaint_blend_kernel(float* __restrict__ 
   }
 }
 
+// colorization: re-impose the gray channel after an update (controllable_generation.py:143-154 of the reference).  With
+//   decouple(v)[j] = sum_i v[i]*M[i][j], couple = the same contraction with M^-1, and channel 0 of the decoupled space the gray one:
+//   masked_mean = m*gray0 ; masked = masked_mean + z0*std ; x = couple(masked, decouple(x)[1], decouple(x)[2]) ;
+//   x_mean = couple(masked_mean, decouple(x)[1], decouple(x)[2]) with the NEW x (a second decouple).
+// init: the initial state (:180-182), x holding the prior: couple(decouple(gray)*mask + decouple(prior*(1 - mask))) - the prior loses
+// its channel 0 in IMAGE space, so channel 0 of the sum is m*gray0 + decouple(0, prior1, prior2)[0].
+// One thread owns 4 consecutive pixels of one sample in all three planes.  z: a tape tensor of the state's size whose channel-0 plane
+// is read, or - z == nullptr and draw - the same elements of a full-size randn fill of (seed, stream_id): element e is lane e % 4 of
+// counter e / 4, so a group whose first element is no multiple of 4 takes its lanes from two counters.  Every contraction is
+// (v0*A0j + v1*A1j) + v2*A2j.  vec: every pointer is 16-byte aligned and hw % 4 == 0 - the planes move as float4, else element-wise.
+struct ColorMatrix { float m[3][3], inv[3][3]; };
+
+__device__ __forceinline__ void mat3_contract(const float (&a)[3][3], float v0, float v1, float v2, float out[3]) {
+#pragma unroll
+  for (int j = 0; j < 3; ++j) out[j] = (v0 * a[0][j] + v1 * a[1][j]) + v2 * a[2][j];
+}
+
+__device__ __forceinline__ void load4(const float* p, bool full, int cnt, float v[4]) {
+  if (full) {
+    const float4 a = *reinterpret_cast<const float4*>(p);
+    v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
+  } else {
+    for (int j = 0; j < cnt; ++j) v[j] = p[j];
+  }
+}
+
+__device__ __forceinline__ void store4(float* p, bool full, int cnt, const float v[4]) {
+  if (full) {
+    *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
+  } else {
+    for (int j = 0; j < cnt; ++j) p[j] = v[j];
+  }
+}
+
+__global__ __launch_bounds__(256) void colorize_blend_kernel(float* __restrict__ x, float* __restrict__ x_mean,
+                                                             const float* __restrict__ gray0, const float* __restrict__ z, float m,
+                                                             float std, size_t hw, size_t groups, size_t total, ColorMatrix cm,
+                                                             uint64_t seed, uint64_t stream_id, int draw, int init, int vec) {
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    const size_t b = i / groups, p = (i - b * groups) * 4;
+    const int cnt = p + 3 < hw ? 4 : (int)(hw - p);
+    const bool full = vec && cnt == 4;
+    const size_t e0 = b * 3 * hw + p;                // the group's first element in channel 0 of the state (and of a full-size draw)
+    float c[3][4] = {}, g0[4] = {0.f, 0.f, 0.f, 0.f}, zv[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int k = 0; k < 3; ++k) load4(x + e0 + k * hw, full, cnt, c[k]);
+    load4(gray0 + b * hw + p, full, cnt, g0);
+    if (z) {
+      load4(z + e0, full, cnt, zv);
+    } else if (draw) {
+      const int off = (int)(e0 & 3);
+      float lo[4], hi[4] = {0.f, 0.f, 0.f, 0.f};
+      philox_normal4(e0 >> 2, seed, stream_id, lo);
+      if (off) philox_normal4((e0 >> 2) + 1, seed, stream_id, hi);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) zv[j] = off + j < 4 ? lo[(off + j) & 3] : hi[(off + j) & 3];
+    }
+    float xn[3][4], xm[3][4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      float d[3], o[3];
+      const float masked_mean = m * g0[j];
+      if (init) {
+        mat3_contract(cm.m, c[0][j] * 0.f, c[1][j], c[2][j], d);
+        d[0] = masked_mean + d[0];
+      } else {
+        mat3_contract(cm.m, c[0][j], c[1][j], c[2][j], d);
+        d[0] = (z || draw) ? masked_mean + zv[j] * std : masked_mean;
+      }
+      mat3_contract(cm.inv, d[0], d[1], d[2], o);
+      xn[0][j] = o[0]; xn[1][j] = o[1]; xn[2][j] = o[2];
+      if (x_mean) {
+        mat3_contract(cm.m, o[0], o[1], o[2], d);
+        mat3_contract(cm.inv, masked_mean, d[1], d[2], o);
+        xm[0][j] = o[0]; xm[1][j] = o[1]; xm[2][j] = o[2];
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      store4(x + e0 + k * hw, full, cnt, xn[k]);
+      if (x_mean) store4(x_mean + e0 + k * hw, full, cnt, xm[k]);
+    }
+  }
+}
+
+// gray0 = decouple(gray)[:, 0]: [B, 3, hw] -> [B, 1, hw], once per sampler call
+__global__ __launch_bounds__(256) void colorize_gray0_kernel(const float* __restrict__ gray, float* __restrict__ gray0, size_t hw,
+                                                             size_t total, float m00, float m10, float m20) {
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    const size_t b = i / hw;
+    const float* g = gray + b * 3 * hw + (i - b * hw);
+    gray0[i] = (g[0] * m00 + g[hw] * m10) + g[2 * hw] * m20;
+  }
+}
+
 __global__ void scale_rows_kernel(float* __restrict__ out, const float* __restrict__ in,
                                   const float* __restrict__ scale, int divide, size_t per, size_t total) {
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total;
@@ -448,6 +543,77 @@ int inpaint_blend_launch(float* x, float* x_mean, const float* data, const float
   return CSD_OK;
 }
 
+// the host 3 x 3 matrix M (NULL: the reference's literals, controllable_generation.py:117-119) and its inverse (NULL: the float64
+// inverse of M rounded once) -> ColorMatrix; refuses max |M M^T - I| > 1e-6 and an inverse with max |M inv - I| > 1e-6
+static int color_matrix(const float* matrix, const float* inv_matrix, ColorMatrix* out, const char* who) {
+  static const float ref[9] = {5.7735014e-01f, -8.1649649e-01f, 4.7008697e-08f, 5.7735026e-01f, 4.0824834e-01f, 7.0710671e-01f,
+                               5.7735026e-01f, 4.0824822e-01f, -7.0710683e-01f};
+  const float* m = matrix ? matrix : ref;
+  double worst = 0.0;
+  for (int a = 0; a < 3; ++a)
+    for (int b = 0; b < 3; ++b) {
+      double s = 0.0;
+      for (int k = 0; k < 3; ++k) s += (double)m[3 * a + k] * (double)m[3 * b + k];
+      const double d = std::fabs(s - (a == b ? 1.0 : 0.0));
+      if (!(d <= worst)) worst = d;                  // (a NaN entry lands here too)
+    }
+  CSD_REQUIRE(worst <= 1e-6, "%s: the colorization matrix is not orthogonal: max |M M^T - I| = %.3e (limit 1e-6)", who, worst);
+  float inv[9];
+  if (inv_matrix) {
+    worst = 0.0;
+    for (int a = 0; a < 3; ++a)
+      for (int b = 0; b < 3; ++b) {
+        double s = 0.0;
+        for (int k = 0; k < 3; ++k) s += (double)m[3 * a + k] * (double)inv_matrix[3 * k + b];
+        const double d = std::fabs(s - (a == b ? 1.0 : 0.0));
+        if (!(d <= worst)) worst = d;
+      }
+    CSD_REQUIRE(worst <= 1e-6, "%s: inv_matrix is not the inverse of matrix: max |M inv - I| = %.3e (limit 1e-6)", who, worst);
+    std::copy(inv_matrix, inv_matrix + 9, inv);
+  } else {                                           // adjugate / determinant in double
+    double a[3][3], det = 0.0;
+    for (int k = 0; k < 9; ++k) a[k / 3][k % 3] = m[k];
+    double co[3][3];
+    for (int r = 0; r < 3; ++r)
+      for (int c = 0; c < 3; ++c)
+        co[r][c] = a[(r + 1) % 3][(c + 1) % 3] * a[(r + 2) % 3][(c + 2) % 3] - a[(r + 1) % 3][(c + 2) % 3] * a[(r + 2) % 3][(c + 1) % 3];
+    for (int c = 0; c < 3; ++c) det += a[0][c] * co[0][c];
+    for (int r = 0; r < 3; ++r)
+      for (int c = 0; c < 3; ++c) inv[3 * r + c] = (float)(co[c][r] / det);
+  }
+  for (int k = 0; k < 9; ++k) { out->m[k / 3][k % 3] = m[k]; out->inv[k / 3][k % 3] = inv[k]; }
+  return CSD_OK;
+}
+
+int colorize_blend_launch(float* x, float* x_mean, const float* gray0, const float* z, float m, float std, int B, size_t hw, int init,
+                          const float* matrix, const float* inv_matrix, uint64_t seed, uint64_t stream_id, hipStream_t s) {
+  ColorMatrix cm;
+  int rc = color_matrix(matrix, inv_matrix, &cm, "colorize_blend");
+  if (rc) return rc;
+  if (B <= 0 || hw == 0) return CSD_OK;
+  const uintptr_t bits = reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(x_mean) | reinterpret_cast<uintptr_t>(gray0) |
+                         reinterpret_cast<uintptr_t>(z);
+  CSD_REQUIRE((bits & 3) == 0, "colorize_blend: tensors must be 4-byte aligned");
+  const size_t groups = (hw + 3) / 4, total = (size_t)B * groups;
+  hipLaunchKernelGGL(colorize_blend_kernel, dim3(ew_grid(total)), dim3(256), 0, s, x, init ? nullptr : x_mean, gray0, init ? nullptr : z,
+                     m, std, hw, groups, total, cm, seed, stream_id, (!init && z == nullptr && std != 0.f) ? 1 : 0, init ? 1 : 0,
+                     ((bits & 15) == 0 && hw % 4 == 0) ? 1 : 0);
+  CSD_LAUNCH_CHECK();
+  return CSD_OK;
+}
+
+int colorize_gray0_launch(const float* gray, float* gray0, int B, size_t hw, const float* matrix, hipStream_t s) {
+  ColorMatrix cm;
+  int rc = color_matrix(matrix, nullptr, &cm, "colorize_gray0");
+  if (rc) return rc;
+  const size_t total = (size_t)B * hw;
+  if (total == 0) return CSD_OK;
+  hipLaunchKernelGGL(colorize_gray0_kernel, dim3(ew_grid(total)), dim3(256), 0, s, gray, gray0, hw, total, cm.m[0][0], cm.m[1][0],
+                     cm.m[2][0]);
+  CSD_LAUNCH_CHECK();
+  return CSD_OK;
+}
+
 int scale_rows_launch(float* out, const float* in, const float* scale, int divide, int B, int64_t per,
                       hipStream_t s) {
   const size_t total = (size_t)B * per;
@@ -532,4 +698,17 @@ extern "C" int csd_inpaint_blend(float* x, float* x_mean, const float* data, con
                                  float std, int64_t n, uint64_t seed, uint64_t stream_id, void* stream) {
   CSD_REQUIRE(x && data && mask && n > 0, "inpaint_blend: bad arguments");
   return inpaint_blend_launch(x, x_mean, data, mask, z, mean_scale, std, (size_t)n, seed, stream_id, (hipStream_t)stream);
+}
+
+extern "C" int csd_colorize_blend(float* x, float* x_mean, const float* gray0, const float* z, float mean_scale, float std, int B,
+                                  int64_t hw, int init, const float* matrix, const float* inv_matrix, uint64_t seed,
+                                  uint64_t stream_id, void* stream) {
+  CSD_REQUIRE(x && gray0 && B > 0 && hw > 0 && (init == 0 || init == 1), "colorize_blend: bad arguments");
+  return colorize_blend_launch(x, x_mean, gray0, z, mean_scale, std, B, (size_t)hw, init, matrix, inv_matrix, seed, stream_id,
+                               (hipStream_t)stream);
+}
+
+extern "C" int csd_colorize_gray0(const float* gray, float* gray0, int B, int64_t hw, const float* matrix, void* stream) {
+  CSD_REQUIRE(gray && gray0 && B > 0 && hw > 0, "colorize_gray0: bad arguments");
+  return colorize_gray0_launch(gray, gray0, B, (size_t)hw, matrix, (hipStream_t)stream);
 }

@@ -474,6 +474,69 @@ def inpaint_blend(x, data, mask, z=None, mean_scale=1.0, std=0.0, seed=0, stream
     return x, xm
 
 
+def _color_matrix(matrix):
+    """the host 3 x 3 fp32 array the colorization entries take (None: the library's default, the reference's M)"""
+    if matrix is None:
+        return None
+    m = torch.as_tensor(matrix, dtype=torch.float32).cpu().contiguous()
+    if tuple(m.shape) != (3, 3):
+        raise RuntimeError('colorization matrix must be 3 x 3 (decouple(v)[j] = sum_i v[i] * M[i][j]), got %s' % (tuple(m.shape),))
+    return (ctypes.c_float * 9)(*[float(v) for v in m.flatten()])
+
+
+def _color_state(x, gray0, who):
+    _lib.require_gpu_tensor(x, 'x')
+    if x.dim() != 4 or x.shape[1] != 3:
+        raise RuntimeError('%s: the state must be [B, 3, H, W] (got %s): the decoupled space has three channels' % (who, tuple(x.shape)))
+    B, _, H, W = x.shape
+    if tuple(gray0.shape) != (B, 1, H, W):
+        raise RuntimeError('%s: gray0 has shape %s, the state %s needs %s' % (who, tuple(gray0.shape), tuple(x.shape), (B, 1, H, W)))
+    return B, H * W
+
+
+def colorize_gray0(gray, matrix=None):
+    """Channel 0 of ``decouple(gray)``: [B, 3, H, W] -> [B, 1, H, W], ``(gray[:, 0]*M[0][0] + gray[:, 1]*M[1][0]) + gray[:, 2]*M[2][0]``.
+    The colorizers compute it once per call."""
+    _lib.require_gpu_tensor(gray, 'gray')
+    if gray.dim() != 4 or gray.shape[1] != 3:
+        raise RuntimeError('colorize_gray0: the gray-scale image must be [B, 3, H, W] (got %s)' % (tuple(gray.shape),))
+    B, _, H, W = gray.shape
+    out = _out((B, 1, H, W), torch.float32, gray.device)
+    check(lib().csd_colorize_gray0(_addr(gray, 'gray'), ptr(out), B, H * W, _color_matrix(matrix), current_stream(gray.device)),
+          'colorize_gray0')
+    return out
+
+
+def colorize_start(x, gray0, matrix=None):
+    """In place: the prior ``x`` [B, 3, H, W] becomes the colorizer's initial state ``couple(decouple(gray)*mask +
+    decouple(prior*(1 - mask)))`` (controllable_generation.py:180-182; mask = 1 on channel 0, the prior masked in image space)."""
+    B, hw = _color_state(x, gray0, 'colorize_start')
+    check(lib().csd_colorize_blend(_addr(x, 'x'), None, _addr(gray0, 'gray0'), None, 1.0, 0.0, B, hw, 1, _color_matrix(matrix), None,
+                                   0, 0, current_stream(x.device)), 'colorize_blend')
+    return x
+
+
+def colorize_blend(x, gray0, z=None, mean_scale=1.0, std=0.0, seed=0, stream_id=0, x_mean=True, matrix=None):
+    """In-place re-imposition of the gray channel (controllable_generation.py:150-153), one kernel.  With ``decouple(v)[j] = sum_i v[i] *
+    M[i][j]`` and ``couple`` the same contraction with the inverse: ``masked_mean = mean_scale*gray0; masked = masked_mean + z[:, :1]*std;
+    x = couple(cat(masked, decouple(x)[:, 1:])); x_mean = couple(cat(masked_mean, decouple(x)[:, 1:]))`` (x_mean from the new x);
+    returns ``(x, x_mean)``, ``x_mean=False``: ``(x, None)``.
+
+    ``x`` is [B, 3, H, W], ``gray0`` [B, 1, H, W] (``colorize_gray0``).  ``z`` has ``x``'s shape; only its channel 0 is read.
+    ``z=None``: those elements of ``randn(x.shape, seed, stream_id)`` are made in registers (bit-identical to passing that tensor);
+    with ``std == 0`` nothing is drawn.  ``matrix=None`` is the reference's M; its inverse is the float64 inverse rounded once.  A matrix
+    with max |M M^T - I| > 1e-6 is refused.  The tensors may be views at any element offset: 16-byte accesses are used when every
+    address and H*W allow them."""
+    B, hw = _color_state(x, gray0, 'colorize_blend')
+    if z is not None and z.shape != x.shape:
+        raise RuntimeError('colorize_blend: z has shape %s, x has %s' % (tuple(z.shape), tuple(x.shape)))
+    xm = _out(x.shape, x.dtype, x.device) if x_mean else None
+    check(lib().csd_colorize_blend(_addr(x, 'x'), ptr(xm), _addr(gray0, 'gray0'), _addr(z, 'z') if z is not None else None,
+                                   float(mean_scale), float(std), B, hw, 0, _color_matrix(matrix), None, int(seed), int(stream_id),
+                                   current_stream(x.device)), 'colorize_blend')
+    return x, xm
+
+
 def _band_matrix(matrix):
     """the host 4 x 4 fp32 array csd_band_split / csd_band_merge take (None: the library's orthonormal Haar matrix)"""
     if matrix is None:

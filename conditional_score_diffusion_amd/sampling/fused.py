@@ -179,16 +179,20 @@ def inpaint_tables(sde, ts):
     return mean_scale.contiguous(), std.contiguous()
 
 
-DRAW_KINDS = ('z_y0', 'z_y', 'zy', 'z', 'z_blend')      # csd_pc_noise_draws (include/csd.h): kind ids
+DRAW_KINDS = ('z_y0', 'z_y', 'zy', 'z', 'z_blend', 'z_colorize')      # csd_pc_noise_draws (include/csd.h): kind ids
 DRAW_PHASES = ('corrector', 'predictor', 'none')        # ... and phase ids
 
 
-def noise_draws(handle, B, predictor, corrector, std_y=False, use_path=False, inpaint=False, n_steps=1):
+def noise_draws(handle, B, predictor, corrector, std_y=False, use_path=False, inpaint=False, n_steps=1, colorize=False):
     """The draws behind the prior of a fused loop, in the order it consumes them, as the library lists them (csd_pc_noise_draws; no
     GPU): rows ``(step, kind, phase, elems, tape_offset, philox_stream)`` with step -1 in front of the loop, kind / phase indexing
-    DRAW_KINDS / DRAW_PHASES.  ``predictor`` / ``corrector``: the rule ids of csd_pc_params.  A combination the loop refuses raises
-    RuntimeError with the library's message."""
-    args = (handle, int(B), int(predictor), int(corrector), int(bool(std_y)), int(bool(use_path)), int(bool(inpaint)), int(n_steps))
+    DRAW_KINDS / DRAW_PHASES.  ``predictor`` / ``corrector``: the rule ids of csd_pc_params.  ``colorize``: the schedule of a
+    csd_pc_colorize_* call (the library's ``inpaint`` argument is then 2).  A combination the loop refuses raises RuntimeError with the
+    library's message."""
+    if inpaint and colorize:
+        raise NotImplementedError('inpaint and colorize exclude each other: one re-imposition per loop')
+    args = (handle, int(B), int(predictor), int(corrector), int(bool(std_y)), int(bool(use_path)), 2 if colorize else int(bool(inpaint)),
+            int(n_steps))
     n = lib().csd_pc_noise_draws(*args, None, 0)
     if n < 0:
         check(int(n), 'pc_noise_draws')
@@ -241,8 +245,8 @@ def path_tables(sy, ts):
 
 class Prepared:
     """One fused loop ready to be enqueued (``prepare``): the state ``x`` (prior in, result out), the condition ``y``, the filled
-    csd_pc_params ``p`` / csd_pc_inpaint_params ``ip`` (None: not an inpainting run), the record tensor ``rec`` and the timesteps
-    ``ts``.  ``keep`` holds every host array and device tensor the two structs point into: the object must stay alive until the
+    csd_pc_params ``p`` / csd_pc_inpaint_params ``ip`` (None: not an inpainting run) / csd_pc_colorize_params ``cp`` (None: not a
+    colorization run), the record tensor ``rec`` and the timesteps ``ts``.  ``keep`` holds every host array and device tensor the two structs point into: the object must stay alive until the
     library call that reads them has returned."""
 
     def __init__(self, **kw):
@@ -251,13 +255,17 @@ class Prepared:
 
 def prepare(model, sde, shape, y, p_steps, snr, eps, denoise, noise_tape=None, seed=None, record=False,
             unconditional_label=None, global_norm=None, predictor=None, corrector=None, probability_flow=False, use_path=False,
-            corr_alpha=None, continuous=True, inpaint=None, blend=True):
+            corr_alpha=None, continuous=True, inpaint=None, blend=True, colorize=None):
     """Everything ``run`` does before it calls the library - argument checks, per-step tables, prior, tape, record buffer, the two
     parameter structs - as a ``Prepared``; ``run`` is ``launch(prepare(...))``.  sampling/cascade.py prepares every stage this way and
     hands them to ONE csd_pc_cascade_sample.  ``blend=False`` (inpainting): the initial state stays the bare prior and ``data`` is
     used as it is - the cascade's link writes the data and blends on the device."""
     if seed is None:
         seed = fresh_seed()
+    if inpaint is not None and colorize is not None:
+        raise NotImplementedError('inpaint= and colorize= exclude each other: the device loop re-imposes one constraint per run')
+    if colorize is not None and len(shape) == 5:
+        raise NotImplementedError('colorization on the device loop is not provided for the 3-D networks (csd_pc_colorize_* refuse them)')
     if inpaint is not None and len(shape) == 5:
         raise NotImplementedError('inpainting on the device loop is not provided for the 3-D networks (csd_pc_inpaint_* refuse them)')
     c_sde = sde['x'] if isinstance(sde, dict) else sde
@@ -297,6 +305,18 @@ def prepare(model, sde, shape, y, p_steps, snr, eps, denoise, noise_tape=None, s
         data = data.to(dev, torch.float32).contiguous()
         mask = mask.to(dev, torch.float32).expand_as(data).contiguous()
         ip_mean, ip_std = inpaint_tables(c_sde, ts)
+    if colorize is not None:
+        if getattr(model, 'y_scale', 0):
+            raise NotImplementedError('colorization on the device loop is not provided for %s (the Kx super-resolution networks, '
+                                      'ddpm_KxSR / ncsnpp_KxSR, are conditional; csd_pc_colorize_* refuse y_scale)' % type(model).__name__)
+        if y is not None or isinstance(sde, dict) or use_path:
+            raise NotImplementedError('colorization on the device loop runs unconditional networks on a single SDE')
+        gray = colorize
+        if tuple(gray.shape) != tuple(shape) or len(shape) != 4 or shape[1] != 3:
+            raise ValueError('colorize: the gray-scale image has shape %s, the sampler runs %s; colorization needs [B, 3, H, W]'
+                             % (tuple(gray.shape), tuple(shape)))
+        gray0 = ops.colorize_gray0(gray.to(dev, torch.float32).contiguous())      # once per call
+        cp_mean, cp_std = inpaint_tables(c_sde, ts)
     if use_path:
         if not isinstance(sde, dict):
             raise NotImplementedError('use_path needs the two-SDE (CMDE / VS-CMDE) setting: sde = {"x": ..., "y": ...}')
@@ -313,8 +333,8 @@ def prepare(model, sde, shape, y, p_steps, snr, eps, denoise, noise_tape=None, s
         x = x.to(dev).contiguous()
         flat = torch.cat([t.reshape(-1) for t in tape[1:]]).to(dev).contiguous() if len(tape) > 1 else None
         # draws and elements: an x draw has the state's size, a y draw that of y (the low-resolution y of a y_scale network)
-        check_tape(noise_draws(model._h, B, pid, cid, std_y is not None, use_path, inpaint is not None, p_steps), tape[1:],
-                   int(x.numel()), int(y.numel()) if y is not None else 0)
+        check_tape(noise_draws(model._h, B, pid, cid, std_y is not None, use_path, inpaint is not None, p_steps,
+                               colorize=colorize is not None), tape[1:], int(x.numel()), int(y.numel()) if y is not None else 0)
     else:
         x = ops.randn(tuple(shape), seed, 0, dev)
         if ve:
@@ -324,7 +344,7 @@ def prepare(model, sde, shape, y, p_steps, snr, eps, denoise, noise_tape=None, s
         flat = None
     model.eval()
     model._ensure_packed()
-    n_rec = p_steps + (1 if inpaint is not None else 0)
+    n_rec = p_steps + (1 if inpaint is not None or colorize is not None else 0)
     rec = ops._out((n_rec,) + tuple(x.shape), torch.float32, dev) if record else None
     rec_steps = rec
     ip = None
@@ -339,6 +359,15 @@ def prepare(model, sde, shape, y, p_steps, snr, eps, denoise, noise_tape=None, s
         ip = _lib.PCInpaintParams()
         ip.data, ip.mask = data.data_ptr(), mask.data_ptr()
         ip.mean_scale, ip.std = _fp(ip_mean), _fp(ip_std)
+    cp = None
+    if colorize is not None:
+        ops.colorize_start(x, gray0)                                  # couple(decouple(gray)*mask + decouple(prior*(1 - mask)))
+        if record:
+            rec[0].copy_(x)
+            rec_steps = rec[1:]
+        cp = _lib.PCColorizeParams()
+        cp.gray0 = gray0.data_ptr()
+        cp.mean_scale, cp.std = _fp(cp_mean), _fp(cp_std)             # (matrix / inv_matrix NULL: the library's default)
     p = _lib.PCParams()
     p.n_steps = p_steps
     p.labels, p.std_x, p.G = _fp(labels), _fp(std_x), _fp(G)
@@ -367,30 +396,35 @@ def prepare(model, sde, shape, y, p_steps, snr, eps, denoise, noise_tape=None, s
     keep = (labels, std_x, G, std_y, pred_tab, corr_tab, path_tab, corr_alpha, rd_tab, flat, rec)
     if inpaint is not None:
         keep += (ip_mean, ip_std, data, mask)
-    return Prepared(model=model, dev=dev, B=B, x=x, y=yy, p=p, ip=ip, rec=rec, ts=ts, p_steps=p_steps, global_norm=global_norm,
+    if colorize is not None:
+        keep += (cp_mean, cp_std, gray0)
+    return Prepared(model=model, dev=dev, B=B, x=x, y=yy, p=p, ip=ip, cp=cp, rec=rec, ts=ts, p_steps=p_steps, global_norm=global_norm,
                     data=data if inpaint is not None else None, mask=mask if inpaint is not None else None, keep=keep)
 
 
 def launch(prep):
-    """Enqueue a ``Prepared`` loop through its single-stage entry (csd_pc_sample / csd_pc_inpaint_sample, or the two step calls per
-    PC step under ``global_norm``); returns ``(samples, record_or_None, timesteps)``."""
+    """Enqueue a ``Prepared`` loop through its single-stage entry (csd_pc_sample / csd_pc_inpaint_sample / csd_pc_colorize_sample, or
+    the two step calls per PC step under ``global_norm``); returns ``(samples, record_or_None, timesteps)``."""
     model, dev, B, x, yy, p, ip, p_steps = prep.model, prep.dev, prep.B, prep.x, prep.y, prep.p, prep.ip, prep.p_steps
+    cp = getattr(prep, 'cp', None)
     global_norm = prep.global_norm
     ws = model._workspace(B)
     scratch_bytes = lib().csd_pc_inpaint_scratch_bytes if ip is not None else lib().csd_pc_scratch_bytes
     scratch = ops._scratch(scratch_bytes(model._h, B), dev)
-    if ip is not None:
+    if ip is not None or cp is not None:
+        l, name = lib(), 'pc_inpaint' if ip is not None else 'pc_colorize'
+        sample, begin, end = (getattr(l, 'csd_%s_%s' % (name, f)) for f in ('sample', 'step_begin', 'step_end'))
         args = (model._h, ptr(model._packed), ptr(ws), ws.numel(), ptr(scratch), scratch.numel(), ptr(x), None, B, ctypes.byref(p),
-                ctypes.byref(ip))
+                ctypes.byref(ip if ip is not None else cp))
         if global_norm is None:
-            check(lib().csd_pc_inpaint_sample(*args, current_stream(dev)), 'pc_inpaint_sample')
+            check(sample(*args, current_stream(dev)), name + '_sample')
         else:
             reduce_fn, global_batch = global_norm
             sums = torch.zeros(2, dtype=torch.float32, device=dev)
             for i in range(p_steps):
-                check(lib().csd_pc_inpaint_step_begin(*args, i, ptr(sums), current_stream(dev)), 'pc_inpaint_step_begin')
+                check(begin(*args, i, ptr(sums), current_stream(dev)), name + '_step_begin')
                 reduce_fn(sums)
-                check(lib().csd_pc_inpaint_step_end(*args, i, ptr(sums), int(global_batch), current_stream(dev)), 'pc_inpaint_step_end')
+                check(end(*args, i, ptr(sums), int(global_batch), current_stream(dev)), name + '_step_end')
     elif global_norm is None:
         check(lib().csd_pc_sample(model._h, ptr(model._packed), ptr(ws), ws.numel(), ptr(scratch), scratch.numel(),
                                   ptr(x), ptr(yy) if yy is not None else None, B, ctypes.byref(p),
@@ -410,7 +444,7 @@ def launch(prep):
 
 def run(model, sde, shape, y, p_steps, snr, eps, denoise, noise_tape=None, seed=None, record=False,
         unconditional_label=None, global_norm=None, predictor=None, corrector=None, probability_flow=False, use_path=False,
-        corr_alpha=None, continuous=True, inpaint=None):
+        corr_alpha=None, continuous=True, inpaint=None, colorize=None):
     """Run the fused loop; returns (samples, record_or_None, timesteps).  ``seed=None``: a fresh key per call (fresh_seed).
 
     ``predictor`` / ``corrector``: the registered classes (default: the reverse-diffusion / Langevin pair); see ``fusable``.
@@ -429,6 +463,12 @@ def run(model, sde, shape, y, p_steps, snr, eps, denoise, noise_tape=None, seed=
     then the rows of ``noise_draws`` (per step [z_corrector] z_blend [z_predictor] z_blend); without a tape the prior is
     ``ops.randn`` stream 0.  ``record`` then returns [p_steps + 1, ...]: the initial state followed by every step.
 
+    ``colorize``: the gray-scale image [B, 3, H, W] - colorization with an unconditional 3-channel network (csd_pc_colorize_sample;
+    controllable_generation.py:95-191 of the reference): the loop starts from couple(decouple(gray)*mask + decouple(prior*(1 - mask)))
+    and re-imposes the gray channel of the decoupled space at every step's noise level after each phase (``ops.colorize_blend``).  Draw
+    order, tape layout, ``record`` and the refusals are those of ``inpaint``, with a full-size z_colorize draw (channel 0 used) where
+    inpainting has its z_blend; ``inpaint`` and ``colorize`` together are refused.
+
     ``global_norm``: None = the Langevin step size uses the batch means of THIS call's batch (the reference run on this batch;
     one library call enqueues the whole loop).  Otherwise ``(reduce_fn, global_batch)``: the batch is one shard of a larger one
     and the step size must use the means over the GLOBAL batch (identical to one reference process holding all of it,
@@ -438,4 +478,4 @@ def run(model, sde, shape, y, p_steps, snr, eps, denoise, noise_tape=None, seed=
     return launch(prepare(model, sde, shape, y, p_steps, snr, eps, denoise, noise_tape=noise_tape, seed=seed, record=record,
                           unconditional_label=unconditional_label, global_norm=global_norm, predictor=predictor, corrector=corrector,
                           probability_flow=probability_flow, use_path=use_path, corr_alpha=corr_alpha, continuous=continuous,
-                          inpaint=inpaint))
+                          inpaint=inpaint, colorize=colorize))

@@ -236,6 +236,100 @@ def get_pc_inpainter(sde, predictor, corrector, snr, n_steps=1, probability_flow
     return pc_inpainter
 
 
+def get_colorization_fn(config, sde, eps, n_steps_each=1):
+    """The colorizer of a config, read like ``get_inpainting_fn`` reads it (``config.sampling.csd_device_loop``: the device loop)."""
+    return get_pc_colorizer(sde=sde, predictor=get_predictor(config.sampling.predictor.lower()),
+                            corrector=get_corrector(config.sampling.corrector.lower()), snr=config.sampling.snr,
+                            n_steps=n_steps_each, probability_flow=config.sampling.probability_flow,
+                            continuous=config.training.continuous, denoise=config.sampling.noise_removal, eps=eps,
+                            device_loop=config.sampling.get('csd_device_loop', False))
+
+
+def get_pc_colorizer(sde, predictor, corrector, snr, n_steps=1, probability_flow=False, continuous=False, denoise=True, eps=1e-5,
+                     device_loop=False):
+    """Image colorization with an unconditional 3-channel model (controllable_generation.py:95-191 of the reference, without its
+    ``inverse_scaler``): ``pc_colorizer(model, gray_scale_img, show_evolution=False, noise_tape=None, seed=None, global_norm=None) ->
+    (x, info)``; ``gray_scale_img`` is [B, 3, H, W] with equal channels.  A fixed orthonormal 3 x 3 matrix rotates the channels so that
+    channel 0 is the gray one; after every corrector / predictor update that channel is replaced by the gray image perturbed to the
+    current noise level (``ops.colorize_blend``, one kernel) and the state rotated back.
+
+    ``device_loop=False`` (the default) is the step-by-step loop: two update objects per step, the prior and the draws from torch's
+    generator (``sde.prior_sampling`` / ``torch.randn_like``), the re-imposition through ``ops.colorize_blend`` with that draw.  It
+    takes none of the three keywords and raises NotImplementedError for them.
+
+    ``device_loop=True`` runs the whole sampler (``sde.N`` steps) as one call of the fused device loop (``fused.run(...,
+    colorize=gray_scale_img)``): Philox noise on the device (``seed=``; None = a fresh key), ``noise_tape=`` in the draw order prior |
+    per step [z_corrector] z_colorize [z_predictor] z_colorize (full-size draws), ``global_norm=(reduce_fn, global_batch)``,
+    NonFiniteError instead of NaN images.  A (model, sde, predictor, corrector, n_steps) combination the loop does not cover raises
+    NotImplementedError naming the reason - there is no silent fall-back to the step-by-step loop."""
+    from .. import ops
+
+    pred_fn = functools.partial(shared_predictor_update_fn, sde=sde, predictor=predictor, probability_flow=probability_flow,
+                                continuous=continuous)
+    corr_fn = functools.partial(shared_corrector_update_fn, sde=sde, corrector=corrector, continuous=continuous, snr=snr,
+                                n_steps=n_steps)
+
+    def why_not_fused(model):
+        """None when the device loop covers this sampler, else the reason"""
+        from ..models.ddpm import HipUNet
+        if not isinstance(model, HipUNet):
+            return 'the model is a %s, not a HipUNet' % type(model).__name__
+        if getattr(model, 'y_channels', 0) > 0:
+            return 'colorization uses an unconditional network, this one takes a %d-channel condition' % model.y_channels
+        if getattr(model, 'x_channels', 3) != 3:
+            return 'colorization needs a 3-channel state, this network has %d channels' % model.x_channels
+        if n_steps != 1:
+            return 'n_steps = %d corrector steps per update (the device loop runs 1)' % n_steps
+        if isinstance(sde, dict):
+            return 'a single SDE is needed, not an {x, y} pair'
+        pred = NonePredictor if predictor is None else predictor
+        corr = NoneCorrector if corrector is None else corrector
+        if not fused.fusable(model, sde, pred, corr, n_steps, probability_flow, continuous):
+            return 'the device loop does not implement (%s, %s, %s, probability_flow=%s, continuous=%s)' % (
+                type(sde).__name__, pred.__name__, corr.__name__, probability_flow, continuous)
+        if model.device.type != 'cuda':
+            return 'the model is on %s, the device loop runs on the GPU' % model.device
+        return None
+
+    def fused_colorizer(model, gray, show_evolution, noise_tape, seed, global_norm):
+        why = why_not_fused(model)
+        if why is not None:
+            raise NotImplementedError('get_pc_colorizer(device_loop=True): ' + why)
+        label = 'fourier' if getattr(model, 'embedding_type', 'positional') == 'fourier' else 'sigma'
+        x, rec, _ = fused.run(model, sde, tuple(gray.shape), None, sde.N, snr, eps, denoise, noise_tape=noise_tape, seed=seed,
+                              record=show_evolution, unconditional_label=label, global_norm=global_norm,
+                              predictor=NonePredictor if predictor is None else predictor,
+                              corrector=NoneCorrector if corrector is None else corrector, probability_flow=probability_flow,
+                              continuous=continuous, colorize=gray)
+        return x, ({'evolution': rec.cpu()} if show_evolution else {})
+
+    def pc_colorizer(model, gray_scale_img, show_evolution=False, noise_tape=None, seed=None, global_norm=None):
+        if device_loop:
+            return fused_colorizer(model, gray_scale_img, show_evolution, noise_tape, seed, global_norm)
+        for name, value in (('noise_tape', noise_tape), ('seed', seed), ('global_norm', global_norm)):
+            if value is not None:
+                raise NotImplementedError('%s is only available on the device loop: get_pc_colorizer(..., device_loop=True)' % name)
+        with torch.no_grad():
+            gray = gray_scale_img.contiguous().float()
+            gray0 = ops.colorize_gray0(gray)                                  # once per call
+            timesteps = torch.linspace(sde.T, eps, sde.N)
+            mean_scale, std = fused.inpaint_tables(sde, timesteps)            # p_t(x | gray) per step: host scalars
+            x = ops.colorize_start(sde.prior_sampling(gray.shape).to(gray.device).float().contiguous(), gray0)
+            evolution = [x.cpu()] if show_evolution else None
+            x_mean = x
+            for i in range(sde.N):
+                vec_t = torch.ones(gray.shape[0], device=gray.device) * timesteps[i]
+                for update_fn in (corr_fn, pred_fn):
+                    x, _ = update_fn(x, vec_t, model=model)
+                    x, x_mean = ops.colorize_blend(x.contiguous(), gray0, torch.randn_like(x), float(mean_scale[i]), float(std[i]))
+                if show_evolution:
+                    evolution.append(x.cpu())
+            info = {'evolution': torch.stack(evolution)} if show_evolution else {}
+            return (x_mean if denoise else x), info
+
+    return pc_colorizer
+
+
 def shared_predictor_update_fn(x, t, sde, model, predictor, probability_flow, continuous):
     score_fn = mutils.get_score_fn(sde, model, conditional=False, train=False, continuous=continuous)
     obj = (NonePredictor if predictor is None else predictor)(sde, score_fn, probability_flow)

@@ -275,12 +275,14 @@ int csd_pc_sample(csd_unet* net, const void* packed, void* workspace, size_t wor
  *   std_y                  [zy z corrector] [zy z predictor]        (zy: the y_t of that phase's evaluation)
  *   path_coef (use_path)   z_y0 in front of the loop | z_y of the bridge, [z predictor], [z corrector]
  *   inpainting             [z corrector] z_blend [z predictor] z_blend       (a `none` phase draws its z_blend)
+ *   colorization           [z corrector] z_colorize [z predictor] z_colorize (the same places; only channel 0 of the draw is used)
  * csd_pc_noise_draws lists them for a handle, a batch size and the fields of csd_pc_params the schedule depends on (has_std_y,
- * has_path_coef: the pointer is given; inpaint: a csd_pc_inpaint_* call).  It returns the number of draws behind the prior and fills
- * up to `cap` rows of 6: {step (-1: in front of the loop), kind (0 z_y0, 1 z_y, 2 zy, 3 z, 4 z_blend), phase (0 corrector,
- * 1 predictor, 2 none), elements, tape offset in floats, Philox stream}.  It needs no GPU.  It refuses, with CSD_ERR_INVALID and the
- * message of the sampling entries (which make the same check): both rules `none`; std_y or path_coef with y_channels == 0; std_y and
- * path_coef together; inpainting with y_channels > 0, std_y, path_coef, x_squeeze, y_scale or an arch-2 handle. */
+ * has_path_coef: the pointer is given; inpaint: 1 = a csd_pc_inpaint_* call, 2 = a csd_pc_colorize_* call).  It returns the number of
+ * draws behind the prior and fills up to `cap` rows of 6: {step (-1: in front of the loop), kind (0 z_y0, 1 z_y, 2 zy, 3 z, 4 z_blend,
+ * 5 z_colorize), phase (0 corrector, 1 predictor, 2 none), elements, tape offset in floats, Philox stream}.  It needs no GPU.  It
+ * refuses, with CSD_ERR_INVALID and the message of the sampling entries (which make the same check): both rules `none`; std_y or
+ * path_coef with y_channels == 0; std_y and path_coef together; inpainting or colorization with y_channels > 0, std_y, path_coef,
+ * x_squeeze, y_scale or an arch-2 handle; colorization with x_channels != 3. */
 int64_t csd_pc_noise_draws(const csd_unet* net, int B, int predictor, int corrector, int has_std_y, int has_path_coef, int inpaint,
                            int n_steps, int64_t* rows, int cap);
 /* The same loop one PC step at a time, for the GLOBAL-NORM exactness mode of batch-sharded sampling (identical to
@@ -335,6 +337,51 @@ int csd_pc_inpaint_step_end(csd_unet* net, const void* packed, void* workspace, 
  * below - and nothing is drawn when std == 0.  16-byte loads and stores when every pointer is 16-byte aligned. */
 int csd_inpaint_blend(float* x, float* x_mean, const float* data, const float* mask, const float* z, float mean_scale,
                       float std, int64_t n, uint64_t seed, uint64_t stream_id, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Colorization with an unconditional 3-channel network on the same device loop (controllable_generation.py:95-191 of the reference).
+ * The constraint lives in a rotated channel space: decouple(v)[b, j] = sum_i v[b, i] * M[i][j] with a fixed orthonormal 3 x 3 M,
+ * couple the same contraction with M^-1; channel 0 of the decoupled space is the gray channel.  After the update of EVERY phase (a
+ * `none` phase included), in fp32, every contraction summed as (v0*A0j + v1*A1j) + v2*A2j:
+ *     masked_mean = mean_scale[i]*gray0 ; masked = masked_mean + z0*std[i]          (gray0 = decouple(gray)[:, 0], z0 = z[:, 0])
+ *     x = couple(masked, decouple(x)[1], decouple(x)[2]) ; x_mean = couple(masked_mean, decouple(x)[1], decouple(x)[2]) with the NEW x
+ * x (in): the initial state couple(decouple(gray)*mask + decouple(prior*(1 - mask))), mask = 1 on channel 0 - the prior is masked in
+ * IMAGE space (the reference's order): csd_colorize_blend with init = 1 makes it from the prior.
+ * Draws: one x draw (kind 5, z_colorize) behind every phase, where inpainting has its z_blend - a full-size draw like the reference's
+ * randn_like, of which only the channel-0 plane is read; without a tape the blend makes exactly those elements of the draw's Philox
+ * stream in registers.  csd_pc_noise_draws lists the schedule with inpaint = 2.
+ * matrix / inv_matrix: HOST 3 x 3 row-major, NULL = the reference's M / the float64 inverse of matrix rounded once to fp32.  Refused
+ * with CSD_ERR_INVALID: max |M M^T - I| > 1e-6, an inv_matrix with max |M inv - I| > 1e-6, and - before any buffer is touched - an
+ * arch-2 handle, x_squeeze, y_scale, y_channels > 0, x_channels != 3, std_y and path_coef.
+ * scratch: csd_pc_scratch_bytes of the handle (the blend needs no buffer; the name below is an alias, not a second sizing entry).
+ * denoise, record, the finiteness contract, the single synchronisation and the two step calls are those of csd_pc_inpaint_*.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct csd_pc_colorize_params {
+  const float* gray0;           /* device [B, 1, S, S]: channel 0 of decouple(gray), csd_colorize_gray0                */
+  const float* mean_scale;      /* host [n_steps]: mean of p_t(x | data) = mean_scale * data (1 for the VE SDEs)      */
+  const float* std;             /* host [n_steps]: the SDE's marginal std                                             */
+  const float* matrix;          /* host 3 x 3 M or NULL                                                               */
+  const float* inv_matrix;      /* host 3 x 3 M^-1 or NULL                                                            */
+} csd_pc_colorize_params;
+
+#define csd_pc_colorize_scratch_bytes csd_pc_scratch_bytes
+int csd_pc_colorize_sample(csd_unet* net, const void* packed, void* workspace, size_t workspace_bytes, void* scratch,
+                           size_t scratch_bytes, float* x, const float* y, int B, const csd_pc_params* p,
+                           const csd_pc_colorize_params* cp, void* stream);
+int csd_pc_colorize_step_begin(csd_unet* net, const void* packed, void* workspace, size_t workspace_bytes, void* scratch,
+                               size_t scratch_bytes, float* x, const float* y, int B, const csd_pc_params* p,
+                               const csd_pc_colorize_params* cp, int step, float* norm_sums, void* stream);
+int csd_pc_colorize_step_end(csd_unet* net, const void* packed, void* workspace, size_t workspace_bytes, void* scratch,
+                             size_t scratch_bytes, float* x, const float* y, int B, const csd_pc_params* p,
+                             const csd_pc_colorize_params* cp, int step, const float* norm_sums, int global_batch, void* stream);
+/* The re-imposition alone, in place on x [B, 3, hw] (x_mean may be NULL).  z: a tensor of x's size whose channel-0 plane holds the
+ * normals, or NULL: those elements of the randn fill of (seed, stream_id) in registers; nothing is drawn when std == 0.  init = 1: x
+ * holds the prior and becomes the initial state (mean_scale = 1; z, std and x_mean are not used).  16-byte loads and stores when every
+ * pointer is 16-byte aligned and hw is a multiple of 4, element-wise otherwise.  No atomics: bitwise repeatable. */
+int csd_colorize_blend(float* x, float* x_mean, const float* gray0, const float* z, float mean_scale, float std, int B, int64_t hw,
+                       int init, const float* matrix, const float* inv_matrix, uint64_t seed, uint64_t stream_id, void* stream);
+/* gray0 [B, 1, hw] = channel 0 of decouple(gray [B, 3, hw]): once per sampler call */
+int csd_colorize_gray0(const float* gray, float* gray0, int B, int64_t hw, const float* matrix, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Band split / merge (csrc/band.hip): the 2x2-block, stride-2 orthogonal transform of the Haar multi-scale models, per image channel,

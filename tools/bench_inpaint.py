@@ -8,6 +8,11 @@ evaluations each); its time is a host clock around the call and a device synchro
 alternating pairs.  Reports ms per PC step of both paths (mean, min, max over the repeats) and writes the JSON:
 
   python tools/bench_inpaint.py [--steps 20] [--reps 5] [--batch 64] [--precision fp16x3] [--out profiles/inpaint_bench.json]
+
+--colorize measures PC colorization (get_pc_colorizer) the same way on the same network and schedule, with a gray-scale batch in place
+of data and mask, and writes profiles/colorize_bench.json.  It also times the two re-imposition kernels alone at the run's state size,
+alternately, between device events: ops.inpaint_blend and ops.colorize_blend, both drawing their noise in registers and both writing
+x_mean (`blend_kernels_us`).
 """
 import argparse
 import json
@@ -53,14 +58,77 @@ def timed(fn, model, data, mask, **kw):
     return dt, x
 
 
+def timed_colorize(fn, model, gray, **kw):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    x, _ = fn(model, gray, **kw)
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    if not bool(torch.isfinite(x).all()):
+        raise RuntimeError('the colorizer returned non-finite values')
+    return dt, x
+
+
+def blend_kernels_us(shape, dev, reps=50):
+    """microseconds per launch of the two re-imposition kernels on a state of ``shape``, alternating windows of 10 launches"""
+    from conditional_score_diffusion_amd import ops
+    x = ops.randn(shape, 3, 0, dev)
+    data, mask = torch.rand(shape, device=dev), (torch.rand(shape, device=dev) < 0.5).float()
+    gray0 = ops.colorize_gray0(torch.rand(shape, device=dev))
+    calls = {'inpaint_blend': lambda: ops.inpaint_blend(x, data, mask, None, 1.0, 0.5, seed=1, stream_id=1),
+             'colorize_blend': lambda: ops.colorize_blend(x, gray0, None, 1.0, 0.5, seed=1, stream_id=1)}
+    us = {k: [] for k in calls}
+    for fn in calls.values():
+        fn()
+    for _ in range(reps):
+        for k, fn in calls.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(10):
+                fn()
+            e1.record()
+            e1.synchronize()
+            us[k].append(e0.elapsed_time(e1) * 100.0)
+    return {k: {'mean': float(np.mean(v)), 'min': float(np.min(v)), 'max': float(np.max(v))} for k, v in us.items()}
+
+
+def main_colorize(a, cfg, model, dev):
+    S, B = cfg.data.image_size, a.batch
+    rs = np.random.RandomState(78)
+    gray = torch.from_numpy(np.repeat(rs.uniform(0, 1, size=(B, 1, S, S)).astype(np.float32), 3, axis=1).copy()).to(dev)
+    sde = sde_lib.VESDE(cfg.model.sigma_min_x, cfg.model.sigma_max_x, a.steps)
+    kw = dict(snr=cfg.sampling.snr, n_steps=1, probability_flow=False, continuous=True, denoise=True, eps=1e-5)
+    paths = {'step_by_step': (unconditional.get_pc_colorizer(sde, get_predictor('reverse_diffusion'), get_corrector('langevin'), **kw), {}),
+             'device_loop': (unconditional.get_pc_colorizer(sde, get_predictor('reverse_diffusion'), get_corrector('langevin'),
+                                                            device_loop=True, **kw), {'seed': 1})}
+    for name, (fn, extra) in paths.items():                 # warm-up
+        timed_colorize(fn, model, gray, **extra)
+    ms = {name: [] for name in paths}
+    for _ in range(a.reps):
+        for name, (fn, extra) in paths.items():
+            ms[name].append(timed_colorize(fn, model, gray, **extra)[0] * 1e3 / a.steps)
+    r = {'workload': 'PC colorization, unconditional ddpm nf 128 ch_mult (1,2,2,2) 64x64, VE reverse_diffusion/langevin',
+         'device': torch.cuda.get_device_name(0), 'batch': B, 'precision': a.precision, 'pc_steps_per_run': a.steps, 'reps': a.reps}
+    for name, v in ms.items():
+        r[name] = {'ms_per_pc_step_mean': float(np.mean(v)), 'ms_per_pc_step_min': float(np.min(v)), 'ms_per_pc_step_max': float(np.max(v)),
+                   'ms_per_pc_step_runs': [round(float(t), 4) for t in v]}
+    r['step_by_step_over_device_loop'] = r['step_by_step']['ms_per_pc_step_mean'] / r['device_loop']['ms_per_pc_step_mean']
+    r['blend_kernels_us'] = blend_kernels_us((B, 3, S, S), dev)
+    r['colorize_blend_over_inpaint_blend'] = r['blend_kernels_us']['colorize_blend']['mean'] / r['blend_kernels_us']['inpaint_blend']['mean']
+    return r
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--steps', type=int, default=20)
     ap.add_argument('--reps', type=int, default=5)
     ap.add_argument('--batch', type=int, default=64)
     ap.add_argument('--precision', default='fp16x3')
-    ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'inpaint_bench.json'))
+    ap.add_argument('--colorize', action='store_true')
+    ap.add_argument('--out', default=None)
     a = ap.parse_args()
+    if a.out is None:
+        a.out = os.path.join(ROOT, 'profiles', 'colorize_bench.json' if a.colorize else 'inpaint_bench.json')
     if not torch.cuda.is_available():
         raise SystemExit('bench_inpaint.py measures on the GPU; there is none here (nothing measured)')
     dev = torch.device('cuda:0')
@@ -69,6 +137,8 @@ def main():
     model = mutils.create_model(cfg)
     model.load_state_dict(bench.synth_weights({k: tuple(v.shape) for k, v in model.state_dict().items()}, 0))
     model = model.to(dev).eval()
+    if a.colorize:
+        return write(a.out, main_colorize(a, cfg, model, dev))
     S, B = cfg.data.image_size, a.batch
     rs = np.random.RandomState(77)
     data = torch.from_numpy(rs.uniform(0, 1, size=(B, 3, S, S)).astype(np.float32)).to(dev)
@@ -94,8 +164,12 @@ def main():
         r[name] = {'ms_per_pc_step_mean': float(np.mean(v)), 'ms_per_pc_step_min': float(np.min(v)), 'ms_per_pc_step_max': float(np.max(v)),
                    'ms_per_pc_step_runs': [round(float(t), 4) for t in v]}
     r['step_by_step_over_device_loop'] = r['step_by_step']['ms_per_pc_step_mean'] / r['device_loop']['ms_per_pc_step_mean']
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, 'w') as f:
+    write(a.out, r)
+
+
+def write(out, r):
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    with open(out, 'w') as f:
         json.dump(r, f, indent=1)
         f.write('\n')
     print(json.dumps(r), flush=True)
