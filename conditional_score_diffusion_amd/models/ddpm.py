@@ -11,7 +11,9 @@ The nn.Module holds ONLY the parameters, named exactly like the reference ``stat
 reference checkpoints load with ``load_state_dict``; the parameter table itself comes from the
 library (csd_unet_param_info), which rebuilds the module list from the config the way
 ``DDPM.__init__`` does.  ``forward`` hands raw device pointers to ``csd_unet_forward``; all
-arithmetic runs in libcsd_hip.so.  There is no PyTorch fallback.
+arithmetic runs in libcsd_hip.so.  There is no PyTorch fallback.  The operator-granular training
+executors (``train_executor = 'operators'``: ``_TrainOpsNHWC`` / ``_TrainOpsNCHW``, the yardstick of the
+planned training graph) are executors of ``topology.run_unet`` on ``topology.build_modules``' list.
 """
 import ctypes
 import math
@@ -20,9 +22,10 @@ import os
 import torch
 import torch.nn as nn
 
-from .. import _lib, ops
+from .. import _lib, grad_ops, grad_ops_nhwc, ops
 from .._lib import check, current_stream, lib, ptr, require_gpu_tensor
 from . import utils
+from .topology import Executor, build_modules, run_unet
 
 
 class _Node(nn.Module):
@@ -47,11 +50,34 @@ def _model_key(config, key, default):
     return default if v is None else v
 
 
+def _precision(config, precision):
+    """arithmetic of the 3x3 contractions: the constructor argument, else config.model.csd_precision, else $CSD_PRECISION, else
+    'fp16x3'.  'fp32' (exact fp32 MFMA), 'fp16x3' (split-fp16 operands, three fp16 MFMAs per product: fp32-class accuracy - the
+    DEFAULT: a model built from an unchanged reference config computes in the reference's precision class), 'fp16f8' (split operands,
+    correction products with e4m3 operands on the fp8 matrix cores: 1e-5-class accuracy on the tested weights, opt-in), 'fp16' (opt-in,
+    not certified).  Not a reference key."""
+    if precision is None:
+        precision = _model_key(config, 'csd_precision', None)
+    if precision is None:
+        precision = os.environ.get('CSD_PRECISION', 'fp16x3')
+    if precision not in _lib.PREC_IDS:
+        raise ValueError('unknown csd precision %r (choose from %s)' % (precision, sorted(_lib.PREC_IDS)))
+    return precision
+
+
+def _activation(config):
+    """config.model.nonlinearity as a name of _lib.ACT_IDS (models/layers.py:29-41)"""
+    act = config.model.nonlinearity.lower()
+    if act not in _lib.ACT_IDS or act == 'none':
+        raise NotImplementedError('activation function does not exist!')
+    return act
+
+
 class _HandleSurface:
     """What a network that owns a ``csd_unet`` handle offers to its callers (``sampling/fused.py``, the likelihood, the benches): the
-    handle ``_h``, the packed weights ``_packed`` (``_ensure_packed()`` packs again when a parameter moved or changed), the activation
-    workspace ``_workspace(B)`` and ``stats(B)``.  Expects ``_h``, ``_param_names``, ``_packed``, ``_packed_key``, ``_ws`` and ``device``
-    on the instance.  Every byte buffer comes from ``ops._scratch``."""
+    handle ``_h`` (``_create_unet``), the library's parameter table, the packed weights ``_packed`` (``_ensure_packed()`` packs again
+    when a parameter moved or changed), the activation workspace ``_workspace(B)``, the evaluation ``_unet_forward`` and ``stats(B)``.
+    Expects ``_param_names``, ``y_channels`` and ``device`` on the instance.  Every byte buffer comes from ``ops._scratch``."""
 
     def __del__(self):
         try:
@@ -60,6 +86,35 @@ class _HandleSurface:
                 self._h = None
         except Exception:
             pass
+
+    def _create_unet(self, cfg):
+        """the handle of a filled csd_unet_config; nothing is packed yet"""
+        self._cfg, self._h = cfg, ctypes.c_void_p()
+        check(lib().csd_unet_create(ctypes.byref(cfg), ctypes.byref(self._h)), 'unet_create')
+        self._packed = self._packed_key = self._ws = None
+
+    def _param_table(self):
+        """[(state_dict name, shape)] as the library rebuilt it from the config (up to 5 dimensions: the 3-D conv weights)"""
+        out = []
+        name, ndim, shape = ctypes.c_char_p(), ctypes.c_int(), (ctypes.c_int64 * 5)()
+        for i in range(lib().csd_unet_num_params(self._h)):
+            check(lib().csd_unet_param_info(self._h, i, ctypes.byref(name), ctypes.byref(ndim), shape), 'param_info')
+            out.append((name.value.decode(), tuple(shape[j] for j in range(ndim.value))))
+        return out
+
+    def _unet_forward(self, x, y, labels, out_shape, y_noise=None, y_sigma=0.0):
+        """one csd_unet_forward on inputs whose shapes the caller has checked"""
+        B = x.shape[0]
+        if self.y_channels:
+            y = y.contiguous()
+        self._ensure_packed()
+        ws = self._workspace(B)
+        out = ops._out(out_shape, torch.float32, x.device)
+        check(lib().csd_unet_forward(self._h, ptr(self._packed), ptr(ws), ws.numel(), ptr(x.contiguous()),
+                                     ptr(y) if self.y_channels else None, ptr(labels), ptr(out), B,
+                                     ptr(y_noise) if y_noise is not None else None, float(y_sigma),
+                                     current_stream(x.device)), 'unet_forward')
+        return out
 
     # -- packing -----------------------------------------------------------------------------------
     def _ensure_packed(self):
@@ -108,17 +163,7 @@ class HipUNet(nn.Module, _HandleSurface):
     def __init__(self, config, precision=None):
         super().__init__()
         m, d = config.model, config.data
-        # arithmetic of the 3x3 contractions: 'fp32' (exact fp32 MFMA), 'fp16x3' (split-fp16 operands, three fp16 MFMAs per product:
-        # fp32-class accuracy - the DEFAULT: a model built from an unchanged reference config computes in the reference's precision
-        # class), 'fp16f8' (split operands, correction products with e4m3 operands on the fp8 matrix cores: 1e-5-class accuracy on the
-        # tested weights, opt-in), 'fp16' (opt-in, not certified).  Not a reference key: config.model.csd_precision or $CSD_PRECISION.
-        if precision is None:
-            precision = m.get('csd_precision', None) if hasattr(m, 'get') else getattr(m, 'csd_precision', None)
-        if precision is None:
-            precision = os.environ.get('CSD_PRECISION', 'fp16x3')
-        if precision not in _lib.PREC_IDS:
-            raise ValueError('unknown csd precision %r (choose from %s)' % (precision, sorted(_lib.PREC_IDS)))
-        self.precision = precision
+        self.precision = precision = _precision(config, precision)
         self.nf = m.nf
         self.num_res_blocks = m.num_res_blocks
         self.attn_resolutions = tuple(m.attn_resolutions)
@@ -128,10 +173,7 @@ class HipUNet(nn.Module, _HandleSurface):
         self.image_size = int(d.effective_image_size)
         self.out_channels = int(self._out_channels(config))
         self.x_channels, self.y_channels = self._channels(config)
-        act = m.nonlinearity.lower()
-        if act not in _lib.ACT_IDS or act == 'none':
-            raise NotImplementedError('activation function does not exist!')   # models/layers.py:29-41
-        self._act_name = act
+        self._act_name = act = _activation(config)
         self._train_calls = 0
         self.train_layout = os.environ.get('CSD_TRAIN_LAYOUT', 'nhwc')     # 'nhwc' | 'nchw' (see _train_forward)
         self.train_executor = os.environ.get('CSD_TRAIN_EXECUTOR', 'planned')   # 'planned' (csd_unet_backward) | 'operators' (autograd)
@@ -159,14 +201,9 @@ class HipUNet(nn.Module, _HandleSurface):
         cfg.x_squeeze = int(self.x_squeeze)
         cfg.y_scale = int(self.y_scale)
         self._extra_config(cfg, config)
-        self._cfg = cfg
-        self._h = ctypes.c_void_p()
-        check(lib().csd_unet_create(ctypes.byref(cfg), ctypes.byref(self._h)), 'unet_create')
-        self._dropout = float(m.get('dropout', 0.0)) if hasattr(m, 'get') else float(getattr(m, 'dropout', 0.0))
+        self._create_unet(cfg)
+        self._dropout = float(_model_key(config, 'dropout', 0.0))
         self._build_params()
-        self._packed = None
-        self._packed_key = None
-        self._ws = None
 
     # -- parameters ------------------------------------------------------------------------------
     def _channels(self, config):
@@ -177,15 +214,6 @@ class HipUNet(nn.Module, _HandleSurface):
 
     def _extra_config(self, cfg, config):
         """hook: architecture-specific fields of csd_unet_config"""
-
-    def _param_table(self):
-        n = lib().csd_unet_num_params(self._h)
-        out = []
-        name, ndim, shape = ctypes.c_char_p(), ctypes.c_int(), (ctypes.c_int64 * 4)()
-        for i in range(n):
-            check(lib().csd_unet_param_info(self._h, i, ctypes.byref(name), ctypes.byref(ndim), shape), 'param_info')
-            out.append((name.value.decode(), tuple(shape[j] for j in range(ndim.value))))
-        return out
 
     def _build_params(self):
         table = self._param_table()
@@ -255,18 +283,7 @@ class HipUNet(nn.Module, _HandleSurface):
                 raise RuntimeError('the fused y-perturbation is a sampling feature; it has no input gradient')
             return self._input_grad_forward(x, y, labels)
         labels = self._check_io(x, y, labels)
-        B = x.shape[0]
-        if self.y_channels:
-            y = y.contiguous()
-        self._ensure_packed()
-        ws = self._workspace(B)
-        out = ops._out(self._out_shape(B), torch.float32, x.device)
-        check(lib().csd_unet_forward(self._h, ptr(self._packed), ptr(ws), ws.numel(), ptr(x.contiguous()),
-                                     ptr(y) if self.y_channels else None, ptr(labels), ptr(out), B,
-                                     ptr(y_noise) if y_noise is not None else None, float(y_sigma),
-                                     current_stream(x.device)), 'unet_forward')
-        return out
-
+        return self._unet_forward(x, y, labels, self._out_shape(x.shape[0]), y_noise, y_sigma)
 
     def _check_io(self, x, y, labels):
         """shapes of one call's x, y, labels; returns the labels as a contiguous float32 tensor on x's device"""
@@ -327,7 +344,6 @@ class HipUNet(nn.Module, _HandleSurface):
         gradient needs.  ``self.train_layout``: 'nhwc' (default) keeps activations in the library's layout between layers
         (grad_ops_nhwc: no layout change anywhere but the network's NCHW input and output), 'nchw' runs every layer through
         the NCHW per-operator ABI (grad_ops)."""
-        from .. import ops
         if not self._cfg.resamp_with_conv:
             raise NotImplementedError('training with resamp_with_conv=False is not provided')
         if self.train_executor == 'planned' and self.arch == 0 and self.train_layout == 'nhwc':
@@ -338,91 +354,90 @@ class HipUNet(nn.Module, _HandleSurface):
         if self.y_scale:
             raise NotImplementedError('a network with y_scale (ddpm_KxSR) trains on the planned graph only (CSD_TRAIN_EXECUTOR=planned, '
                                       'CSD_TRAIN_LAYOUT=nhwc)')
-        nhwc = self.train_layout == 'nhwc'
-        if nhwc:
-            from .. import grad_ops_nhwc as G
-        else:
-            from .. import grad_ops as G
-        m, prec, act = self.all_modules, self.precision, self._act_name
         labels = self._check_io(x, y, labels)
         self._train_calls += 1
-        drop = [0]
-        cdim = 3 if nhwc else 1            # channel axis of an activation
-        side = (lambda t: t.shape[1]) if nhwc else (lambda t: t.shape[-1])
-        bias_add = G.bias_add if nhwc else G.bias_add_nchw
-
-        def dropout(h):
-            drop[0] += 1
-            return G.dropout(h, self._dropout, self.dropout_seed, (self._train_calls << 16) + drop[0])
-
-        def res(node, h, temb):
-            cin, cout = h.shape[cdim], node.Conv_0.weight.shape[0]
-            t = G.groupnorm_act(h, node.GroupNorm_0.weight, node.GroupNorm_0.bias, 32, 1e-6, act)
-            t = G.conv2d(t, node.Conv_0.weight, node.Conv_0.bias, precision=prec)
-            if temb is not None:
-                t = bias_add(t, G.linear(temb, node.Dense_0.weight, node.Dense_0.bias, act_in=act))
-            t = G.groupnorm_act(t, node.GroupNorm_1.weight, node.GroupNorm_1.bias, 32, 1e-6, act)
-            t = G.conv2d(dropout(t), node.Conv_1.weight, node.Conv_1.bias, precision=prec)
-            if cin != cout:
-                h = G.nin(h, node.NIN_0.W, node.NIN_0.b, prec)
-            return G.axpby(h, t)
-
-        def attn(node, h):
-            t = G.groupnorm_act(h, node.GroupNorm_0.weight, node.GroupNorm_0.bias, 32, 1e-6, 'none')
-            if nhwc:      # q | k | v from ONE 1x1 contraction (weights concatenated: data movement), packed per pixel
-                W = torch.cat([node.NIN_0.W, node.NIN_1.W, node.NIN_2.W], dim=1)
-                b = torch.cat([node.NIN_0.b, node.NIN_1.b, node.NIN_2.b])
-                a = G.attention(G.nin(t, W, b, prec))
-            else:
-                a = G.attention(G.nin(t, node.NIN_0.W, node.NIN_0.b, prec), G.nin(t, node.NIN_1.W, node.NIN_1.b, prec),
-                                G.nin(t, node.NIN_2.W, node.NIN_2.b, prec))
-            return G.axpby(h, G.nin(a, node.NIN_3.W, node.NIN_3.b, prec))
-
+        ex = (_TrainOpsNHWC if self.train_layout == 'nhwc' else _TrainOpsNCHW)(self)
         h = torch.cat([x, y], dim=1) if self.y_channels else x
-        i = 0
-        temb = None
-        if self.conditional:
-            temb = ops.timestep_embedding(labels, self.nf)
-            temb = G.linear(temb, m[0].weight, m[0].bias)
-            temb = G.linear(temb, m[1].weight, m[1].bias, act_in=act)
-            i = 2
+        temb = ops.timestep_embedding(labels, self.nf) if self.conditional else None
         if not self.centered:
-            h = G.axpby(h, None, 2.0, 0.0, -1.0, 1.0)
-        if nhwc:          # network input is the reference's NCHW; from here on activations are [B, H, W, C]
-            hs = [G.conv2d(h, m[i].weight, m[i].bias, precision=prec, layout=G.OUT_NHWC)]
-        else:
-            hs = [G.conv2d(h, m[i].weight, m[i].bias, precision=prec)]
-        i += 1
-        for lvl in range(self.num_resolutions):
-            for _ in range(self.num_res_blocks):
-                h = res(m[i], hs[-1], temb)
-                i += 1
-                if side(h) in self.attn_resolutions:
-                    h = attn(m[i], h)
-                    i += 1
-                hs.append(h)
-            if lvl != self.num_resolutions - 1:
-                hs.append(G.conv2d(hs[-1], m[i].Conv_0.weight, m[i].Conv_0.bias, stride=2, downsample_pad=True, precision=prec))
-                i += 1
-        h = res(m[i], hs[-1], temb)
-        h = attn(m[i + 1], h)
-        h = res(m[i + 2], h, temb)
-        i += 3
-        for lvl in reversed(range(self.num_resolutions)):
-            for _ in range(self.num_res_blocks + 1):
-                h = res(m[i], torch.cat([h, hs.pop()], dim=cdim), temb)
-                i += 1
-            if side(h) in self.attn_resolutions:
-                h = attn(m[i], h)
-                i += 1
-            if lvl != 0:
-                h = G.conv2d(h, m[i].Conv_0.weight, m[i].Conv_0.bias, up2=True, precision=prec)
-                i += 1
-        assert not hs and i == len(m) - 2
-        h = G.groupnorm_act(h, m[i].weight, m[i].bias, 32, 1e-6, act)
-        if nhwc:
-            return G.conv2d(h, m[i + 1].weight, m[i + 1].bias, precision=prec, layout=G.IN_NHWC)
-        return G.conv2d(h, m[i + 1].weight, m[i + 1].bias, precision=prec)
+            h = ex.O.axpby(h, None, 2.0, 0.0, -1.0, 1.0)
+        return run_unet(self._topology(), self.all_modules, ex, h, temb)
+
+    def _topology(self):
+        """the module list of this DDPM-family network (arch 0), as csrc/unet.hip builds it from the same config"""
+        c = self._cfg
+        return build_modules('ddpm', c.nf, c.ch_mult[:c.n_levels], c.num_res_blocks, self.x_channels + self.y_channels, self.out_channels,
+                             [l for l in range(c.n_levels) if self.image_size >> l in self.attn_resolutions], self.conditional)
+
+
+class _TrainOpsNCHW(Executor):
+    """Executor of ``topology.run_unet`` for the training mode of the 2-D DDPM family: the arithmetic of each module of the reference
+    forward (models/ddpm.py:149-213) on the differentiable NCHW operators of grad_ops.  One object per forward: it counts the dropout
+    sites, whose Philox stream ids are ``(model._train_calls << 16) + k``, k = 1, 2, ... in module order."""
+
+    O = grad_ops
+    bias_add = staticmethod(grad_ops.bias_add_nchw)
+
+    def __init__(self, model):
+        self.model, self.prec, self.act, self.drops = model, model.precision, model._act_name, 0
+
+    def qkv_attention(self, node, t):
+        O, p = self.O, self.prec
+        return O.attention(O.nin(t, node.NIN_0.W, node.NIN_0.b, p), O.nin(t, node.NIN_1.W, node.NIN_1.b, p),
+                           O.nin(t, node.NIN_2.W, node.NIN_2.b, p))
+
+    def stem(self, node, m, x):
+        return self.O.conv2d(x, node.weight, node.bias, precision=self.prec)
+
+    head_conv = stem
+
+    def res(self, node, m, h, temb):
+        O, act, model = self.O, self.act, self.model
+        t = O.groupnorm_act(h, node.GroupNorm_0.weight, node.GroupNorm_0.bias, 32, 1e-6, act)
+        t = O.conv2d(t, node.Conv_0.weight, node.Conv_0.bias, precision=self.prec)
+        if temb is not None:
+            t = self.bias_add(t, O.linear(temb, node.Dense_0.weight, node.Dense_0.bias, act_in=act))
+        t = O.groupnorm_act(t, node.GroupNorm_1.weight, node.GroupNorm_1.bias, 32, 1e-6, act)
+        self.drops += 1
+        t = O.dropout(t, model._dropout, model.dropout_seed, (model._train_calls << 16) + self.drops)
+        t = O.conv2d(t, node.Conv_1.weight, node.Conv_1.bias, precision=self.prec)
+        if m.cin != m.cout:
+            h = O.nin(h, node.NIN_0.W, node.NIN_0.b, self.prec)
+        return O.axpby(h, t)
+
+    def attn(self, node, m, h):
+        O = self.O
+        t = O.groupnorm_act(h, node.GroupNorm_0.weight, node.GroupNorm_0.bias, 32, 1e-6, 'none')
+        return O.axpby(h, O.nin(self.qkv_attention(node, t), node.NIN_3.W, node.NIN_3.b, self.prec))
+
+    def downsample(self, node, m, h, temb):
+        return self.O.conv2d(h, node.Conv_0.weight, node.Conv_0.bias, stride=2, downsample_pad=True, precision=self.prec)
+
+    def upsample(self, node, m, h, temb):
+        return self.O.conv2d(h, node.Conv_0.weight, node.Conv_0.bias, up2=True, precision=self.prec)
+
+    def gn(self, node, m, h):
+        return self.O.groupnorm_act(h, node.weight, node.bias, 32, 1e-6, self.act)
+
+
+class _TrainOpsNHWC(_TrainOpsNCHW):
+    """... on grad_ops_nhwc: activations stay in the library's layout [B, H, W, C] between layers; only the first convolution (NCHW
+    in) and the last (NCHW out) change it."""
+
+    O, cdim = grad_ops_nhwc, 3
+    bias_add = staticmethod(grad_ops_nhwc.bias_add)
+
+    def qkv_attention(self, node, t):
+        """q | k | v from ONE 1x1 contraction (weights concatenated: data movement), packed per pixel"""
+        W = torch.cat([node.NIN_0.W, node.NIN_1.W, node.NIN_2.W], dim=1)
+        b = torch.cat([node.NIN_0.b, node.NIN_1.b, node.NIN_2.b])
+        return self.O.attention(self.O.nin(t, W, b, self.prec))
+
+    def stem(self, node, m, x):
+        return self.O.conv2d(x, node.weight, node.bias, precision=self.prec, layout=self.O.OUT_NHWC)
+
+    def head_conv(self, node, m, h):
+        return self.O.conv2d(h, node.weight, node.bias, precision=self.prec, layout=self.O.IN_NHWC)
 
 
 def _release_shared_ws(model_ref, owner):

@@ -1,8 +1,9 @@
 """NCSN++ score networks (reference models/ncsnpp.py:39-401) on the per-operator C ABI.
 
 Registers ``ncsnpp`` and ``ncsnpp_paired`` with the reference's constructor / call signatures and the reference's
-``state_dict`` keys (``all_modules.{i}.…``).  The module list is rebuilt from the config exactly as
-``NCSNpp.__init__`` does (:44-236) and ``forward`` follows ``NCSNpp.forward`` (:238-388) step for step; every
+``state_dict`` keys (``all_modules.{i}.…``).  The module list of ``NCSNpp.__init__`` (:44-236) comes from
+``topology.build_modules`` and the walk of ``NCSNpp.forward`` (:238-388) from ``topology.run_unet``; the class ``NCSNpp``
+below is the executor of that walk - the arithmetic of one module per method - and every
 tensor operation is a HIP kernel behind ``include/csd.h`` (conv, GroupNorm(+act), attention, upfirdn2d FIR
 resampling, Linear, Fourier / positional embedding, axpby, bias add) - torch only allocates buffers, concatenates
 skip connections (a copy) and slices views.  There is no PyTorch fallback.
@@ -19,38 +20,48 @@ in {positional, fourier}, ``skip_rescale`` either
 way, attention at any resolutions.  Other values raise NotImplementedError (never a silent fallback).
 """
 import math
-import os
 
 import numpy as np
 import torch
 import torch.nn as nn
 
-from .. import _lib, ops
+from .. import ops
 from .._lib import require_gpu_tensor
 from . import utils
-from .ddpm import HipUNet, _KxSR, _Node, _fan_avg_uniform
+from .ddpm import HipUNet, _KxSR, _Node, _activation, _fan_avg_uniform, _model_key, _precision
+from .topology import Executor, build_modules, run_unet
 
 
 def _groups(c):
     return min(c // 4, 32)          # models/layerspp.py:67,219,231; ncsnpp.py:200-233
 
 
-class NCSNpp(nn.Module):
+def _check_options(config):
+    """the options of NCSNpp.__init__ (models/ncsnpp.py:44-75) that the HIP path covers; anything else is refused"""
+    m = config.model
+    assert m.progressive.lower() in ['none', 'output_skip', 'residual']
+    assert m.progressive_input.lower() in ['none', 'input_skip', 'residual']
+    assert m.embedding_type.lower() in ['fourier', 'positional']
+    if m.resblock_type.lower() != 'biggan':
+        raise NotImplementedError("ncsnpp on the HIP path: resblock_type 'biggan' only (got %r)" % m.resblock_type)
+    if m.progressive.lower() == 'residual':
+        # (its pyramid_upsample is up_or_down_sampling.Conv2d(up=True) = upsample_conv_2d, which fails upstream; no config uses it)
+        raise NotImplementedError("ncsnpp on the HIP path: progressive='residual' is not provided")
+    if m.progressive_combine.lower() != 'sum':
+        raise NotImplementedError("ncsnpp on the HIP path: progressive_combine 'sum' only (got %r)" % m.progressive_combine)
+    if m.embedding_type.lower() == 'fourier':
+        assert config.training.continuous, "Fourier features are only used for continuous training."
+
+
+class NCSNpp(nn.Module, Executor):
     """``ncsnpp`` (models/ncsnpp.py:39-236)."""
 
     def __init__(self, config, precision=None):
         super().__init__()
         m, d = config.model, config.data
-        get = (lambda k, dflt=None: m.get(k, dflt)) if hasattr(m, 'get') else (lambda k, dflt=None: getattr(m, k, dflt))
-        if precision is None:
-            precision = get('csd_precision') or os.environ.get('CSD_PRECISION', 'fp16x3')
-        if precision not in _lib.PREC_IDS:
-            raise ValueError('unknown csd precision %r' % (precision,))
-        self.precision = precision
+        self.precision = _precision(config, precision)
         self.config = config
-        self.act = m.nonlinearity.lower()
-        if self.act not in _lib.ACT_IDS or self.act == 'none':
-            raise NotImplementedError('activation function does not exist!')
+        self.act = _activation(config)
         self.nf = nf = m.nf
         ch_mult = tuple(m.ch_mult)
         self.num_res_blocks = m.num_res_blocks
@@ -67,75 +78,15 @@ class NCSNpp(nn.Module):
         self.progressive_input = m.progressive_input.lower()
         self.embedding_type = m.embedding_type.lower()
         self.init_scale = m.init_scale
-        combine = m.progressive_combine.lower()
-        assert self.progressive in ['none', 'output_skip', 'residual']
-        assert self.progressive_input in ['none', 'input_skip', 'residual']
-        assert self.embedding_type in ['fourier', 'positional']
-        if self.resblock_type != 'biggan':
-            raise NotImplementedError("ncsnpp on the HIP path: resblock_type 'biggan' only (got %r)" % self.resblock_type)
-        if self.progressive == 'residual':
-            # (its pyramid_upsample is up_or_down_sampling.Conv2d(up=True) = upsample_conv_2d, which fails upstream; no config uses it)
-            raise NotImplementedError("ncsnpp on the HIP path: progressive='residual' is not provided")
-        if combine != 'sum':
-            raise NotImplementedError("ncsnpp on the HIP path: progressive_combine 'sum' only (got %r)" % combine)
-        channels = d.num_channels
-        self.channels = channels
-
-        # ---- module list, in the order of NCSNpp.__init__ ----
-        mods = []          # (kind, dict)
-        if self.embedding_type == 'fourier':
-            assert config.training.continuous, "Fourier features are only used for continuous training."
-            mods.append(('fourier', dict(size=nf, scale=m.fourier_scale)))
-            embed_dim = 2 * nf
-        else:
-            embed_dim = nf
-        if self.conditional:
-            mods.append(('linear', dict(cin=embed_dim, cout=nf * 4)))
-            mods.append(('linear', dict(cin=nf * 4, cout=nf * 4)))
-        mods.append(('conv3', dict(cin=channels, cout=nf, init_scale=1.)))
-        hs_c = [nf]
-        in_ch = nf
-        input_pyramid_ch = channels
-        for i_level in range(self.num_resolutions):
-            for _ in range(self.num_res_blocks):
-                out_ch = nf * ch_mult[i_level]
-                mods.append(('res', dict(cin=in_ch, cout=out_ch, up=False, down=False)))
-                in_ch = out_ch
-                if self.all_resolutions[i_level] in self.attn_resolutions:
-                    mods.append(('attn', dict(c=in_ch)))
-                hs_c.append(in_ch)
-            if i_level != self.num_resolutions - 1:
-                mods.append(('res', dict(cin=in_ch, cout=in_ch, up=False, down=True)))
-                if self.progressive_input == 'input_skip':
-                    mods.append(('combine', dict(dim1=input_pyramid_ch, dim2=in_ch)))
-                elif self.progressive_input == 'residual':
-                    mods.append(('pyr_down', dict(cin=input_pyramid_ch, cout=in_ch)))     # ncsnpp.py:171-173
-                    input_pyramid_ch = in_ch
-                hs_c.append(in_ch)
-        in_ch = hs_c[-1]
-        mods.append(('res', dict(cin=in_ch, cout=in_ch, up=False, down=False)))
-        mods.append(('attn', dict(c=in_ch)))
-        mods.append(('res', dict(cin=in_ch, cout=in_ch, up=False, down=False)))
-        for i_level in reversed(range(self.num_resolutions)):
-            for _ in range(self.num_res_blocks + 1):
-                out_ch = nf * ch_mult[i_level]
-                mods.append(('res', dict(cin=in_ch + hs_c.pop(), cout=out_ch, up=False, down=False)))
-                in_ch = out_ch
-            if self.all_resolutions[i_level] in self.attn_resolutions:
-                mods.append(('attn', dict(c=in_ch)))
-            if self.progressive == 'output_skip':
-                mods.append(('gn', dict(c=in_ch)))
-                mods.append(('conv3', dict(cin=in_ch, cout=channels, init_scale=self.init_scale)))
-            if i_level != 0:
-                mods.append(('res', dict(cin=in_ch, cout=in_ch, up=True, down=False)))
-        assert not hs_c
-        if self.progressive != 'output_skip':
-            mods.append(('gn', dict(c=in_ch)))
-            mods.append(('conv3', dict(cin=in_ch, cout=channels, init_scale=self.init_scale)))
-        self._mods = mods
-        self.all_modules = nn.ModuleList([self._make_node(k, a) for k, a in mods])
+        _check_options(config)
+        self.channels = channels = d.num_channels
+        self.fourier_scale = _model_key(config, 'fourier_scale', 16)
+        self._topology = build_modules('ncsnpp', nf, ch_mult, m.num_res_blocks, channels, channels, self._attn_levels(self.all_resolutions[0]),
+                                       self.conditional, self.embedding_type == 'fourier', self.progressive, self.progressive_input,
+                                       self.init_scale)
+        self.all_modules = nn.ModuleList([self._make_node(mod.kind, mod) for mod in self._topology])   # (list order: the RNG's too)
         self._fir_cache = {}
-        self._dropout_p = float(get('dropout', 0.0) or 0.0)
+        self._dropout_p = float(_model_key(config, 'dropout', 0.0))
         self.dropout_seed = int(getattr(config, 'seed', 0) or 0)
         self._train_calls = 0
         self._drop_count = 0
@@ -160,30 +111,30 @@ class NCSNpp(nn.Module):
             node.add_module(sub, g)
 
         if kind == 'fourier':
-            P('W', torch.randn(a['size']) * a['scale'], grad=False)          # layerspp.py:37
+            P('W', torch.randn(a.cin) * self.fourier_scale, grad=False)          # layerspp.py:37
         elif kind == 'linear':
-            P('weight', _fan_avg_uniform((a['cout'], a['cin']), 1., False))  # ncsnpp.py:97-101
-            P('bias', torch.zeros(a['cout']))
-        elif kind == 'conv3':
-            P('weight', _fan_avg_uniform((a['cout'], a['cin'], 3, 3), a['init_scale'], False))
-            P('bias', torch.zeros(a['cout']))
+            P('weight', _fan_avg_uniform((a.cout, a.cin), 1., False))  # ncsnpp.py:97-101
+            P('bias', torch.zeros(a.cout))
+        elif kind == 'conv':
+            P('weight', _fan_avg_uniform((a.cout, a.cin, 3, 3), a.init_scale, False))
+            P('bias', torch.zeros(a.cout))
         elif kind == 'gn':
-            P('weight', torch.ones(a['c']))
-            P('bias', torch.zeros(a['c']))
+            P('weight', torch.ones(a.cin))
+            P('bias', torch.zeros(a.cin))
         elif kind == 'combine':
-            conv('Conv_0', a['dim2'], a['dim1'], 1, 1.)                      # layerspp.py:49
+            conv('Conv_0', a.cout, a.cin, 1, 1.)                      # layerspp.py:49
         elif kind == 'pyr_down':                                             # layerspp.Downsample(with_conv=True), :130-147
-            conv('Conv2d_0' if self.fir else 'Conv_0', a['cout'], a['cin'], 3, 1.)
+            conv('Conv2d_0' if self.fir else 'Conv_0', a.cout, a.cin, 3, 1.)
         elif kind == 'attn':
-            gn('GroupNorm_0', a['c'])
+            gn('GroupNorm_0', a.cin)
             for j in range(4):
                 nin = _Node()
                 scale = self.init_scale if j == 3 else 0.1                   # layerspp.py:69-72; NIN default 0.1
-                nin.register_parameter('W', nn.Parameter(_fan_avg_uniform((a['c'], a['c']), scale, True)))
-                nin.register_parameter('b', nn.Parameter(torch.zeros(a['c'])))
+                nin.register_parameter('W', nn.Parameter(_fan_avg_uniform((a.cin, a.cin), scale, True)))
+                nin.register_parameter('b', nn.Parameter(torch.zeros(a.cin)))
                 node.add_module('NIN_%d' % j, nin)
         elif kind == 'res':
-            cin, cout = a['cin'], a['cout']
+            cin, cout = a.cin, a.cout
             gn('GroupNorm_0', cin)
             conv('Conv_0', cout, cin, 3, 1.)
             if self.conditional:
@@ -193,7 +144,7 @@ class NCSNpp(nn.Module):
                 node.add_module('Dense_0', dn)
             gn('GroupNorm_1', cout)
             conv('Conv_1', cout, cout, 3, self.init_scale)
-            if cin != cout or a['up'] or a['down']:
+            if cin != cout or a.up or a.down:
                 conv('Conv_2', cout, cin, 1, 1.)
         else:
             raise AssertionError(kind)
@@ -233,22 +184,9 @@ class NCSNpp(nn.Module):
         p = k.shape[0] - factor
         return ops.upfirdn2d(x, k, down=factor, pad=((p + 1) // 2, p // 2))
 
-    def _pyr_down(self, node, x):
-        """layerspp.Downsample(with_conv=True) of the 'residual' input pyramid (layerspp.py:130-165).  fir: conv_downsample_2d =
-        FIR, then a VALID stride-2 3x3 conv on the (H+1)-wide result; run as the library's stride-2 convolution (pad (0,1,0,1))
-        on an (H+2)-wide FIR output - its first H/2 rows/columns read exactly the valid window - and cropped."""
-        O = self._O
-        if not self.fir:
-            return O.conv2d(x, node.Conv_0.weight, node.Conv_0.bias, stride=2, downsample_pad=True, precision=self.precision)
-        k = self._fir(x.device, 1.0)
-        p = (k.shape[0] - 2) + 2
-        z = ops.upfirdn2d(x, k, pad=((p + 1) // 2, p // 2 + 1))
-        y = O.conv2d(z, node.Conv2d_0.weight, node.Conv2d_0.bias, stride=2, downsample_pad=True, precision=self.precision)
-        return y[:, :, :-1, :-1].contiguous()
-
-    # ---- blocks ----
+    # ---- the executor of topology.run_unet: its arithmetic, on the operator set O ----
     @property
-    def _O(self):
+    def O(self):
         """operator set: the differentiable shells of grad_ops (HIP forward + backward kernels) while training under autograd,
         the plain forward wrappers otherwise"""
         if self.training and torch.is_grad_enabled():
@@ -265,38 +203,81 @@ class NCSNpp(nn.Module):
         return grad_ops.dropout(h, self._dropout_p, self.dropout_seed, (self._train_calls << 16) + self._drop_count)
 
     def _conv(self, node, x, ksize):
-        return self._O.conv2d(x, node.weight, node.bias, precision=self.precision if ksize == 3 else 'fp32')
+        return self.O.conv2d(x, node.weight, node.bias, precision=self.precision if ksize == 3 else 'fp32')
 
-    def _res(self, node, a, x, temb):
+    def _skip_add(self, x, h):
+        return self.O.axpby(x, h, post=(1.0 / math.sqrt(2.0)) if self.skip_rescale else 1.0)
+
+    def emb_fourier(self, node, a, time_cond):
+        return ops.fourier_embedding(time_cond, node.W)
+
+    def stem(self, node, a, x):
+        return self._conv(node, x, 3)
+
+    head_conv = stem
+
+    def res(self, node, a, x, temb):
         """ResnetBlockBigGANpp.forward (models/layerspp.py:242-274)."""
-        cin, cout = a['cin'], a['cout']
-        O = self._O
-        h = O.groupnorm_act(x, node.GroupNorm_0.weight, node.GroupNorm_0.bias, groups=_groups(cin), act=self.act)
-        if a['up']:
+        O = self.O
+        h = O.groupnorm_act(x, node.GroupNorm_0.weight, node.GroupNorm_0.bias, groups=_groups(a.cin), act=self.act)
+        if a.up:
             h, x = self._upsample_2d(h), self._upsample_2d(x)
-        elif a['down']:
+        elif a.down:
             h, x = self._downsample_2d(h), self._downsample_2d(x)
         h = self._conv(node.Conv_0, h, 3)
-        if temb is not None:
+        if self.conditional:
             h = O.bias_add_nchw(h, O.linear(temb, node.Dense_0.weight, node.Dense_0.bias, act_in=self.act))
-        h = O.groupnorm_act(h, node.GroupNorm_1.weight, node.GroupNorm_1.bias, groups=_groups(cout), act=self.act)
+        h = O.groupnorm_act(h, node.GroupNorm_1.weight, node.GroupNorm_1.bias, groups=_groups(a.cout), act=self.act)
         h = self._conv(node.Conv_1, self._dropout(h), 3)
-        if cin != cout or a['up'] or a['down']:
+        if a.cin != a.cout or a.up or a.down:
             x = self._conv(node.Conv_2, x, 1)
-        return O.axpby(x, h, post=(1.0 / math.sqrt(2.0)) if self.skip_rescale else 1.0)
+        return self._skip_add(x, h)
 
-    def _attn(self, node, a, x):
+    downsample = upsample = res            # (BigGAN blocks whose record has `down` / `up` set)
+
+    def combine(self, node, a, pyramid, h):
+        """Combine 'sum' (models/layerspp.py:53-57) behind the image pyramid's resampling: Conv_0(pyramid) + h"""
+        pyramid = self._downsample_2d(pyramid)
+        return pyramid, self.O.axpby(self._conv(node.Conv_0, pyramid, 1), h)
+
+    def pyr_down(self, node, a, x, h):
+        """layerspp.Downsample(with_conv=True) of the 'residual' input pyramid (layerspp.py:130-165), added to h (ncsnpp.py:302-309).
+        fir: conv_downsample_2d = FIR, then a VALID stride-2 3x3 conv on the (H+1)-wide result; run as the library's stride-2
+        convolution (pad (0,1,0,1)) on an (H+2)-wide FIR output - its first H/2 rows/columns read exactly the valid window - and cropped."""
+        O = self.O
+        if not self.fir:
+            y = O.conv2d(x, node.Conv_0.weight, node.Conv_0.bias, stride=2, downsample_pad=True, precision=self.precision)
+        else:
+            k = self._fir(x.device, 1.0)
+            p = (k.shape[0] - 2) + 2
+            z = ops.upfirdn2d(x, k, pad=((p + 1) // 2, p // 2 + 1))
+            y = O.conv2d(z, node.Conv2d_0.weight, node.Conv2d_0.bias, stride=2, downsample_pad=True, precision=self.precision)
+            y = y[:, :, :-1, :-1].contiguous()
+        return self._skip_add(y, h)
+
+    def gn(self, node, a, h):
+        return self.O.groupnorm_act(h, node.weight, node.bias, groups=_groups(a.cin), act=self.act)
+
+    def pyr_conv(self, node, a, ph, pyramid):
+        """the level's image, added to the upsampled pyramid of the levels below (ncsnpp.py:339-361, 'output_skip')"""
+        ph = self._conv(node, ph, 3)
+        return ph if pyramid is None else self.O.axpby(self._upsample_2d(pyramid), ph)
+
+    def attn(self, node, a, x):
         """AttnBlockpp.forward (models/layerspp.py:75-91)."""
-        C = a['c']
-        O = self._O
+        C = a.cin
+        O = self.O
         h = O.groupnorm_act(x, node.GroupNorm_0.weight, node.GroupNorm_0.bias, groups=_groups(C), act='none')
 
         def nin(n, t):        # NIN = per-pixel matmul with W [in, out] (models/layers.py:555-564) = 1x1 conv with W^T
             return O.conv2d(t, n.W.t().reshape(C, C, 1, 1).contiguous(), n.b, precision='fp32')
 
         q, k, v = nin(node.NIN_0, h), nin(node.NIN_1, h), nin(node.NIN_2, h)
-        h = nin(node.NIN_3, O.attention(q, k, v))
-        return O.axpby(x, h, post=(1.0 / math.sqrt(2.0)) if self.skip_rescale else 1.0)
+        return self._skip_add(x, nin(node.NIN_3, O.attention(q, k, v)))
+
+    def _attn_levels(self, side):
+        """the levels at which a network on side x side images has attention behind its blocks"""
+        return [l for l in range(self.num_resolutions) if side // 2 ** l in self.attn_resolutions]
 
     # ---- forward: NCSNpp.forward (models/ncsnpp.py:238-388) ----
     def forward(self, x, time_cond):
@@ -305,88 +286,17 @@ class NCSNpp(nn.Module):
         if not self.training and torch.is_grad_enabled() and x.requires_grad:
             raise NotImplementedError("input gradients are provided by the planned NCSN++ graph only; this operator-granular class "
                                       "(progressive_input='residual') has none")
+        if self._attn_levels(x.shape[-1]) != self._attn_levels(self.all_resolutions[0]):
+            raise ValueError('ncsnpp: the module list was built for images of side %d (config.data.effective_image_size), where attention '
+                             'runs at other levels than on this input of side %d' % (self.all_resolutions[0], x.shape[-1]))
         x = x.contiguous().float()
         time_cond = time_cond.contiguous().float()
-        mods, nodes = self._mods, self.all_modules
-        O = self._O
         self._train_calls += 1
         self._drop_count = 0
-        i = 0
-        if self.embedding_type == 'fourier':
-            temb = ops.fourier_embedding(time_cond, nodes[i].W)
-            i += 1
-        else:
-            temb = ops.timestep_embedding(time_cond, self.nf)
-        if self.conditional:
-            temb = O.linear(temb, nodes[i].weight, nodes[i].bias)
-            i += 1
-            temb = O.linear(temb, nodes[i].weight, nodes[i].bias, act_in=self.act)
-            i += 1
-        else:
-            temb = None
+        temb = time_cond if self.embedding_type == 'fourier' else ops.timestep_embedding(time_cond, self.nf)
         if not self.centered:
-            x = O.axpby(x, None, alpha=2.0, gamma=-1.0)
-        input_pyramid = x if self.progressive_input != 'none' else None
-        hs = [self._conv(nodes[i], x, 3)]
-        i += 1
-        for i_level in range(self.num_resolutions):
-            for _ in range(self.num_res_blocks):
-                h = self._res(nodes[i], mods[i][1], hs[-1], temb)
-                i += 1
-                if h.shape[-1] in self.attn_resolutions:
-                    h = self._attn(nodes[i], mods[i][1], h)
-                    i += 1
-                hs.append(h)
-            if i_level != self.num_resolutions - 1:
-                h = self._res(nodes[i], mods[i][1], hs[-1], temb)
-                i += 1
-                if self.progressive_input == 'input_skip':
-                    input_pyramid = self._downsample_2d(input_pyramid)
-                    # Combine 'sum' (models/layerspp.py:53-57): Conv_0(input_pyramid) + h
-                    h = O.axpby(self._conv(nodes[i].Conv_0, input_pyramid, 1), h)
-                    i += 1
-                elif self.progressive_input == 'residual':           # ncsnpp.py:302-309
-                    input_pyramid = self._pyr_down(nodes[i], input_pyramid)
-                    i += 1
-                    h = O.axpby(input_pyramid, h, post=(1.0 / math.sqrt(2.0)) if self.skip_rescale else 1.0)
-                    input_pyramid = h
-                hs.append(h)
-        h = hs[-1]
-        h = self._res(nodes[i], mods[i][1], h, temb)
-        i += 1
-        h = self._attn(nodes[i], mods[i][1], h)
-        i += 1
-        h = self._res(nodes[i], mods[i][1], h, temb)
-        i += 1
-        pyramid = None
-        for i_level in reversed(range(self.num_resolutions)):
-            for _ in range(self.num_res_blocks + 1):
-                h = self._res(nodes[i], mods[i][1], torch.cat([h, hs.pop()], dim=1), temb)
-                i += 1
-            if h.shape[-1] in self.attn_resolutions:
-                h = self._attn(nodes[i], mods[i][1], h)
-                i += 1
-            if self.progressive == 'output_skip':
-                ph = O.groupnorm_act(h, nodes[i].weight, nodes[i].bias, groups=_groups(mods[i][1]['c']), act=self.act)
-                i += 1
-                ph = self._conv(nodes[i], ph, 3)
-                i += 1
-                pyramid = ph if pyramid is None else O.axpby(self._upsample_2d(pyramid), ph)
-            if i_level != 0:
-                h = self._res(nodes[i], mods[i][1], h, temb)
-                i += 1
-        assert not hs
-        if self.progressive == 'output_skip':
-            h = pyramid
-        else:
-            h = O.groupnorm_act(h, nodes[i].weight, nodes[i].bias, groups=_groups(mods[i][1]['c']), act=self.act)
-            i += 1
-            h = self._conv(nodes[i], h, 3)
-            i += 1
-        assert i == len(nodes)
-        return h
-
-
+            x = self.O.axpby(x, None, alpha=2.0, gamma=-1.0)
+        return run_unet(self._topology, self.all_modules, self, x, temb)
 
 
 class NCSNpp_paired(NCSNpp):
@@ -399,8 +309,6 @@ class NCSNpp_paired(NCSNpp):
         return {'x': out[:, :xc], 'y': out[:, xc:]}
 
 
-
-
 # ------------------------------------------------------------------------------------------------------------------
 # Planned-graph executor (csrc/unet.hip, arch 1): the same NHWC kernels, fused GroupNorm statistics, fp16-MFMA conv
 # schedules and fused PC loop as the DDPM family.  These are the classes the registry hands out; the operator-granular
@@ -411,21 +319,11 @@ class HipNCSNpp(HipUNet):
 
     def __init__(self, config, precision=None):
         m = config.model
-        if m.resblock_type.lower() != 'biggan':
-            raise NotImplementedError("ncsnpp on the HIP path: resblock_type 'biggan' only (got %r)" % m.resblock_type)
-        if m.progressive.lower() == 'residual':
-            # (its pyramid_upsample is up_or_down_sampling.Conv2d(up=True) = upsample_conv_2d, which fails upstream; no config uses it)
-            raise NotImplementedError("ncsnpp on the HIP path: progressive='residual' is not provided")
-        if m.progressive_combine.lower() != 'sum':
-            raise NotImplementedError("ncsnpp on the HIP path: progressive_combine 'sum' only")
+        _check_options(config)
         if not m.conditional:
             raise NotImplementedError('ncsnpp on the HIP path: time-conditional networks only')
-        assert m.progressive.lower() in ['none', 'output_skip'] and m.progressive_input.lower() in ['none', 'input_skip', 'residual']
-        assert m.embedding_type.lower() in ['fourier', 'positional']
-        if m.embedding_type.lower() == 'fourier':
-            assert config.training.continuous, "Fourier features are only used for continuous training."
         self.embedding_type = m.embedding_type.lower()
-        self._fourier_scale = float(m.get('fourier_scale', 16) if hasattr(m, 'get') else getattr(m, 'fourier_scale', 16))
+        self._fourier_scale = float(_model_key(config, 'fourier_scale', 16))
         self._init_scale = float(m.init_scale)
         self._pyramid_out = m.progressive.lower() == 'output_skip'
         self._config = config

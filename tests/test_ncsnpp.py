@@ -64,6 +64,43 @@ def test_forward_vs_reference(case, precision, tol):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize('case', list(cases.NCSNPP_CASES))
+@pytest.mark.parametrize('precision', ['fp32', 'fp16x3'])
+def test_operator_class_eval_forward_vs_reference(case, precision):
+    """The eval-mode forward of the operator-granular classes (``ncsnpp_ops`` / ``ncsnpp_paired_ops``: the A/B yardstick of the planned
+    graph in tools/bench_ncsnpp_cifar.py and tools/bench_other.py) against the reference's outputs, with the bound of the planned
+    class above: 2e-5 of the output maximum.  Measured where this test was written, per case (fp32 / fp16x3), identical before and after
+    the executor moved onto models/topology.py: fourier_skip 1.72e-6 / 1.42e-6, positional_plain 1.76e-6 / 1.61e-6, paired_skip
+    1.51e-6 / 1.19e-6, residual_input 1.58e-6 / 1.28e-6, nofir_skip 1.66e-6 / 1.43e-6, nofir_residual 1.41e-6 / 1.20e-6."""
+    from conditional_score_diffusion_amd.models import utils as mutils
+    cfg, B, x, labels = cases.ncsnpp_case(case)
+    paired = cfg.model.name == 'ncsnpp_paired'
+    cfg.model.name += '_ops'
+    cfg.model.csd_precision = precision
+    dev = torch.device('cuda:0')
+    model = mutils.create_model(cfg)
+    shapes = {k: tuple(v.shape) for k, v in model.state_dict().items()}
+    model.load_state_dict(cases.ncsnpp_params(shapes, 5))
+    model = model.to(dev).eval()
+    x, labels = x.to(dev), labels.to(dev)
+    with torch.no_grad():
+        if paired:
+            r = model({'x': x[:, :3], 'y': x[:, 3:]}, labels)
+            y = torch.cat([r['x'], r['y']], dim=1)
+        else:
+            y = model(x, labels)
+    ref = torch.from_numpy(np.load(GOLD)[case + '_out'])
+    err = (y.cpu() - ref).abs().max().item() / ref.abs().max().item()
+    print('ncsnpp_ops eval', case, precision, '%.3e' % err)
+    assert err < 2e-5, (case, precision, err)
+    # an input on which attention would sit at other levels than in the module list is refused, never computed
+    S = x.shape[-1]
+    big = torch.zeros(1, x.shape[1], 2 * S, 2 * S, device=dev)
+    with pytest.raises(ValueError, match='side %d.*side %d' % (S, 2 * S)):
+        model({'x': big[:, :3], 'y': big[:, 3:]}, labels[:1]) if paired else model(big, labels[:1])
+
+
+@pytest.mark.gpu
 def test_score_fn_and_generic_pc_sampler_run():
     """The registry, get_score_fn (Fourier label = log sigma) and the per-step PC loop accept the new family."""
     from conditional_score_diffusion_amd import sde_lib
