@@ -176,6 +176,7 @@ SIGNATURES = {
     'csd_fir_pyr_conv': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _f, _vp, _vp]),
     'csd_upfirdn2d': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     'csd_fused_bias_act': (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i64, _i, _i, _f, _f, _vp]),
+    'csd_fir_resample_nhwc': (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _vp]),
     'csd_nearest_up2': (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
     'csd_timestep_embedding': (_i, [_vp, _vp, _i, _i, _vp]),
     'csd_conv_wgrad_scratch_bytes': (_sz, [_i, _i, _i, _i, _i, _i, _i, _i]),

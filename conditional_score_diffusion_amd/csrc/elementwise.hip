@@ -730,7 +730,9 @@ int fir_resample_nhwc_launch(const float* in, float* out, int B, int H, int W, i
     for (int b = 0; b < 4; ++b) { f.k[a * 4 + b] = taps4[flip ? 3 - a : a] * taps4[flip ? 3 - b : b]; sum += f.k[a * 4 + b]; }
   for (int a = 0; a < 16; ++a) f.k[a] = f.k[a] / sum * (up ? 4.f : 1.f) * scale;
   const size_t total = (size_t)B * (up ? H * 2 : H / 2) * (up ? W * 2 : W / 2) * C;
-  if (C % 4 == 0) {
+  // (the 16-byte form needs 16-byte aligned tensors: every workspace tensor is; a caller's offset pointer takes the scalar form)
+  const bool aligned = ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out)) & 15) == 0;
+  if (C % 4 == 0 && aligned) {
     hipLaunchKernelGGL(fir_resample_nhwc4_kernel, dim3((unsigned)std::min<size_t>(cdiv64(total / 4, 256), 65536)), dim3(256), 0, s,
                        reinterpret_cast<const float4*>(in), reinterpret_cast<float4*>(out), H, W, C / 4, up, f, total / 4);
   } else {
@@ -820,6 +822,16 @@ extern "C" int csd_upfirdn2d(const float* x, const float* kernel, float* out, in
                      kernel, out, H, W, OH, OW, kh, kw, up_x, up_y, down_x, down_y, pad_x0, pad_y0, tiles_x);
   CSD_LAUNCH_CHECK();
   return CSD_OK;
+}
+
+extern "C" int csd_fir_resample_nhwc(const float* x, float* out, int B, int H, int W, int C, const float* fir_kernel, int up, void* stream) {
+  CSD_REQUIRE(x && out && fir_kernel, "fir_resample_nhwc: null argument");
+  CSD_REQUIRE(B >= 1 && C >= 1 && H >= 1 && W >= 1 && (up || (H % 2 == 0 && W % 2 == 0)),
+              "fir_resample_nhwc: bad shape B=%d H=%d W=%d C=%d (downsampling needs even sides)", B, H, W, C);
+  float sum = 0.f;
+  for (int i = 0; i < 4; ++i) { CSD_REQUIRE(std::isfinite(fir_kernel[i]), "fir_resample_nhwc: non-finite FIR tap"); sum += fir_kernel[i]; }
+  CSD_REQUIRE(sum != 0.f, "fir_resample_nhwc: the FIR taps sum to zero");
+  return fir_resample_nhwc_launch(x, out, B, H, W, C, fir_kernel, up ? 1 : 0, (hipStream_t)stream);
 }
 
 extern "C" int csd_fused_bias_act(const float* x, const float* bias, const float* ref, float* out, int64_t numel,

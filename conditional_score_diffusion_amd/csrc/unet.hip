@@ -423,19 +423,21 @@ static int build_modules(Net& n) {
                 CSD_MAX_IO_CHANNELS, c.out_channels);
     CSD_REQUIRE(c.act >= CSD_ACT_SWISH && c.act <= CSD_ACT_ELU, "unet: bad activation id %d", c.act);
     CSD_REQUIRE(c.precision >= CSD_PREC_F32 && c.precision <= CSD_PREC_F16F8, "unet: bad precision id %d", c.precision);
-    if (c.x_squeeze) {      // the 2x super-resolution networks: x is the image [B, x_channels / 4, 2S, 2S] (include/csd.h)
-      CSD_REQUIRE(c.x_squeeze == 1, "unet: x_squeeze must be 0 or 1 (got %d)", c.x_squeeze);
-      CSD_REQUIRE(c.x_channels % 4 == 0, "unet: x_squeeze needs x_channels %% 4 == 0 (got x_channels = %d)", c.x_channels);
-      CSD_REQUIRE(c.image_size <= 1024, "unet: x_squeeze is provided up to image_size 1024 (got %d)", c.image_size);
-      CSD_REQUIRE(c.out_channels >= c.x_channels, "unet: x_squeeze needs out_channels >= x_channels (got %d < %d)", c.out_channels,
-                  c.x_channels);
-    }
   } else {
     CSD_REQUIRE(c.n_levels >= 1 && c.n_levels <= CSD_MAX_LEVELS, "ncsnpp: bad n_levels %d", c.n_levels);
     CSD_REQUIRE(c.nf % 8 == 0, "ncsnpp: nf=%d must be a multiple of 8", c.nf);
     CSD_REQUIRE(c.image_size % (1 << (c.n_levels - 1)) == 0, "ncsnpp: image_size %d not divisible by 2^%d", c.image_size,
                 c.n_levels - 1);
-    CSD_REQUIRE(c.x_channels >= 1 && c.x_channels + c.y_channels <= 8, "ncsnpp: x+y channels must be <= 8");
+    // (as for the DDPM family: the input is assembled into in_cpad <= 32 channels; the output pyramid and the head store one 32-cout tile.
+    // More than 8 channels are provided for the paired networks - ncsnpp_paired, ncsnpp_2xSR: y_channels > 0; the unconditional network
+    // keeps its limit of 8 and its message)
+    CSD_REQUIRE(c.x_channels >= 1 && c.y_channels >= 0, "ncsnpp: bad channel counts %d+%d", c.x_channels, c.y_channels);
+    if (c.y_channels > 0)
+      CSD_REQUIRE(c.x_channels + c.y_channels <= CSD_MAX_IO_CHANNELS, "ncsnpp: x+y channels must be <= %d (got %d+%d)", CSD_MAX_IO_CHANNELS,
+                  c.x_channels, c.y_channels);
+    else
+      CSD_REQUIRE(c.x_channels <= 8, "ncsnpp: x+y channels must be <= 8 for a network without a condition (got %d; the paired networks "
+                  "take up to %d)", c.x_channels, CSD_MAX_IO_CHANNELS);
     CSD_REQUIRE(c.out_channels == c.x_channels + c.y_channels, "ncsnpp: the network maps its %d input channels to as many outputs",
                 c.x_channels + c.y_channels);
     CSD_REQUIRE(c.act >= CSD_ACT_SWISH && c.act <= CSD_ACT_ELU, "ncsnpp: bad activation id %d", c.act);
@@ -445,6 +447,13 @@ static int build_modules(Net& n) {
                 c.progressive);
     CSD_REQUIRE(c.progressive_input >= 0 && c.progressive_input <= 3, "ncsnpp: bad progressive_input id %d", c.progressive_input);
     CSD_REQUIRE(c.n_fir == 4, "ncsnpp: a 4-tap FIR kernel is required (got %d taps)", c.n_fir);
+  }
+  if (c.x_squeeze) {      // the 2x super-resolution networks: x is the image [B, x_channels / 4, 2S, 2S] (include/csd.h)
+    CSD_REQUIRE(c.x_squeeze == 1, "unet: x_squeeze must be 0 or 1 (got %d)", c.x_squeeze);
+    CSD_REQUIRE(c.x_channels % 4 == 0, "unet: x_squeeze needs x_channels %% 4 == 0 (got x_channels = %d)", c.x_channels);
+    CSD_REQUIRE(c.image_size <= 1024, "unet: x_squeeze is provided up to image_size 1024 (got %d)", c.image_size);
+    CSD_REQUIRE(c.out_channels >= c.x_channels, "unet: x_squeeze needs out_channels >= x_channels (got %d < %d)", c.out_channels,
+                c.x_channels);
   }
   const int nf = c.nf, channels = c.x_channels + c.y_channels, last = c.n_levels - 1;
   const bool fourier = pp && c.embedding_type == 1, pyr_out = pp && c.progressive == 1;
@@ -652,8 +661,11 @@ extern "C" int csd_unet_create(const csd_unet_config* cfg, csd_unet** out) {
   CSD_REQUIRE(cfg && out, "unet_create: null argument");
   std::unique_ptr<csd_unet> h(new csd_unet());
   h->net.cfg = *cfg;
-  CSD_REQUIRE(!cfg->x_squeeze || cfg->arch == 0, "unet_create: x_squeeze = %d is provided for the DDPM family (arch 0) only, not arch %d",
-              cfg->x_squeeze, cfg->arch);
+  CSD_REQUIRE(!cfg->x_squeeze || cfg->arch == 0 || cfg->arch == 1,
+              "unet_create: x_squeeze = %d is provided for arch 0 / 1, not for the 3-D networks (arch %d)", cfg->x_squeeze, cfg->arch);
+  CSD_REQUIRE(!cfg->x_squeeze || cfg->arch != 1 || cfg->y_channels > 0,
+              "unet_create: x_squeeze = %d on arch 1 is provided for the paired networks (ncsnpp_2xSR: y_channels > 0), not without a condition",
+              cfg->x_squeeze);
   if (cfg->y_scale) {      // the direct Kx super-resolution networks: y is [B, y_channels, S / K, S / K] (include/csd.h)
     CSD_REQUIRE(cfg->y_scale >= 2, "unet_create: y_scale must be 0 or >= 2 (got %d)", cfg->y_scale);
     CSD_REQUIRE(cfg->arch == 0 || cfg->arch == 1, "unet_create: y_scale = %d is provided for arch 0 / 1, not for the 3-D networks (arch %d)",

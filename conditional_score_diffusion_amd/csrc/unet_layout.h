@@ -26,7 +26,7 @@ static int build_packed_layout(Net& n) {
   // the 6 -> nf stem: with the input padded to 16 channels (zeros) it runs on the fp16 matrix cores like every other 3x3 (one K step
   // per tap) instead of the fp32 ones (36 MFMAs of 64 cycles per 32 pixels: 380 us per evaluation at 160^2, B = 64, MFMA-bound)
   if (n.cfg.arch == 0 && net_ns && !CSD_TUNE_ENV("CSD_STEM_F32")) n.in_cpad = 16;
-  // more than 8 assembled channels (DDPM family only: 9 .. CSD_MAX_IO_CHANNELS): the next multiple of 16 in every precision - the fp32
+  // more than 8 assembled channels (both families: 9 .. CSD_MAX_IO_CHANNELS): the next multiple of 16 in every precision - the fp32
   // kernel's and the fp16 kernels' K chunk alike.  Everything that reads the assembled tensor or packs the first layer's weights takes
   // its width from in_cpad: OP_ASSEMBLE and its buffer (unet_plan.h), the first layer's proto / pack below (zero weights for the padding
   // channels), stem.hip's own padding (stem_cpad: the same wide_cpad)
@@ -136,6 +136,12 @@ static int build_packed_layout(Net& n) {
     // (y_scale: the YS variant of the <= 8 channel kernel holds up to 4 x channels and the four taps of up to 4 y channels; other
     // splits keep the assemble pass)
     if (c.y_scale && (c.y_channels > 4 || c.x_channels > 4)) return false;
+    // (NCSN++ above 8 channels keeps the assemble pass + generic convolution: with an input pyramid the assembled tensor is written
+    // anyway, and on the network stem_wide_kernel measured no faster - 14.37 against 14.36 / 14.44 ms per evaluation at 9 + 3 -> 128
+    // channels, 80^2, B = 64, DESIGN.md 4d.  A wide NCSN++ WITHOUT an input pyramid, where the fused layer would also save the assemble
+    // launch, has not been measured and keeps the same plan until it is; the tuning switch CSD_PP_WIDE_STEM is the other side of
+    // that measurement)
+    if (pp && c.x_channels + c.y_channels > 8 && !CSD_TUNE_ENV("CSD_PP_WIDE_STEM")) return false;
     PackedConv pc;
     if (proto_conv(&pc.proto, n.in_cpad, 0, m.cout, 9)) return false;
     pc.ns = net_ns;

@@ -599,27 +599,21 @@ class DDPM_paired(_Paired):
         return {'x': out[:, :c], 'y': out[:, c:]}
 
 
-@utils.register_model(name='ddpm_2xSR')
-class DDPM_2xSR(_Paired):
-    """One 2x stage of the sequential super-resolution cascades (models/ddpm.py:39-52,300-314): the DDPM U-Net behind a parameter-free
-    space-to-depth squeeze of x.  ``forward({'x': [B, cx, 2S, 2S], 'y': [B, cy, S, S]}, labels) -> {'x': [B, cx, 2S, 2S],
+class _Squeeze2x:
+    """The 2x super-resolution wrappers (models/ddpm.py:39-52,300-314, models/ncsnpp.py:403-432) over a paired network: the U-Net behind
+    a parameter-free space-to-depth squeeze of x.  ``forward({'x': [B, cx, 2S, 2S], 'y': [B, cy, S, S]}, labels) -> {'x': [B, cx, 2S, 2S],
     'y': [B, cy, S, S]}`` with S = data.effective_image_size.  The squeeze is addressing inside the library's boundary kernels
-    (csd_unet_config.x_squeeze): no squeezed copy of x, and the returned ``'x'`` is a view of the buffer the network wrote.  The
-    parameters are the reference ``DDPM_2xSR``'s (the squeeze has none)."""
+    (csd_unet_config.x_squeeze): no squeezed copy of x, and the returned ``'x'`` is a view of the buffer the network wrote."""
 
     x_squeeze = 1
 
-    def __init__(self, config, precision=None):
+    @staticmethod
+    def _sq_validate(config, name):
         d = config.data
         hi, S, lo = int(d.shape_x[1]), int(d.effective_image_size), int(d.shape_y[1])
         if not (hi == 2 * S == 2 * lo and int(d.shape_x[2]) == hi and int(d.shape_y[2]) == lo):
-            raise ValueError('ddpm_2xSR: the image side data.shape_x[1] = %d must be twice data.effective_image_size = %d and twice '
-                             'data.shape_y[1] = %d (square images)' % (hi, S, lo))
-        super().__init__(config, precision)
-
-    def _channels(self, config):
-        cx = 4 * int(config.data.shape_x[0])
-        return cx, int(config.model.input_channels) - cx
+            raise ValueError('%s: the image side data.shape_x[1] = %d must be twice data.effective_image_size = %d and twice '
+                             'data.shape_y[1] = %d (square images)' % (name, hi, S, lo))
 
     def _split(self, out):
         B, S = out.shape[0], self.image_size
@@ -628,6 +622,20 @@ class DDPM_2xSR(_Paired):
 
     def forward(self, input_dict, labels):
         return self._split(self._run(input_dict['x'], input_dict['y'], labels))
+
+
+@utils.register_model(name='ddpm_2xSR')
+class DDPM_2xSR(_Squeeze2x, _Paired):
+    """One 2x stage of the sequential super-resolution cascades (models/ddpm.py:39-52,300-314): the DDPM U-Net behind the squeeze of x
+    (_Squeeze2x).  The parameters are the reference ``DDPM_2xSR``'s (the squeeze has none)."""
+
+    def __init__(self, config, precision=None):
+        self._sq_validate(config, 'ddpm_2xSR')
+        super().__init__(config, precision)
+
+    def _channels(self, config):
+        cx = 4 * int(config.data.shape_x[0])
+        return cx, int(config.model.input_channels) - cx
 
 
 class _KxSR:

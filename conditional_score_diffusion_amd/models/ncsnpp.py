@@ -1,6 +1,6 @@
 """NCSN++ score networks (reference models/ncsnpp.py:39-401) on the per-operator C ABI.
 
-Registers ``ncsnpp`` and ``ncsnpp_paired`` with the reference's constructor / call signatures and the reference's
+Registers ``ncsnpp``, ``ncsnpp_paired``, ``ncsnpp_2xSR`` and ``ncsnpp_KxSR`` with the reference's constructor / call signatures and the reference's
 ``state_dict`` keys (``all_modules.{i}.…``).  The module list of ``NCSNpp.__init__`` (:44-236) comes from
 ``topology.build_modules`` and the walk of ``NCSNpp.forward`` (:238-388) from ``topology.run_unet``; the class ``NCSNpp``
 below is the executor of that walk - the arithmetic of one module per method - and every
@@ -28,7 +28,7 @@ import torch.nn as nn
 from .. import ops
 from .._lib import require_gpu_tensor
 from . import utils
-from .ddpm import HipUNet, _KxSR, _Node, _activation, _fan_avg_uniform, _model_key, _precision
+from .ddpm import HipUNet, _KxSR, _Node, _Squeeze2x, _activation, _fan_avg_uniform, _model_key, _precision
 from .topology import Executor, build_modules, run_unet
 
 
@@ -358,6 +358,8 @@ class HipNCSNpp(HipUNet):
             return self._train_forward_planned(x, y, labels)
         if self.y_scale:
             raise NotImplementedError('a network with y_scale (ncsnpp_KxSR) trains on the planned graph only (CSD_TRAIN_EXECUTOR=planned)')
+        if self.x_squeeze:
+            raise NotImplementedError('a squeezed network (ncsnpp_2xSR) trains on the planned graph only (CSD_TRAIN_EXECUTOR=planned)')
         twin = self.__dict__.get('_twin')
         if twin is None:
             twin = NCSNpp(self._config, precision=self.precision)
@@ -425,6 +427,20 @@ class NCSNpp_KxSR(_KxSR, NCSNppPairedPlanned):
         super().__init__(config, precision)
 
 
+class NCSNpp_2xSR(_Squeeze2x, NCSNppPairedPlanned):
+    """``ncsnpp_2xSR`` (models/ncsnpp.py:403-432): one 2x stage of the sequential super-resolution cascades - the planned NCSN++ on
+    ``4 cx + cy`` channels behind the space-to-depth squeeze of x (models/ddpm.py: _Squeeze2x).  The ``state_dict`` is the reference's:
+    its SqueezeBlock has no parameters."""
+
+    def __init__(self, config, precision=None):
+        self._sq_validate(config, 'ncsnpp_2xSR')
+        super().__init__(config, precision)
+
+    def _channels(self, config):
+        cx = 4 * int(config.data.shape_x[0])
+        return cx, int(config.data.num_channels) - cx
+
+
 def create_ncsnpp(config, **kw):
     """``ncsnpp``: the planned graph executor (every option the HIP path covers runs on it)"""
     return NCSNppPlanned(config, **kw)
@@ -436,6 +452,7 @@ def create_ncsnpp_paired(config, **kw):
 
 utils.register_model(create_ncsnpp, name='ncsnpp')
 utils.register_model(create_ncsnpp_paired, name='ncsnpp_paired')
+utils.register_model(NCSNpp_2xSR, name='ncsnpp_2xSR')
 utils.register_model(NCSNpp_KxSR, name='ncsnpp_KxSR')
 utils.register_model(NCSNpp, name='ncsnpp_ops')
 utils.register_model(NCSNpp_paired, name='ncsnpp_paired_ops')

@@ -62,14 +62,15 @@ def conv2d(x, weight, bias=None, stride=1, downsample_pad=False, up2=False, prec
 
 def fir_pyr_conv(x, weight, bias=None, res=None, fir_kernel=(1, 3, 3, 1), out_scale=1.0):
     """The 'residual' input pyramid of NCSN++ (layerspp.Downsample(with_conv=True), layerspp.py:129-163) on NHWC fp32 tensors:
-    ``(Downsample(x) + res) * out_scale``.  x [B, H, H, Cin], weight [Cout, Cin, 3, 3] OIHW, res [B, H/2, H/2, Cout] or None.
+    ``(Downsample(x) + res) * out_scale``.  x [B, H, H, P] with P >= Cin floats per pixel (the first Cin are read: the padded assembled
+    input of a network is such a tensor), weight [Cout, Cin, 3, 3] OIHW, res [B, H/2, H/2, Cout] or None.
     ``fir_kernel`` (4 taps): conv_downsample_2d (FIR with pads (2, 2), then a VALID stride-2 conv); None: fir = False
     (F.pad(0, 1, 0, 1) + stride-2 conv).  csd_fir_pyr_conv.  Returns [B, H/2, H/2, Cout]."""
     import ctypes
     x, weight = _c(x, 'x'), _c(weight, 'weight')
-    B, H, W, Cin = x.shape
-    Cout = weight.shape[0]
-    if H != W or H % 2 or tuple(weight.shape[1:]) != (Cin, 3, 3):
+    B, H, W, pix = x.shape
+    Cout, Cin = weight.shape[0], weight.shape[1]
+    if H != W or H % 2 or weight.dim() != 4 or tuple(weight.shape[2:]) != (3, 3) or Cin > pix:
         raise RuntimeError('fir_pyr_conv: x %s / weight %s do not match' % (tuple(x.shape), tuple(weight.shape)))
     if bias is not None:
         bias = _c(bias, 'bias')
@@ -88,9 +89,25 @@ def fir_pyr_conv(x, weight, bias=None, res=None, fir_kernel=(1, 3, 3, 1), out_sc
         taps = (ctypes.c_float * 4)(*[float(v) for v in fir_kernel])
     y = _out((B, H // 2, H // 2, Cout), torch.float32, x.device)
     sc = _scratch(lib().csd_fir_pyr_conv_scratch_bytes(Cin, Cout), x.device)
-    check(lib().csd_fir_pyr_conv(ptr(x), ptr(weight), ptr(bias), ptr(res), ptr(y), B, Cin, Cout, H, Cin,
+    check(lib().csd_fir_pyr_conv(ptr(x), ptr(weight), ptr(bias), ptr(res), ptr(y), B, Cin, Cout, H, pix,
                                  ctypes.cast(taps, ctypes.c_void_p) if taps is not None else None, float(out_scale), ptr(sc),
                                  current_stream(x.device)), 'fir_pyr_conv')
+    return y
+
+
+def fir_resample_nhwc(x, fir_kernel=(1, 3, 3, 1), up=False):
+    """FIR resampling by 2 of an NHWC fp32 tensor [B, H, W, C] with a separable 4-tap kernel: upsample_2d / downsample_2d of
+    models/up_or_down_sampling.py:196-257 as the NCSN++ plans run them (csd_fir_resample_nhwc).  Returns [B, 2H, 2W, C] or
+    [B, H/2, W/2, C]."""
+    import ctypes
+    x = _c(x, 'x')
+    B, H, W, C = x.shape
+    if len(fir_kernel) != 4:
+        raise NotImplementedError('fir_resample_nhwc: 4-tap FIR kernels only')
+    taps = (ctypes.c_float * 4)(*[float(v) for v in fir_kernel])
+    y = _out((B, 2 * H, 2 * W, C) if up else (B, H // 2, W // 2, C), torch.float32, x.device)
+    check(lib().csd_fir_resample_nhwc(ptr(x), ptr(y), B, H, W, C, ctypes.cast(taps, ctypes.c_void_p), int(bool(up)),
+                                      current_stream(x.device)), 'fir_resample_nhwc')
     return y
 
 

@@ -108,7 +108,7 @@ def _why_not_one_call(model, sde, st, inpaint, check_device=True):
     """None when csd_pc_cascade_sample can run this stage, else the reason (``check_device=False``: leave out where the model lies)"""
     from ..models.ddpm import HipUNet
     if not isinstance(model, HipUNet):
-        return 'the model is a %s, not a DDPM-family HipUNet (NCSN++ and 3-D stages are out of scope)' % type(model).__name__
+        return 'the model is a %s, not a planned 2-D HipUNet (DDPM family or NCSN++; 3-D stages are out of scope)' % type(model).__name__
     if getattr(model, 'y_scale', 0):
         return 'the Kx networks (y_scale) do not run in a cascade'
     if inpaint != (model.y_channels == 0):

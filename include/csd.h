@@ -90,7 +90,8 @@ int csd_profile_stop_ex(int n_classes, double* ms, int64_t* launches, double* fl
 #define CSD_MAX_ATTN 8
 /* arch 0 (DDPM family): x_channels + y_channels and out_channels may each be up to this many (the 16-slice MRI -> PET slabs: 16 + 16 in,
  * 32 out; the Haar-band models: 12; the SR-flow Haar models: 9 + 3).  Above 8 input channels the assembled input is padded to the next
- * multiple of 16 with exact zeros.  arch 1 (NCSN++) keeps x_channels + y_channels <= 8. */
+ * multiple of 16 with exact zeros.  arch 1 (NCSN++) takes the same widths with a condition (y_channels > 0;
+ * out_channels == x_channels + y_channels; without one it keeps x_channels <= 8); its input pyramids read the padded assembled tensor, its output pyramid and head store up to 32 channels. */
 #define CSD_MAX_IO_CHANNELS 32
 
 typedef struct csd_unet_config {
@@ -130,7 +131,7 @@ typedef struct csd_unet_config {
   /* ---- arch 2 (3-D DDPM family, models/ddpm3D.py) only: the extents of the volume behind the channel, D, H, W (config.data.shape_x[1:]).
    * arch 2 ignores image_size, the attention fields and the arch-1 fields above; arch 0 / 1 ignore vol. ---- */
   int32_t vol[3];
-  /* ---- arch 0 only: the 2x super-resolution networks (models/ddpm.py:39-52,300-314, DDPM_2xSR).  1: x is the HIGH-resolution image
+  /* ---- arch 0, and arch 1 with y_channels > 0: the 2x super-resolution networks (models/ddpm.py:39-52,300-314, DDPM_2xSR; models/ncsnpp.py:403-432, NCSNpp_2xSR).  1: x is the HIGH-resolution image
    * [B, x_channels / 4, 2S, 2S] (S = image_size) and the network sees its space-to-depth squeeze,
    *     x'[b, 4c + 2dy + dx, i, j] = x[b, c, 2i + dy, 2j + dx],
    * so x_channels stays the count the NETWORK sees (a multiple of 4).  The library's boundary kernels address the image directly: no
@@ -524,6 +525,11 @@ int csd_upfirdn2d(const float* x, const float* kernel, float* out, int N, int C,
 size_t csd_fir_pyr_conv_scratch_bytes(int Cin, int Cout);
 int csd_fir_pyr_conv(const float* x, const float* w, const float* bias, const float* res, float* out, int B, int Cin, int Cout, int H,
                      int x_pixel_stride, const float* fir_kernel, float out_scale, void* scratch, void* stream);
+/* FIR resampling by 2 of an NHWC tensor with a separable 4-tap kernel (host pointer): upsample_2d / downsample_2d of
+ * models/up_or_down_sampling.py:196-257, as the NCSN++ plans run it on their pyramids and BigGAN blocks.  x [B, H, W, C] ->
+ * out [B, 2H, 2W, C] (up != 0) or [B, H/2, W/2, C]; any C >= 1 (C % 4 == 0 with 16-byte aligned x and out takes the 16-byte form, the
+ * same sums in the same order), deterministic. */
+int csd_fir_resample_nhwc(const float* x, float* out, int B, int H, int W, int C, const float* fir_kernel, int up, void* stream);
 int csd_fused_bias_act(const float* x, const float* bias, const float* ref, float* out, int64_t numel,
                        int C, int64_t inner, int act, int grad, float alpha, float scale, void* stream);
 /* nearest-neighbour x2 upsample (F.interpolate in models/layers.py:601) */

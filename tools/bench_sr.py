@@ -13,6 +13,8 @@ attention at 20 / 10 / 5, two blocks per level) at nf 96, ch_mult (1, 1, 2, 2), 
                         library boundary replaces
   pc_step_ms            one predictor-corrector step (two evaluations, the two-SDE VE pair, on-device noise) on the fused device loop
   pc_step_by_step_ms    the same step on the step-by-step loop (sampling/conditional.py's fallback, torch noise)
+``--family ncsnpp`` runs the same stage on ncsnpp_2xSR / ncsnpp_paired (Fourier embedding, FIR resampling, input and output skip
+pyramids) and MERGES its result into the output file under the key ``ncsnpp_2xSR``, beside the DDPM figures and without touching them.
 Windows as tools/bench_wide.py: `warmup` calls, then the median of three device-event windows of `steps` calls; the PC loops: one warm
 run, then the median of three timed runs of `pc-steps` steps.  One JSON object, also printed.
 """
@@ -36,6 +38,21 @@ SHAPE = dict(image_channels=3, y_channels=3, S=80, nf=96, ch_mult=(1, 1, 2, 2), 
 def make_config(name, precision):
     k = SHAPE
     cx, cy, S = k['image_channels'], k['y_channels'], k['S']
+    if name.startswith('ncsnpp'):
+        cfg = cases.make_ncsnpp_config(name=name, nf=k['nf'], ch_mult=k['ch_mult'], num_res_blocks=k['num_res_blocks'],
+                                       attn_resolutions=k['attn_resolutions'], image_size=S, channels=4 * cx + cy)
+        d, m = cfg.data, cfg.model
+        d.shape_x, d.shape_y = [4 * cx, S, S], [cy, S, S]
+        if name == 'ncsnpp_2xSR':
+            d.image_size, d.effective_image_size = 2 * S, S
+            d.shape_x = [cx, 2 * S, 2 * S]
+        m.sigma_min_x = m.sigma_min = m.sigma_min_y = 5e-3
+        m.sigma_max_x = m.sigma_max = float(np.sqrt(4 * cx * S * S))
+        m.sigma_max_y = float(np.sqrt(cy * S * S))
+        m.csd_precision = precision
+        cfg.sampling.snr = 0.15
+        cfg.sampling.predictor, cfg.sampling.corrector = 'conditional_reverse_diffusion', 'conditional_langevin'
+        return cfg
     cfg = cases.make_config(name=name, nf=k['nf'], ch_mult=k['ch_mult'], num_res_blocks=k['num_res_blocks'],
                             attn_resolutions=k['attn_resolutions'], image_size=S, x_ch=4 * cx, y_ch=cy)
     d, m = cfg.data, cfg.model
@@ -97,6 +114,7 @@ def main():
     ap.add_argument('--pc-steps', type=int, default=8)
     ap.add_argument('--precision', default='fp16x3')
     ap.add_argument('--batch', type=int, default=0)
+    ap.add_argument('--family', default='ddpm', choices=('ddpm', 'ncsnpp'))
     ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'sr_bench.json'))
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -109,13 +127,20 @@ def main():
     dev = torch.device('cuda:0')
     B = args.batch or SHAPE['B']
     cx, cy, S = SHAPE['image_channels'], SHAPE['y_channels'], SHAPE['S']
-    cfg = make_config('ddpm_2xSR', args.precision)
-    p = so.synth_params(so.ddpm_param_shapes(so.NetCfg.from_config(cfg)), 0)
+    pp = args.family == 'ncsnpp'
+    sq_name, plain_name = ('ncsnpp_2xSR', 'ncsnpp_paired') if pp else ('ddpm_2xSR', 'ddpm_paired')
+    cfg = make_config(sq_name, args.precision)
+    if pp:
+        with torch.device('meta'):
+            shapes = {k: tuple(v.shape) for k, v in mutils.create_model(cfg).state_dict().items()}
+        p = cases.ncsnpp_params(shapes, 0)
+    else:
+        p = so.synth_params(so.ddpm_param_shapes(so.NetCfg.from_config(cfg)), 0)
     nets = {}
-    for name in ('ddpm_2xSR', 'ddpm_paired'):
+    for name, key in ((sq_name, 'ddpm_2xSR'), (plain_name, 'ddpm_paired')):      # (keys: the roles, named after the DDPM pair)
         net = mutils.create_model(make_config(name, args.precision))
         net.load_state_dict(p)
-        nets[name] = net.to(dev).eval()
+        nets[key] = net.to(dev).eval()
     rs = np.random.RandomState(0)
     x = torch.from_numpy((rs.standard_normal((B, cx, 2 * S, 2 * S)) * 5).astype(np.float32)).to(dev)
     y = torch.from_numpy(rs.uniform(0, 1, (B, cy, S, S)).astype(np.float32)).to(dev)
@@ -166,6 +191,15 @@ def main():
         return median3(one)
     out['pc_step_ms'], out['pc_step_ms_spread'] = timed(lambda: sampler(net, y, seed=1))
     out['pc_step_by_step_ms'], out['pc_step_by_step_ms_spread'] = timed(lambda: sampler(plain, y))
+    if pp:                                         # merge: the DDPM figures of the file stay as they are
+        out['model'] = sq_name
+        whole = json.load(open(args.out)) if os.path.exists(args.out) else {}
+        whole['ncsnpp_2xSR'] = out
+        out = whole
+    elif os.path.exists(args.out):                 # (and a DDPM run keeps the NCSN++ entry of the file)
+        old = json.load(open(args.out))
+        if 'ncsnpp_2xSR' in old:
+            out['ncsnpp_2xSR'] = old['ncsnpp_2xSR']
     text = json.dumps(out, indent=1, sort_keys=True)
     os.makedirs(os.path.dirname(args.out), exist_ok=True)
     with open(args.out, 'w') as f:
