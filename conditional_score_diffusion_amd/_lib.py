@@ -91,6 +91,18 @@ WEIGHT_EPOCH = [0]     # bumped by every raw-kernel write to model parameters (o
 _vp, _i, _i64, _f, _sz, _u64 = (ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float,
                                 ctypes.c_size_t, ctypes.c_uint64)
 _d = ctypes.c_double
+# the arguments every PC-loop entry starts with: handle, packed, workspace + bytes, scratch + bytes, x, y, B, csd_pc_params
+_PC = [_vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _i, ctypes.POINTER(PCParams)]
+
+
+def _pc_entries(family, struct=None):
+    """the three entries of one PC-loop family: _PC [+ the family's constraint struct] + sample (stream), step_begin (step, norm_sums,
+    stream), step_end (step, norm_sums, global_batch, stream)"""
+    base = _PC + ([ctypes.POINTER(struct)] if struct is not None else [])
+    tails = {'sample': [_vp], 'step_begin': [_i, _vp, _vp], 'step_end': [_i, _vp, _i, _vp]}
+    return {'csd_%s_%s' % (family, name): (_i, base + tail) for name, tail in tails.items()}
+
+
 SIGNATURES = {
     'csd_version': (ctypes.c_char_p, []),
     'csd_last_error': (ctypes.c_char_p, []),
@@ -114,24 +126,12 @@ SIGNATURES = {
     'csd_unet_stats': (_i, [_vp, _i, ctypes.POINTER(_i64), ctypes.POINTER(ctypes.c_double),
                             ctypes.POINTER(ctypes.c_double)]),
     'csd_pc_scratch_bytes': (_sz, [_vp, _i]),
-    'csd_pc_sample': (_i, [_vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _i, ctypes.POINTER(PCParams), _vp]),
+    **_pc_entries('pc'),
+    **_pc_entries('pc_inpaint', PCInpaintParams),
+    **_pc_entries('pc_colorize', PCColorizeParams),
     'csd_pc_noise_draws': (_i64, [_vp, _i, _i, _i, _i, _i, _i, _i, ctypes.POINTER(_i64), _i]),
-    'csd_pc_step_begin': (_i, [_vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _i, ctypes.POINTER(PCParams), _i, _vp, _vp]),
-    'csd_pc_step_end': (_i, [_vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _i, ctypes.POINTER(PCParams), _i, _vp, _i, _vp]),
     'csd_pc_inpaint_scratch_bytes': (_sz, [_vp, _i]),
-    'csd_pc_inpaint_sample': (_i, [_vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _i, ctypes.POINTER(PCParams),
-                                   ctypes.POINTER(PCInpaintParams), _vp]),
-    'csd_pc_inpaint_step_begin': (_i, [_vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _i, ctypes.POINTER(PCParams),
-                                       ctypes.POINTER(PCInpaintParams), _i, _vp, _vp]),
-    'csd_pc_inpaint_step_end': (_i, [_vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _i, ctypes.POINTER(PCParams),
-                                     ctypes.POINTER(PCInpaintParams), _i, _vp, _i, _vp]),
     'csd_inpaint_blend': (_i, [_vp, _vp, _vp, _vp, _vp, _f, _f, _i64, _u64, _u64, _vp]),
-    'csd_pc_colorize_sample': (_i, [_vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _i, ctypes.POINTER(PCParams),
-                                    ctypes.POINTER(PCColorizeParams), _vp]),
-    'csd_pc_colorize_step_begin': (_i, [_vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _i, ctypes.POINTER(PCParams),
-                                        ctypes.POINTER(PCColorizeParams), _i, _vp, _vp]),
-    'csd_pc_colorize_step_end': (_i, [_vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _i, ctypes.POINTER(PCParams),
-                                      ctypes.POINTER(PCColorizeParams), _i, _vp, _i, _vp]),
     'csd_colorize_blend': (_i, [_vp, _vp, _vp, _vp, _f, _f, _i, _i64, _i, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float),
                                 _u64, _u64, _vp]),
     'csd_colorize_gray0': (_i, [_vp, _vp, _i, _i64, ctypes.POINTER(ctypes.c_float), _vp]),

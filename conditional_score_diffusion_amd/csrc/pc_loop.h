@@ -39,6 +39,9 @@ enum { DRAW_ZY0 = 0, DRAW_ZY_PATH = 1, DRAW_ZY = 2, DRAW_Z = 3, DRAW_BLEND = 4, 
 enum { BLEND_NONE = 0, BLEND_INPAINT = 1, BLEND_COLORIZE = 2 };      // what is re-imposed behind every phase (the `inpaint` argument of csd_pc_noise_draws)
 // the re-imposition of a call: its mode and that mode's struct
 struct PCBlend { int mode = BLEND_NONE; const csd_pc_inpaint_params* ip = nullptr; const csd_pc_colorize_params* cp = nullptr; };
+// what a mode's refusals call its entries (csd_<entry>_sample / _step_begin / _step_end) and its constraint
+static const char* const BLEND_ENTRY[] = {"pc_sample", "pc_inpaint", "pc_colorize"};
+static const char* const BLEND_NOUN[] = {"", "inpainting", "colorization"};
 enum { PHASE_CORRECTOR = 0, PHASE_PREDICTOR = 1, PHASE_NONE = 2 };
 struct PCDraw { int kind, phase; size_t elems, offset; };      // offset: floats of the step's draws in front of it
 struct PCDrawAt { size_t offset; uint64_t stream; size_t elems; };      // where one draw of one step is: tape offset and Philox stream
@@ -76,24 +79,21 @@ static int pc_schedule(PCSchedule* sc, const csd_unet* net, int B, int predictor
   const csd_unet_config& cf = net->net.cfg;
   CSD_REQUIRE(blend >= BLEND_NONE && blend <= BLEND_COLORIZE, "pc_sample: bad inpaint mode %d (0 none, 1 inpainting, 2 colorization)", blend);
   const bool inpaint = blend == BLEND_INPAINT, colorize = blend == BLEND_COLORIZE;
-  CSD_REQUIRE(!(colorize && is3d(net->net)), "pc_colorize: colorization is not provided for the 3-D networks (arch 2) on the device loop");
-  CSD_REQUIRE(!(colorize && cf.x_squeeze), "pc_colorize: colorization is not provided for a handle with x_squeeze (the 2x "
-              "super-resolution networks are conditional)");
-  CSD_REQUIRE(!(colorize && cf.y_scale), "pc_colorize: colorization is not provided for a handle with y_scale (the Kx "
-              "super-resolution networks are conditional)");
+  const char *entry = BLEND_ENTRY[blend], *noun = BLEND_NOUN[blend];
+  if (blend != BLEND_NONE) {
+    CSD_REQUIRE(!is3d(net->net), "%s: %s is not provided for the 3-D networks (arch 2) on the device loop", entry, noun);
+    CSD_REQUIRE(!cf.x_squeeze, "%s: %s is not provided for a handle with x_squeeze (the 2x super-resolution networks are conditional)",
+                entry, noun);
+    CSD_REQUIRE(!cf.y_scale, "%s: %s is not provided for a handle with y_scale (the Kx super-resolution networks are conditional)",
+                entry, noun);
+  }
   CSD_REQUIRE(!(colorize && cf.y_channels != 0), "pc_colorize: colorization runs unconditional networks only (y_channels = %d)", cf.y_channels);
   CSD_REQUIRE(!(colorize && cf.x_channels != 3), "pc_colorize: colorization needs a 3-channel state (x_channels = %d)", cf.x_channels);
-  CSD_REQUIRE(!(inpaint && is3d(net->net)), "pc_inpaint: inpainting is not provided for the 3-D networks (arch 2) on the device loop");
-  CSD_REQUIRE(!(inpaint && cf.x_squeeze), "pc_inpaint: inpainting is not provided for a handle with x_squeeze (the 2x "
-              "super-resolution networks are conditional)");
-  CSD_REQUIRE(!(inpaint && cf.y_scale), "pc_inpaint: inpainting is not provided for a handle with y_scale (the Kx "
-              "super-resolution networks are conditional)");
   CSD_REQUIRE(predictor >= 0 && predictor <= 2 && corrector >= 0 && corrector <= 2, "pc_sample: bad predictor / corrector id");
   CSD_REQUIRE(predictor != 2 || corrector != 2, "pc_sample: predictor and corrector are both 'none'");
   CSD_REQUIRE(!(std_y && cf.y_channels == 0), "pc_sample: std_y given for an unconditional network");
   CSD_REQUIRE(!inpaint || cf.y_channels == 0, "pc_inpaint: inpainting runs unconditional networks only (y_channels = %d)", cf.y_channels);
-  CSD_REQUIRE(!inpaint || (!std_y && !path), "pc_inpaint: std_y / path_coef belong to the conditional samplers");
-  CSD_REQUIRE(!colorize || (!std_y && !path), "pc_colorize: std_y / path_coef belong to the conditional samplers");
+  CSD_REQUIRE(blend == BLEND_NONE || (!std_y && !path), "%s: std_y / path_coef belong to the conditional samplers", entry);
   CSD_REQUIRE(!path || (cf.y_channels > 0 && !std_y), "pc_sample: use_path needs a conditioning image and no marginal std_y");
   *sc = PCSchedule();
   // (y_scale = K: y, its noise and the bridge's y_t live at S / K; a sample of net_out is the x block, then the downsampled y block)
@@ -142,9 +142,8 @@ extern "C" int64_t csd_pc_noise_draws(const csd_unet* net, int B, int predictor,
 struct PCCtx : PCScratch, PCSchedule {
   Evaluator ev; const float* pk; float* ws;
   const csd_pc_params* p;
-  const csd_pc_inpaint_params* ip = nullptr;         // inpainting: the known pixels are re-imposed after every phase (csd_pc_inpaint_*)
-  const csd_pc_colorize_params* cp = nullptr;        // colorization: the gray channel is re-imposed after every phase (csd_pc_colorize_*)
-  bool blends() const { return ip || cp; }
+  // what the call re-imposes after every phase: the known pixels (csd_pc_inpaint_*), the gray channel (csd_pc_colorize_*) or nothing
+  PCBlend bl;
   float* x; const float* y;
   int B, nchunk;
   int64_t per, net_stride;
@@ -183,15 +182,12 @@ static int pc_setup(PCCtx* c, csd_unet* net, const void* packed, void* workspace
   const size_t hw = sample_elems(cf);
   c->pk = static_cast<const float*>(packed); c->ws = static_cast<float*>(workspace);
   c->p = p; c->x = x; c->y = y; c->B = B; c->s = (hipStream_t)stream;
-  if (bl.mode == BLEND_INPAINT) {
-    const csd_pc_inpaint_params* ip = bl.ip;
-    CSD_REQUIRE(ip && ip->data && ip->mask && ip->mean_scale && ip->std, "pc_inpaint: data, mask, mean_scale and std are required");
-    c->ip = ip;
-  } else if (bl.mode == BLEND_COLORIZE) {
-    const csd_pc_colorize_params* cp = bl.cp;
-    CSD_REQUIRE(cp && cp->gray0 && cp->mean_scale && cp->std, "pc_colorize: gray0, mean_scale and std are required");
-    c->cp = cp;
-  }
+  const csd_pc_inpaint_params* ip = bl.ip;
+  const csd_pc_colorize_params* cp = bl.cp;
+  CSD_REQUIRE(bl.mode != BLEND_INPAINT || (ip && ip->data && ip->mask && ip->mean_scale && ip->std),
+              "pc_inpaint: data, mask, mean_scale and std are required");
+  CSD_REQUIRE(bl.mode != BLEND_COLORIZE || (cp && cp->gray0 && cp->mean_scale && cp->std), "pc_colorize: gray0, mean_scale and std are required");
+  c->bl = bl;
   static_cast<PCScratch&>(*c) = pc_scratch(scratch, cf, B);
   c->per = (int64_t)cf.x_channels * hw;
   c->nchunk = sumsq_nchunk(c->per);
@@ -205,19 +201,24 @@ static int pc_setup(PCCtx* c, csd_unet* net, const void* packed, void* workspace
 // colorization: the gray channel instead, in the decoupled channel space (colorize_blend_kernel); its draw stands where the blend's does.
 static int pc_blend(const PCCtx& c, int i, int phase) {
   const csd_pc_params* p = c.p;
-  const bool want_mean = phase == 1 && i == p->n_steps - 1 && p->denoise;
-  if (c.cp) {
-    const PCDrawAt d = c.draw(i, DRAW_COLORIZE, phase);
-    const size_t hw = c.nx / ((size_t)c.B * 3);
-    ProfScope prof(CSD_PROF_SAMPLER, 0, ((p->noise_tape ? 7.0 : 6.0) + 1.0) * c.nx * 4 / 3, c.s);
-    return colorize_blend_launch(c.x, want_mean ? c.x_mean : nullptr, c.cp->gray0, p->noise_tape ? p->noise_tape + d.offset : nullptr,
-                                 c.cp->mean_scale[i], c.cp->std[i], c.B, hw, 0, c.cp->matrix, c.cp->inv_matrix, p->seed, d.stream, c.s);
+  float* mean = (phase == 1 && i == p->n_steps - 1 && p->denoise) ? c.x_mean : nullptr;
+  const PCDrawAt d = c.draw(i, c.bl.mode == BLEND_COLORIZE ? DRAW_COLORIZE : DRAW_BLEND, phase);
+  const float* z = p->noise_tape ? p->noise_tape + d.offset : nullptr;
+  switch (c.bl.mode) {
+    case BLEND_INPAINT: {
+      const csd_pc_inpaint_params& ip = *c.bl.ip;
+      ProfScope prof(CSD_PROF_SAMPLER, 0, (z ? 5.0 : 4.0) * c.nx * 4, c.s);
+      return inpaint_blend_launch(c.x, mean, ip.data, ip.mask, z, ip.mean_scale[i], ip.std[i], c.nx, p->seed, d.stream, c.s);
+    }
+    case BLEND_COLORIZE: {
+      const csd_pc_colorize_params& cp = *c.bl.cp;
+      const size_t hw = c.nx / ((size_t)c.B * 3);
+      ProfScope prof(CSD_PROF_SAMPLER, 0, ((z ? 7.0 : 6.0) + 1.0) * c.nx * 4 / 3, c.s);
+      return colorize_blend_launch(c.x, mean, cp.gray0, z, cp.mean_scale[i], cp.std[i], c.B, hw, 0, cp.matrix, cp.inv_matrix, p->seed,
+                                   d.stream, c.s);
+    }
   }
-  const PCDrawAt d = c.draw(i, DRAW_BLEND, phase);
-  ProfScope prof(CSD_PROF_SAMPLER, 0, (p->noise_tape ? 5.0 : 4.0) * c.nx * 4, c.s);
-  return inpaint_blend_launch(c.x, want_mean ? c.x_mean : nullptr, c.ip->data, c.ip->mask,
-                              p->noise_tape ? p->noise_tape + d.offset : nullptr, c.ip->mean_scale[i], c.ip->std[i], c.nx, p->seed,
-                              d.stream, c.s);
+  return CSD_OK;                                   // BLEND_NONE: nothing to re-impose
 }
 
 // phase 0: corrector (sampling/conditional.py:208-209), phase 1: predictor (:211).  part bit 0: network + noise + (corrector:
@@ -226,7 +227,7 @@ static int pc_phase(const PCCtx& c, int i, int phase, int part, float* sums_out,
   int rc;
   const csd_pc_params* p = c.p;
   if (!c.has[phase]) {                       // 'none': x stays, x_mean = x (sampling/predictors.py:182-200, correctors.py:145-163)
-    if (c.blends()) return (part & 2) ? pc_blend(c, i, phase) : CSD_OK;      // (the reference wraps the 'none' update functions as well)
+    if (c.bl.mode != BLEND_NONE) return (part & 2) ? pc_blend(c, i, phase) : CSD_OK;      // (the reference wraps the 'none' update functions as well)
     if ((part & 2) && c.is_last(phase) && i == p->n_steps - 1 && p->denoise)
       CSD_CHECK_HIP(hipMemcpyAsync(c.x_mean, c.x, c.nx * sizeof(float), hipMemcpyDeviceToDevice, c.s));
     return CSD_OK;
@@ -272,7 +273,7 @@ static int pc_phase(const PCCtx& c, int i, int phase, int part, float* sums_out,
       rc = reverse_diffusion_update_launch(c.x, c.x_mean, c.net_out, c.net_stride, zp, p->std_x[i], p->G[i], c.B, c.per, c.s);
     }
     if (rc) return rc;
-    if (c.blends() && (rc = pc_blend(c, i, phase))) return rc;
+    if ((rc = pc_blend(c, i, phase))) return rc;
   }
   return CSD_OK;
 }

@@ -64,6 +64,22 @@ __global__ __launch_bounds__(SQ_THREADS) void sumsq_rows_kernel(const float* __r
   }
 }
 
+// The loop of the five update kernels on the network's (row-strided) output: element i of sample b reads net[b*net_stride + i - b*per]
+// (a paired network emits [score_x | score_y] per sample, so net_stride >= per) and divides by std; rule(x_i, score, z_i) yields
+// (x_mean_i, the new x_i).  Each kernel writes its rule inline, in the reference's order of operations (fp contraction is off).
+template <class Rule>
+__device__ __forceinline__ void strided_update(float* __restrict__ x, float* __restrict__ x_mean, const float* __restrict__ net,
+                                               int64_t net_stride, const float* __restrict__ z, float std, int64_t per, size_t total,
+                                               Rule rule) {
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    const size_t b = i / (size_t)per;
+    const float score = net[b * net_stride + (i - b * per)] / std;
+    const float2 u = rule(x[i], score, z[i]);
+    x_mean[i] = u.x;
+    x[i] = u.y;
+  }
+}
+
 __global__ __launch_bounds__(256) void langevin_update_kernel(float* __restrict__ x, float* __restrict__ x_mean,
                                                               const float* __restrict__ net,
                                                               int64_t net_stride, const float* __restrict__ z,
@@ -100,14 +116,10 @@ __global__ __launch_bounds__(256) void langevin_update_kernel(float* __restrict_
   __syncthreads();
   const float step = s_step;
   const float nz = sqrtf(step * 2.f);
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total;
-       i += (size_t)gridDim.x * blockDim.x) {
-    const size_t b = i / (size_t)per;
-    const float score = net[b * net_stride + (i - b * per)] / std;
-    const float xm = x[i] + step * score;
-    x_mean[i] = xm;
-    x[i] = xm + nz * z[i];
-  }
+  strided_update(x, x_mean, net, net_stride, z, std, per, total, [=](float xi, float score, float zi) {
+    const float xm = xi + step * score;
+    return make_float2(xm, xm + nz * zi);
+  });
 }
 
 // global-norm exactness mode: sums[0] = sum_b ||net_b||/std, sums[1] = sum_b ||z_b|| over THIS rank's samples,
@@ -144,13 +156,10 @@ __global__ __launch_bounds__(256) void langevin_update_global_kernel(float* __re
   const float step = r * r * 2.f * alpha;
   if (blockIdx.x == 0 && threadIdx.x == 0 && nonfinite && !(fabsf(step) <= 3.0e38f)) *nonfinite = 1;
   const float nz = sqrtf(step * 2.f);
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-    const size_t b = i / (size_t)per;
-    const float score = net[b * net_stride + (i - b * per)] / std;
-    const float xm = x[i] + step * score;
-    x_mean[i] = xm;
-    x[i] = xm + nz * z[i];
-  }
+  strided_update(x, x_mean, net, net_stride, z, std, per, total, [=](float xi, float score, float zi) {
+    const float xm = xi + step * score;
+    return make_float2(xm, xm + nz * zi);
+  });
 }
 
 __global__ __launch_bounds__(256) void reverse_diffusion_update_kernel(float* __restrict__ x,
@@ -160,15 +169,11 @@ __global__ __launch_bounds__(256) void reverse_diffusion_update_kernel(float* __
                                                                        const float* __restrict__ z, float std,
                                                                        float G, int64_t per, size_t total) {
   const float G2 = G * G;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total;
-       i += (size_t)gridDim.x * blockDim.x) {
-    const size_t b = i / (size_t)per;
-    const float score = net[b * net_stride + (i - b * per)] / std;
+  strided_update(x, x_mean, net, net_stride, z, std, per, total, [=](float xi, float score, float zi) {
     const float rev_f = 0.f - G2 * score;   // f = 0 for VE
-    const float xm = x[i] - rev_f;
-    x_mean[i] = xm;
-    x[i] = xm + G * z[i];
-  }
+    const float xm = xi - rev_f;
+    return make_float2(xm, xm + G * zi);
+  });
 }
 
 // the reverse-diffusion update of an SDE with a linear forward drift, and of the probability flow of any SDE, in the reference's order
@@ -180,10 +185,7 @@ __global__ __launch_bounds__(256) void reverse_diffusion_drift_update_kernel(flo
                                                                              float a, float b, int drift, int sub_x, float kappa,
                                                                              float g_noise, int64_t per, size_t total) {
   const float G2 = G * G;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-    const size_t bi = i / (size_t)per;
-    const float score = net[bi * net_stride + (i - bi * per)] / std;
-    const float xi = x[i];
+  strided_update(x, x_mean, net, net_stride, z, std, per, total, [=](float xi, float score, float zi) {
     float f = 0.f;
     if (drift) {
       f = (a * xi) * b;
@@ -191,9 +193,19 @@ __global__ __launch_bounds__(256) void reverse_diffusion_drift_update_kernel(flo
     }
     const float rev_f = f - (G2 * score) * kappa;
     const float xm = xi - rev_f;
-    x_mean[i] = xm;
-    x[i] = xm + g_noise * z[i];
-  }
+    return make_float2(xm, xm + g_noise * zi);
+  });
+}
+
+// x_mean = p*x + (a/std)*net, x = x_mean + c*z on the network's (row-strided) output: the affine update rules inside the fused loop
+__global__ __launch_bounds__(256) void affine_net_update_kernel(float* __restrict__ x, float* __restrict__ x_mean,
+                                                                const float* __restrict__ net, int64_t net_stride,
+                                                                const float* __restrict__ z, float std, float p, float a, float c,
+                                                                int64_t per, size_t total) {
+  strided_update(x, x_mean, net, net_stride, z, std, per, total, [=](float xi, float score, float zi) {
+    const float xm = p * xi + a * score;
+    return make_float2(xm, xm + c * zi);
+  });
 }
 
 // out[b] = ||a_b||_2 (fp64 sum of squares, one workgroup per sample): the per-sample norms of the Langevin step size
@@ -274,6 +286,24 @@ __global__ void randn_kernel(float* __restrict__ out, size_t n, uint64_t seed, u
   }
 }
 
+// the 4-wide accessors of the two blend kernels: a group of 4 consecutive floats as one float4 (full), or its first cnt elements
+__device__ __forceinline__ void load4(const float* p, bool full, int cnt, float v[4]) {
+  if (full) {
+    const float4 a = *reinterpret_cast<const float4*>(p);
+    v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
+  } else {
+    for (int j = 0; j < cnt; ++j) v[j] = p[j];
+  }
+}
+
+__device__ __forceinline__ void store4(float* p, bool full, int cnt, const float v[4]) {
+  if (full) {
+    *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
+  } else {
+    for (int j = 0; j < cnt; ++j) p[j] = v[j];
+  }
+}
+
 // inpainting: re-impose the known pixels after an update (sampling/unconditional.py:268-271), in the reference's order of operations:
 //   masked_mean = m*data ; masked = masked_mean + std*z ; x = x*(1 - mask) + masked*mask ; x_mean = x*(1 - mask) + masked_mean*mask
 // (x_mean from the NEW x).  m, std: per-call scalars (all samples share one time).  z: the tape, or - z == nullptr and draw - the
@@ -290,16 +320,10 @@ __global__ __launch_bounds__(256) void inpaint_blend_kernel(float* __restrict__ 
     const bool full = vec && base + 3 < n;
     const int cnt = base + 3 < n ? 4 : (int)(n - base);
     float xv[4] = {0.f, 0.f, 0.f, 0.f}, dv[4] = {0.f, 0.f, 0.f, 0.f}, mk[4] = {0.f, 0.f, 0.f, 0.f}, zv[4] = {0.f, 0.f, 0.f, 0.f};
-    if (full) {
-      const float4 a = *reinterpret_cast<const float4*>(x + base), b = *reinterpret_cast<const float4*>(data + base),
-                   c = *reinterpret_cast<const float4*>(mask + base);
-      xv[0] = a.x; xv[1] = a.y; xv[2] = a.z; xv[3] = a.w;
-      dv[0] = b.x; dv[1] = b.y; dv[2] = b.z; dv[3] = b.w;
-      mk[0] = c.x; mk[1] = c.y; mk[2] = c.z; mk[3] = c.w;
-      if (z) { const float4 d = *reinterpret_cast<const float4*>(z + base); zv[0] = d.x; zv[1] = d.y; zv[2] = d.z; zv[3] = d.w; }
-    } else {
-      for (int j = 0; j < cnt; ++j) { xv[j] = x[base + j]; dv[j] = data[base + j]; mk[j] = mask[base + j]; if (z) zv[j] = z[base + j]; }
-    }
+    load4(x + base, full, cnt, xv);
+    load4(data + base, full, cnt, dv);
+    load4(mask + base, full, cnt, mk);
+    if (z) load4(z + base, full, cnt, zv);
     if (!z && draw) philox_normal4(i, seed, stream_id, zv);
     float xn[4], xm[4];
 #pragma unroll
@@ -310,12 +334,8 @@ __global__ __launch_bounds__(256) void inpaint_blend_kernel(float* __restrict__ 
       xn[j] = xv[j] * keep + masked * mk[j];
       xm[j] = xn[j] * keep + masked_mean * mk[j];
     }
-    if (full) {
-      *reinterpret_cast<float4*>(x + base) = make_float4(xn[0], xn[1], xn[2], xn[3]);
-      if (x_mean) *reinterpret_cast<float4*>(x_mean + base) = make_float4(xm[0], xm[1], xm[2], xm[3]);
-    } else {
-      for (int j = 0; j < cnt; ++j) { x[base + j] = xn[j]; if (x_mean) x_mean[base + j] = xm[j]; }
-    }
+    store4(x + base, full, cnt, xn);
+    if (x_mean) store4(x_mean + base, full, cnt, xm);
   }
 }
 
@@ -334,23 +354,6 @@ struct ColorMatrix { float m[3][3], inv[3][3]; };
 __device__ __forceinline__ void mat3_contract(const float (&a)[3][3], float v0, float v1, float v2, float out[3]) {
 #pragma unroll
   for (int j = 0; j < 3; ++j) out[j] = (v0 * a[0][j] + v1 * a[1][j]) + v2 * a[2][j];
-}
-
-__device__ __forceinline__ void load4(const float* p, bool full, int cnt, float v[4]) {
-  if (full) {
-    const float4 a = *reinterpret_cast<const float4*>(p);
-    v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
-  } else {
-    for (int j = 0; j < cnt; ++j) v[j] = p[j];
-  }
-}
-
-__device__ __forceinline__ void store4(float* p, bool full, int cnt, const float v[4]) {
-  if (full) {
-    *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
-  } else {
-    for (int j = 0; j < cnt; ++j) p[j] = v[j];
-  }
 }
 
 __global__ __launch_bounds__(256) void colorize_blend_kernel(float* __restrict__ x, float* __restrict__ x_mean,
@@ -432,10 +435,16 @@ __global__ __launch_bounds__(256) void finite_check_kernel(const float* __restri
 
 static int ew_grid(size_t total) { return (int)std::min<size_t>(cdiv64(total, 256), 4096); }
 
-int finite_check_launch(const float* x, size_t total, int* nonfinite, hipStream_t s) {
-  hipLaunchKernelGGL(finite_check_kernel, dim3(ew_grid(total)), dim3(256), 0, s, x, total, nonfinite);
+// the launch of a grid-stride kernel over `work` items: 256 threads, at most 4096 workgroups
+template <class Kernel, class... Args>
+static int ew_launch(Kernel kernel, size_t work, hipStream_t s, Args... args) {
+  hipLaunchKernelGGL(kernel, dim3(ew_grid(work)), dim3(256), 0, s, args...);
   CSD_LAUNCH_CHECK();
   return CSD_OK;
+}
+
+int finite_check_launch(const float* x, size_t total, int* nonfinite, hipStream_t s) {
+  return ew_launch(finite_check_kernel, total, s, x, total, nonfinite);
 }
 
 int sumsq_rows_launch(const float* net, int64_t net_stride, const float* z, double* partial, int B, int64_t per,
@@ -450,10 +459,8 @@ int langevin_update_launch(float* x, float* x_mean, const float* net, int64_t ne
                            const double* partial, int nchunk, float std, float snr, float alpha, int B, int64_t per,
                            hipStream_t s, int* nonfinite) {
   const size_t total = (size_t)B * per;
-  hipLaunchKernelGGL(langevin_update_kernel, dim3(ew_grid(total)), dim3(256), 0, s, x, x_mean, net, net_stride, z,
-                     partial, nchunk, std, snr, alpha, B, per, total, nonfinite);
-  CSD_LAUNCH_CHECK();
-  return CSD_OK;
+  return ew_launch(langevin_update_kernel, total, s, x, x_mean, net, net_stride, z, partial, nchunk, std, snr, alpha, B, per, total,
+                   nonfinite);
 }
 
 int norm_sums_launch(const double* partial, int nchunk, float std, int B, float* sums, hipStream_t s) {
@@ -466,69 +473,39 @@ int langevin_update_global_launch(float* x, float* x_mean, const float* net, int
                                   const float* sums, int Bg, float std, float snr, float alpha, int B, int64_t per,
                                   hipStream_t s, int* nonfinite) {
   const size_t total = (size_t)B * per;
-  hipLaunchKernelGGL(langevin_update_global_kernel, dim3(ew_grid(total)), dim3(256), 0, s, x, x_mean, net, net_stride, z,
-                     sums, Bg, std, snr, alpha, per, total, nonfinite);
-  CSD_LAUNCH_CHECK();
-  return CSD_OK;
+  return ew_launch(langevin_update_global_kernel, total, s, x, x_mean, net, net_stride, z, sums, Bg, std, snr, alpha, per, total,
+                   nonfinite);
 }
 
 int reverse_diffusion_update_launch(float* x, float* x_mean, const float* net, int64_t net_stride, const float* z,
                                     float std, float G, int B, int64_t per, hipStream_t s) {
   const size_t total = (size_t)B * per;
-  hipLaunchKernelGGL(reverse_diffusion_update_kernel, dim3(ew_grid(total)), dim3(256), 0, s, x, x_mean, net,
-                     net_stride, z, std, G, per, total);
-  CSD_LAUNCH_CHECK();
-  return CSD_OK;
+  return ew_launch(reverse_diffusion_update_kernel, total, s, x, x_mean, net, net_stride, z, std, G, per, total);
 }
 
 int reverse_diffusion_drift_update_launch(float* x, float* x_mean, const float* net, int64_t net_stride, const float* z, float std,
                                           float G, float a, float b, int drift, int sub_x, float kappa, float g_noise, int B,
                                           int64_t per, hipStream_t s) {
   const size_t total = (size_t)B * per;
-  hipLaunchKernelGGL(reverse_diffusion_drift_update_kernel, dim3(ew_grid(total)), dim3(256), 0, s, x, x_mean, net, net_stride, z,
-                     std, G, a, b, drift, sub_x, kappa, g_noise, per, total);
-  CSD_LAUNCH_CHECK();
-  return CSD_OK;
-}
-
-// x_mean = p*x + (a/std)*net, x = x_mean + c*z on the network's (row-strided) output: the affine update rules inside the fused loop
-__global__ __launch_bounds__(256) void affine_net_update_kernel(float* __restrict__ x, float* __restrict__ x_mean,
-                                                                const float* __restrict__ net, int64_t net_stride,
-                                                                const float* __restrict__ z, float std, float p, float a, float c,
-                                                                int64_t per, size_t total) {
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-    const size_t b = i / (size_t)per;
-    const float score = net[b * net_stride + (i - b * per)] / std;
-    const float xm = p * x[i] + a * score;
-    x_mean[i] = xm;
-    x[i] = xm + c * z[i];
-  }
+  return ew_launch(reverse_diffusion_drift_update_kernel, total, s, x, x_mean, net, net_stride, z, std, G, a, b, drift, sub_x, kappa,
+                   g_noise, per, total);
 }
 
 int affine_net_update_launch(float* x, float* x_mean, const float* net, int64_t net_stride, const float* z, float std, float p,
                              float a, float c, int B, int64_t per, hipStream_t s) {
   const size_t total = (size_t)B * per;
-  hipLaunchKernelGGL(affine_net_update_kernel, dim3(ew_grid(total)), dim3(256), 0, s, x, x_mean, net, net_stride, z, std, p, a, c,
-                     per, total);
-  CSD_LAUNCH_CHECK();
-  return CSD_OK;
+  return ew_launch(affine_net_update_kernel, total, s, x, x_mean, net, net_stride, z, std, p, a, c, per, total);
 }
 
 int affine_noise_update_launch(float* x, float* x_mean, const float* score, const float* z, float p, float a, float c,
                                size_t total, hipStream_t s) {
-  hipLaunchKernelGGL(affine_noise_update_kernel, dim3(ew_grid(total)), dim3(256), 0, s, x, x_mean, score, z, p, a, c,
-                     total);
-  CSD_LAUNCH_CHECK();
-  return CSD_OK;
+  return ew_launch(affine_noise_update_kernel, total, s, x, x_mean, score, z, p, a, c, total);
 }
 
 int randn_launch(float* out, int64_t n, uint64_t seed, uint64_t stream_id, hipStream_t s) {
   if (n <= 0) return CSD_OK;
   CSD_REQUIRE((reinterpret_cast<uintptr_t>(out) & 15) == 0, "randn: output must be 16-byte aligned");
-  hipLaunchKernelGGL(randn_kernel, dim3(ew_grid((size_t)(n + 3) / 4)), dim3(256), 0, s, out, (size_t)n, seed,
-                     stream_id);
-  CSD_LAUNCH_CHECK();
-  return CSD_OK;
+  return ew_launch(randn_kernel, (size_t)(n + 3) / 4, s, out, (size_t)n, seed, stream_id);
 }
 
 int inpaint_blend_launch(float* x, float* x_mean, const float* data, const float* mask, const float* z, float m, float std, size_t n,
@@ -537,10 +514,8 @@ int inpaint_blend_launch(float* x, float* x_mean, const float* data, const float
   const uintptr_t bits = reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(x_mean) | reinterpret_cast<uintptr_t>(data) |
                          reinterpret_cast<uintptr_t>(mask) | reinterpret_cast<uintptr_t>(z);
   CSD_REQUIRE((bits & 3) == 0, "inpaint_blend: tensors must be 4-byte aligned");
-  hipLaunchKernelGGL(inpaint_blend_kernel, dim3(ew_grid((n + 3) / 4)), dim3(256), 0, s, x, x_mean, data, mask, z, m, std, n, seed,
-                     stream_id, (z == nullptr && std != 0.f) ? 1 : 0, (bits & 15) == 0 ? 1 : 0);
-  CSD_LAUNCH_CHECK();
-  return CSD_OK;
+  return ew_launch(inpaint_blend_kernel, (n + 3) / 4, s, x, x_mean, data, mask, z, m, std, n, seed, stream_id,
+                   (z == nullptr && std != 0.f) ? 1 : 0, (bits & 15) == 0 ? 1 : 0);
 }
 
 // the host 3 x 3 matrix M (NULL: the reference's literals, controllable_generation.py:117-119) and its inverse (NULL: the float64
@@ -595,11 +570,9 @@ int colorize_blend_launch(float* x, float* x_mean, const float* gray0, const flo
                          reinterpret_cast<uintptr_t>(z);
   CSD_REQUIRE((bits & 3) == 0, "colorize_blend: tensors must be 4-byte aligned");
   const size_t groups = (hw + 3) / 4, total = (size_t)B * groups;
-  hipLaunchKernelGGL(colorize_blend_kernel, dim3(ew_grid(total)), dim3(256), 0, s, x, init ? nullptr : x_mean, gray0, init ? nullptr : z,
-                     m, std, hw, groups, total, cm, seed, stream_id, (!init && z == nullptr && std != 0.f) ? 1 : 0, init ? 1 : 0,
-                     ((bits & 15) == 0 && hw % 4 == 0) ? 1 : 0);
-  CSD_LAUNCH_CHECK();
-  return CSD_OK;
+  return ew_launch(colorize_blend_kernel, total, s, x, init ? nullptr : x_mean, gray0, init ? nullptr : z, m, std, hw, groups, total, cm,
+                   seed, stream_id, (!init && z == nullptr && std != 0.f) ? 1 : 0, init ? 1 : 0,
+                   ((bits & 15) == 0 && hw % 4 == 0) ? 1 : 0);
 }
 
 int colorize_gray0_launch(const float* gray, float* gray0, int B, size_t hw, const float* matrix, hipStream_t s) {
@@ -608,20 +581,14 @@ int colorize_gray0_launch(const float* gray, float* gray0, int B, size_t hw, con
   if (rc) return rc;
   const size_t total = (size_t)B * hw;
   if (total == 0) return CSD_OK;
-  hipLaunchKernelGGL(colorize_gray0_kernel, dim3(ew_grid(total)), dim3(256), 0, s, gray, gray0, hw, total, cm.m[0][0], cm.m[1][0],
-                     cm.m[2][0]);
-  CSD_LAUNCH_CHECK();
-  return CSD_OK;
+  return ew_launch(colorize_gray0_kernel, total, s, gray, gray0, hw, total, cm.m[0][0], cm.m[1][0], cm.m[2][0]);
 }
 
 int scale_rows_launch(float* out, const float* in, const float* scale, int divide, int B, int64_t per,
                       hipStream_t s) {
   const size_t total = (size_t)B * per;
   if (total == 0) return CSD_OK;
-  hipLaunchKernelGGL(scale_rows_kernel, dim3(ew_grid(total)), dim3(256), 0, s, out, in, scale, divide,
-                     (size_t)per, total);
-  CSD_LAUNCH_CHECK();
-  return CSD_OK;
+  return ew_launch(scale_rows_kernel, total, s, out, in, scale, divide, (size_t)per, total);
 }
 
 // use_path bridge (sde_lib.py:323-339): y_t = w0 * y0 + w1 * y_{t+tau} + std * z, in place on the state; prev == nullptr: w1 term absent

@@ -232,17 +232,17 @@ def get_autoregressive_sampler(stages, coord_space='bicubic', predictor='default
                       corrector=st['corrector'], probability_flow=st['probability_flow'], continuous=st['continuous'])
             shape = model._x_shape(B)
             if inpaint:
-                label = 'fourier' if getattr(model, 'embedding_type', 'positional') == 'fourier' else 'sigma'
                 data = first_data(lr) if k == 0 else ops._out(shape, torch.float32, dev)       # (k >= 1: the library zeroes and fills it)
-                prep = fused.prepare(model, sde, shape, None, st['p_steps'], st['snr'], st['eps'], st['denoise'], unconditional_label=label,
-                                     inpaint=(data, mask_for(data)), blend=(k == 0), **kw)
+                prep = fused.prepare(model, sde, shape, None, st['p_steps'], st['snr'], st['eps'], st['denoise'],
+                                     unconditional_label=fused.unconditional_label(model), inpaint=(data, mask_for(data)), blend=(k == 0),
+                                     **kw)
             else:
                 prep = fused.prepare(model, sde, shape, None, st['p_steps'], st['snr'], st['eps'], st['denoise'], **kw)
             preps.append(prep)
             g = arr[k]
             g.net, g.packed = model._h, model._packed.data_ptr()
             g.pc = ctypes.pointer(prep.p)
-            g.inpaint = ctypes.pointer(prep.ip) if prep.ip is not None else None
+            g.inpaint = ctypes.pointer(prep.constraint.struct) if prep.constraint is not None else None
             g.x = prep.x.data_ptr()
             g.link = 0 if (k == 0 or coord_space == 'bicubic') else (2 if inpaint else 1)
             # the image a Haar stage hands on: a caller buffer where it is returned (the last level, every level with
@@ -266,7 +266,7 @@ def get_autoregressive_sampler(stages, coord_space='bicubic', predictor='default
         if coord_space == 'bicubic':
             images = [p.x for p in preps]
         elif inpaint:
-            images = [preps[k + 1].data[:, :C] for k in range(n - 1)] + [outs[-1]]
+            images = [preps[k + 1].constraint.data[:, :C] for k in range(n - 1)] + [outs[-1]]
         else:
             images = outs
         del arr                                  # (it pointed into preps, alive until here; the call synchronised)

@@ -191,8 +191,12 @@ def noise_draws(handle, B, predictor, corrector, std_y=False, use_path=False, in
     library's message."""
     if inpaint and colorize:
         raise NotImplementedError('inpaint and colorize exclude each other: one re-imposition per loop')
-    args = (handle, int(B), int(predictor), int(corrector), int(bool(std_y)), int(bool(use_path)), 2 if colorize else int(bool(inpaint)),
-            int(n_steps))
+    return _noise_draws(handle, B, predictor, corrector, std_y, use_path, 2 if colorize else int(bool(inpaint)), n_steps)
+
+
+def _noise_draws(handle, B, predictor, corrector, std_y, use_path, blend, n_steps):
+    """``noise_draws`` with the library's own ``inpaint`` integer: 0 none, 1 inpainting, 2 colorization (``_Constraint.draws``)"""
+    args = (handle, int(B), int(predictor), int(corrector), int(bool(std_y)), int(bool(use_path)), int(blend), int(n_steps))
     n = lib().csd_pc_noise_draws(*args, None, 0)
     if n < 0:
         check(int(n), 'pc_noise_draws')
@@ -243,11 +247,97 @@ def path_tables(sy, ts):
     return torch.tensor(rows, dtype=torch.float32).contiguous(), std0
 
 
+def unconditional_label(model):
+    """the ``unconditional_label`` of an unconditional run on ``model``: the network sees log sigma(t) behind a Fourier embedding and
+    sigma(t) otherwise (the VE SDEs; VP / sub-VP take t*(N-1) whatever is passed)"""
+    return 'fourier' if getattr(model, 'embedding_type', 'positional') == 'fourier' else 'sigma'
+
+
+class _Constraint:
+    """What one loop re-imposes behind every phase, as ``prepare`` resolves ``inpaint=`` / ``colorize=``: everything that differs
+    between the constrained entry families.  A kind sets ``family`` (its entries are csd_<family>_sample / _step_begin / _step_end),
+    ``noun`` (what its refusals call it) and ``draws`` (the ``inpaint`` integer of csd_pc_noise_draws), checks its own argument
+    against the state's shape (``check_shape``), fills its ctypes ``struct`` and the tensors ``keep`` that the struct points into
+    (``fill``) and turns the prior into the initial state (``start``).  ``scratch_bytes`` names the entry that sizes the loop's scratch:
+    the plain one unless the family exports its own.  The constructor makes every refusal, on the host."""
+    scratch_bytes = 'csd_pc_scratch_bytes'
+
+    def __init__(self, arg, model, shape, y, sde, use_path):
+        who = (self.noun, self.family)
+        if len(shape) == 5:
+            raise NotImplementedError('%s on the device loop is not provided for the 3-D networks (csd_%s_* refuse them)' % who)
+        if getattr(model, 'y_scale', 0):
+            raise NotImplementedError('%s on the device loop is not provided for %s (the Kx super-resolution networks, ddpm_KxSR / '
+                                      'ncsnpp_KxSR, are conditional; csd_%s_* refuse y_scale)' % (who[0], type(model).__name__, who[1]))
+        if y is not None or isinstance(sde, dict) or use_path:
+            raise NotImplementedError('%s on the device loop runs unconditional networks on a single SDE' % who[0])
+        self.check_shape(arg, tuple(shape))
+        self.arg = arg
+
+
+class _Inpaint(_Constraint):
+    """``inpaint=(data, mask)``: the known pixels (csd_pc_inpaint_params).  ``blend=False``: the initial state stays the bare prior"""
+    family, noun, draws, blend = 'pc_inpaint', 'inpainting', 1, True
+    scratch_bytes = 'csd_pc_inpaint_scratch_bytes'
+
+    def check_shape(self, arg, shape):
+        if tuple(arg[0].shape) != shape:
+            raise ValueError('inpaint: data has shape %s, the sampler runs %s' % (tuple(arg[0].shape), shape))
+
+    def fill(self, dev, c_sde, ts):
+        data, mask = self.arg
+        self.data = data.to(dev, torch.float32).contiguous()
+        self.mask = mask.to(dev, torch.float32).expand_as(self.data).contiguous()
+        mean, std = inpaint_tables(c_sde, ts)
+        self.struct = _lib.PCInpaintParams()
+        self.struct.data, self.struct.mask = self.data.data_ptr(), self.mask.data_ptr()
+        self.struct.mean_scale, self.struct.std = _fp(mean), _fp(std)
+        self.keep = (mean, std, self.data, self.mask)
+
+    def start(self, x, record):
+        if self.blend:
+            ops.inpaint_blend(x, self.data, self.mask, x_mean=False)      # prior*(1 - mask) + data*mask
+        elif record:
+            raise NotImplementedError('record needs the initial state, which blend=False leaves to the caller')
+
+
+class _Colorize(_Constraint):
+    """``colorize=gray``: the gray channel of the decoupled channel space (csd_pc_colorize_params)"""
+    family, noun, draws = 'pc_colorize', 'colorization', 2
+
+    def check_shape(self, gray, shape):
+        if tuple(gray.shape) != shape or len(shape) != 4 or shape[1] != 3:
+            raise ValueError('colorize: the gray-scale image has shape %s, the sampler runs %s; colorization needs [B, 3, H, W]'
+                             % (tuple(gray.shape), shape))
+
+    def fill(self, dev, c_sde, ts):
+        self.gray0 = ops.colorize_gray0(self.arg.to(dev, torch.float32).contiguous())      # once per call
+        mean, std = inpaint_tables(c_sde, ts)
+        self.struct = _lib.PCColorizeParams()
+        self.struct.gray0 = self.gray0.data_ptr()
+        self.struct.mean_scale, self.struct.std = _fp(mean), _fp(std)                 # (matrix / inv_matrix NULL: the library's default)
+        self.keep = (mean, std, self.gray0)
+
+    def start(self, x, record):
+        ops.colorize_start(x, self.gray0)               # couple(decouple(gray)*mask + decouple(prior*(1 - mask)))
+
+
+def _resolve(inpaint, colorize, blend, *run):
+    """the ``_Constraint`` of ``prepare``'s ``inpaint=`` / ``colorize=`` (None: neither); ``run``: what the refusals look at"""
+    if inpaint is not None and colorize is not None:
+        raise NotImplementedError('inpaint= and colorize= exclude each other: the device loop re-imposes one constraint per run')
+    if inpaint is not None:
+        con = _Inpaint(inpaint, *run)
+        con.blend = blend
+        return con
+    return _Colorize(colorize, *run) if colorize is not None else None
+
+
 class Prepared:
     """One fused loop ready to be enqueued (``prepare``): the state ``x`` (prior in, result out), the condition ``y``, the filled
-    csd_pc_params ``p`` / csd_pc_inpaint_params ``ip`` (None: not an inpainting run) / csd_pc_colorize_params ``cp`` (None: not a
-    colorization run), the record tensor ``rec`` and the timesteps ``ts``.  ``keep`` holds every host array and device tensor the two structs point into: the object must stay alive until the
-    library call that reads them has returned."""
+    csd_pc_params ``p``, the ``constraint`` (a ``_Constraint`` with its filled ``struct``; None: a plain run), the record tensor
+    ``rec`` and the timesteps ``ts``.  ``keep`` holds every host array and device tensor the two structs point into: the object must
+    stay alive until the library call that reads them has returned."""
 
     def __init__(self, **kw):
         self.__dict__.update(kw)
@@ -262,12 +352,7 @@ def prepare(model, sde, shape, y, p_steps, snr, eps, denoise, noise_tape=None, s
     used as it is - the cascade's link writes the data and blends on the device."""
     if seed is None:
         seed = fresh_seed()
-    if inpaint is not None and colorize is not None:
-        raise NotImplementedError('inpaint= and colorize= exclude each other: the device loop re-imposes one constraint per run')
-    if colorize is not None and len(shape) == 5:
-        raise NotImplementedError('colorization on the device loop is not provided for the 3-D networks (csd_pc_colorize_* refuse them)')
-    if inpaint is not None and len(shape) == 5:
-        raise NotImplementedError('inpainting on the device loop is not provided for the 3-D networks (csd_pc_inpaint_* refuse them)')
+    con = _resolve(inpaint, colorize, blend, model, shape, y, sde, use_path)      # (every refusal of a constraint: host only)
     c_sde = sde['x'] if isinstance(sde, dict) else sde
     dev = model.device
     if dev.type != 'cuda':
@@ -293,30 +378,8 @@ def prepare(model, sde, shape, y, p_steps, snr, eps, denoise, noise_tape=None, s
     if cid == 0 and corr_alpha is None:
         corr_alpha = langevin_alphas(c_sde, ts)
     path_tab, path_std0 = None, 0.0
-    if inpaint is not None:
-        if getattr(model, 'y_scale', 0):
-            raise NotImplementedError('inpainting on the device loop is not provided for %s (the Kx super-resolution networks, '
-                                      'ddpm_KxSR / ncsnpp_KxSR, are conditional; csd_pc_inpaint_* refuse y_scale)' % type(model).__name__)
-        if y is not None or isinstance(sde, dict) or use_path:
-            raise NotImplementedError('inpainting on the device loop runs unconditional networks on a single SDE')
-        data, mask = inpaint
-        if tuple(data.shape) != tuple(shape):
-            raise ValueError('inpaint: data has shape %s, the sampler runs %s' % (tuple(data.shape), tuple(shape)))
-        data = data.to(dev, torch.float32).contiguous()
-        mask = mask.to(dev, torch.float32).expand_as(data).contiguous()
-        ip_mean, ip_std = inpaint_tables(c_sde, ts)
-    if colorize is not None:
-        if getattr(model, 'y_scale', 0):
-            raise NotImplementedError('colorization on the device loop is not provided for %s (the Kx super-resolution networks, '
-                                      'ddpm_KxSR / ncsnpp_KxSR, are conditional; csd_pc_colorize_* refuse y_scale)' % type(model).__name__)
-        if y is not None or isinstance(sde, dict) or use_path:
-            raise NotImplementedError('colorization on the device loop runs unconditional networks on a single SDE')
-        gray = colorize
-        if tuple(gray.shape) != tuple(shape) or len(shape) != 4 or shape[1] != 3:
-            raise ValueError('colorize: the gray-scale image has shape %s, the sampler runs %s; colorization needs [B, 3, H, W]'
-                             % (tuple(gray.shape), tuple(shape)))
-        gray0 = ops.colorize_gray0(gray.to(dev, torch.float32).contiguous())      # once per call
-        cp_mean, cp_std = inpaint_tables(c_sde, ts)
+    if con is not None:
+        con.fill(dev, c_sde, ts)
     if use_path:
         if not isinstance(sde, dict):
             raise NotImplementedError('use_path needs the two-SDE (CMDE / VS-CMDE) setting: sde = {"x": ..., "y": ...}')
@@ -333,8 +396,8 @@ def prepare(model, sde, shape, y, p_steps, snr, eps, denoise, noise_tape=None, s
         x = x.to(dev).contiguous()
         flat = torch.cat([t.reshape(-1) for t in tape[1:]]).to(dev).contiguous() if len(tape) > 1 else None
         # draws and elements: an x draw has the state's size, a y draw that of y (the low-resolution y of a y_scale network)
-        check_tape(noise_draws(model._h, B, pid, cid, std_y is not None, use_path, inpaint is not None, p_steps,
-                               colorize=colorize is not None), tape[1:], int(x.numel()), int(y.numel()) if y is not None else 0)
+        check_tape(_noise_draws(model._h, B, pid, cid, std_y is not None, use_path, con.draws if con is not None else 0, p_steps),
+                   tape[1:], int(x.numel()), int(y.numel()) if y is not None else 0)
     else:
         x = ops.randn(tuple(shape), seed, 0, dev)
         if ve:
@@ -344,30 +407,14 @@ def prepare(model, sde, shape, y, p_steps, snr, eps, denoise, noise_tape=None, s
         flat = None
     model.eval()
     model._ensure_packed()
-    n_rec = p_steps + (1 if inpaint is not None or colorize is not None else 0)
+    n_rec = p_steps + (1 if con is not None else 0)          # a constrained run records its initial state in front of the steps
     rec = ops._out((n_rec,) + tuple(x.shape), torch.float32, dev) if record else None
     rec_steps = rec
-    ip = None
-    if inpaint is not None:
-        if blend:
-            ops.inpaint_blend(x, data, mask, x_mean=False)            # prior*(1 - mask) + data*mask
-        elif record:
-            raise NotImplementedError('record needs the initial state, which blend=False leaves to the caller')
+    if con is not None:
+        con.start(x, record)
         if record:
             rec[0].copy_(x)
             rec_steps = rec[1:]
-        ip = _lib.PCInpaintParams()
-        ip.data, ip.mask = data.data_ptr(), mask.data_ptr()
-        ip.mean_scale, ip.std = _fp(ip_mean), _fp(ip_std)
-    cp = None
-    if colorize is not None:
-        ops.colorize_start(x, gray0)                                  # couple(decouple(gray)*mask + decouple(prior*(1 - mask)))
-        if record:
-            rec[0].copy_(x)
-            rec_steps = rec[1:]
-        cp = _lib.PCColorizeParams()
-        cp.gray0 = gray0.data_ptr()
-        cp.mean_scale, cp.std = _fp(cp_mean), _fp(cp_std)             # (matrix / inv_matrix NULL: the library's default)
     p = _lib.PCParams()
     p.n_steps = p_steps
     p.labels, p.std_x, p.G = _fp(labels), _fp(std_x), _fp(G)
@@ -394,50 +441,32 @@ def prepare(model, sde, shape, y, p_steps, snr, eps, denoise, noise_tape=None, s
         global_norm = None                      # only the Langevin corrector couples the samples of a batch
     yy = y.contiguous() if y is not None else None
     keep = (labels, std_x, G, std_y, pred_tab, corr_tab, path_tab, corr_alpha, rd_tab, flat, rec)
-    if inpaint is not None:
-        keep += (ip_mean, ip_std, data, mask)
-    if colorize is not None:
-        keep += (cp_mean, cp_std, gray0)
-    return Prepared(model=model, dev=dev, B=B, x=x, y=yy, p=p, ip=ip, cp=cp, rec=rec, ts=ts, p_steps=p_steps, global_norm=global_norm,
-                    data=data if inpaint is not None else None, mask=mask if inpaint is not None else None, keep=keep)
+    if con is not None:
+        keep += con.keep
+    return Prepared(model=model, dev=dev, B=B, x=x, y=yy, p=p, constraint=con, rec=rec, ts=ts, p_steps=p_steps, global_norm=global_norm,
+                    keep=keep)
 
 
 def launch(prep):
     """Enqueue a ``Prepared`` loop through its single-stage entry (csd_pc_sample / csd_pc_inpaint_sample / csd_pc_colorize_sample, or
     the two step calls per PC step under ``global_norm``); returns ``(samples, record_or_None, timesteps)``."""
-    model, dev, B, x, yy, p, ip, p_steps = prep.model, prep.dev, prep.B, prep.x, prep.y, prep.p, prep.ip, prep.p_steps
-    cp = getattr(prep, 'cp', None)
-    global_norm = prep.global_norm
+    model, dev, B, x, p, con = prep.model, prep.dev, prep.B, prep.x, prep.p, prep.constraint
     ws = model._workspace(B)
-    scratch_bytes = lib().csd_pc_inpaint_scratch_bytes if ip is not None else lib().csd_pc_scratch_bytes
-    scratch = ops._scratch(scratch_bytes(model._h, B), dev)
-    if ip is not None or cp is not None:
-        l, name = lib(), 'pc_inpaint' if ip is not None else 'pc_colorize'
-        sample, begin, end = (getattr(l, 'csd_%s_%s' % (name, f)) for f in ('sample', 'step_begin', 'step_end'))
-        args = (model._h, ptr(model._packed), ptr(ws), ws.numel(), ptr(scratch), scratch.numel(), ptr(x), None, B, ctypes.byref(p),
-                ctypes.byref(ip if ip is not None else cp))
-        if global_norm is None:
-            check(sample(*args, current_stream(dev)), name + '_sample')
-        else:
-            reduce_fn, global_batch = global_norm
-            sums = torch.zeros(2, dtype=torch.float32, device=dev)
-            for i in range(p_steps):
-                check(begin(*args, i, ptr(sums), current_stream(dev)), name + '_step_begin')
-                reduce_fn(sums)
-                check(end(*args, i, ptr(sums), int(global_batch), current_stream(dev)), name + '_step_end')
-    elif global_norm is None:
-        check(lib().csd_pc_sample(model._h, ptr(model._packed), ptr(ws), ws.numel(), ptr(scratch), scratch.numel(),
-                                  ptr(x), ptr(yy) if yy is not None else None, B, ctypes.byref(p),
-                                  current_stream(dev)), 'pc_sample')
+    family, scratch_bytes = (con.family, con.scratch_bytes) if con is not None else ('pc', _Constraint.scratch_bytes)
+    scratch = ops._scratch(getattr(lib(), scratch_bytes)(model._h, B), dev)
+    sample, begin, end = (getattr(lib(), 'csd_%s_%s' % (family, f)) for f in ('sample', 'step_begin', 'step_end'))
+    args = (model._h, ptr(model._packed), ptr(ws), ws.numel(), ptr(scratch), scratch.numel(), ptr(x), ptr(prep.y), B, ctypes.byref(p))
+    if con is not None:
+        args += (ctypes.byref(con.struct),)                 # (prepare refused a y: the constrained families run unconditional networks)
+    if prep.global_norm is None:
+        check(sample(*args, current_stream(dev)), family + '_sample')
     else:
-        reduce_fn, global_batch = global_norm
+        reduce_fn, global_batch = prep.global_norm
         sums = torch.zeros(2, dtype=torch.float32, device=dev)
-        args = (model._h, ptr(model._packed), ptr(ws), ws.numel(), ptr(scratch), scratch.numel(), ptr(x),
-                ptr(yy) if yy is not None else None, B, ctypes.byref(p))
-        for i in range(p_steps):
-            check(lib().csd_pc_step_begin(*args, i, ptr(sums), current_stream(dev)), 'pc_step_begin')
+        for i in range(prep.p_steps):
+            check(begin(*args, i, ptr(sums), current_stream(dev)), family + '_step_begin')
             reduce_fn(sums)
-            check(lib().csd_pc_step_end(*args, i, ptr(sums), int(global_batch), current_stream(dev)), 'pc_step_end')
+            check(end(*args, i, ptr(sums), int(global_batch), current_stream(dev)), family + '_step_end')
     # (prep.keep held the host arrays until the enqueue returned: they are read at enqueue time only)
     return x, prep.rec, prep.ts
 

@@ -160,19 +160,12 @@ def get_pc_inpainter(sde, predictor, corrector, snr, n_steps=1, probability_flow
     from .. import ops
     from ..losses import _bstd
 
-    pred_fn = functools.partial(shared_predictor_update_fn, sde=sde, predictor=predictor, probability_flow=probability_flow,
-                                continuous=continuous)
-    corr_fn = functools.partial(shared_corrector_update_fn, sde=sde, corrector=corrector, continuous=continuous, snr=snr,
-                                n_steps=n_steps)
-
     def blend(a, b, mask):
         """a*(1 - mask) + b*mask = a + (b - a)*mask on the device"""
         from ..grad_ops import _mul
         return ops.axpby(a, _mul(ops.axpby(b, a, 1.0, -1.0), mask))
 
-    def inpaint_update(update_fn, model, data, mask, x, t):
-        vec_t = torch.ones(data.shape[0], device=data.device) * t
-        x, x_mean = update_fn(x, vec_t, model=model)
+    def inpaint_update(data, mask, x, vec_t):
         m, std = _bstd(sde, data, vec_t)                       # mean scale / std of p_t(x | data): [B] host scalars
         mean = data if bool(torch.all(m == 1)) else ops.scale_rows(data, m.to(data.device))
         masked = ops.axpby(mean, ops.scale_rows(torch.randn_like(x), std.to(data.device)))
@@ -180,58 +173,16 @@ def get_pc_inpainter(sde, predictor, corrector, snr, n_steps=1, probability_flow
         x_mean = blend(x, mean, mask)
         return x, x_mean
 
-    def why_not_fused(model):
-        """None when the device loop covers this sampler, else the reason"""
-        from ..models.ddpm import HipUNet
-        if not isinstance(model, HipUNet):
-            return 'the model is a %s, not a HipUNet' % type(model).__name__
-        if getattr(model, 'y_channels', 0) > 0:
-            return 'inpainting uses an unconditional network, this one takes a %d-channel condition' % model.y_channels
-        if n_steps != 1:
-            return 'n_steps = %d corrector steps per update (the device loop runs 1)' % n_steps
-        if isinstance(sde, dict):
-            return 'a single SDE is needed, not an {x, y} pair'
-        pred = NonePredictor if predictor is None else predictor
-        corr = NoneCorrector if corrector is None else corrector
-        if not fused.fusable(model, sde, pred, corr, n_steps, probability_flow, continuous):
-            return 'the device loop does not implement (%s, %s, %s, probability_flow=%s, continuous=%s)' % (
-                type(sde).__name__, pred.__name__, corr.__name__, probability_flow, continuous)
-        if model.device.type != 'cuda':
-            return 'the model is on %s, the device loop runs on the GPU' % model.device
-        return None
-
-    def fused_inpainter(model, data, mask, show_evolution, noise_tape, seed, global_norm):
-        why = why_not_fused(model)
-        if why is not None:
-            raise NotImplementedError('get_pc_inpainter(device_loop=True): ' + why)
-        label = 'fourier' if getattr(model, 'embedding_type', 'positional') == 'fourier' else 'sigma'
-        x, rec, _ = fused.run(model, sde, tuple(data.shape), None, sde.N, snr, eps, denoise, noise_tape=noise_tape, seed=seed,
-                              record=show_evolution, unconditional_label=label, global_norm=global_norm,
-                              predictor=NonePredictor if predictor is None else predictor,
-                              corrector=NoneCorrector if corrector is None else corrector, probability_flow=probability_flow,
-                              continuous=continuous, inpaint=(data, mask))
-        return x, ({'evolution': rec.cpu()} if show_evolution else {})
+    run = _constrained_pc_sampler('get_pc_inpainter', 'inpainting', sde, predictor, corrector, snr, n_steps, probability_flow, continuous,
+                                  denoise, eps, device_loop)
 
     def pc_inpainter(model, data, mask, show_evolution=False, noise_tape=None, seed=None, global_norm=None):
-        if device_loop:
-            return fused_inpainter(model, data, mask, show_evolution, noise_tape, seed, global_norm)
-        for name, value in (('noise_tape', noise_tape), ('seed', seed), ('global_norm', global_norm)):
-            if value is not None:
-                raise NotImplementedError('%s is only available on the device loop: get_pc_inpainter(..., device_loop=True)' % name)
-        with torch.no_grad():
-            data, mask = data.contiguous().float(), mask.contiguous().float()
-            x = blend(sde.prior_sampling(data.shape).to(data.device), data, mask)
-            evolution = [x.cpu()] if show_evolution else None
-            timesteps = torch.linspace(sde.T, eps, sde.N)
-            x_mean = x
-            for i in range(sde.N):
-                t = timesteps[i]
-                x, x_mean = inpaint_update(corr_fn, model, data, mask, x, t)
-                x, x_mean = inpaint_update(pred_fn, model, data, mask, x, t)
-                if show_evolution:
-                    evolution.append(x.cpu())
-            info = {'evolution': torch.stack(evolution)} if show_evolution else {}
-            return (x_mean if denoise else x), info
+        def start(timesteps):
+            d, m = data.contiguous().float(), mask.contiguous().float()
+            x = blend(sde.prior_sampling(d.shape).to(d.device), d, m)
+            return x, lambda x, i, vec_t: inpaint_update(d, m, x, vec_t)
+
+        return run(model, data, {'inpaint': (data, mask)}, start, show_evolution, noise_tape, seed, global_norm)
 
     return pc_inpainter
 
@@ -264,10 +215,41 @@ def get_pc_colorizer(sde, predictor, corrector, snr, n_steps=1, probability_flow
     NotImplementedError naming the reason - there is no silent fall-back to the step-by-step loop."""
     from .. import ops
 
+    def three_channels(model):
+        if getattr(model, 'x_channels', 3) != 3:
+            return 'colorization needs a 3-channel state, this network has %d channels' % model.x_channels
+        return None
+
+    run = _constrained_pc_sampler('get_pc_colorizer', 'colorization', sde, predictor, corrector, snr, n_steps, probability_flow, continuous,
+                                  denoise, eps, device_loop, extra_check=three_channels)
+
+    def pc_colorizer(model, gray_scale_img, show_evolution=False, noise_tape=None, seed=None, global_norm=None):
+        def start(timesteps):
+            gray = gray_scale_img.contiguous().float()
+            gray0 = ops.colorize_gray0(gray)                                  # once per call
+            mean_scale, std = fused.inpaint_tables(sde, timesteps)            # p_t(x | gray) per step: host scalars
+            x = ops.colorize_start(sde.prior_sampling(gray.shape).to(gray.device).float().contiguous(), gray0)
+            return x, lambda x, i, vec_t: ops.colorize_blend(x.contiguous(), gray0, torch.randn_like(x), float(mean_scale[i]),
+                                                             float(std[i]))
+
+        return run(model, gray_scale_img, {'colorize': gray_scale_img}, start, show_evolution, noise_tape, seed, global_norm)
+
+    return pc_colorizer
+
+
+def _constrained_pc_sampler(name, noun, sde, predictor, corrector, snr, n_steps, probability_flow, continuous, denoise, eps, device_loop,
+                            extra_check=lambda model: None):
+    """The PC sampler behind ``get_pc_inpainter`` / ``get_pc_colorizer`` (``name``; ``noun``: what its refusals call the constraint):
+    ``run(model, like, constraint, start, show_evolution, noise_tape, seed, global_norm) -> (x, info)``.  ``like``: the tensor whose
+    shape and device the state takes.  ``constraint``: the keyword ``fused.run`` takes for it on the device loop.  ``start(timesteps)
+    -> (x0, reimpose)``: the step-by-step loop's initial state and its ``reimpose(x, i, vec_t) -> (x, x_mean)`` behind every update of
+    step ``i``, both with the getter's own draws.  ``extra_check(model)``: one more reason the device loop does not cover the model."""
     pred_fn = functools.partial(shared_predictor_update_fn, sde=sde, predictor=predictor, probability_flow=probability_flow,
                                 continuous=continuous)
     corr_fn = functools.partial(shared_corrector_update_fn, sde=sde, corrector=corrector, continuous=continuous, snr=snr,
                                 n_steps=n_steps)
+    pred = NonePredictor if predictor is None else predictor
+    corr = NoneCorrector if corrector is None else corrector
 
     def why_not_fused(model):
         """None when the device loop covers this sampler, else the reason"""
@@ -275,15 +257,14 @@ def get_pc_colorizer(sde, predictor, corrector, snr, n_steps=1, probability_flow
         if not isinstance(model, HipUNet):
             return 'the model is a %s, not a HipUNet' % type(model).__name__
         if getattr(model, 'y_channels', 0) > 0:
-            return 'colorization uses an unconditional network, this one takes a %d-channel condition' % model.y_channels
-        if getattr(model, 'x_channels', 3) != 3:
-            return 'colorization needs a 3-channel state, this network has %d channels' % model.x_channels
+            return '%s uses an unconditional network, this one takes a %d-channel condition' % (noun, model.y_channels)
+        why = extra_check(model)
+        if why is not None:
+            return why
         if n_steps != 1:
             return 'n_steps = %d corrector steps per update (the device loop runs 1)' % n_steps
         if isinstance(sde, dict):
             return 'a single SDE is needed, not an {x, y} pair'
-        pred = NonePredictor if predictor is None else predictor
-        corr = NoneCorrector if corrector is None else corrector
         if not fused.fusable(model, sde, pred, corr, n_steps, probability_flow, continuous):
             return 'the device loop does not implement (%s, %s, %s, probability_flow=%s, continuous=%s)' % (
                 type(sde).__name__, pred.__name__, corr.__name__, probability_flow, continuous)
@@ -291,43 +272,34 @@ def get_pc_colorizer(sde, predictor, corrector, snr, n_steps=1, probability_flow
             return 'the model is on %s, the device loop runs on the GPU' % model.device
         return None
 
-    def fused_colorizer(model, gray, show_evolution, noise_tape, seed, global_norm):
-        why = why_not_fused(model)
-        if why is not None:
-            raise NotImplementedError('get_pc_colorizer(device_loop=True): ' + why)
-        label = 'fourier' if getattr(model, 'embedding_type', 'positional') == 'fourier' else 'sigma'
-        x, rec, _ = fused.run(model, sde, tuple(gray.shape), None, sde.N, snr, eps, denoise, noise_tape=noise_tape, seed=seed,
-                              record=show_evolution, unconditional_label=label, global_norm=global_norm,
-                              predictor=NonePredictor if predictor is None else predictor,
-                              corrector=NoneCorrector if corrector is None else corrector, probability_flow=probability_flow,
-                              continuous=continuous, colorize=gray)
-        return x, ({'evolution': rec.cpu()} if show_evolution else {})
-
-    def pc_colorizer(model, gray_scale_img, show_evolution=False, noise_tape=None, seed=None, global_norm=None):
+    def run(model, like, constraint, start, show_evolution, noise_tape, seed, global_norm):
         if device_loop:
-            return fused_colorizer(model, gray_scale_img, show_evolution, noise_tape, seed, global_norm)
-        for name, value in (('noise_tape', noise_tape), ('seed', seed), ('global_norm', global_norm)):
+            why = why_not_fused(model)
+            if why is not None:
+                raise NotImplementedError('%s(device_loop=True): %s' % (name, why))
+            x, rec, _ = fused.run(model, sde, tuple(like.shape), None, sde.N, snr, eps, denoise, noise_tape=noise_tape, seed=seed,
+                                  record=show_evolution, unconditional_label=fused.unconditional_label(model), global_norm=global_norm,
+                                  predictor=pred, corrector=corr, probability_flow=probability_flow, continuous=continuous, **constraint)
+            return x, ({'evolution': rec.cpu()} if show_evolution else {})
+        for kw, value in (('noise_tape', noise_tape), ('seed', seed), ('global_norm', global_norm)):
             if value is not None:
-                raise NotImplementedError('%s is only available on the device loop: get_pc_colorizer(..., device_loop=True)' % name)
+                raise NotImplementedError('%s is only available on the device loop: %s(..., device_loop=True)' % (kw, name))
         with torch.no_grad():
-            gray = gray_scale_img.contiguous().float()
-            gray0 = ops.colorize_gray0(gray)                                  # once per call
             timesteps = torch.linspace(sde.T, eps, sde.N)
-            mean_scale, std = fused.inpaint_tables(sde, timesteps)            # p_t(x | gray) per step: host scalars
-            x = ops.colorize_start(sde.prior_sampling(gray.shape).to(gray.device).float().contiguous(), gray0)
+            x, reimpose = start(timesteps)
             evolution = [x.cpu()] if show_evolution else None
             x_mean = x
             for i in range(sde.N):
-                vec_t = torch.ones(gray.shape[0], device=gray.device) * timesteps[i]
+                vec_t = torch.ones(like.shape[0], device=like.device) * timesteps[i]
                 for update_fn in (corr_fn, pred_fn):
                     x, _ = update_fn(x, vec_t, model=model)
-                    x, x_mean = ops.colorize_blend(x.contiguous(), gray0, torch.randn_like(x), float(mean_scale[i]), float(std[i]))
+                    x, x_mean = reimpose(x, i, vec_t)
                 if show_evolution:
                     evolution.append(x.cpu())
             info = {'evolution': torch.stack(evolution)} if show_evolution else {}
             return (x_mean if denoise else x), info
 
-    return pc_colorizer
+    return run
 
 
 def shared_predictor_update_fn(x, t, sde, model, predictor, probability_flow, continuous):
@@ -353,9 +325,8 @@ def get_pc_sampler(sde, shape, predictor, corrector, snr, p_steps, c_steps, prob
         steps = p_steps * (c_steps + 1)
         if fused.fusable(model, sde, predictor, corrector, c_steps, probability_flow, continuous):
             # the network's label: sigma(t) or log sigma(t) for the VE SDEs; VP / sub-VP take t*(N-1) whatever is passed here
-            label = 'fourier' if getattr(model, 'embedding_type', 'positional') == 'fourier' else 'sigma'
-            x, rec, ts = fused.run(model, sde, shape, None, p_steps, snr, eps, denoise, noise_tape=noise_tape,
-                                   seed=seed, record=show_evolution, unconditional_label=label, global_norm=global_norm,
+            x, rec, ts = fused.run(model, sde, shape, None, p_steps, snr, eps, denoise, noise_tape=noise_tape, seed=seed,
+                                   record=show_evolution, unconditional_label=fused.unconditional_label(model), global_norm=global_norm,
                                    predictor=predictor, corrector=corrector, probability_flow=probability_flow,
                                    continuous=continuous)
             info = {'times': ts, 'steps': steps}
