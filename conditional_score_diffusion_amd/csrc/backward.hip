@@ -314,11 +314,15 @@ __global__ __launch_bounds__(256) void conv_wgrad4_kernel(const float* x, const 
   }
 }
 
-__global__ void wgrad_reduce_kernel(const float* __restrict__ partial, float* __restrict__ dw, size_t n, int splits) {
+// beta = 1 (the accumulating backward): dw += the fp32 value the overwrite form stores - rounded first, then ONE fp32 addition, which
+// is autograd's p.grad += g.  The old value is read by the thread that stores, once, at the store's width: no other thread touches it.
+__global__ void wgrad_reduce_kernel(const float* __restrict__ partial, float* __restrict__ dw, size_t n, int splits, int beta) {
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+    const float old = beta ? dw[i] : 0.f;         // (issued ahead of the split loop: its latency hides behind the partial reads)
     double s = 0.0;
     for (int k = 0; k < splits; ++k) s += (double)partial[(size_t)k * n + i];
-    dw[i] = (float)s;
+    const float v = (float)s;
+    dw[i] = beta ? old + v : v;
   }
 }
 
@@ -416,6 +420,7 @@ struct GemmDesc {
   int M, N, K;
   long long sam, sak, sbk, sbn, scm, scn, za, zb, zc;
   float alpha;
+  int beta = 0;                                   // 1: C += the fp32 value the overwrite form stores (one fp32 addition, no contraction)
 };
 
 typedef float bg_f16v __attribute__((ext_vector_type(16)));
@@ -461,7 +466,12 @@ __global__ __launch_bounds__(256) void bgemm_kernel(const float* __restrict__ A,
 #pragma unroll
   for (int i = 0; i < 16; ++i) {                  // D[(i/4)*8 + (lane/32)*4 + i%4][lane%32]
     const int gm = m0 + wm + (i >> 2) * 8 + lk * 4 + (i & 3), gn = n0 + wn + li;
-    if (gm < d.M && gn < d.N) Cm[(long long)gm * d.scm + (long long)gn * d.scn] = d.alpha * acc[i];
+    if (gm < d.M && gn < d.N) {
+#pragma clang fp contract(off)                    // (alpha * acc is rounded before the addition: never one fma with the old value)
+      float* c = &Cm[(long long)gm * d.scm + (long long)gn * d.scn];
+      const float v = d.alpha * acc[i];
+      *c = d.beta ? *c + v : v;
+    }
   }
 }
 
@@ -521,7 +531,7 @@ __global__ __launch_bounds__(256) void sum_inner_kernel(const float* __restrict_
 // out[c] = sum_r x[r][c]  (fp64 accumulation, fixed order): 64 columns x 4 row lanes per workgroup, rows r = lane, lane+4, ...
 // (blockIdx.y = 1: the second (x1, out1) pair of the same shape - the dgamma / dbeta rows of one GroupNorm backward in one launch)
 __global__ __launch_bounds__(256) void sum_rows_kernel(const float* __restrict__ x, float* __restrict__ out, int R, int C,
-                                                       const float* __restrict__ x1, float* __restrict__ out1) {
+                                                       const float* __restrict__ x1, float* __restrict__ out1, int beta) {
   if (blockIdx.y) { x = x1; out = out1; }
   __shared__ double sh[4][64];
   const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
@@ -533,7 +543,10 @@ __global__ __launch_bounds__(256) void sum_rows_kernel(const float* __restrict__
   }
   sh[ty][tx] = s;
   __syncthreads();
-  if (ty == 0 && c < C) out[c] = (float)(sh[0][tx] + sh[1][tx] + sh[2][tx] + sh[3][tx]);
+  if (ty == 0 && c < C) {                         // beta = 1: out += the rounded sum (one fp32 addition)
+    const float v = (float)(sh[0][tx] + sh[1][tx] + sh[2][tx] + sh[3][tx]);
+    out[c] = beta ? out[c] + v : v;
+  }
 }
 
 // dy == null: out = act(x);  else out = dy * act'(x)
@@ -615,7 +628,7 @@ extern "C" size_t csd_conv_wgrad_scratch_bytes(int B, int Cin, int Cout, int H, 
 
 // layout CSD_IN_NHWC: x is NHWC [B,H,W,Cin]; CSD_OUT_NHWC: dy is NHWC [B,OH,OW,Cout]; CSD_SPLIT_BF16: split-bf16 arithmetic allowed (else exact fp32)
 static int wgrad_impl(const float* x, const float* dy, float* dw, int B, int Cin, int Cout, int H, int W, int ksize, int stride,
-                      int pad_mode, int up2, int layout, void* scratch, void* stream) {
+                      int pad_mode, int up2, int layout, void* scratch, void* stream, int beta = 0) {
   CSD_REQUIRE(x && dy && dw && scratch, "conv2d_wgrad: null argument");
   CSD_REQUIRE(ksize == 1 || ksize == 3, "conv2d_wgrad: ksize must be 1 or 3");
   CSD_REQUIRE(stride == 1 || stride == 2, "conv2d_wgrad: stride must be 1 or 2");
@@ -654,7 +667,7 @@ static int wgrad_impl(const float* x, const float* dy, float* dw, int B, int Cin
     else if ((rc = csd_zero_insert_odd_nhwc(dyh, ext, B, OH, OW, Cout, s))) return rc;
     if ((rc = wgrad_bf16_launch(up ? ext : xh, up ? dyh : ext, partial2, B, FH, FW, Cin, Cout, 3, S2, per2, s))) return rc;
     const size_t n = (size_t)Cout * Cin * 9;
-    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(ew_grid(n)), dim3(256), 0, s, partial2, dw, n, S2);
+    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(ew_grid(n)), dim3(256), 0, s, partial2, dw, n, S2, beta);
     CSD_LAUNCH_CHECK();
     return CSD_OK;
   }
@@ -662,7 +675,7 @@ static int wgrad_impl(const float* x, const float* dy, float* dw, int B, int Cin
     // split-bf16 operands on the bf16 matrix cores (wgrad_bf16.hip): the fp16 precision modes of the training step
     if ((rc = wgrad_bf16_launch(xh, dyh, partial, B, H, W, Cin, Cout, ksize, S, per, s))) return rc;
     const size_t n = (size_t)Cout * Cin * ksize * ksize;
-    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(ew_grid(n)), dim3(256), 0, s, partial, dw, n, S);
+    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(ew_grid(n)), dim3(256), 0, s, partial, dw, n, S, beta);
     CSD_LAUNCH_CHECK();
     return CSD_OK;
   }
@@ -677,7 +690,7 @@ static int wgrad_impl(const float* x, const float* dy, float* dw, int B, int Cin
                          pad, up, per, n_ci, n_co);
     CSD_LAUNCH_CHECK();
     const size_t n = (size_t)Cout * Cin * ksize * ksize;
-    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(ew_grid(n)), dim3(256), 0, s, partial, dw, n, S);
+    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(ew_grid(n)), dim3(256), 0, s, partial, dw, n, S, beta);
     CSD_LAUNCH_CHECK();
     return CSD_OK;
   }
@@ -691,7 +704,7 @@ static int wgrad_impl(const float* x, const float* dy, float* dw, int B, int Cin
                        pad, up, per, n_ci, n_co);
   CSD_LAUNCH_CHECK();
   const size_t n = (size_t)Cout * Cin * ksize * ksize;
-  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(ew_grid(n)), dim3(256), 0, s, partial, dw, n, S);
+  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(ew_grid(n)), dim3(256), 0, s, partial, dw, n, S, beta);
   CSD_LAUNCH_CHECK();
   return CSD_OK;
 }
@@ -704,6 +717,12 @@ extern "C" int csd_conv2d_wgrad(const float* x, const float* dy, float* dw, int 
 extern "C" int csd_conv2d_wgrad_ex(const float* x, const float* dy, float* dw, int B, int Cin, int Cout, int H, int W,
                                    int ksize, int stride, int pad_mode, int up2, int layout, void* scratch, void* stream) {
   return wgrad_impl(x, dy, dw, B, Cin, Cout, H, W, ksize, stride, pad_mode, up2, layout, scratch, stream);
+}
+
+// csd_conv2d_wgrad_ex with dw (=|+=): beta = 1 adds the gradient to what dw holds (the accumulating planned backward)
+int csd::conv2d_wgrad_beta(const float* x, const float* dy, float* dw, int B, int Cin, int Cout, int H, int W, int ksize, int stride,
+                           int pad_mode, int up2, int layout, void* scratch, void* stream, int beta) {
+  return wgrad_impl(x, dy, dw, B, Cin, Cout, H, W, ksize, stride, pad_mode, up2, layout, scratch, stream, beta);
 }
 
 extern "C" int csd_groupnorm_act_backward(const float* x, const float* gamma, const float* beta, const float* dy, float* dx,
@@ -723,6 +742,13 @@ extern "C" int csd_bgemm(const float* A, const float* Bm, float* Cm, int M, int 
   CSD_REQUIRE(A && Bm && Cm && M > 0 && N > 0 && K > 0 && batch > 0, "bgemm: bad arguments");
   GemmDesc d{M, N, K, sam, sak, sbk, sbn, scm, scn, za, zb, zc, alpha};
   return bgemm_launch(A, Bm, Cm, d, batch, (hipStream_t)stream);
+}
+
+int csd::bgemm_beta(const float* A, const float* Bm, float* Cm, int M, int N, int K, int64_t sam, int64_t sak, int64_t sbk, int64_t sbn,
+                    int64_t scm, int64_t scn, float alpha, int beta, void* stream) {
+  CSD_REQUIRE(A && Bm && Cm && M > 0 && N > 0 && K > 0, "bgemm: bad arguments");
+  GemmDesc d{M, N, K, sam, sak, sbk, sbn, scm, scn, 0, 0, 0, alpha, beta};
+  return bgemm_launch(A, Bm, Cm, d, 1, (hipStream_t)stream);
 }
 
 // scratch of the attention backward: the probabilities P [B, L, L] | their gradient dP
@@ -800,16 +826,18 @@ extern "C" int csd_sum_inner(const float* x, float* out, int64_t rows, int64_t i
   return CSD_OK;
 }
 
-extern "C" int csd_sum_rows(const float* x, float* out, int R, int C, void* stream) {
+extern "C" int csd_sum_rows(const float* x, float* out, int R, int C, void* stream) { return csd::sum_rows_beta(x, out, R, C, 0, stream); }
+
+int csd::sum_rows_beta(const float* x, float* out, int R, int C, int beta, void* stream) {
   CSD_REQUIRE(x && out && R > 0 && C > 0, "sum_rows: bad arguments");
-  hipLaunchKernelGGL(sum_rows_kernel, dim3(cdiv(C, 64)), dim3(256), 0, (hipStream_t)stream, x, out, R, C, nullptr, nullptr);
+  hipLaunchKernelGGL(sum_rows_kernel, dim3(cdiv(C, 64)), dim3(256), 0, (hipStream_t)stream, x, out, R, C, nullptr, nullptr, beta);
   CSD_LAUNCH_CHECK();
   return CSD_OK;
 }
 
-int csd::sum_rows2(const float* x0, float* out0, const float* x1, float* out1, int R, int C, void* stream) {
+int csd::sum_rows2(const float* x0, float* out0, const float* x1, float* out1, int R, int C, void* stream, int beta) {
   CSD_REQUIRE(x0 && out0 && x1 && out1 && R > 0 && C > 0, "sum_rows2: bad arguments");
-  hipLaunchKernelGGL(sum_rows_kernel, dim3(cdiv(C, 64), 2), dim3(256), 0, (hipStream_t)stream, x0, out0, R, C, x1, out1);
+  hipLaunchKernelGGL(sum_rows_kernel, dim3(cdiv(C, 64), 2), dim3(256), 0, (hipStream_t)stream, x0, out0, R, C, x1, out1, beta);
   CSD_LAUNCH_CHECK();
   return CSD_OK;
 }

@@ -361,8 +361,16 @@ int gn_finalize_tiles_launch(const double* p0, int tpi0, int C0, const double* p
 int gn_apply_launch(const float* x, const float* nscale, const float* nshift, float* y, int B, int HW,
                     int C, int act, hipStream_t s, float* mask = nullptr, float p_drop = 0.f, uint64_t seed = 0, uint64_t stream_id = 0,
                     void* hi = nullptr, void* lo = nullptr);
+// the final writers of the planned backward's parameter gradients take `beta`: 0 stores the gradient (the C ABI's form), 1 adds it to what
+// the slot holds - the fp32 value the store would have written, rounded first, then ONE fp32 addition (csd_unet_backward_acc)
 // two csd_sum_rows of one shape in one launch (backward.hip)
-int sum_rows2(const float* x0, float* out0, const float* x1, float* out1, int R, int C, void* stream);
+int sum_rows2(const float* x0, float* out0, const float* x1, float* out1, int R, int C, void* stream, int beta = 0);
+int sum_rows_beta(const float* x, float* out, int R, int C, int beta, void* stream);
+// csd_conv2d_wgrad_ex / one csd_bgemm (batch 1) with beta (backward.hip)
+int conv2d_wgrad_beta(const float* x, const float* dy, float* dw, int B, int Cin, int Cout, int H, int W, int ksize, int stride,
+                      int pad_mode, int up2, int layout, void* scratch, void* stream, int beta);
+int bgemm_beta(const float* A, const float* Bm, float* Cm, int M, int N, int K, int64_t sam, int64_t sak, int64_t sbk, int64_t sbn,
+               int64_t scm, int64_t scn, float alpha, int beta, void* stream);
 // csd_groupnorm_act_nhwc with the training forward's dropout fused into the apply pass (train_nhwc.hip)
 int groupnorm_act_dropout_nhwc(const float* x, const float* gamma, const float* beta, float* y, float* rs, float* ms, float* mask,
                                float p_drop, uint64_t seed, uint64_t stream_id, int B, int C, int HW, int groups, float eps, int act,
@@ -405,7 +413,7 @@ int fir_pyr_dgrad_launch(const float* dy, const float* gt, float* dx, int64_t db
 int fir_pyr_wgrad_slices(int B, int Cin, int Cout);
 size_t fir_pyr_wgrad_scratch_floats(int B, int Cin, int Cout);
 int fir_pyr_wgrad_launch(const float* x, int64_t sb, int sp, int64_t sc, int B, int H, int Cin, const float* dy, int Cout, const float* taps4,
-                         bool fir, float* dw, float* scratch, hipStream_t s);
+                         bool fir, float* dw, float* scratch, hipStream_t s, int beta = 0);
 int fourier_embedding_launch(const float* t, const float* W, float* out, int B, int E, hipStream_t s);
 // per-operator convolution of the C ABI (ops_api.hip) with an optional NHWC residual added in the epilogue; GroupNorm backward with
 // an optional addend (train_nhwc.hip): the fused forms the planned training graph (train_graph.h) uses

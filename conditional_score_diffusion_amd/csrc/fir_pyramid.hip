@@ -245,7 +245,7 @@ __global__ void fir_pyr_wgrad_kernel(const float* __restrict__ x, int64_t sb, in
 
 // weight gradient, stage 2: dW[o, c, a, b] (=|+=) sum_{u, v} (sum_sl part) * k2[a + 3 - u][b + 3 - v]  (fixed order, fp64)
 __global__ void fir_pyr_unfold_kernel(const float* __restrict__ part, int nsl, int Cin, int Cout, PyrTaps k, double inv_s2,
-                                      float* __restrict__ dw) {
+                                      float* __restrict__ dw, int beta) {
   const int64_t n = (int64_t)Cout * Cin * 9;
   for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < n; e += (int64_t)gridDim.x * blockDim.x) {
     const int ab = (int)(e % 9);
@@ -266,7 +266,8 @@ __global__ void fir_pyr_unfold_kernel(const float* __restrict__ part, int nsl, i
         acc += s * kk;
       }
     }
-    dw[e] = (float)acc;
+    const float v = (float)acc;                  // beta = 1: dw += the rounded value (one fp32 addition)
+    dw[e] = beta ? dw[e] + v : v;
   }
 }
 
@@ -328,7 +329,7 @@ int fir_pyr_wgrad_slices(int B, int Cin, int Cout) {
 size_t fir_pyr_wgrad_scratch_floats(int B, int Cin, int Cout) { return (size_t)fir_pyr_wgrad_slices(B, Cin, Cout) * 36 * Cin * Cout; }
 
 int fir_pyr_wgrad_launch(const float* x, int64_t sb, int sp, int64_t sc, int B, int H, int Cin, const float* dy, int Cout, const float* taps4,
-                         bool fir, float* dw, float* scratch, hipStream_t s) {
+                         bool fir, float* dw, float* scratch, hipStream_t s, int beta) {
   const int nsl = fir_pyr_wgrad_slices(B, Cin, Cout);
   const int64_t n = (int64_t)nsl * Cin * Cout;
   if (fir)
@@ -338,7 +339,7 @@ int fir_pyr_wgrad_launch(const float* x, int64_t sb, int sp, int64_t sc, int B, 
   CSD_LAUNCH_CHECK();
   double inv_s2;
   const PyrTaps k = pyr_taps(fir ? taps4 : nullptr, &inv_s2);
-  hipLaunchKernelGGL(fir_pyr_unfold_kernel, dim3(pyr_grid((int64_t)Cout * Cin * 9)), dim3(256), 0, s, scratch, nsl, Cin, Cout, k, inv_s2, dw);
+  hipLaunchKernelGGL(fir_pyr_unfold_kernel, dim3(pyr_grid((int64_t)Cout * Cin * 9)), dim3(256), 0, s, scratch, nsl, Cin, Cout, k, inv_s2, dw, beta);
   CSD_LAUNCH_CHECK();
   return CSD_OK;
 }

@@ -48,6 +48,7 @@ struct TConv {
   int layout = NHWC;            // conv: | CSD_WEIGHT_T for a data gradient (wgrad adds CSD_SPLIT_BF16 by the precision)
   const float *res = nullptr, *temb = nullptr;      // conv: NHWC tensor / per-sample [B, Cout] row added in the epilogue
   const void* planes = nullptr; // conv: the operand's fp16 planes (conv2d_operand_planes)
+  bool temp = false;            // wgrad: dw is a temporary of the backward, not a parameter slot: stored, also by an accumulating backward
 };
 static const char* const QKV_W[3] = {"NIN_0.W", "NIN_1.W", "NIN_2.W"};      // the attention block's q, k, v projections
 static const char* const QKV_B[3] = {"NIN_0.b", "NIN_1.b", "NIN_2.b"};
@@ -129,13 +130,15 @@ __global__ void split_c_kernel(const float4* __restrict__ in, int ca4, int cb4, 
   }
 }
 
-// rows of `width` floats: dst[r*dpitch + j] = src[r*spitch + j]   (q|k|v weight concatenation and its inverse)
-__global__ void copy2d_kernel(const float* __restrict__ src, int spitch, float* __restrict__ dst, int dpitch, int width, int rows) {
+// rows of `width` floats: dst[r*dpitch + j] (=|+=) src[r*spitch + j]   (q|k|v weight concatenation and its inverse; beta = 1: the
+// accumulating backward's scatter of the concatenated gradient into the three parameter slots)
+__global__ void copy2d_kernel(const float* __restrict__ src, int spitch, float* __restrict__ dst, int dpitch, int width, int rows, int beta) {
   const size_t n = (size_t)width * rows;
   for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
     const size_t r = i / width;
     const int j = (int)(i - r * width);
-    dst[r * dpitch + j] = src[r * spitch + j];
+    const float v = src[r * spitch + j];
+    dst[r * dpitch + j] = beta ? dst[r * dpitch + j] + v : v;
   }
 }
 
@@ -167,6 +170,7 @@ struct TG {
   GradMarks* gm = nullptr;      // backward only
   size_t gm_next = 0;
   bool pg = true;               // backward: parameter gradients wanted (false: csd_unet_backward_ex with grads == NULL)
+  int gacc = 0;                 // backward: 1 = every parameter slot G[i] += its gradient (csd_unet_backward_acc), 0 = G[i] = its gradient
   bool want_dx = false;         // backward: d loss / d x wanted (d_x = the caller's [B, x_channels, S, S] NCHW buffer)
   float* d_x = nullptr;
   float* dpyr = nullptr;        // NCSN++ input pyramid: x-channel gradient [B, cx, side, side] NCHW of the finest level combined so far
@@ -219,8 +223,8 @@ struct TG {
     if (!pg) return CSD_OK;
     const size_t m = top;
     float* sc = alloc_bytes(csd_conv_wgrad_scratch_bytes(B, Cin, Cout, H, H, a.k, a.stride, a.up2));
-    TG_RUN(csd_conv2d_wgrad_ex(x, dy, dw, B, Cin, Cout, H, H, a.k, a.stride, a.dpad, a.up2,
-                               a.layout | (prec == CSD_PREC_F32 ? 0 : CSD_SPLIT_BF16), sc, s));
+    TG_RUN(conv2d_wgrad_beta(x, dy, dw, B, Cin, Cout, H, H, a.k, a.stride, a.dpad, a.up2,
+                             a.layout | (prec == CSD_PREC_F32 ? 0 : CSD_SPLIT_BF16), sc, s, a.temp ? 0 : gacc));
     top = m;
     return CSD_OK;
   }
@@ -243,7 +247,7 @@ struct TG {
     float* brow = alloc((size_t)B * C);
     float* sc = alloc_bytes(csd_groupnorm_nhwc_scratch_bytes(B, C, H * H));
     TG_RUN(groupnorm_act_backward_nhwc_add(x, gamma, beta, rs, ms, dy, add, dx, grow, brow, C, B, C, H * H, G_of(C), a, sc, s));
-    if (pg) TG_RUN(sum_rows2(grow, dgamma, brow, dbeta, B, C, s));
+    if (pg) TG_RUN(sum_rows2(grow, dgamma, brow, dbeta, B, C, s, gacc));
     top = m;
     return CSD_OK;
   }
@@ -259,13 +263,14 @@ struct TG {
     top = m;
     return CSD_OK;
   }
-  int bias_grad(const float* dy, float* db, int C, int H) {          // conv bias: batch + pixel sum of an NHWC gradient
+  // conv bias: batch + pixel sum of an NHWC gradient (temp: db is a temporary of the backward, as TConv::temp)
+  int bias_grad(const float* dy, float* db, int C, int H, bool temp = false) {
     if (!pg) return CSD_OK;
     const size_t m = top;
     float* bc = alloc((size_t)B * C);
     int rc = sum_pixels(dy, bc, C, H);
     if (rc) return rc;
-    TG_RUN(csd_sum_rows(bc, db, B, C, s));
+    TG_RUN(sum_rows_beta(bc, db, B, C, temp ? 0 : gacc, s));
     top = m;
     return CSD_OK;
   }
@@ -402,7 +407,7 @@ struct TG {
   // the q | k | v weight of ONE contraction, [NIN_0.W | NIN_1.W | NIN_2.W] ([C, 3C]) into wc, and (bc != null) its bias [3C] into bc
   int qkv_weight(int mod, int C, float* wc, float* bc) {
     for (int j = 0; j < 3 && !dry; ++j) {
-      hipLaunchKernelGGL(copy2d_kernel, dim3(launch_blocks((size_t)C * C)), dim3(256), 0, s, W(mod, QKV_W[j]), C, wc + j * C, 3 * C, C, C);
+      hipLaunchKernelGGL(copy2d_kernel, dim3(launch_blocks((size_t)C * C)), dim3(256), 0, s, W(mod, QKV_W[j]), C, wc + j * C, 3 * C, C, C, 0);
       CSD_LAUNCH_CHECK();
       if (bc) TG_RUN(copy(W(mod, QKV_B[j]), bc + j * C, C));
     }
@@ -649,8 +654,8 @@ struct TG {
       TG_RUN(csd_act(x, nullptr, ax, act_in, (int64_t)B * K, s));
       a = ax;
     }
-    TG_RUN(csd_bgemm(dy, a, dw, N, K, B, 1, N, K, 1, K, 1, 1, 0, 0, 0, 1.f, s));         // dW[n,k] = sum_b dy[b,n] a[b,k]
-    TG_RUN(csd_sum_rows(dy, db, B, N, s));
+    TG_RUN(bgemm_beta(dy, a, dw, N, K, B, 1, N, K, 1, K, 1, 1.f, gacc, s));              // dW[n,k] (=|+=) sum_b dy[b,n] a[b,k]
+    TG_RUN(sum_rows_beta(dy, db, B, N, gacc, s));
     if (dact_acc) {
       float* da = alloc((size_t)B * K);
       TG_RUN(csd_bgemm(dy, w, da, B, K, N, N, 1, K, 1, K, 1, 1, 0, 0, 0, 1.f, s));       // da[b,k] = sum_n dy[b,n] W[n,k]
@@ -693,7 +698,7 @@ struct TG {
     if (pg) {
       float* dd = alloc((size_t)B * cout);
       rc = sum_pixels(d1, dd, cout, Ho); if (rc) return rc;
-      TG_RUN(csd_sum_rows(dd, DW(m.idx, "Conv_0.bias"), B, cout, s));
+      TG_RUN(sum_rows_beta(dd, DW(m.idx, "Conv_0.bias"), B, cout, gacc, s));
       if (f.dense) {
         rc = linear_bwd(st.temb2_act, CSD_ACT_NONE, W(m.idx, "Dense_0.weight"), dd, DW(m.idx, "Dense_0.weight"), DW(m.idx, "Dense_0.bias"), dtemb_act,
                         4 * n.cfg.nf, cout);
@@ -744,7 +749,7 @@ struct TG {
     if (pg) {                                        // bias: NCHW gradient -> per-(sample, channel) sums -> batch sum
       float* bc = alloc((size_t)B * Co);
       TG_RUN(csd_sum_inner(dP, bc, (int64_t)B * Co, (int64_t)H * H, s));
-      TG_RUN(csd_sum_rows(bc, DW(mc.idx, "bias"), B, Co, s));
+      TG_RUN(sum_rows_beta(bc, DW(mc.idx, "bias"), B, Co, gacc, s));
     }
     float* dg = alloc(act_n(H, C));
     rc = conv(dP, W(mc.idx, "weight"), nullptr, dg, Co, C, H, {.layout = CSD_OUT_NHWC | CSD_WEIGHT_T}); if (rc) return rc;      // NCHW in
@@ -788,13 +793,18 @@ struct TG {
     float* wc = alloc((size_t)C * 3 * C);
     float* dwc = alloc((size_t)C * 3 * C);
     float* dbc = alloc(3 * C);
-    rc = wgrad(dqkv, sp.op0, dwc, 3 * C, C, H, {.k = 1}); if (rc) return rc;           // dW[i, o] with o over 3C
-    rc = bias_grad(dqkv, dbc, 3 * C, H); if (rc) return rc;
+    rc = wgrad(dqkv, sp.op0, dwc, 3 * C, C, H, {.k = 1, .temp = true}); if (rc) return rc;      // dW[i, o] with o over 3C
+    rc = bias_grad(dqkv, dbc, 3 * C, H, true); if (rc) return rc;
     rc = qkv_weight(m.idx, C, wc, nullptr); if (rc) return rc;
     for (int j = 0; j < 3 && !dry && pg; ++j) {
-      hipLaunchKernelGGL(copy2d_kernel, dim3(launch_blocks((size_t)C * C)), dim3(256), 0, s, dwc + j * C, 3 * C, DW(m.idx, QKV_W[j]), C, C, C);
+      hipLaunchKernelGGL(copy2d_kernel, dim3(launch_blocks((size_t)C * C)), dim3(256), 0, s, dwc + j * C, 3 * C, DW(m.idx, QKV_W[j]), C, C, C, gacc);
       CSD_LAUNCH_CHECK();
-      TG_RUN(copy(dbc + j * C, DW(m.idx, QKV_B[j]), C));
+      if (gacc) {                                    // (the bias slice: one row of the same kernel; the overwrite form stays a device copy)
+        hipLaunchKernelGGL(copy2d_kernel, dim3(launch_blocks((size_t)C)), dim3(256), 0, s, dbc + j * C, C, DW(m.idx, QKV_B[j]), C, C, 1, 1);
+        CSD_LAUNCH_CHECK();
+      } else {
+        TG_RUN(copy(dbc + j * C, DW(m.idx, QKV_B[j]), C));
+      }
     }
     rc = conv(dqkv, wc, nullptr, da, 3 * C, C, H, {.k = 1}); if (rc) return rc;    // dt = dqkv . Wcat^T (Wcat read as OIHW [C, 3C])
     rc = gn_bwd(h, W(m.idx, "GroupNorm_0.weight"), W(m.idx, "GroupNorm_0.bias"), sp.rs0, sp.ms0, da, dh, DW(m.idx, "GroupNorm_0.weight"),
@@ -942,7 +952,7 @@ struct TG {
           rc = bias_grad(dh, DW(m.idx, pyr_sub(c, true)), C, side); if (rc) return rc;
           if (pg) {
             float* part = alloc(fir_pyr_wgrad_scratch_floats(B, Cin, C));
-            TG_RUN(fir_pyr_wgrad_launch(ps.p, ps.sb, ps.sp, ps.sc, B, Hs, Cin, dh, C, pyr_taps(), fir, DW(m.idx, pyr_sub(c, false)), part, s));
+            TG_RUN(fir_pyr_wgrad_launch(ps.p, ps.sb, ps.sp, ps.sc, B, Hs, Cin, dh, C, pyr_taps(), fir, DW(m.idx, pyr_sub(c, false)), part, s, gacc));
           }
           if (dsrc || (sp.in1 < 0 && want_dx)) {
             float* gt = alloc((size_t)36 * Cin * C);
@@ -1026,7 +1036,9 @@ struct TG {
       float* d1 = alloc((size_t)B * 4 * nf);
       TG_RUN(csd_act(st.temb1, dact1, d1, act, (int64_t)B * 4 * nf, s));
       rc = linear_bwd(st.emb, CSD_ACT_NONE, W(l0, "weight"), d1, DW(l0, "weight"), DW(l0, "bias"), nullptr, st.emb_dim, 4 * nf); if (rc) return rc;
-      if (st.fourier_mod >= 0 && !dry)               // the Fourier W is a fixed buffer of the reference (requires_grad = False): its slot reads zero
+      // the Fourier W is a fixed buffer of the reference (requires_grad = False): its slot reads zero - and an accumulating backward adds
+      // that zero: the slot is left as it is
+      if (st.fourier_mod >= 0 && !dry && !gacc)
         CSD_CHECK_HIP(hipMemsetAsync(DW(st.fourier_mod, "W"), 0, (size_t)nf * sizeof(float), s));
       top = mk;
     }
@@ -1109,8 +1121,17 @@ extern "C" int csd_unet_backward(csd_unet* net, const float* const* params, floa
 
 extern "C" int csd_unet_backward_ex(csd_unet* net, const float* const* params, float* const* grads, float* d_x, void* workspace,
                                     size_t workspace_bytes, const float* d_out, int B, uint64_t call_index, void* stream) {
+  return csd_unet_backward_acc(net, params, grads, d_x, workspace, workspace_bytes, d_out, B, call_index, 0, 1, stream);
+}
+
+extern "C" int csd_unet_backward_acc(csd_unet* net, const float* const* params, float* const* grads, float* d_x, void* workspace,
+                                     size_t workspace_bytes, const float* d_out, int B, uint64_t call_index, int accumulate,
+                                     int record_marks, void* stream) {
   int rc = train_check(net);
   if (rc) return rc;
+  CSD_REQUIRE((accumulate == 0 || accumulate == 1) && (record_marks == 0 || record_marks == 1),
+              "backward_acc: accumulate (%d) and record_marks (%d) are 0 or 1", accumulate, record_marks);
+  CSD_REQUIRE(!accumulate || grads, "backward_acc: accumulate = 1 needs parameter gradients (grads) to add to");
   CSD_REQUIRE(params && workspace && d_out, "backward: null argument");
   CSD_REQUIRE(grads || d_x, "backward_ex: neither parameter gradients (grads) nor the input gradient (d_x) requested");
   if (d_x) {
@@ -1140,9 +1161,10 @@ extern "C" int csd_unet_backward_ex(csd_unet* net, const float* const* params, f
   for (auto& t : st.t) t.g = nullptr;
   TG g(net->net, st, B, (hipStream_t)stream, false, params, grads, static_cast<float*>(workspace));
   g.pg = grads != nullptr;
+  g.gacc = accumulate;
   g.want_dx = d_x != nullptr;
   g.d_x = d_x;
-  if (g.pg) {                                        // (the gradient-ready marks describe parameter gradients: none without them)
+  if (g.pg && record_marks) {                                        // (the gradient-ready marks describe parameter gradients: none without them)
     std::lock_guard<std::mutex> lk(g_train_mu);
     auto it = g_marks.find(&net->net);
     g.gm = it == g_marks.end() ? nullptr : &it->second;

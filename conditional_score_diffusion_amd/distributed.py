@@ -171,6 +171,7 @@ class GradSync:
         self._launched = [False] * len(self.buckets)
         self._handles = []
         self._closed = False
+        self._held = False          # hold(): a micro-batch of a gradient-accumulation window that is not the last
         self._hook_handles = []     # removed by close(): a GradSync that is replaced must not keep reducing the shared buffer
         if self.grouped:
             for i, p in enumerate(flat.params):
@@ -246,9 +247,15 @@ class GradSync:
             return loss * (float(local_n) / float(global_n))
         return loss if self.world == 1 else loss / self.world
 
+    def hold(self, held=True):
+        """Gradient accumulation (DDP's ``no_sync``): while held, a backward only adds to the flat gradient - the hooks neither count
+        nor launch and ``finish()`` is not to be called.  The window's last backward runs released: its hooks (operator executors,
+        3-D) or its gradient-ready events (planned graph: only that backward records them) launch every bucket exactly once."""
+        self._held = bool(held)
+
     def _make_hook(self, i):
         def hook(param):
-            if self._closed:
+            if self._closed or self._held:
                 return
             if getattr(self, '_events', None):        # planned graph: nothing was accumulated (the hook fires for an undefined
                 return                                # gradient too); finish() launches every bucket from its gradient-ready event
@@ -265,6 +272,8 @@ class GradSync:
 
     def finish(self):
         """Call after ``backward``: every bucket reduced, the flat gradient holds the global mean."""
+        if self._held:
+            raise RuntimeError('GradSync.finish() while held: release the hold (hold(False)) before the last backward of the window')
         if self.grouped:
             ev = getattr(self, '_events', None)
             if ev and not any(self._launched):

@@ -514,9 +514,14 @@ class _PlannedNet(torch.autograd.Function):
         gtable = (ctypes.c_void_p * len(grads))(*[g.data_ptr() for g in grads])
         # d loss / d x from the same call when autograd asks for it (csd_unet_backward_ex: the parameter gradients are unchanged)
         dx = ops._out(model._x_shape(B), torch.float32, dout.device) if ctx.needs_input_grad[1] else None
-        check(lib().csd_unet_backward_ex(model._h, ctx.table, gtable, ptr(dx), ptr(ctx.ws), ctx.ws.numel(), ptr(dout), B, ctx.call,
-                                         current_stream(dout.device)), 'unet_backward')
-        if ctx.fin is not None:          # (the backward releases the workspace itself; the finalizer of this context must not fire later)
+        # gradient accumulation (train.Trainer sets both before each backward of a window; absent: one backward per step, as ever):
+        # in direct mode the kernels ADD to the .grad views from the window's second micro-batch on, and only the window's last
+        # backward records the gradient-ready events.  Off direct mode autograd accumulates the returned gradients itself.
+        acc = 1 if direct and getattr(model, 'grad_accumulate', False) else 0
+        marks = 1 if getattr(model, 'grad_marks', True) else 0
+        check(lib().csd_unet_backward_acc(model._h, ctx.table, gtable, ptr(dx), ptr(ctx.ws), ctx.ws.numel(), ptr(dout), B, ctx.call,
+                                          acc, marks, current_stream(dout.device)), 'unet_backward')
+        if ctx.fin is not None:         # (the backward releases the workspace itself; the finalizer of this context must not fire later)
             ctx.fin.detach()
             _release_shared_ws(lambda: model, ctx.call)
         if direct:

@@ -13,6 +13,10 @@ Replaces ``BaseSdeGenerativeModel.training_step`` / ``configure_optimizers`` (li
   is launched on a communication stream that waits for its own event only.  (Measured on ONE GPU only: the event order and the
   gradients are tested, the overlap itself has never run on more than one device.)
 * ONE fused kernel applies clipping + Adam + EMA (optim.FusedAdam / csd_adam_step).
+* ``config.training.accumulate_grad_batches = k`` (run_lib.py:58,68,98: Lightning's gradient accumulation): one ``train_step`` call is
+  one micro-batch, its loss scaled by 1 / k; the gradients of k micro-batches are summed - on the planned graph by the backward
+  kernels themselves (csd_unet_backward_acc adds to the flat buffer's views), elsewhere by autograd - the all-reduce is held back
+  (DDP's no_sync) until the k-th, and clip + Adam + EMA run once per window.
 """
 import torch
 
@@ -52,6 +56,12 @@ class Trainer:
             model.grad_sink = True
             self.sync.attach_planned(model)           # per-bucket gradient-ready events: the all-reduce overlaps the backward
         self.step = 0                     # completed optimizer steps (the warm-up factor of step k is k / warmup)
+        t = config.training
+        has_t = (lambda k: k in t) if hasattr(t, '__contains__') else (lambda k: hasattr(t, k))
+        self.accumulate = int(t.accumulate_grad_batches) if has_t('accumulate_grad_batches') else 1
+        if self.accumulate < 1:
+            raise ValueError('training.accumulate_grad_batches must be >= 1, got %r' % (t.accumulate_grad_batches,))
+        self.pending = 0                  # micro-batches accumulated in the flat gradient since the last optimizer step
 
     def close(self):
         """retire the gradient synchronisation: autograd hooks removed, gradient-ready events destroyed, the network handle's marks
@@ -85,25 +95,59 @@ class Trainer:
     def train_step(self, batch, global_n=None):
         """-> detached loss of this rank's shard.  ``batch`` is the loss_fn's: ``x`` or ``(y, x)``.  ``global_n``: images of the GLOBAL
         batch when the shards are ragged (a global batch that does not divide by the world size, distributed.shard_bounds): the
-        rank's mean loss is then weighted by its share of the images instead of 1 / world."""
+        rank's mean loss is then weighted by its share of the images instead of 1 / world.
+
+        With ``training.accumulate_grad_batches = k > 1`` one call is one MICRO-batch, as in Lightning: the (unscaled) loss of the
+        micro-batch is returned, its gradient joins the window's with weight 1 / k, and the optimizer steps on every k-th call
+        (``self.step`` counts optimizer steps: warm-up and the VS-CMDE schedule are constant within a window, like Lightning's
+        ``global_step``; the dropout streams advance per micro-batch).  ``global_n`` is then the global MICRO-batch."""
+        k = self.accumulate
         if self._vs is not None:
             self.reconfigure_conditioning_sde()
-        self.optimizer.zero_grad()
+        if self.pending == 0:
+            self.optimizer.zero_grad()
+        if k > 1:
+            # the planned backward adds to the .grad views from the window's second micro-batch on and records its gradient-ready
+            # events on the last one only; until then the all-reduce is held back (hooks and events alike)
+            self.model.grad_accumulate = self.pending > 0
+            self.model.grad_marks = self.pending + 1 == k
+            self.sync.hold(self.pending + 1 < k)
         loss = self.loss_fn(self.model, batch)
         if global_n:
             first = batch[0] if isinstance(batch, (tuple, list)) else batch
-            self.sync.scale_loss(loss, local_n=first.shape[0], global_n=global_n).backward()
+            scaled = self.sync.scale_loss(loss, local_n=first.shape[0], global_n=global_n)
         else:
-            self.sync.scale_loss(loss).backward()
+            scaled = self.sync.scale_loss(loss)
+        (scaled if k == 1 else scaled / k).backward()
+        self.pending += 1
+        if self.pending == k:
+            self._optimizer_step()
+        return loss.detach()
+
+    def flush(self):
+        """End of an epoch inside a window (Lightning steps with what has accumulated, without rescaling): -> True if it stepped."""
+        if self.pending == 0:
+            return False
+        self._optimizer_step()
+        return True
+
+    def _optimizer_step(self):
+        if self.accumulate > 1:
+            self.sync.hold(False)
+            self.model.grad_accumulate, self.model.grad_marks = False, True
+        self.pending = 0
         self.sync.finish()
         # Lightning's gradient_clip_val (run_lib.py:58-59): 0 disables; losses.optimization_manager: negative disables
         clip = float(self.config.optim.grad_clip)
         self.optimize_fn(self.optimizer, self.flat.params, self.step, grad_clip=clip if clip > 0 else -1.0, ema=self.ema)
         self.step += 1
-        return loss.detach()
 
     # -- checkpoint / resume (Lightning keeps the same pieces in its .ckpt: state_dict, optimizer_states, the EMA callback state) --
     def state_dict(self):
+        if self.pending:
+            raise RuntimeError('Trainer.state_dict() inside a gradient-accumulation window (%d of %d micro-batches accumulated): the '
+                               'partial gradient is not part of a checkpoint; save after the window\'s last train_step or after flush()'
+                               % (self.pending, self.accumulate))
         return {'model': {k: v.detach().clone() for k, v in self.model.state_dict().items()},
                 'optimizer': {k: (v.clone() if torch.is_tensor(v) else v) for k, v in self.optimizer.state_dict().items()},
                 'ema': {k: (v.clone() if torch.is_tensor(v) else v) for k, v in self.ema.state_dict().items()},

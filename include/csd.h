@@ -698,7 +698,8 @@ int csd_attention_backward_nhwc(const float* qkv, const float* dout, float* dqkv
  * models/ddpm.py:149-213 + models/layers.py:524-675 in `model.train()` mode, run_lib.py:55-73).
  *   csd_unet_train_forward: the forward with nn.Dropout(dropout_p) active (mask = Philox keyed by (dropout_seed,
  *     (call_index << 16) + running dropout index), models/layers.py:647,662); every tensor a gradient needs stays in `workspace`.
- *   csd_unet_backward: given d loss / d out ([B, out_channels, S, S]), writes d loss / d parameter i to grads[i] (overwrite).
+ *   csd_unet_backward: given d loss / d out ([B, out_channels, S, S]), writes d loss / d parameter i to grads[i] (overwrite; csd_unet_backward_acc
+ *     below adds instead).
  * params[i] / grads[i]: device pointers of parameter i in csd_unet_param_info order and layout (fp32, 16-byte aligned).
  * One backward per forward, same handle / workspace / B / call_index; the workspace must not be touched in between: a second
  * forward into the same workspace before the backward makes that backward fail with CSD_ERR_STATE (it names the first forward's
@@ -722,6 +723,18 @@ int csd_unet_backward(csd_unet* net, const float* const* params, float* const* g
  * depend on it - and, at level 0, into d_x). */
 int csd_unet_backward_ex(csd_unet* net, const float* const* params, float* const* grads, float* d_x, void* workspace,
                          size_t workspace_bytes, const float* d_out, int B, uint64_t call_index, void* stream);
+/* csd_unet_backward_acc: csd_unet_backward_ex for gradient accumulation over micro-batches (Lightning's accumulate_grad_batches,
+ * run_lib.py:58,68,98).  csd_unet_backward_ex(...) is csd_unet_backward_acc(..., accumulate = 0, record_marks = 1).
+ *   accumulate = 1: grads[i] = grads[i] + v for every parameter, v bit for bit the fp32 value the overwrite form stores (a value that
+ *     comes out of an fp64 reduction is rounded to fp32 first), the sum ONE fp32 addition: autograd's p.grad += g.  The add sits in
+ *     the final writer of each gradient (no pass over all parameters, no atomics, the same split-K order: bitwise repeatable).
+ *     The slot of a parameter that takes no gradient (the fixed Gaussian-Fourier W) is left untouched.  Needs grads != NULL.
+ *     d_x does not depend on `accumulate`.
+ *   record_marks = 0: the gradient-ready events (csd_unet_backward_marks) are not recorded and csd_unet_backward_marks_epoch does not
+ *     advance - the micro-batches of a window whose gradients are not final yet; the window's last backward passes 1. */
+int csd_unet_backward_acc(csd_unet* net, const float* const* params, float* const* grads, float* d_x, void* workspace,
+                          size_t workspace_bytes, const float* d_out, int B, uint64_t call_index, int accumulate, int record_marks,
+                          void* stream);
 /* The library keeps one recorded training graph per (handle, workspace).  A caller that frees a workspace (a monitoring forward's
  * private one) tells the library so: the record is dropped (no error if there is none).  csd_unet_destroy drops all of a handle's. */
 int csd_unet_train_release(csd_unet* net, const void* workspace);

@@ -4,6 +4,11 @@ image_to_image_translation/edges2shoes_ours_DV.py) - one full step = loss forwar
 all-reduce + fused clip/Adam/EMA.  One process per GPU (launch with torch.distributed.run for N > 1; the batch is sharded).
 
     python tools/bench_train.py [--steps 10 --warmup 3 --batch 50 --precision fp32]
+
+`--accumulate K` (one process): one optimizer step of K micro-batches of batch / K (training.accumulate_grad_batches = K) timed three
+ways - the accumulating planned backward (csd_unet_backward_acc adds to the flat gradient), the same with direct mode off (the backward
+fills a temporary buffer and autograd adds it per parameter: the only route before csd_unet_backward_acc), and one step at K = 1 on the
+whole batch - written under a new key of profiles/train_accumulate.json (`--out`).
 """
 import argparse
 import json
@@ -55,6 +60,56 @@ def make_ncsnpp_config(precision):
     return c
 
 
+def bench_accumulate(a, dev):
+    """-> the record of one `--accumulate K` run (single process)"""
+    K = a.accumulate
+    if a.batch % K:
+        sys.exit('--accumulate %d does not divide --batch %d' % (K, a.batch))
+
+    def timed(k, direct):
+        cfg = make_config(a.precision) if a.model == 'ddpm_paired' else make_ncsnpp_config(a.precision)
+        if k > 1:
+            cfg.training.accumulate_grad_batches = k
+        torch.manual_seed(0)
+        model = mutils.create_model(cfg).to(dev)
+        m = cfg.model
+        sde = {'x': sde_lib.cVESDE(m.sigma_min_x, m.sigma_max_x, m.num_scales), 'y': sde_lib.VESDE(m.sigma_min_y, m.sigma_max_y, m.num_scales)}
+        tr = train.Trainer(cfg, model, sde)
+        if not direct:
+            model.grad_sink = False           # the planned backward hands autograd one gradient per parameter to accumulate
+        B = a.batch // k
+        g = torch.Generator().manual_seed(1)
+        batch = (torch.rand(B, 3, 64, 64, generator=g).to(dev), torch.rand(B, 3, 64, 64, generator=g).to(dev))
+        for _ in range(a.warmup * k):
+            loss = tr.train_step(batch)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(a.steps * k):
+            loss = tr.train_step(batch)
+        torch.cuda.synchronize()
+        ms = 1e3 * (time.perf_counter() - t0) / a.steps
+        assert tr.step == a.warmup + a.steps and tr.pending == 0
+        rec = {'ms_per_optimizer_step': ms, 'micro_batches': k, 'micro_batch': B, 'loss': float(loss),
+               'peak_memory_MiB': torch.cuda.max_memory_allocated(dev) / 2.0 ** 20}
+        n_tensors = len(tr.flat.params)
+        tr.close()
+        del tr, model
+        torch.cuda.empty_cache()
+        torch.cuda.reset_peak_memory_stats(dev)
+        return rec, n_tensors
+
+    acc, n_tensors = timed(K, True)
+    auto, _ = timed(K, False)
+    full, _ = timed(1, True)
+    return {'model': a.model, 'precision': a.precision, 'batch': a.batch, 'accumulate': K, 'steps': a.steps, 'warmup': a.warmup,
+            'accumulating_backward': acc, 'autograd_accumulation': auto, 'full_batch_k1': full,
+            # launches on top of the overwrite form, per micro-batch: the accumulating backward adds none (each final writer reads the
+            # old value itself; the q | k | v bias slices run as 3 one-row kernels per attention block in place of 3 device copies);
+            # autograd's route adds one elementwise add per parameter tensor and one allocation of the whole gradient
+            'extra_launches_per_micro_batch': {'accumulating_backward': 0, 'autograd_accumulation': n_tensors},
+            'device': torch.cuda.get_device_name(dev), 'data': 'synthetic'}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--model', default='ddpm_paired', choices=['ddpm_paired', 'ncsnpp_paired'])
@@ -63,6 +118,9 @@ def main():
     ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--batch', type=int, default=50, help='global batch')
     ap.add_argument('--precision', default='fp32')
+    ap.add_argument('--accumulate', type=int, default=0, help='K > 1: time one optimizer step of K micro-batches of batch / K (see above)')
+    ap.add_argument('--out', default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'profiles', 'train_accumulate.json'),
+                    help='--accumulate: the JSON file that receives the record under its own key')
     a = ap.parse_args()
     world = int(os.environ.get('WORLD_SIZE', '1'))
     rank = int(os.environ.get('RANK', '0'))
@@ -77,6 +135,21 @@ def main():
         os.environ['CSD_TRAIN_EXECUTOR'] = a.executor
     cfg = make_config(a.precision) if a.model == 'ddpm_paired' else make_ncsnpp_config(a.precision)
     import conditional_score_diffusion_amd.models.ncsnpp  # noqa: F401
+    if a.accumulate > 1:
+        if grouped or world > 1:
+            sys.exit('--accumulate is a one-process measurement')
+        rec = bench_accumulate(a, dev)
+        key = '%s_%s_B%d_K%d' % (a.model, a.precision, a.batch, a.accumulate)
+        book = {}
+        if os.path.exists(a.out):
+            with open(a.out) as f:
+                book = json.load(f)
+        book[key] = rec
+        with open(a.out, 'w') as f:
+            json.dump(book, f, indent=1, sort_keys=True)
+            f.write('\n')
+        print(json.dumps({key: rec}))
+        return
     torch.manual_seed(0)
     model = mutils.create_model(cfg).to(dev)
     m = cfg.model
