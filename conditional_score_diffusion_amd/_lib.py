@@ -73,6 +73,16 @@ class OdeCoef(ctypes.Structure):
     _fields_ = [('c', ctypes.c_double * 7)]
 
 
+DSM_PARTS = 64         # include/csd.h CSD_DSM_PARTS: fp64 partials per (sample, segment) of csd_dsm_residual
+
+
+class DsmSegment(ctypes.Structure):
+    """csd_dsm_segment: offset / length in floats inside a network output row; a, b, w, z device addresses (z NULL: the Philox fill
+    of (seed, stream_id))"""
+    _fields_ = [('offset', ctypes.c_int64), ('length', ctypes.c_int64), ('a', ctypes.c_void_p), ('b', ctypes.c_void_p),
+                ('w', ctypes.c_void_p), ('z', ctypes.c_void_p), ('stream_id', ctypes.c_uint64)]
+
+
 def build(verbose=False):
     """Compile libcsd_hip.so for gfx950 (hipcc cross-compiles without a GPU)."""
     cmd = ['make', '-C', CSRC, '-j', str(min(8, os.cpu_count() or 1))]
@@ -211,6 +221,8 @@ SIGNATURES = {
     'csd_global_norm_scratch_bytes': (_sz, []),
     'csd_global_norm': (_i, [_vp, _vp, _i64, _vp, _vp]),
     'csd_ema_update': (_i, [_vp, _vp, _i64, _f, _vp]),
+    'csd_dsm_perturb': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i64, _u64, _u64, _vp]),
+    'csd_dsm_residual': (_i, [_vp, _i64, ctypes.POINTER(DsmSegment), _i, _vp, _vp, _vp, _vp, _i, _u64, _vp]),
     'csd_dropout': (_i, [_vp, _vp, _vp, _f, _u64, _u64, _i64, _vp]),
     'csd_pf_ode_state': (_i, [_vp, _vp, _vp, _vp, _i, _i64, _vp]),
     'csd_pf_ode_scratch_bytes': (_sz, [_i, _i64]),

@@ -167,6 +167,41 @@ __device__ __forceinline__ void wg_copy_to_lds(char* __restrict__ dst, const cha
     }
   }
 }
+// ---- Philox4x32-10 + Box-Muller ------------------------------------------------------------------
+__device__ __forceinline__ void philox_round(uint32_t& c0, uint32_t& c1, uint32_t& c2, uint32_t& c3,
+                                             uint32_t k0, uint32_t k1) {
+  const uint64_t p0 = (uint64_t)0xD2511F53u * c0;
+  const uint64_t p1 = (uint64_t)0xCD9E8D57u * c2;
+  const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0;
+  const uint32_t n1 = (uint32_t)p1;
+  const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
+  const uint32_t n3 = (uint32_t)p0;
+  c0 = n0; c1 = n1; c2 = n2; c3 = n3;
+}
+
+// the four standard normals of Philox counter i: key = seed, (c2, c3) = stream_id; lane j is element 4*i + j of the stream
+// (every kernel that draws takes its normals from here, so a draw does not depend on which kernel made it: contraction is off inside)
+__device__ __forceinline__ void philox_normal4(size_t i, uint64_t seed, uint64_t stream_id, float v[4]) {
+#pragma clang fp contract(off)
+  uint32_t c0 = (uint32_t)i, c1 = (uint32_t)(i >> 32), c2 = (uint32_t)stream_id, c3 = (uint32_t)(stream_id >> 32);
+  uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    philox_round(c0, c1, c2, c3, k0, k1);
+    k0 += 0x9E3779B9u;
+    k1 += 0xBB67AE85u;
+  }
+  // uniforms in (0,1]: (u32 + 1) * 2^-32 computed via the top 24 bits to stay exact in fp32
+  const float u0 = ((float)(c0 >> 8) + 1.0f) * (1.0f / 16777216.0f);
+  const float u1 = ((float)(c1 >> 8) + 0.5f) * (1.0f / 16777216.0f);
+  const float u2 = ((float)(c2 >> 8) + 1.0f) * (1.0f / 16777216.0f);
+  const float u3 = ((float)(c3 >> 8) + 0.5f) * (1.0f / 16777216.0f);
+  const float r0 = sqrtf(-2.0f * logf(u0)), r1 = sqrtf(-2.0f * logf(u2));
+  float s0, cs0, s1, cs1;
+  sincosf(6.283185307179586f * u1, &s0, &cs0);
+  sincosf(6.283185307179586f * u3, &s1, &cs1);
+  v[0] = r0 * cs0; v[1] = r0 * s0; v[2] = r1 * cs1; v[3] = r1 * s1;
+}
 #endif
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 

@@ -11,6 +11,10 @@ csd_scale_rows + csd_axpby; per-sample squared norms: csd_row_norms); the remain
 backward kernels of csrc/backward.hip, dropout on), the residual / per-sample reduction are differentiable HIP operators too,
 and the returned scalar is autograd-connected - ``loss.backward()`` fills ``param.grad`` of every network parameter
 (SURVEY.md 8 rows a19/a20).  The last reduction over the B per-sample values is torch arithmetic on a [B] tensor.
+
+``fused=True`` on either factory (opt-in; ``config.training.csd_fused_loss`` for the Trainer) returns
+``loss_fn(model, batch, noise=None, t=None, seed=None)``: the same objective as csd_dsm_perturb -> the planned network ->
+csd_dsm_residual, with Philox noise keyed by (seed, forward call index) instead of torch's generator (see the fused route below).
 """
 import torch
 
@@ -59,8 +63,10 @@ def _g2(sde, t):
     return (sde.sde(torch.zeros(t.shape[0], 1, 1, 1), t)[1].flatten().double()) ** 2
 
 
-def get_sde_loss_fn(sde, train, reduce_mean=True, continuous=True, likelihood_weighting=True, eps=1e-5):
-    """losses.py:55-97 (unconditional)."""
+def get_sde_loss_fn(sde, train, reduce_mean=True, continuous=True, likelihood_weighting=True, eps=1e-5, fused=False, seed=None):
+    """losses.py:55-97 (unconditional).  ``fused=True``: the fused route (``_fused_loss_fn`` below), ``seed`` its default Philox key."""
+    if fused:
+        return _fused_loss_fn(sde, train, False, reduce_mean, continuous, likelihood_weighting, eps, seed)
 
     def loss_fn(model, batch):
         score_fn = mutils.get_score_fn(sde, model, train=train, continuous=continuous)
@@ -78,14 +84,18 @@ def get_sde_loss_fn(sde, train, reduce_mean=True, continuous=True, likelihood_we
 
 
 def get_general_sde_loss_fn(sde, train, conditional=False, reduce_mean=True, continuous=True, likelihood_weighting=True,
-                            eps=1e-5):
-    """losses.py:99-232: unconditional, SR3 (one conditional SDE, clean y) and the two-SDE CMDE / VS-CMDE branch."""
+                            eps=1e-5, fused=False, seed=None):
+    """losses.py:99-232: unconditional, SR3 (one conditional SDE, clean y) and the two-SDE CMDE / VS-CMDE branch.
+    ``fused=True``: the fused route (``_fused_loss_fn`` below), ``seed`` its default Philox key."""
     if not conditional:
-        return get_sde_loss_fn(sde, train, reduce_mean, continuous, likelihood_weighting, eps)
+        return get_sde_loss_fn(sde, train, reduce_mean, continuous, likelihood_weighting, eps, fused, seed)
     if isinstance(sde, dict):
         if len(sde) != 2:
             raise NotImplementedError('multi-speed losses with >= 3 SDEs (losses.py:148-183) are not provided')
         assert likelihood_weighting, 'For the variance reduction technique in inverse problems, we only support likelihood weighting for the time being.'
+    if fused:
+        return _fused_loss_fn(sde, train, True, reduce_mean, continuous, likelihood_weighting, eps, seed)
+    if isinstance(sde, dict):
 
         def loss_fn(model, batch):
             y, x = batch
@@ -116,6 +126,184 @@ def get_general_sde_loss_fn(sde, train, conditional=False, reduce_mean=True, con
         if likelihood_weighting:
             losses = losses * _g2(sde, t).to(losses)
         return losses.mean().float()
+
+    return loss_fn
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# fused route (``fused=True``): the objective as two HIP passes around the planned network (csrc/dsm_loss.hip)
+#
+# Every score function of models/utils.py is score = s_b * h with a per-sample factor, so every variant above is
+#     loss = sum_b sum_segments w_b * sum_i (a_b * h[b, i] + b_b * z[b, i])^2
+# over the x block (and, with two SDEs, the y block) of the network's flat per-sample output row.  The per-sample numbers are taken
+# from the SAME functions the default route calls - the score function evaluated on a likelihood._Probe gives s_b and the labels,
+# _bstd the perturbation's (m, std), _g2 the likelihood weight - and no formula is restated per SDE:
+#     likelihood_weighting   a = s,        b = 1 / std,   w = g^2 * r / B
+#     otherwise              a = s * std,  b = 1,         w = r / B            r = 1 / numel (reduce_mean) or 1 / 2
+# They are written on the host and uploaded in ONE asynchronous copy per step; the step never waits for the device.
+#
+# Noise.  ``noise`` is an explicit tape in the order of the default route's randn_like calls ([z] or [z_y, z_x]).  Without one, z is
+# never stored: csd_dsm_perturb and csd_dsm_residual both make element b * D + i of the Philox fill of (seed, stream) in registers.
+# seed defaults to model.dropout_seed; with ``call`` the index the forward is about to take (model._train_calls + 1)
+#     stream = 2^63 + 2 * call + k,   k = 0 for x, 1 for y            (eval mode: 2^63 + 2^62 + 2 * model._train_calls + k)
+# The dropout masks of that forward use (seed, (call << 16) + j): below 2^63 for every call < 2^47, so the two families of
+# (seed, stream) pairs are disjoint for every call, and distinct calls get distinct noise streams.  z is thus a function of
+# (seed, call) alone: a run resumed from Trainer.state_dict() (which keeps _train_calls) repeats it without any torch RNG state.
+# ------------------------------------------------------------------------------------------------------------------
+_NOISE_STREAM = 1 << 63
+_EVAL_STREAM = 1 << 62
+# How keyed noise reaches the two passes: 'registers' (each pass makes its normals itself) or 'fill' (one csd_randn fill per segment,
+# read by both).  The values are bitwise the same; 'registers' measured 12 % faster at the SR3-160 shape, B = 64 (tools/bench_train.py
+# --fused-loss, profiles/train_fused_loss.json: noise_forms).
+FUSED_NOISE_FORM = 'registers'
+
+
+def _dsm_tables(sde, t, numels, embedding_type='positional', conditional=False, reduce_mean=True, continuous=True,
+                likelihood_weighting=True):
+    """Host side of the fused route: ``(labels [B] float32, {'x': {...}[, 'y': {...}]})`` with float64 ``a, b, w`` and the float32
+    ``m, std`` of the perturbation per segment, at the per-sample times ``t``.  ``numels``: floats per sample of each segment
+    ({'x': ..} or, with two SDEs, {'x': .., 'y': ..})."""
+    import types
+    from . import likelihood
+    pair = isinstance(sde, dict)
+    t = t.detach().cpu().float()
+    B = t.shape[0]
+
+    class _PairProbe(likelihood._Probe):
+        def __call__(self, x, labels):
+            self.labels = labels
+            return {k: torch.ones_like(v) for k, v in x.items()}
+
+    probe = (_PairProbe if pair else likelihood._Probe)(types.SimpleNamespace(embedding_type=embedding_type))
+    one = torch.ones(B, 1, 1, 1)
+    s = mutils.get_score_fn(sde, probe, conditional=conditional, train=False, continuous=continuous)(
+        {'x': one, 'y': one.clone()} if conditional else one, t)
+    total = sum(int(n) for n in numels.values())
+    r = (1.0 / total if reduce_mean else 0.5) / B
+    tables = {}
+    for k in (('x', 'y') if pair else ('x',)):
+        sde_k = sde[k] if pair else sde
+        m, std = _bstd(sde_k, None, t)
+        s_k = (s[k] if pair else s).reshape(B).double()
+        if likelihood_weighting:
+            a, b, w = s_k, 1.0 / std.double(), _g2(sde_k, t) * r
+        else:
+            a, b, w = s_k * std.double(), torch.ones(B, dtype=torch.float64), torch.full((B,), r, dtype=torch.float64)
+        tables[k] = {'m': m.float(), 'std': std, 'a': a, 'b': b, 'w': w}
+    return probe.labels.reshape(B).float(), tables
+
+
+class _CoefficientUpload:
+    """Pinned staging of a step's per-sample coefficients (the ode_solver.CoefficientRing pattern): the rows are written into a slot
+    and leave in ONE asynchronous copy to a fresh device tensor.  A slot is rewritten 8 uploads later, after the event recorded behind
+    its copy - long past by then, so the host does not wait."""
+    SLOTS = 8
+
+    def __init__(self):
+        self.host, self.events, self.k = None, [None] * self.SLOTS, 0
+
+    def __call__(self, rows, dev):
+        B = rows[0].shape[0]
+        n = len(rows) * B
+        if self.host is None or self.host.shape[1] < n:
+            self.host, self.events = torch.empty(self.SLOTS, n, dtype=torch.float32).pin_memory(), [None] * self.SLOTS
+        if self.events[self.k] is not None:
+            self.events[self.k].synchronize()
+        slot = self.host[self.k, :n]
+        for i, row in enumerate(rows):
+            slot[i * B:(i + 1) * B].copy_(row)
+        out = torch.empty(n, dtype=torch.float32, device=dev)
+        out.copy_(slot, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record(torch.cuda.current_stream(dev))
+        self.events[self.k] = ev
+        self.k = (self.k + 1) % self.SLOTS
+        return [out[i * B:(i + 1) * B] for i in range(len(rows))]
+
+
+class _DsmResidual(torch.autograd.Function):
+    """loss = sum_b sum_seg w sum (a h + b z)^2 as ONE node: the forward writes d loss / d h beside the value (csd_dsm_residual),
+    the backward scales it by the incoming scalar (csd_scale_rows)."""
+
+    @staticmethod
+    def forward(ctx, out, segments, seed):
+        loss, _, d_out = ops.dsm_residual(out, segments, seed)
+        ctx.d_out = d_out
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        d_out = ctx.d_out
+        scale = g.detach().to(device=d_out.device, dtype=torch.float32).reshape(1).expand(d_out.shape[0]).contiguous()
+        return ops.scale_rows(d_out, scale), None, None
+
+
+def _require_fused(model, tensors, sde):
+    from .models.ddpm import HipUNet
+    if isinstance(sde, dict) and len(sde) != 2:
+        raise NotImplementedError('the fused loss takes one SDE or the {x, y} pair, not %d SDEs' % len(sde))
+    if getattr(model, 'arch', None) == 2 or model.__class__.__name__.startswith('DDPM3D'):
+        raise NotImplementedError('the fused loss is not provided for the 3-D classes (%s)' % model.__class__.__name__)
+    if not (isinstance(model, HipUNet) and model.arch == 0 and model.train_executor == 'planned' and model.train_layout == 'nhwc'):
+        raise NotImplementedError('the fused loss needs a HipUNet on the planned training executor (DDPM family, '
+                                  'CSD_TRAIN_EXECUTOR=planned, CSD_TRAIN_LAYOUT=nhwc), got %s' % model.__class__.__name__)
+    for name, v in tensors:
+        if not (isinstance(v, torch.Tensor) and v.is_cuda):
+            raise NotImplementedError('the fused loss runs on GPU tensors only: %s is on %s' % (name, getattr(v, 'device', type(v))))
+
+
+def _fused_loss_fn(sde, train, conditional, reduce_mean, continuous, likelihood_weighting, eps, seed0):
+    """``loss_fn(model, batch, noise=None, t=None, seed=None)``: the objectives above on csd_dsm_perturb -> the planned network ->
+    csd_dsm_residual.  ``t``: per-sample times (default: the default route's torch.rand draw); ``noise``: the tape; ``seed``: the
+    Philox key (default: the factory's ``seed``, else model.dropout_seed).  Training mode returns an autograd-connected device scalar
+    behind the unchanged ``_PlannedNet`` node; eval mode runs the planned inference forward and writes no gradient."""
+    pair = isinstance(sde, dict)
+    if pair and len(sde) != 2:
+        raise NotImplementedError('the fused loss takes one SDE or the {x, y} pair, not %d SDEs' % len(sde))
+    upload = _CoefficientUpload()
+
+    def loss_fn(model, batch, noise=None, t=None, seed=None):
+        y, x = batch if conditional else (None, batch)
+        _require_fused(model, [('x', x)] + ([('y', y)] if conditional else []), sde)
+        B, dev = x.shape[0], x.device
+        if t is None:
+            t = torch.rand(B) * ((sde['x'] if pair else sde).T - eps) + eps
+        numels = {'x': x[0].numel(), 'y': y[0].numel()} if pair else {'x': x[0].numel()}
+        labels, tab = _dsm_tables(sde, t, numels, getattr(model, 'embedding_type', 'positional'), conditional, reduce_mean,
+                                  continuous, likelihood_weighting)
+        keys = ('x', 'y') if pair else ('x',)
+        rows = upload([labels] + [tab[k][c] for k in keys for c in ('m', 'std', 'a', 'b', 'w')], dev)
+        labels_d, coef = rows[0], {k: dict(zip(('m', 'std', 'a', 'b', 'w'), rows[1 + 5 * i:6 + 5 * i])) for i, k in enumerate(keys)}
+        if seed is None:
+            seed = seed0 if seed0 is not None else model.dropout_seed
+        base = _NOISE_STREAM + 2 * (model._train_calls + 1) if train else _NOISE_STREAM + _EVAL_STREAM + 2 * model._train_calls
+        stream = {'x': base, 'y': base + 1}
+        z = {}
+        if noise is not None:
+            tape = [noise] if isinstance(noise, torch.Tensor) else list(noise)
+            if len(tape) != len(keys):
+                raise ValueError('the noise tape holds %d tensors, this objective draws %d' % (len(tape), len(keys)))
+            z = dict(zip(('y', 'x') if pair else ('x',), [v.to(device=dev, dtype=torch.float32).contiguous() for v in tape]))
+        elif FUSED_NOISE_FORM == 'fill':
+            z = {k: ops.randn(tuple(v.shape), seed, stream[k], dev) for k, v in (('x', x), ('y', y)) if k in keys}
+        data = {'x': x, 'y': y}
+        pert = {k: ops.dsm_perturb(data[k], coef[k]['std'], None if bool(torch.all(tab[k]['m'] == 1)) else coef[k]['m'], z.get(k),
+                                   seed, stream[k]) for k in keys}
+        model.train() if train else model.eval()
+        if train:
+            out = model._run(pert['x'], pert['y'] if pair else y, labels_d)
+        else:
+            with torch.no_grad():
+                out = model._run(pert['x'], pert['y'] if pair else y, labels_d)
+        segments, off = [], 0
+        for k in keys:
+            n = numels[k]
+            segments.append({'offset': off, 'length': n, 'a': coef[k]['a'], 'b': coef[k]['b'], 'w': coef[k]['w'],
+                             'z': z.get(k), 'stream_id': stream[k]})
+            off += n
+        if out.requires_grad:
+            return _DsmResidual.apply(out, segments, seed)
+        return ops.dsm_residual(out, segments, seed, want_d_out=False)[0].reshape(())
 
     return loss_fn
 

@@ -623,6 +623,58 @@ def scale_rows(x, scale, divide=False):
     return out
 
 
+def dsm_perturb(x, std, m=None, z=None, seed=0, stream_id=0):
+    """``x_t[b] = m[b] * x[b] + std[b] * z[b]`` in one kernel with the three roundings of ``losses._perturb`` (bitwise that route).
+    ``m``, ``std``: device [B]; ``m=None``: 1 (the VE SDEs).  ``z=None``: the normals of ``randn(x.shape, seed, stream_id)`` made in
+    registers (bit-identical to passing that tensor)."""
+    x, std = _c(x, 'x'), _c(std, 'std')
+    B = x.shape[0]
+    tensors = [('std', std, (B,))] + ([('m', _c(m, 'm'), (B,))] if m is not None else []) + \
+              ([('z', _c(z, 'z'), tuple(x.shape))] if z is not None else [])
+    for name, t, shape in tensors:
+        if tuple(t.shape) != shape:
+            raise RuntimeError('dsm_perturb: %s has shape %s, expected %s' % (name, tuple(t.shape), shape))
+    out = _out(x.shape, x.dtype, x.device)
+    check(lib().csd_dsm_perturb(ptr(out), ptr(x), ptr(m.contiguous()) if m is not None else None, ptr(std),
+                                ptr(z.contiguous()) if z is not None else None, B, x.numel() // B, int(seed), int(stream_id),
+                                current_stream(x.device)), 'dsm_perturb')
+    return out
+
+
+def dsm_residual(net, segments, seed=0, want_d_out=True):
+    """The weighted denoising score-matching residual over 1 or 2 segments of the network's flat per-sample output rows (include/csd.h:
+    csd_dsm_residual).  ``net`` [B, ...] contiguous; ``segments``: dicts with ``offset``, ``length`` (floats inside a row), ``a``, ``b``,
+    ``w`` (device [B]) and either ``z`` (device [B, length]) or ``stream_id`` (the Philox fill of ``(seed, stream_id)``).
+    Returns ``(loss, loss_rows, d_out)``: a [1] float32 tensor = sum_b loss_rows[b], the [B] float64 per-sample values, and
+    ``2 w a (a h + b z)`` in ``net``'s shape (zeros outside the segments; None with ``want_d_out=False``)."""
+    net = _c(net, 'net')
+    B = net.shape[0]
+    segs = (_lib.DsmSegment * max(len(segments), 1))()
+    keep = []
+    for k, s in enumerate(segments[:len(segs)]):
+        c = [_c(s[n], n) for n in ('a', 'b', 'w')]
+        for n, t in zip('abw', c):
+            if tuple(t.shape) != (B,):
+                raise RuntimeError('dsm_residual: %s of segment %d has shape %s, expected (%d,)' % (n, k, tuple(t.shape), B))
+        z = s.get('z')
+        if z is not None:
+            z = _c(z, 'z')
+            if z.numel() != B * int(s['length']):
+                raise RuntimeError('dsm_residual: z of segment %d has %d elements, expected %d' % (k, z.numel(), B * int(s['length'])))
+        keep += c + [z]
+        segs[k].offset, segs[k].length = int(s['offset']), int(s['length'])
+        segs[k].a, segs[k].b, segs[k].w = (t.data_ptr() for t in c)
+        segs[k].z = z.data_ptr() if z is not None else None
+        segs[k].stream_id = int(s.get('stream_id', 0))
+    dev = net.device
+    d_out = _out(net.shape, torch.float32, dev) if want_d_out else None
+    partials = _out(B * max(len(segments), 1) * _lib.DSM_PARTS, torch.float64, dev)
+    rows, loss = _out(B, torch.float64, dev), _out(1, torch.float32, dev)
+    check(lib().csd_dsm_residual(ptr(net), net.numel() // B, segs, len(segments), ptr(d_out), ptr(partials), ptr(rows), ptr(loss), B,
+                                 int(seed), current_stream(dev)), 'dsm_residual')
+    return loss, rows, d_out
+
+
 def langevin_step(x, net, z, std, snr, alpha=1.0):
     """In-place Langevin corrector update (sampling/correctors.py:51-78,88-108); ``alpha`` = sde.alphas[timestep] for the VP / subVP
     SDEs, 1 for the VE SDEs; returns (x, x_mean)."""

@@ -80,10 +80,20 @@ class Trainer:
         conditional = isinstance(sde, dict) or model.__class__.__name__ != 'DDPM' and getattr(model, 'y_channels', 0) > 0
         # the 3-D classes take {'x', 'y'} by their class (they have no y_channels): conditional for the paired ones, not for ddpm3D
         conditional = conditional or model.__class__.__name__ in ('DDPM3D_paired', 'DDPM3D_paired_SR3')
+        # training.csd_fused_loss: both objectives on the fused HIP passes (losses._fused_loss_fn), their noise keyed by this rank's
+        # seed and the forward's call index - a resumed run repeats z without any torch RNG state
+        has_t = (lambda k: k in t) if hasattr(t, '__contains__') else (lambda k: hasattr(t, k))
+        self.fused_loss = bool(t.csd_fused_loss) if has_t('csd_fused_loss') else False
+        kw = {}
+        if self.fused_loss:
+            import torch.distributed as dist
+            from .distributed import rank_seed
+            rank = dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
+            kw = {'fused': True, 'seed': rank_seed(int(getattr(config, 'seed', 0) or 0), rank)}
         self.loss_fn = losses.get_general_sde_loss_fn(sde, True, conditional=conditional, reduce_mean=t.reduce_mean,
-                                                      continuous=t.continuous, likelihood_weighting=t.likelihood_weighting)
+                                                      continuous=t.continuous, likelihood_weighting=t.likelihood_weighting, **kw)
         self.eval_loss_fn = losses.get_general_sde_loss_fn(sde, False, conditional=conditional, reduce_mean=t.reduce_mean,
-                                                           continuous=t.continuous, likelihood_weighting=t.likelihood_weighting)
+                                                           continuous=t.continuous, likelihood_weighting=t.likelihood_weighting, **kw)
 
     def reconfigure_conditioning_sde(self):
         """callbacks.py:44-56 + ConditionalSdeGenerativeModel.reconfigure_conditioning_sde (:179-195): sde['y'] at the current step"""
@@ -92,7 +102,7 @@ class Trainer:
         self.sde['y'] = sde_lib.VESDE(sigma_min=self.sigma_min_y, sigma_max=self.sigma_max_y, N=self.config.model.num_scales)
         self._build_loss_fns()
 
-    def train_step(self, batch, global_n=None):
+    def train_step(self, batch, global_n=None, **loss_kwargs):
         """-> detached loss of this rank's shard.  ``batch`` is the loss_fn's: ``x`` or ``(y, x)``.  ``global_n``: images of the GLOBAL
         batch when the shards are ragged (a global batch that does not divide by the world size, distributed.shard_bounds): the
         rank's mean loss is then weighted by its share of the images instead of 1 / world.
@@ -100,7 +110,12 @@ class Trainer:
         With ``training.accumulate_grad_batches = k > 1`` one call is one MICRO-batch, as in Lightning: the (unscaled) loss of the
         micro-batch is returned, its gradient joins the window's with weight 1 / k, and the optimizer steps on every k-th call
         (``self.step`` counts optimizer steps: warm-up and the VS-CMDE schedule are constant within a window, like Lightning's
-        ``global_step``; the dropout streams advance per micro-batch).  ``global_n`` is then the global MICRO-batch."""
+        ``global_step``; the dropout streams advance per micro-batch).  ``global_n`` is then the global MICRO-batch.
+
+        ``loss_kwargs`` (``t=``, ``noise=``, ``seed=``) go to the fused loss function (``training.csd_fused_loss``) only."""
+        if loss_kwargs and not self.fused_loss:
+            raise TypeError('train_step(%s=...) needs training.csd_fused_loss: the default loss function draws its own t and noise'
+                            % ', '.join(sorted(loss_kwargs)))
         k = self.accumulate
         if self._vs is not None:
             self.reconfigure_conditioning_sde()
@@ -112,7 +127,7 @@ class Trainer:
             self.model.grad_accumulate = self.pending > 0
             self.model.grad_marks = self.pending + 1 == k
             self.sync.hold(self.pending + 1 < k)
-        loss = self.loss_fn(self.model, batch)
+        loss = self.loss_fn(self.model, batch, **loss_kwargs)
         if global_n:
             first = batch[0] if isinstance(batch, (tuple, list)) else batch
             scaled = self.sync.scale_loss(loss, local_n=first.shape[0], global_n=global_n)

@@ -614,6 +614,45 @@ int csd_global_norm(const float* a, float* out, int64_t n, void* scratch, void* 
 int csd_ema_update(float* ema, const float* param, int64_t n, float decay, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The denoising score-matching objective of a training step (csrc/dsm_loss.hip; losses.py:55-232 of the reference) as two passes
+ * around csd_unet_train_forward.  Every score function is score = s_b h with a per-sample factor, so each variant of the objective is
+ *     loss = sum_b sum_segments w_b sum_i (a_b h[b, i] + b_b z[b, i])^2
+ * over 1 or 2 segments of the network's flat per-sample output row: the caller folds the SDE (marginal std, g^2, the score scaling),
+ * the per-sample reduction (mean or half sum) and the batch mean (1 / B) into the per-sample device arrays a, b, w [B] - written on
+ * the host and uploaded in one copy per step; neither entry synchronises with the host.
+ * Noise: z is a device tensor, or NULL = element b * length + i of a csd_randn fill of (seed, stream_id) made in registers -
+ * bit-identical to passing that fill, without writing or reading it.  csd_dsm_perturb and csd_dsm_residual given the same
+ * (seed, stream_id) see the same normals.  A training step that keys its dropout masks by (seed, (call << 16) + k) - the planned
+ * network does, call < 2^47 - keeps the noise disjoint from them with stream ids that have bit 63 set.
+ * Both entries validate before they touch the device (CSD_ERR_INVALID, csd_last_error names the cause); results are bitwise repeatable
+ * and a sample's values depend on its batch position only through its Philox element numbers.
+ * ---------------------------------------------------------------------------------------- */
+/* xt[b, i] = fl(fl(m[b] x[b, i]) + fl(std[b] z[b, i])): three single roundings, no contraction.  x, xt [B, per_sample] (distinct buffers);
+ * m, std device [B]; m == NULL: m[b] = 1 (the VE SDEs).  16-byte accesses when x, xt and z allow them. */
+int csd_dsm_perturb(float* xt, const float* x, const float* m, const float* std, const float* z, int B, int64_t per_sample,
+                    uint64_t seed, uint64_t stream_id, void* stream);
+#define CSD_DSM_PARTS 64
+typedef struct csd_dsm_segment {
+  int64_t offset, length;     /* floats: the segment is [offset, offset + length) of every sample's row */
+  const float* a;             /* device [B] each */
+  const float* b;
+  const float* w;
+  const float* z;             /* device [B, length], or NULL: the csd_randn fill of (seed, stream_id) */
+  uint64_t stream_id;
+} csd_dsm_segment;
+/* net: sample b's row starts at net + b * net_stride.  segments: a HOST array of n_seg = 1 or 2 disjoint segments inside
+ * [0, net_stride) (the x block and the y block of a paired network, in either order).
+ *   d_out (or NULL: nothing written) [B, net_stride]: 2 w a (a h + b z) on the segments - the gradient of *loss with respect to net,
+ *       csd_unet_backward_acc's d_out - and 0 at every row position outside them;
+ *   partials: B * n_seg * CSD_DSM_PARTS doubles of scratch, every one written before it is read;
+ *   loss_rows [B] doubles: sum of w (a h + b z)^2 over the sample's segments, fp64, added in a fixed order;
+ *   loss: one float = the rows added in index order (with 1 / B in w: the batch mean of the per-sample losses).
+ * Refused: B < 1 or > 65535, n_seg outside 1..2, a null or misaligned pointer (floats 4 bytes, doubles 8), a segment that is empty or
+ * reaches beyond net_stride, overlapping segments. */
+int csd_dsm_residual(const float* net, int64_t net_stride, const csd_dsm_segment* segments, int n_seg, float* d_out, double* partials,
+                     double* loss_rows, float* loss, int B, uint64_t seed, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * NHWC forms of the training operators (csrc/train_nhwc.hip): the differentiable DDPM-family graph keeps activations in
  * the library's internal layout [B, H, W, C], so no layer pays an NCHW<->NHWC change.  Same kernels as above.
  * ---------------------------------------------------------------------------------------- */

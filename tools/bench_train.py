@@ -9,6 +9,12 @@ all-reduce + fused clip/Adam/EMA.  One process per GPU (launch with torch.distri
 ways - the accumulating planned backward (csd_unet_backward_acc adds to the flat gradient), the same with direct mode off (the backward
 fills a temporary buffer and autograd adds it per parameter: the only route before csd_unet_backward_acc), and one step at K = 1 on the
 whole batch - written under a new key of profiles/train_accumulate.json (`--out`).
+
+`--fused-loss` (one process): the default loss route against `training.csd_fused_loss` in alternating windows of --steps steps on one
+device, at the config's batch of 50 and at 7 (one rank's shard of 50 over 8), with the default route's own window-to-window spread as
+the yardstick; the time of csd_dsm_perturb + csd_dsm_residual alone at those shapes (the loss path's share of a step); and both noise
+forms of the two kernels (normals made in registers twice / one csd_randn fill read twice) at the SR3-160 shape, B = 64 - written to
+profiles/train_fused_loss.json.
 """
 import argparse
 import json
@@ -110,6 +116,89 @@ def bench_accumulate(a, dev):
             'device': torch.cuda.get_device_name(dev), 'data': 'synthetic'}
 
 
+def _event_ms(fn, reps, warmup, dev):
+    """mean device time of fn() in ms between two events, after warm-up"""
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize(dev)
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(reps):
+        fn()
+    e1.record()
+    torch.cuda.synchronize(dev)
+    return e0.elapsed_time(e1) / reps
+
+
+def _loss_kernels_ms(B, shapes, dev, form, reps=50):
+    """csd_dsm_perturb per tensor + one csd_dsm_residual over them (with d_out), noise `form`: 'registers' | 'fill'"""
+    from conditional_score_diffusion_amd import ops
+    g = torch.Generator().manual_seed(2)
+    xs = [torch.rand((B,) + s, generator=g).to(dev) for s in shapes]
+    coef = [(torch.rand(B, generator=g) + 0.5).to(dev) for _ in range(3)]
+    per = [int(np.prod(s)) for s in shapes]
+    net = torch.randn(B, sum(per), generator=g).to(dev)
+
+    def run():
+        z = [ops.randn(x.shape, 7, (1 << 63) + k, dev) if form == 'fill' else None for k, x in enumerate(xs)]
+        for k, x in enumerate(xs):
+            ops.dsm_perturb(x, coef[0], None, z[k], 7, (1 << 63) + k)
+        segs, off = [], 0
+        for k, n in enumerate(per):
+            segs.append({'offset': off, 'length': n, 'a': coef[0], 'b': coef[1], 'w': coef[2], 'z': z[k], 'stream_id': (1 << 63) + k})
+            off += n
+        ops.dsm_residual(net, segs, 7)
+
+    return _event_ms(run, reps, 5, dev)
+
+
+def bench_fused_loss(a, dev, windows=3):
+    """-> the record of one `--fused-loss` run (single process)"""
+    rec = {'model': a.model, 'precision': a.precision, 'steps_per_window': a.steps, 'warmup': a.warmup, 'windows': windows,
+           'device': torch.cuda.get_device_name(dev), 'data': 'synthetic', 'routes': {}}
+    for B in (a.batch, 7):
+        trainers = {}
+        for fused in (False, True):
+            cfg = make_config(a.precision)
+            cfg.training.csd_fused_loss = fused
+            torch.manual_seed(0)
+            model = mutils.create_model(cfg).to(dev)
+            m = cfg.model
+            sde = {'x': sde_lib.cVESDE(m.sigma_min_x, m.sigma_max_x, m.num_scales), 'y': sde_lib.VESDE(m.sigma_min_y, m.sigma_max_y, m.num_scales)}
+            trainers[fused] = train.Trainer(cfg, model, sde)
+        g = torch.Generator().manual_seed(1)
+        batch = (torch.rand(B, 3, 64, 64, generator=g).to(dev), torch.rand(B, 3, 64, 64, generator=g).to(dev))
+        sps = {False: [], True: []}
+        for fused in (False, True):
+            for _ in range(a.warmup):
+                trainers[fused].train_step(batch)
+        for _ in range(windows):
+            for fused in (False, True):
+                torch.cuda.synchronize(dev)
+                t0 = time.perf_counter()
+                for _ in range(a.steps):
+                    loss = trainers[fused].train_step(batch)
+                torch.cuda.synchronize(dev)
+                sps[fused].append(a.steps / (time.perf_counter() - t0))
+        kern_ms = _loss_kernels_ms(B, [(3, 64, 64), (3, 64, 64)], dev, 'registers')
+        d, f = sps[False], sps[True]
+        spread = max(d) - min(d)
+        rec['routes']['B%d' % B] = {
+            'default_steps_per_s': d, 'fused_steps_per_s': f, 'default_mean': float(np.mean(d)), 'fused_mean': float(np.mean(f)),
+            'default_window_spread': spread, 'fused_not_slower_than_default_by_more_than_spread': bool(np.mean(f) >= np.mean(d) - spread),
+            'fused_loss_kernels_ms': kern_ms, 'fused_loss_kernels_share_of_step': kern_ms * 1e-3 * float(np.mean(f)),
+            'default_minus_fused_ms_per_step': 1e3 * (1.0 / float(np.mean(d)) - 1.0 / float(np.mean(f)))}
+        for tr in trainers.values():
+            tr.close()
+        del trainers
+        torch.cuda.empty_cache()
+    forms = {form: _loss_kernels_ms(64, [(3, 160, 160)], dev, form) for form in ('registers', 'fill')}
+    again = {form: _loss_kernels_ms(64, [(3, 160, 160)], dev, form) for form in ('registers', 'fill')}
+    rec['noise_forms'] = {'shape': 'SR3-160, B = 64: perturb + residual over 64 x 3 x 160 x 160', 'ms': forms, 'ms_repeat': again,
+                          'faster': min(forms, key=forms.get)}
+    return rec
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--model', default='ddpm_paired', choices=['ddpm_paired', 'ncsnpp_paired'])
@@ -119,6 +208,7 @@ def main():
     ap.add_argument('--batch', type=int, default=50, help='global batch')
     ap.add_argument('--precision', default='fp32')
     ap.add_argument('--accumulate', type=int, default=0, help='K > 1: time one optimizer step of K micro-batches of batch / K (see above)')
+    ap.add_argument('--fused-loss', action='store_true', help='default loss route vs training.csd_fused_loss, and the noise forms (see above)')
     ap.add_argument('--out', default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'profiles', 'train_accumulate.json'),
                     help='--accumulate: the JSON file that receives the record under its own key')
     a = ap.parse_args()
@@ -135,6 +225,16 @@ def main():
         os.environ['CSD_TRAIN_EXECUTOR'] = a.executor
     cfg = make_config(a.precision) if a.model == 'ddpm_paired' else make_ncsnpp_config(a.precision)
     import conditional_score_diffusion_amd.models.ncsnpp  # noqa: F401
+    if a.fused_loss:
+        if grouped or world > 1 or a.model != 'ddpm_paired':
+            sys.exit('--fused-loss is a one-process measurement of ddpm_paired')
+        rec = bench_fused_loss(a, dev)
+        out = os.path.join(os.path.dirname(a.out), 'train_fused_loss.json') if os.path.basename(a.out) == 'train_accumulate.json' else a.out
+        with open(out, 'w') as f:
+            json.dump(rec, f, indent=1, sort_keys=True)
+            f.write('\n')
+        print(json.dumps(rec))
+        return
     if a.accumulate > 1:
         if grouped or world > 1:
             sys.exit('--accumulate is a one-process measurement')
