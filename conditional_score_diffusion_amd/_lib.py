@@ -31,6 +31,7 @@ class UNetConfig(ctypes.Structure):
                 ('centered', ctypes.c_int32), ('act', ctypes.c_int32), ('precision', ctypes.c_int32),
                 ('skip_rescale', ctypes.c_int32), ('progressive', ctypes.c_int32), ('progressive_input', ctypes.c_int32),
                 ('embedding_type', ctypes.c_int32), ('n_fir', ctypes.c_int32), ('fir_kernel', ctypes.c_float * 8),
+                ('planned_train', ctypes.c_int32), # arch 2: 1 = the handle serves the planned training graph (csrc/train_graph3d.h)
                 ('y_scale', ctypes.c_int32),       # arch 0 / 1: K >= 2 = y is [B, y_channels, S / K, S / K] (the Kx super-resolution networks)
                 ('vol', ctypes.c_int32 * 3),       # arch 2: D, H, W
                 ('x_squeeze', ctypes.c_int32)]     # arch 0: 1 = x is the image [B, x_channels / 4, 2S, 2S] (the 2x super-resolution networks)

@@ -458,6 +458,18 @@ int conv2d_impl(const float* x, const float* weight, const float* bias, const fl
 int groupnorm_act_backward_nhwc_add(const float* x, const float* gamma, const float* beta, const float* rs, const float* ms,
                                     const float* dy, const float* add, float* dx, float* dgamma_rows, float* dbeta_rows,
                                     int row_stride, int B, int C, int HW, int groups, int act, void* scratch, void* stream);
+// the same over x = x0 [B, HW, C0] (| x1 [B, HW, C - C0]) with the gradient written per source; acc0 / acc1 = 1: that destination already
+// holds a gradient (another consumer's) and takes this one in one fp32 addition.  One source: C0 = C, x1 = dx1 = NULL
+struct GnBwdSplit {
+  const float* x0 = nullptr;
+  const float* x1 = nullptr;
+  float* dx0 = nullptr;
+  float* dx1 = nullptr;
+  int C0 = 0, acc0 = 0, acc1 = 0;
+};
+int groupnorm_act_backward_nhwc_split(const GnBwdSplit& t, const float* gamma, const float* beta, const float* rs, const float* ms,
+                                      const float* dy, const float* add, float* dgamma_rows, float* dbeta_rows, int row_stride, int B, int C,
+                                      int HW, int groups, int act, void* scratch, void* stream);
 int axpby_launch(const float* a, const float* b, float* out, float alpha, float beta, float gamma, float post, size_t n,
                  hipStream_t s);
 int bias_add_nchw_launch(const float* x, const float* bias, float* out, int B, int C, size_t inner, int bias_stride, int act,
@@ -498,11 +510,23 @@ struct Conv3dCall {
 };
 bool conv3d_is_direct(int precision, int C0);                   // the fp32 direct kernel (CSD_PREC_F32, or C0 no multiple of 16)
 size_t conv3d_wpack_size(int Cin, int Cout, bool direct);      // bytes of one packed weight (MFMA: with the weight ring's slack)
-int conv3d_pack_launch(const float* weight, void* wpack, int Cin, int Cout, bool direct, hipStream_t s);
+// flip_t: `weight` is the forward layer's [Cin, Cout, 3, 3, 3] and the pack is its data gradient's, weight[ci][co][26 - tap] (the values of
+// packing weight.flip(2, 3, 4).transpose(0, 1), without that copy)
+int conv3d_pack_launch(const float* weight, void* wpack, int Cin, int Cout, bool direct, hipStream_t s, bool flip_t = false);
 int conv3d_launch(const Conv3dCall& c, hipStream_t s);
 // x, y (+ y_sigma * y_noise) NCDHW -> (2v - 1 unless centered) -> 3x3x3 convolution -> NDHWC; wpack in the direct layout
 int conv3d_stem_launch(const float* x, const float* y, const float* y_noise, float y_sigma, const void* wpack, const float* bias, float* out,
                        int B, int Cx, int Cy, int Cout, int D, int H, int W, int centered, hipStream_t s);
+
+// conv3d_grad.hip: csd_conv3d_wgrad with beta (1: dw = fl32(dw + V), V the value beta = 0 stores; the split-K order is the same);
+// the stem's data gradient at the network boundary: dy [B, D, H, W, Cout] NDHWC, w [Cout, Cin, 3, 3, 3] -> dx [B, nx, D, H, W] NCDHW, the
+// first nx input channels, times `scale` (2 for the 2v - 1 input map): one fp32 fmaf chain per output in tap-major, cout-minor order
+// ci_off, Cin_dw (> 0): `a` is ONE source of a two-source layer, dw its [Cout, Cin_dw, 27] weight gradient, of which the input-channel
+// slice ci_off .. ci_off + Cin is written (each element's sum is the one a single-source call of that source gives)
+int conv3d_wgrad_beta(const float* a, const float* dy, float* dw, int B, int Cin, int Cout, int D, int H, int W, int precision, void* scratch,
+                      void* stream, int beta, int ci_off = 0, int Cin_dw = 0);
+int conv3d_stem_dx_launch(const float* dy, const float* w, float* dx, int B, int nx, int Cin, int Cout, int D, int H, int W, float scale,
+                          hipStream_t s);
 
 // wgrad_bf16.hip: weight gradient of a stride-1 3x3 / 1x1 convolution with split-bf16 operands (NHWC x, dy; partial [S][Cout][Cin][taps])
 int wgrad_bf16_launch(const float* xh, const float* dyh, float* partial, int B, int H, int W, int Cin, int Cout, int ksize, int S,

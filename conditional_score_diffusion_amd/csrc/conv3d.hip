@@ -88,7 +88,13 @@ __device__ __forceinline__ half8 ld_h8(const char* p) { return *(const __attribu
 
 // ---- weight packs ----------------------------------------------------------------------------------------------------------------
 // MFMA: [cout tile][chunk][tap][hi | lo][lane][8 halves]; lane l feeds cout (l & 31) of the tile with channels 8*(l >> 5) + j of the chunk
-__global__ void conv3d_pack_mfma_kernel(const float* __restrict__ w, _Float16* __restrict__ wp, int Cin, int Cout, int nck, size_t total) {
+// flip_t: w is the FORWARD layer's weight [Cin][Cout][27] and the pack is that of its data gradient's convolution, w[ci][co][26 - tap]:
+// what packing weight.flip(2, 3, 4).transpose(0, 1) gives, without the copy
+__device__ __forceinline__ size_t c3_widx(int co, int ci, int tap, int Cin, int Cout, int flip_t) {
+  return flip_t ? ((size_t)ci * Cout + co) * C3_TAPS + (C3_TAPS - 1 - tap) : ((size_t)co * Cin + ci) * C3_TAPS + tap;
+}
+__global__ void conv3d_pack_mfma_kernel(const float* __restrict__ w, _Float16* __restrict__ wp, int Cin, int Cout, int nck, size_t total,
+                                        int flip_t) {
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
     const int j = (int)(i & 7);
     const int lane = (int)((i >> 3) & 63);
@@ -98,7 +104,7 @@ __global__ void conv3d_pack_mfma_kernel(const float* __restrict__ w, _Float16* _
     const int tile = (int)(r / nck);
     const int co = tile * 32 + (lane & 31);
     const int ci = ck * C3_KC + 8 * (lane >> 5) + j;
-    const float v = co < Cout ? w[((size_t)co * Cin + ci) * C3_TAPS + tap] * C3_WSCALE : 0.f;
+    const float v = co < Cout ? w[c3_widx(co, ci, tap, Cin, Cout, flip_t)] * C3_WSCALE : 0.f;
     const _Float16 hi = (_Float16)v;
     const size_t step = ((size_t)tile * nck + ck) * C3_TAPS + tap;
     _Float16* dst = wp + step * (C3_STEP_BYTES / 2) + lane * 8 + j;
@@ -108,13 +114,13 @@ __global__ void conv3d_pack_mfma_kernel(const float* __restrict__ w, _Float16* _
 }
 
 // direct kernel: [tap][Cin][Cout] (threads of a wave read consecutive couts)
-__global__ void conv3d_pack_direct_kernel(const float* __restrict__ w, float* __restrict__ wt, int Cin, int Cout, size_t total) {
+__global__ void conv3d_pack_direct_kernel(const float* __restrict__ w, float* __restrict__ wt, int Cin, int Cout, size_t total, int flip_t) {
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
     const int co = (int)(i % Cout);
     size_t r = i / Cout;
     const int ci = (int)(r % Cin);
     const int tap = (int)(r / Cin);
-    wt[i] = w[((size_t)co * Cin + ci) * C3_TAPS + tap];
+    wt[i] = w[c3_widx(co, ci, tap, Cin, Cout, flip_t)];
   }
 }
 
@@ -452,18 +458,18 @@ size_t conv3d_wpack_size(int Cin, int Cout, bool direct) {
   return direct ? (size_t)C3_TAPS * Cin * Cout * sizeof(float) : mfma_pack_bytes(Cin, Cout);
 }
 
-int conv3d_pack_launch(const float* weight, void* wpack, int Cin, int Cout, bool direct, hipStream_t s) {
+int conv3d_pack_launch(const float* weight, void* wpack, int Cin, int Cout, bool direct, hipStream_t s, bool flip_t) {
   if (direct) {
     const size_t nw = (size_t)C3_TAPS * Cin * Cout;
     hipLaunchKernelGGL(conv3d_pack_direct_kernel, dim3((unsigned)std::min<size_t>(cdiv64(nw, 256), 4096)), dim3(256), 0, s, weight,
-                       static_cast<float*>(wpack), Cin, Cout, nw);
+                       static_cast<float*>(wpack), Cin, Cout, nw, flip_t ? 1 : 0);
     CSD_LAUNCH_CHECK();
     return CSD_OK;
   }
   const int nck = Cin / C3_KC, ntiles = cdiv(Cout, 32);
   const size_t nh = (size_t)ntiles * nck * C3_TAPS * 512;
   hipLaunchKernelGGL(conv3d_pack_mfma_kernel, dim3((unsigned)std::min<size_t>(cdiv64(nh, 256), 4096)), dim3(256), 0, s, weight,
-                     static_cast<_Float16*>(wpack), Cin, Cout, nck, nh);
+                     static_cast<_Float16*>(wpack), Cin, Cout, nck, nh, flip_t ? 1 : 0);
   CSD_LAUNCH_CHECK();
   return CSD_OK;
 }

@@ -254,8 +254,12 @@ __global__ __launch_bounds__(W3_THREADS) void conv3d_wgrad_f32_kernel(const Wgra
   k.partial[(size_t)split * nw + idx] = acc;
 }
 
-// dw[co][ci][tap] = sum over splits (split order, fp64) of partial[split][tap][co][ci]
-__global__ void conv3d_wgrad_reduce_kernel(const float* __restrict__ partial, float* __restrict__ dw, int nsplits, int Cin, int Cout) {
+// dw[co][ci][tap] = sum over splits (split order, fp64) of partial[split][tap][co][ci]; beta = 1: added to what dw holds, in one fp32
+// addition of the value beta = 0 stores
+// (ci_off, Cin_dw: the Cin channels are the slice ci_off .. ci_off + Cin of a weight with Cin_dw input channels - one source of a
+// two-source layer; the whole weight: 0, Cin)
+__global__ void conv3d_wgrad_reduce_kernel(const float* __restrict__ partial, float* __restrict__ dw, int nsplits, int Cin, int Cout,
+                                           int beta, int ci_off, int Cin_dw) {
   const int nw = W3_TAPS * Cout * Cin;
   const int idx = blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= nw) return;
@@ -264,7 +268,33 @@ __global__ void conv3d_wgrad_reduce_kernel(const float* __restrict__ partial, fl
   const int ci = idx % Cin;
   const int co = (idx / Cin) % Cout;
   const int tap = idx / (Cin * Cout);
-  dw[((size_t)co * Cin + ci) * W3_TAPS + tap] = (float)s;
+  float* dst = dw + ((size_t)co * Cin_dw + ci_off + ci) * W3_TAPS + tap;
+  const float v = (float)s;
+  *dst = beta ? *dst + v : v;
+}
+
+// the stem's data gradient at the network boundary (common.h): one thread per (b, input channel, voxel)
+__global__ __launch_bounds__(W3_THREADS) void conv3d_stem_dx_kernel(const float* __restrict__ dy, const float* __restrict__ w,
+                                                                    float* __restrict__ dx, int B, int nx, int Cin, int Cout, int D, int H,
+                                                                    int W, float scale) {
+  const size_t vox = (size_t)D * H * W;
+  const size_t total = (size_t)B * nx * vox;
+  const size_t idx = (size_t)blockIdx.x * W3_THREADS + threadIdx.x;
+  if (idx >= total) return;
+  const int vi = (int)(idx % vox);
+  const size_t r = idx / vox;
+  const int ci = (int)(r % nx);
+  const size_t b = r / nx;
+  const int x = vi % W, h = (vi / W) % H, d = vi / (W * H);
+  float acc = 0.f;
+  for (int tap = 0; tap < W3_TAPS; ++tap) {            // y[v] reads x[v + off(tap)]: x[u] feeds y[u - off(tap)]
+    const int dd = d - (tap / 9 - 1), hh = h - ((tap / 3) % 3 - 1), xx = x - (tap % 3 - 1);
+    if (dd < 0 || dd >= D || hh < 0 || hh >= H || xx < 0 || xx >= W) continue;
+    const float* p = dy + (b * vox + ((size_t)dd * H + hh) * W + xx) * Cout;
+    const float* wp = w + (size_t)ci * W3_TAPS + tap;
+    for (int co = 0; co < Cout; ++co) acc = fmaf(p[co], wp[(size_t)co * Cin * W3_TAPS], acc);
+  }
+  dx[idx] = acc * scale;
 }
 
 bool wgrad3d_use_mfma(int Cin, int Cout, int precision) { return precision == CSD_PREC_F16X3 && std::min(Cin, Cout) >= W3_THIN; }
@@ -343,6 +373,17 @@ __global__ void dgrad_scale_finalize_kernel(const float* __restrict__ part, int 
 }
 
 }  // namespace
+
+int conv3d_stem_dx_launch(const float* dy, const float* w, float* dx, int B, int nx, int Cin, int Cout, int D, int H, int W, float scale,
+                          hipStream_t s) {
+  CSD_REQUIRE(dy && w && dx && B >= 1 && nx >= 1 && nx <= Cin && Cout >= 1 && D >= 1 && H >= 1 && W >= 1, "conv3d_stem_dx: bad arguments");
+  const size_t total = (size_t)B * nx * D * H * W;
+  const size_t nb = cdiv64(total, W3_THREADS);
+  CSD_REQUIRE(nb < ((size_t)1 << 31) && (size_t)D * H * W < ((size_t)1 << 28), "conv3d_stem_dx: %zu outputs exceed the kernel's grid", total);
+  hipLaunchKernelGGL(conv3d_stem_dx_kernel, dim3((unsigned)nb), dim3(W3_THREADS), 0, s, dy, w, dx, B, nx, Cin, Cout, D, H, W, scale);
+  CSD_LAUNCH_CHECK();
+  return CSD_OK;
+}
 }  // namespace csd
 
 using namespace csd;
@@ -358,6 +399,13 @@ extern "C" size_t csd_conv3d_wgrad_scratch_bytes(int B, int Cin, int Cout, int D
 
 extern "C" int csd_conv3d_wgrad(const float* a_in, const float* dy, float* dw, int B, int Cin, int Cout, int D, int H, int W, int precision,
                                 void* scratch, void* stream) {
+  return conv3d_wgrad_beta(a_in, dy, dw, B, Cin, Cout, D, H, W, precision, scratch, stream, 0);
+}
+
+int csd::conv3d_wgrad_beta(const float* a_in, const float* dy, float* dw, int B, int Cin, int Cout, int D, int H, int W, int precision,
+                           void* scratch, void* stream, int beta, int ci_off, int Cin_dw) {
+  if (Cin_dw <= 0) Cin_dw = Cin;
+  CSD_REQUIRE(ci_off >= 0 && ci_off + Cin <= Cin_dw, "conv3d_wgrad: input channels %d .. %d are no slice of %d", ci_off, ci_off + Cin, Cin_dw);
   CSD_REQUIRE(a_in && dy && dw && scratch, "conv3d_wgrad: null argument");
   CSD_REQUIRE(precision == CSD_PREC_F16X3 || precision == CSD_PREC_F32,
               "conv3d_wgrad: precision must be fp16x3 (CSD_PREC_F16X3: split bf16) or fp32 (CSD_PREC_F32)");
@@ -385,7 +433,7 @@ extern "C" int csd_conv3d_wgrad(const float* a_in, const float* dy, float* dw, i
     hipLaunchKernelGGL(conv3d_wgrad_f32_kernel, dim3((unsigned)nblocks), dim3(W3_THREADS), 0, s, a);
     CSD_LAUNCH_CHECK();
   }
-  hipLaunchKernelGGL(conv3d_wgrad_reduce_kernel, dim3((unsigned)cdiv(nw, 256)), dim3(256), 0, s, a.partial, dw, (int)nsplits, Cin, Cout);
+  hipLaunchKernelGGL(conv3d_wgrad_reduce_kernel, dim3((unsigned)cdiv(nw, 256)), dim3(256), 0, s, a.partial, dw, (int)nsplits, Cin, Cout, beta, ci_off, Cin_dw);
   CSD_LAUNCH_CHECK();
   return CSD_OK;
 }

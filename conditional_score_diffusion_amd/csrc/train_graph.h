@@ -1047,12 +1047,22 @@ struct TG {
 #undef TG_RUN
 };
 
+// arch 2 (train_graph3d.h, included behind this file): the dry run's peak in floats, the forward and the backward on a TrainState
+static size_t train3d_workspace_peak(Net& net, int B, float dropout_p);
+static int train3d_forward(Net& net, TrainState& st, int B, hipStream_t s, const float* const* params, float* ws, float p_drop, uint64_t seed,
+                           uint64_t call, const float* x, const float* y, const float* labels, float* out);
+static int train3d_backward(Net& net, TrainState& st, int B, hipStream_t s, const float* const* params, float* const* grads, float* ws,
+                            float* d_x, int accumulate, GradMarks* gm, const float* d_out);
+
 static int train_check(const csd_unet* net) {
   CSD_REQUIRE(net, "train: null handle");
   const csd_unet_config& c = net->net.cfg;
-  CSD_REQUIRE(c.arch != 2, "train graph: the 3-D networks (arch 2) have no planned training graph, input gradient or probability-flow "
-                           "right-hand side; they train on the per-operator path");
-  CSD_REQUIRE(c.arch == 0 || c.arch == 1, "train graph: arch %d has no planned training graph", c.arch);
+  // (arch 2, the 3-D networks: train_graph3d.h, for a handle created with planned_train = 1; what build_modules3d refused never became a
+  // handle.  They have no probability-flow right-hand side and no device-loop inpainting: the likelihood refuses them in Python)
+  CSD_REQUIRE(c.arch != 2 || c.planned_train, "train graph: this handle of the 3-D networks (arch 2) was created without "
+                                              "csd_unet_config.planned_train: it has no planned training graph or input gradient and "
+                                              "trains on the per-operator path (the probability-flow right-hand side is not wired to 3-D)");
+  CSD_REQUIRE(c.arch == 0 || c.arch == 1 || c.arch == 2, "train graph: arch %d has no planned training graph", c.arch);
   if (c.arch == 0) CSD_REQUIRE(c.resamp_with_conv, "train graph: resamp_with_conv = False is not provided");
   CSD_REQUIRE((c.x_channels + c.y_channels) >= 1, "train graph: no input channels");
   return CSD_OK;
@@ -1062,6 +1072,10 @@ static int train_check(const csd_unet* net) {
 
 extern "C" size_t csd_unet_train_workspace_bytes(csd_unet* net, int B, float dropout_p) {
   if (!net || train_check(net) || B < 1) return 0;
+  if (is3d(net->net)) {
+    const size_t peak = train3d_workspace_peak(net->net, B, dropout_p);
+    return peak ? peak * sizeof(float) + 256 : 0;
+  }
   TrainState st;
   TG g(net->net, st, B, nullptr, true, nullptr, nullptr, reinterpret_cast<float*>(uintptr_t(256)));
   g.p_drop = dropout_p;
@@ -1091,9 +1105,14 @@ extern "C" int csd_unet_train_forward(csd_unet* net, const float* const* params,
   train_state_purge_stale(&net->net, workspace);
   TrainState& st = train_state_of(&net->net, workspace);
   st.valid = false;
-  TG g(net->net, st, B, (hipStream_t)stream, false, params, nullptr, static_cast<float*>(workspace));
-  g.p_drop = dropout_p; g.seed = dropout_seed; g.call = call_index;
-  rc = g.forward(x, y, labels, out);
+  if (is3d(net->net)) {
+    rc = train3d_forward(net->net, st, B, (hipStream_t)stream, params, static_cast<float*>(workspace), dropout_p, dropout_seed, call_index, x,
+                         y, labels, out);
+  } else {
+    TG g(net->net, st, B, (hipStream_t)stream, false, params, nullptr, static_cast<float*>(workspace));
+    g.p_drop = dropout_p; g.seed = dropout_seed; g.call = call_index;
+    rc = g.forward(x, y, labels, out);
+  }
   if (rc) return rc;
   st.valid = true; st.B = B; st.ws = workspace; st.p_drop = dropout_p; st.call = call_index;
   return CSD_OK;
@@ -1159,18 +1178,24 @@ extern "C" int csd_unet_backward_acc(csd_unet* net, const float* const* params, 
   for (size_t i = 0; i < net->net.params.size(); ++i)
     CSD_REQUIRE(params[i] && (!grads || grads[i]), "backward: parameter / gradient pointer %zu (%s) is null", i, net->net.params[i].name.c_str());
   for (auto& t : st.t) t.g = nullptr;
-  TG g(net->net, st, B, (hipStream_t)stream, false, params, grads, static_cast<float*>(workspace));
-  g.pg = grads != nullptr;
-  g.gacc = accumulate;
-  g.want_dx = d_x != nullptr;
-  g.d_x = d_x;
-  if (g.pg && record_marks) {                                        // (the gradient-ready marks describe parameter gradients: none without them)
+  GradMarks* gm = nullptr;
+  if (grads && record_marks) {                                       // (the gradient-ready marks describe parameter gradients: none without them)
     std::lock_guard<std::mutex> lk(g_train_mu);
     auto it = g_marks.find(&net->net);
-    g.gm = it == g_marks.end() ? nullptr : &it->second;
+    gm = it == g_marks.end() ? nullptr : &it->second;
   }
-  rc = g.backward(d_out);
-  if (!rc && g.gm) ++g.gm->epoch;
+  if (is3d(net->net)) {
+    rc = train3d_backward(net->net, st, B, (hipStream_t)stream, params, grads, static_cast<float*>(workspace), d_x, accumulate, gm, d_out);
+  } else {
+    TG g(net->net, st, B, (hipStream_t)stream, false, params, grads, static_cast<float*>(workspace));
+    g.pg = grads != nullptr;
+    g.gacc = accumulate;
+    g.want_dx = d_x != nullptr;
+    g.d_x = d_x;
+    g.gm = gm;
+    rc = g.backward(d_out);
+  }
+  if (!rc && gm) ++gm->epoch;
   st.valid = false;                                  // the saved activations are consumed (gradient buffers overwrote nothing, but one backward per forward)
   return rc;
 }

@@ -32,9 +32,11 @@ __device__ __forceinline__ float t_dact(float v, int act) {
 #define TN_THREADS 256
 // pass 1 of the GroupNorm backward: per (sample, pixel chunk) and channel, sum du and sum du*xhat over the chunk's pixels.
 // thread = (pixel row, 4 channels); rows are folded through LDS in row order (deterministic).  partial [B][nchunk][C][2]
+// x = x0 [B, HW, C0] (| x1 [B, HW, C - C0]): the 4 channels of a thread lie in one source (C0 % 4 == 0); one source: C0 = C
 __global__ __launch_bounds__(TN_THREADS) void gn_bwd_stats_nhwc_kernel(
-    const float* __restrict__ x, const float* __restrict__ dy, const float* __restrict__ gamma, const float* __restrict__ beta,
-    const float* __restrict__ rs, const float* __restrict__ ms, double* __restrict__ partial, int HW, int C, int act, int nchunk) {
+    const float* __restrict__ x0, const float* __restrict__ x1, int C0, const float* __restrict__ dy, const float* __restrict__ gamma,
+    const float* __restrict__ beta, const float* __restrict__ rs, const float* __restrict__ ms, double* __restrict__ partial, int HW, int C,
+    int act, int nchunk) {
   extern __shared__ __attribute__((aligned(16))) double sred[];   // [rows][C][2] folded in place
   const int C4 = C >> 2;
   const int rows = TN_THREADS / C4;
@@ -53,8 +55,10 @@ __global__ __launch_bounds__(TN_THREADS) void gn_bwd_stats_nhwc_kernel(
     const float rr[4] = {r4.x, r4.y, r4.z, r4.w}, mm[4] = {m4.x, m4.y, m4.z, m4.w};
     const float gg[4] = {g4.x, g4.y, g4.z, g4.w}, bb[4] = {b4.x, b4.y, b4.z, b4.w};
     const size_t base = (size_t)b * HW * C + c;
+    const int Cs = c < C0 ? C0 : C - C0;               // the source of this thread's channels and its pitch
+    const float* const xs = c < C0 ? x0 + (size_t)b * HW * C0 + c : x1 + (size_t)b * HW * Cs + (c - C0);
     for (int p = p0 + row; p < p1; p += rows) {
-      const float4 xv = *reinterpret_cast<const float4*>(x + base + (size_t)p * C);
+      const float4 xv = *reinterpret_cast<const float4*>(xs + (size_t)p * Cs);
       const float4 dv = *reinterpret_cast<const float4*>(dy + base + (size_t)p * C);
       const float xa[4] = {xv.x, xv.y, xv.z, xv.w}, da[4] = {dv.x, dv.y, dv.z, dv.w};
 #pragma unroll
@@ -133,11 +137,14 @@ __global__ void gn_bwd_final_nhwc_kernel(const double* __restrict__ partial, con
   }
 }
 
-// pass 3: dx, elementwise; thread = (pixel row, 4 channels) with its coefficients in registers
+// pass 3: dx, elementwise; thread = (pixel row, 4 channels) with its coefficients in registers.  x and dx are split at C0 like the
+// statistics pass's x (dx0 | dx1); acc0 / acc1: the destination already holds a gradient of that tensor (an earlier consumer's) and
+// takes this one in ONE fp32 addition, fl(old + v) with v the value the plain store writes
 __global__ __launch_bounds__(TN_THREADS) void gn_bwd_apply_nhwc_kernel(
-    const float* __restrict__ x, const float* __restrict__ dy, const float* __restrict__ gamma, const float* __restrict__ beta,
-    const float* __restrict__ rs, const float* __restrict__ ms, const float* __restrict__ coef, const float* __restrict__ add,
-    float* __restrict__ dx, int HW, int C, int act, int nchunk) {
+    const float* __restrict__ x0, const float* __restrict__ x1, int C0, const float* __restrict__ dy, const float* __restrict__ gamma,
+    const float* __restrict__ beta, const float* __restrict__ rs, const float* __restrict__ ms, const float* __restrict__ coef,
+    const float* __restrict__ add, float* __restrict__ dx0, float* __restrict__ dx1, int acc0, int acc1, int HW, int C, int act,
+    int nchunk) {
   const int C4 = C >> 2;
   const int rows = TN_THREADS / C4;
   const int tid = threadIdx.x;
@@ -156,8 +163,14 @@ __global__ __launch_bounds__(TN_THREADS) void gn_bwd_apply_nhwc_kernel(
     cc[j] = coef[((size_t)b * 3 + 2) * C + c + j];
   }
   const size_t base = (size_t)b * HW * C + c;
+  const bool first = c < C0;
+  const int Cs = first ? C0 : C - C0;
+  const size_t sbase = first ? (size_t)b * HW * C0 + c : (size_t)b * HW * Cs + (c - C0);
+  const float* const xs = (first ? x0 : x1) + sbase;
+  float* const dxs = (first ? dx0 : dx1) + sbase;
+  const bool acc = first ? acc0 != 0 : acc1 != 0;
   for (int p = p0 + row; p < p1; p += rows) {
-    const float4 xv = *reinterpret_cast<const float4*>(x + base + (size_t)p * C);
+    const float4 xv = *reinterpret_cast<const float4*>(xs + (size_t)p * Cs);
     const float4 dv = *reinterpret_cast<const float4*>(dy + base + (size_t)p * C);
     const float xa[4] = {xv.x, xv.y, xv.z, xv.w}, da[4] = {dv.x, dv.y, dv.z, dv.w};
     float o[4];
@@ -171,7 +184,11 @@ __global__ __launch_bounds__(TN_THREADS) void gn_bwd_apply_nhwc_kernel(
       const float4 av = *reinterpret_cast<const float4*>(add + base + (size_t)p * C);
       o[0] += av.x; o[1] += av.y; o[2] += av.z; o[3] += av.w;
     }
-    *reinterpret_cast<float4*>(dx + base + (size_t)p * C) = make_float4(o[0], o[1], o[2], o[3]);
+    if (acc) {
+      const float4 ov = *reinterpret_cast<const float4*>(dxs + (size_t)p * Cs);
+      o[0] = ov.x + o[0]; o[1] = ov.y + o[1]; o[2] = ov.z + o[2]; o[3] = ov.w + o[3];
+    }
+    *reinterpret_cast<float4*>(dxs + (size_t)p * Cs) = make_float4(o[0], o[1], o[2], o[3]);
   }
 }
 
@@ -329,7 +346,20 @@ int csd::groupnorm_act_dropout_nhwc(const float* x, const float* gamma, const fl
 int csd::groupnorm_act_backward_nhwc_add(const float* x, const float* gamma, const float* beta, const float* rs, const float* ms,
                                          const float* dy, const float* add, float* dx, float* dgamma_rows, float* dbeta_rows,
                                          int row_stride, int B, int C, int HW, int groups, int act, void* scratch, void* stream) {
-  CSD_REQUIRE(x && gamma && beta && rs && ms && dy && dx && dgamma_rows && dbeta_rows && scratch, "groupnorm_act_backward_nhwc: null argument");
+  CSD_REQUIRE(x && dx, "groupnorm_act_backward_nhwc: null argument");
+  GnBwdSplit sp;
+  sp.x0 = x; sp.dx0 = dx; sp.C0 = C;
+  return groupnorm_act_backward_nhwc_split(sp, gamma, beta, rs, ms, dy, add, dgamma_rows, dbeta_rows, row_stride, B, C, HW, groups, act,
+                                           scratch, stream);
+}
+
+// ... of a GroupNorm over x = x0 (| x1) (the virtual concatenation of an up block), the gradient written per source (common.h)
+int csd::groupnorm_act_backward_nhwc_split(const GnBwdSplit& t, const float* gamma, const float* beta, const float* rs, const float* ms,
+                                           const float* dy, const float* add, float* dgamma_rows, float* dbeta_rows, int row_stride, int B,
+                                           int C, int HW, int groups, int act, void* scratch, void* stream) {
+  CSD_REQUIRE(t.x0 && t.dx0 && gamma && beta && rs && ms && dy && dgamma_rows && dbeta_rows && scratch, "groupnorm_act_backward_nhwc: null argument");
+  CSD_REQUIRE(t.C0 >= 4 && t.C0 <= C && t.C0 % 4 == 0 && ((t.C0 == C) == (t.x1 == nullptr)) && ((t.x1 == nullptr) == (t.dx1 == nullptr)),
+              "groupnorm_act_backward_nhwc: sources of %d + %d channels and their pointers do not agree", t.C0, C - t.C0);
   CSD_REQUIRE(C % 4 == 0 && C <= 1024 && groups > 0 && C % groups == 0, "groupnorm_act_backward_nhwc: C=%d groups=%d unsupported", C, groups);
   CSD_REQUIRE(row_stride >= C, "groupnorm_act_backward_nhwc: row_stride %d < C", row_stride);
   hipStream_t s = (hipStream_t)stream;
@@ -339,15 +369,15 @@ int csd::groupnorm_act_backward_nhwc_add(const float* x, const float* gamma, con
   if (!L.bytes) return CSD_ERR_INVALID;
   double* const partial = L.bw_partial;
   float* const coef = L.bw_coef;
-  hipLaunchKernelGGL(gn_bwd_stats_nhwc_kernel, dim3(nchunk, B), dim3(TN_THREADS), (size_t)rows * C * 2 * sizeof(double), s, x, dy,
-                     gamma, beta, rs, ms, partial, HW, C, act, nchunk);
+  hipLaunchKernelGGL(gn_bwd_stats_nhwc_kernel, dim3(nchunk, B), dim3(TN_THREADS), (size_t)rows * C * 2 * sizeof(double), s, t.x0, t.x1, t.C0,
+                     dy, gamma, beta, rs, ms, partial, HW, C, act, nchunk);
   CSD_LAUNCH_CHECK();
   const int fl = std::max(1, std::min(std::min(16, nchunk), 1024 / C));      // chunk lanes per channel of the fold
   hipLaunchKernelGGL(gn_bwd_final_nhwc_kernel, dim3(B), dim3(std::min(1024, std::max(256, fl * C))), (size_t)C * 2 * (1 + fl) * sizeof(double), s,
                      partial, gamma, rs, dgamma_rows, dbeta_rows, coef, HW, C, groups, nchunk, row_stride, fl);
   CSD_LAUNCH_CHECK();
-  hipLaunchKernelGGL(gn_bwd_apply_nhwc_kernel, dim3(nchunk, B), dim3(TN_THREADS), 0, s, x, dy, gamma, beta, rs, ms, coef, add, dx,
-                     HW, C, act, nchunk);
+  hipLaunchKernelGGL(gn_bwd_apply_nhwc_kernel, dim3(nchunk, B), dim3(TN_THREADS), 0, s, t.x0, t.x1, t.C0, dy, gamma, beta, rs, ms, coef, add,
+                     t.dx0, t.dx1, t.acc0, t.acc1, HW, C, act, nchunk);
   CSD_LAUNCH_CHECK();
   return CSD_OK;
 }

@@ -10,7 +10,7 @@
 //
 // One translation unit in pieces: this file (structs, the topology = build_modules, the parameter table, the C ABI of the network),
 // pc_loop.h (the fused PC sampler: its noise-draw schedule, the loop, the csd_pc_* entries and the cascade), unet_layout.h (ConvKernel per layer, packed-weight layout + pack_all), unet_plan.h (Builder: the walk's state and one step() per module; build_plan; a batch chunk is planned by a Builder of its own), unet_run.h (run_plan), unet3d.h (the 3-D DDPM
-// family, arch 2: topology, packed layout, plan and executor on conv3d.hip's kernels), train_graph.h (training forward / backward),
+// family, arch 2: topology, packed layout, plan and executor on conv3d.hip's kernels), train_graph.h (training forward / backward; train_graph3d.h: the 3-D family's),
 // plan_digest.h (csd_unet_debug_digest).
 #include <stdarg.h>
 #include <string.h>
@@ -612,6 +612,7 @@ struct csd_unet {
 };
 
 #include "train_graph.h"
+#include "train_graph3d.h"
 #include "plan_digest.h"
 
 extern "C" int csd_profile_select(unsigned class_mask, int step_stride) {

@@ -184,9 +184,12 @@ class GradSync:
         all-reduce on a communication stream that waits for ITS event only: the late layers' gradients are reduced while the
         backward of the early layers still runs.  Without a process group (or off the GPU) nothing is registered."""
         self._model, self._events, self._comm, self._epoch = None, None, None, 0
-        from .models.ddpm import HipUNet
-        # (a planned 3-D network owns a handle too, but trains on the per-operator path: it has no planned backward to mark)
-        if not self.grouped or not self.flat.grad.is_cuda or getattr(model, '_h', None) is None or not isinstance(model, HipUNet):
+        # (a handle alone is not enough: a planned 3-D network without ``planned_train`` owns one but trains on the per-operator path,
+        # which has no planned backward to mark.  The same now holds for a 2-D HipUNet switched to ``train_executor = 'operators'``: it
+        # used to get marks that its autograd backward never records, so finish() reduced every bucket after the backward; without
+        # marks its buckets are launched from the autograd hooks, as for every other hook-driven executor - the same sums either way)
+        if (not self.grouped or not self.flat.grad.is_cuda or getattr(model, '_h', None) is None
+                or getattr(model, 'train_executor', None) != 'planned'):
             return False
         from ._lib import check, lib
         # names of the FLAT buffer's parameters, in its order (a frozen parameter is not in it: indices into the model's full

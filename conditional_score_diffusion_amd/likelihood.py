@@ -240,9 +240,9 @@ def _solve_on_device(rhs, data, sde, rtol, atol, eps):
 
 def _run(model, sde, inverse_scaler, data, y, hutchinson_type, epsilon, rtol, atol, method, eps, conditional, drift_fn,
          device_loop=False):
-    if getattr(model, 'planned', False) and data.dim() == 5:
-        raise NotImplementedError('likelihood: the probability-flow right-hand side (csd_pf_ode_rhs on the planned training graph) is not '
-                                  'provided for the 3-D networks')
+    if (getattr(model, 'planned', False) or getattr(model, 'planned_train', False)) and data.dim() == 5:
+        raise NotImplementedError('likelihood: the probability-flow right-hand side (csd_pf_ode_rhs) is not wired to the planned '
+                                  'training graph of the 3-D networks')
     with torch.no_grad():
         shape = data.shape
         epsilon = _hutchinson_noise(hutchinson_type, data) if epsilon is None else \

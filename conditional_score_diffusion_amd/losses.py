@@ -243,8 +243,11 @@ def _require_fused(model, tensors, sde):
     if isinstance(sde, dict) and len(sde) != 2:
         raise NotImplementedError('the fused loss takes one SDE or the {x, y} pair, not %d SDEs' % len(sde))
     if getattr(model, 'arch', None) == 2 or model.__class__.__name__.startswith('DDPM3D'):
-        raise NotImplementedError('the fused loss is not provided for the 3-D classes (%s)' % model.__class__.__name__)
-    if not (isinstance(model, HipUNet) and model.arch == 0 and model.train_executor == 'planned' and model.train_layout == 'nhwc'):
+        if not getattr(model, 'planned_train', False):
+            raise NotImplementedError('the fused loss is not provided for the 3-D classes (%s) without the planned training graph '
+                                      '(planned_train=True, config.model.csd_planned_train or CSD_PLANNED_TRAIN=1)'
+                                      % model.__class__.__name__)
+    elif not (isinstance(model, HipUNet) and model.arch == 0 and model.train_executor == 'planned' and model.train_layout == 'nhwc'):
         raise NotImplementedError('the fused loss needs a HipUNet on the planned training executor (DDPM family, '
                                   'CSD_TRAIN_EXECUTOR=planned, CSD_TRAIN_LAYOUT=nhwc), got %s' % model.__class__.__name__)
     for name, v in tensors:

@@ -146,6 +146,26 @@ class _HandleSurface:
             self._ws = ops._scratch(need, self.device)
         return self._ws
 
+    # -- the planned training graph (csd_unet_train_forward / csd_unet_backward*): what the autograd nodes _PlannedNet and
+    # _InputGradNet ask of a model beside ``_h``, ``_param_names``, ``_dropout``, ``dropout_seed``, ``_train_calls`` and the shapes
+    # ``_x_shape(B)`` / ``_out_shape(B)`` of one call's x (and d_x) and output ------------------------------------------------------
+    _train_ws = None
+    _train_ws_busy = False         # a forward whose backward has not run yet holds the shared training workspace
+    _train_ws_owner = None         # ... identified by its call index
+
+    def _train_workspace(self, B):
+        need = lib().csd_unet_train_workspace_bytes(self._h, B, self._dropout)
+        if need == 0:
+            raise RuntimeError('libcsd_hip: cannot plan the training graph at batch %d: %s' % (B, lib().csd_last_error().decode()))
+        if self._train_ws is None or self._train_ws.numel() < need or self._train_ws.device != self.device:
+            self._train_ws = None
+            self._train_ws = ops._scratch(need, self.device)
+        return self._train_ws
+
+    def _train_params(self):
+        params = dict(self.named_parameters())
+        return [params[name] for name in self._param_names]
+
     def stats(self, B):
         """(kernel launches, algorithmic FLOPs, algorithmic bytes) of one evaluation at batch B."""
         n, fl, by = ctypes.c_int64(), ctypes.c_double(), ctypes.c_double()
@@ -314,19 +334,6 @@ class HipUNet(nn.Module, _HandleSurface):
                                    self._xgrad_calls)
 
     # -- training-mode evaluation: ONE planned graph behind the C ABI (csd_unet_train_forward / csd_unet_backward) -------------------
-    def _train_workspace(self, B):
-        need = lib().csd_unet_train_workspace_bytes(self._h, B, self._dropout)
-        if need == 0:
-            raise RuntimeError('libcsd_hip: cannot plan the training graph at batch %d: %s' % (B, lib().csd_last_error().decode()))
-        if self._train_ws is None or self._train_ws.numel() < need or self._train_ws.device != self.device:
-            self._train_ws = None
-            self._train_ws = ops._scratch(need, self.device)
-        return self._train_ws
-
-    def _train_params(self):
-        params = dict(self.named_parameters())
-        return [params[name] for name in self._param_names]
-
     def _train_forward_planned(self, x, y, labels):
         """``model.train()`` + autograd as ONE node: the forward is csd_unet_train_forward (the reference's layer sequence,
         models/ddpm.py:149-213, dropout on, activations kept in a library workspace), the backward csd_unet_backward (every

@@ -35,6 +35,15 @@ refuses what the library refuses (an odd pooled extent of the configured volume,
 Conv_2).  Training mode and input gradients keep the autograd executor.  Inpainting, the likelihood and the ODE sampler on the device are not
 provided for the 3-D networks.  Making the planned path the default is a separate, later decision.
 
+The planned training graph (opt-in: ``config.model.csd_planned_train = True``, the constructor argument ``planned_train=True`` or
+``$CSD_PLANNED_TRAIN=1``; off by default, and then nothing below applies): the model creates the ``arch = 2`` handle (also when ``planned``
+is off) and, on GPU tensors, training mode and eval mode with ``x.requires_grad`` are ONE autograd node over csd_unet_train_forward /
+csd_unet_backward_acc (``ddpm._PlannedNet`` / ``ddpm._InputGradNet``, csrc/train_graph3d.h) instead of the ``_GradOps3D`` graph: the same
+kernels and dropout masks (the same Philox stream ids), activations in a workspace sized by a dry run, every parameter gradient written -
+or, in a ``train.Trainer`` accumulation window, added - straight to its ``.grad`` view, gradient-ready marks for ``distributed.GradSync``
+(``train_executor == 'planned'``), and ``losses.csd_fused_loss`` on volumes (``_run``).  A volume other than the configured one raises
+ValueError.  ``planned`` still decides how eval mode without gradients runs.
+
 Training and input gradients (GPU tensors): in training mode, and in eval mode when ``x.requires_grad`` under autograd, the forward is
 the differentiable, operator-granular one (``_GradOps3D``, the same walk): the layers of ResnetBlockDDPM as grad_ops_3d / grad_ops autograd nodes
 (GroupNorm + act -> Conv_0 -> + Dense_0(act(temb)) -> GroupNorm + act -> Dropout_0 -> Conv_1, + the shortcut), whose backward passes
@@ -52,7 +61,7 @@ import torch.nn as nn
 from .. import _lib, grad_ops_3d, ops
 from .._lib import require_gpu_tensor
 from . import utils
-from .ddpm import _HandleSurface, _Node, _activation, _fan_avg_uniform, _model_key, _precision
+from .ddpm import _HandleSurface, _InputGradNet, _Node, _PlannedNet, _activation, _fan_avg_uniform, _model_key, _precision
 from .topology import Executor, build_modules, run_unet
 
 _PRECISIONS = ('fp32', 'f32', 'fp16x3')
@@ -61,7 +70,7 @@ _PRECISIONS = ('fp32', 'f32', 'fp16x3')
 class DDPM3D(nn.Module, _HandleSurface):
     """``ddpm3D`` (models/ddpm3D.py:38-171): model(x [B, C, D, H, W], labels [B]) -> [B, output_channels, D, H, W]."""
 
-    def __init__(self, config, precision=None, planned=None):
+    def __init__(self, config, precision=None, planned=None, planned_train=None):
         super().__init__()
         m, d = config.model, config.data
         precision = _precision(config, precision)
@@ -97,9 +106,16 @@ class DDPM3D(nn.Module, _HandleSurface):
         if planned is None:
             planned = os.environ.get('CSD_PLANNED', '0').strip().lower() not in ('', '0', 'false', 'no', 'off')
         self.planned = bool(planned)
+        if planned_train is None:
+            planned_train = _model_key(config, 'csd_planned_train', None)
+        if planned_train is None:
+            planned_train = os.environ.get('CSD_PLANNED_TRAIN', '0').strip().lower() not in ('', '0', 'false', 'no', 'off')
+        self.planned_train = bool(planned_train)
         self._h = self._packed = self._packed_key = self._ws = None
-        if self.planned:
+        if self.planned or self.planned_train:
             self._create_handle(config)
+        if self.planned_train:
+            self.train_executor = 'planned'           # (train.Trainer, distributed.GradSync: direct gradient writes, marks, accumulation)
 
     # ---- the planned path: one csd_unet handle (arch 2) for the configured volume ----
     def _channels(self, config):
@@ -133,6 +149,7 @@ class DDPM3D(nn.Module, _HandleSurface):
         cfg.precision = _lib.PREC_IDS[self.precision]
         for i in range(3):
             cfg.vol[i] = vol[i]
+        cfg.planned_train = int(self.planned_train)   # (0: the training entries refuse the handle, as they always did)
         self._create_unet(cfg)
         # the library rebuilds the module list from the config: its parameter table must be this module's state_dict
         table = self._param_table()
@@ -145,8 +162,42 @@ class DDPM3D(nn.Module, _HandleSurface):
         want_grad = torch.is_grad_enabled() and x.requires_grad
         return self.planned and not ((self.training and torch.is_grad_enabled()) or want_grad)
 
-    def _planned_forward(self, x, y, labels):
-        """one csd_unet_forward: x [B, Cx, D, H, W], y [B, Cy, D, H, W] or None -> [B, output_channels, D, H, W]"""
+    # ---- the planned training graph (``planned_train``): the handle's csd_unet_train_forward / csd_unet_backward* behind ddpm.py's nodes ----
+    def _use_train_graph(self, x):
+        """training mode, or eval mode with ``x.requires_grad``, under autograd on GPU tensors (CPU tensors keep the existing refusal)"""
+        grad = torch.is_grad_enabled() and (self.training or x.requires_grad)
+        return self.planned_train and grad and x.is_cuda
+
+    def _x_shape(self, B):
+        return (B, self.x_channels) + self.volume
+
+    def _out_shape(self, B):
+        return (B, int(self.output_channels)) + self.volume
+
+    def _train_graph_forward(self, x, y, labels):
+        """ONE autograd node: ``_PlannedNet`` in training mode (dropout on, every parameter gradient from csd_unet_backward_acc), else
+        ``_InputGradNet`` (dropout 0, the data gradient only).  Only x is differentiated (y is the condition)."""
+        if y is not None and y.requires_grad:             # (the operator path differentiates through its torch.cat; this node does not)
+            raise NotImplementedError('ddpm3D (planned_train): the network differentiates its input x only; y takes no gradient')
+        x, y, labels = self._check_planned_io(x, y, labels)
+        if self.training:
+            self._train_calls += 1
+            return _PlannedNet.apply(self, x, y, labels, *self._train_params())
+        self._xgrad_calls = getattr(self, '_xgrad_calls', 0) + 1
+        return _InputGradNet.apply(self, x, None if y is None else y.detach(), labels.detach(), self._xgrad_calls)
+
+    def _run(self, x, y, labels):
+        """the network on separate x and y -> the raw output [B, output_channels, D, H, W] (``losses.csd_fused_loss``), on the handle"""
+        if self._h is None:
+            raise NotImplementedError('ddpm3D: _run needs the csd_unet handle (planned=True or planned_train=True)')
+        if self._use_train_graph(x):
+            return self._train_graph_forward(x, y, labels)
+        if torch.is_grad_enabled() and (self.training or x.requires_grad):
+            raise NotImplementedError('ddpm3D: gradients through _run need planned_train=True and GPU tensors')
+        return self._planned_forward(x, y, labels)
+
+    def _check_planned_io(self, x, y, labels):
+        """shapes of one call on the handle; returns contiguous float32 x, y (or None), labels"""
         vol = self.volume
         if x.dim() != 5 or x.shape[1] != self.x_channels:
             raise ValueError('ddpm3D: input %s is not [B, %d, D, H, W]' % (tuple(x.shape), self.x_channels))
@@ -160,10 +211,18 @@ class DDPM3D(nn.Module, _HandleSurface):
             require_gpu_tensor(y, 'y')
             if tuple(y.shape) != (B, self.y_channels) + vol:
                 raise ValueError('ddpm3D: y %s is not %s' % (tuple(y.shape), (B, self.y_channels) + vol))
-        labels = labels.contiguous()
+            y = y.float().contiguous()
+        else:
+            y = None
+        labels = labels.to(dtype=torch.float32).contiguous()
         if tuple(labels.shape) != (B,):
             raise ValueError('ddpm3D: labels must have shape [%d]' % B)
-        return self._unet_forward(x, y, labels, (B, int(self.output_channels)) + vol)
+        return x.float().contiguous(), y, labels
+
+    def _planned_forward(self, x, y, labels):
+        """one csd_unet_forward: x [B, Cx, D, H, W], y [B, Cy, D, H, W] or None -> [B, output_channels, D, H, W]"""
+        x, y, labels = self._check_planned_io(x, y, labels)
+        return self._unet_forward(x, y, labels, self._out_shape(x.shape[0]))
 
     # ---- parameters: names, shapes and initialisation of the reference ----
     def _make_node(self, kind, a):
@@ -208,6 +267,8 @@ class DDPM3D(nn.Module, _HandleSurface):
 
     # ---- forward: DDPM3D.forward (models/ddpm3D.py:107-171) ----
     def forward(self, x, labels):
+        if self._use_train_graph(x):
+            return self._train_graph_forward(x, None, labels)
         if self._use_plan(x) and not (self.training and not x.is_cuda):
             return self._planned_forward(x, None, labels)
         want_grad = torch.is_grad_enabled() and x.requires_grad
@@ -323,6 +384,8 @@ class _Paired3D(DDPM3D):
 
     def _paired(self, x, y, labels):
         """the network on (x, y): planned, x and y go to the library separately; else the concatenated input on the operator path"""
+        if self._use_train_graph(x):
+            return self._train_graph_forward(x, y, labels)
         if self._use_plan(x) and not (self.training and not x.is_cuda):
             return self._planned_forward(x, y, labels)
         return DDPM3D.forward(self, torch.cat((x, y), dim=1), labels)

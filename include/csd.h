@@ -120,6 +120,10 @@ typedef struct csd_unet_config {
   int32_t embedding_type;       /* 0 'positional', 1 'fourier' (W [nf] is parameter all_modules.0.W) */
   int32_t n_fir;                /* taps of config.model.fir_kernel (<= 8)                    */
   float fir_kernel[8];
+  /* ---- arch 2 only: 1 = the handle serves the planned training graph (csd_unet_train_*, csd_unet_backward*, csd_unet_backward_marks*;
+   * csrc/train_graph3d.h).  0 (a zero-initialised struct): those entries refuse the handle, naming 3-D, as they did before the graph
+   * existed (csd_unet_train_workspace_bytes returns 0).  arch 0 / 1 always have their graph and ignore the field. ---- */
+  int32_t planned_train;
   /* ---- arch 0 / 1: the direct Kx super-resolution networks (models/ddpm.py:316-331 ddpm_KxSR, models/ncsnpp.py:435-450 NCSNpp_KxSR).
    * K >= 2: y is the LOW-resolution image [B, y_channels, S / K, S / K] (S = image_size); the network sees its bilinear upsample to
    * S x S and returns its y channels downsampled to S / K.  Both resizes are torch's F.interpolate(mode = 'bilinear',
@@ -175,9 +179,10 @@ size_t csd_unet_config_size(void);
  * independent of the batch position).  csd_unet_create refuses, with the reason: resamp_with_conv, conditional = 0, nf % 32 != 0, an
  * extent that is odd or below 2 at a pooled level, a precision other than CSD_PREC_F32 / CSD_PREC_F16X3, and a ch_mult for which an up
  * block's concatenated input is as wide as its output (that block has no Conv_2).  The training entries (csd_unet_train_*,
- * csd_unet_backward*), csd_pc_inpaint_* and csd_unet_debug_digest return CSD_ERR_INVALID for an arch-2 handle (csd_unet_train_workspace_bytes
- * returns 0) with a message that names 3-D; the probability-flow entries (csd_pf_ode_*) take no handle and their callers go through the
- * training entries. */
+ * csd_unet_backward*, csd_unet_backward_marks*) serve an arch-2 handle created with planned_train = 1 (below); without it they return
+ * CSD_ERR_INVALID (csd_unet_train_workspace_bytes returns 0) with a message that names 3-D.  csd_pc_inpaint_* and csd_unet_debug_digest
+ * return CSD_ERR_INVALID for every arch-2 handle with a message that names 3-D; the probability-flow entries (csd_pf_ode_*) take no handle, and
+ * their Python caller refuses the 3-D networks. */
 
 typedef struct csd_unet csd_unet;
 
@@ -743,8 +748,12 @@ int csd_attention_backward_nhwc(const float* qkv, const float* dout, float* dqkv
  * One backward per forward, same handle / workspace / B / call_index; the workspace must not be touched in between: a second
  * forward into the same workspace before the backward makes that backward fail with CSD_ERR_STATE (it names the first forward's
  * call_index) - two forwards of one network may be alive at once when each has its own workspace.
- * csd_unet_train_workspace_bytes depends on B and on whether dropout_p > 0.  Both architectures: arch 0 (models/ddpm.py:149-213) and
- * arch 1 (NCSN++, models/ncsnpp.py:238-388: BigGAN blocks with FIR up / down sampling, Combine 'sum', input / output pyramids).
+ * csd_unet_train_workspace_bytes depends on B and on whether dropout_p > 0.  All architectures: arch 0 (models/ddpm.py:149-213),
+ * arch 1 (NCSN++, models/ncsnpp.py:238-388: BigGAN blocks with FIR up / down sampling, Combine 'sum', input / output pyramids) and
+ * arch 2 with csd_unet_config.planned_train = 1 (the 3-D DDPM family, models/ddpm3D.py:107-171; csrc/train_graph3d.h): x, y, out, d_out and d_x are NCDHW with D, H, W in place
+ * of S, S; the layers, kernels and dropout streams are those of the per-operator training path (csd_conv3d_block without prologue,
+ * csd_groupnorm_act_nhwc with S = D*H*W, csd_conv3d_wgrad, the data gradient scaled by csd_conv3d_dgrad_scale's power of two), so the
+ * same (dropout_seed, call_index) draws the same masks on both.  Every option below holds for arch 2 as it does for arch 0 / 1.
  * ---------------------------------------------------------------------------------------- */
 size_t csd_unet_train_workspace_bytes(csd_unet* net, int B, float dropout_p);
 int csd_unet_train_forward(csd_unet* net, const float* const* params, void* workspace, size_t workspace_bytes, const float* x,
@@ -754,7 +763,8 @@ int csd_unet_backward(csd_unet* net, const float* const* params, float* const* g
                       const float* d_out, int B, uint64_t call_index, void* stream);
 /* csd_unet_backward_ex: csd_unet_backward with optional outputs.
  *   grads == NULL: no parameter gradient is formed (no wgrad, no bias sums, no temb-MLP backward, no gradient-ready marks).
- *   d_x != NULL:   d loss / d x, [B, x_channels, S, S] NCHW fp32 (the x channels of the input only; y takes no gradient).
+ *   d_x != NULL:   d loss / d x, [B, x_channels, S, S] NCHW fp32 (arch 2: [B, x_channels, D, H, W]; the x channels of the input only,
+ *     times the 2v - 1 input map's factor when not centred; y takes no gradient).
  * csd_unet_backward(...) is csd_unet_backward_ex(..., grads, NULL).  The data-gradient kernels are the same with or without grads,
  * so d_x does not depend on whether parameter gradients are formed.  Both architectures; NCSN++ with every progressive_input:
  * 'input_skip' (the input pyramid's gradient chain: d pyr_l = Conv_0^T(dh_l) + FIR-down^T(d pyr_l+1), d x += FIR-down^T(d pyr_1)),

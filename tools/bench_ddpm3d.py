@@ -15,6 +15,10 @@ Writes profiles/ddpm3d_bench.json (``--out`` to change) and prints it:
 ``--train`` measures training instead and writes it under the key ``training`` of the same file (the other keys are kept):
   steps        Trainer.train_step (loss, backward on the grad_ops_3d operators, clip + Adam + EMA) of ``ddpm3D_paired`` with the two-SDE
                loss at B = 2 (``--batch`` is ignored), steps per second over `repeats` windows of `evals` steps
+  planned_train  the same step on the planned training graph (``csd_planned_train``: csd_unet_train_forward / csd_unet_backward_acc writing
+               the flat gradient) on the same weights and batch in the same process, the two paths' windows alternating: steps per second,
+               the ratio, the planned workspace bytes (csd_unet_train_workspace_bytes) beside torch's peak allocated bytes over one step
+               of either path (and what was allocated before the step: parameters, optimizer state, both models)
   wgrad        csd_conv3d_wgrad (split bf16) at the same two layers as achieved TFLOP/s = 2 * 27 * Cin * Cout * voxels * B / time, beside
                torch's own fp32 conv3d weight gradient (torch.nn.grad.conv3d_weight, channels-first), the two alternating
 ``--planned`` measures the planned path (``csd_planned``: one csd_unet_forward per evaluation, the PC loop on the device) beside the
@@ -188,33 +192,73 @@ def train_bench(args, dev):
     from conditional_score_diffusion_amd import sde_lib, train
     vol, nf, ch_mult, nrb = ((12, 12, 8), 32, (1, 2), 1) if args.small else ((96, 96, 16), 64, (1, 1, 2, 2), 2)
     B = 2
-    cfg = make_config(vol, nf, ch_mult, nrb)
-    cfg.training.likelihood_weighting = cfg.training.reduce_mean = True
-    cfg.model.ema_rate = 0.999
-    cfg.model.num_scales, cfg.model.sigma_min_y, cfg.model.sigma_max_y = 1000, 0.01, 1.
-    cfg.optim = ConfigDict(weight_decay=0, optimizer='Adam', lr=2e-4, beta1=0.9, eps=1e-8, warmup=100, grad_clip=1)
-    cfg.seed = 42
+
+    def config(planned_train):
+        cfg = make_config(vol, nf, ch_mult, nrb)
+        cfg.training.likelihood_weighting = cfg.training.reduce_mean = True
+        cfg.model.ema_rate = 0.999
+        cfg.model.num_scales, cfg.model.sigma_min_y, cfg.model.sigma_max_y = 1000, 0.01, 1.
+        cfg.model.csd_planned_train = planned_train
+        cfg.optim = ConfigDict(weight_decay=0, optimizer='Adam', lr=2e-4, beta1=0.9, eps=1e-8, warmup=100, grad_clip=1)
+        cfg.seed = 42
+        return cfg
+    cfg = config(False)
     torch.manual_seed(0)
     model = mutils.create_model(cfg)
     with torch.no_grad():
         for k, v in model.state_dict().items():
             if v.dim() == 5:
                 v.copy_((torch.rand_like(v) * 2 - 1) * (3.0 / (27 * (v.shape[0] + v.shape[1]) / 2)) ** 0.5)
+    state = {k: v.clone() for k, v in model.state_dict().items()}
     model = model.to(dev)
     sde = {'x': sde_lib.cVESDE(0.01, 30., 1000), 'y': sde_lib.VESDE(0.01, 1., 1000)}
     tr = train.Trainer(cfg, model, sde)
     batch = (torch.rand(B, 1, *vol).to(dev), torch.rand(B, 1, *vol).to(dev))
     losses = []
     step = lambda: losses.append(tr.train_step(batch))      # noqa: E731
-    win = timed_windows(step, args.warmup, args.repeats, args.evals)
+    # the planned training graph (planned_train) on the same weights, batch and seeds, in the same process
+    from conditional_score_diffusion_amd._lib import lib
+    cfg_p = config(True)
+    model_p = mutils.create_model(cfg_p)
+    model_p.load_state_dict(state)
+    model_p = model_p.to(dev)
+    tr_p = train.Trainer(cfg_p, model_p, sde)
+    losses_p = []
+    step_p = lambda: losses_p.append(tr_p.train_step(batch))      # noqa: E731
+
+    def peak_of(fn):
+        """torch's peak allocated bytes over one step, and what was allocated before it"""
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats()
+        base = torch.cuda.memory_allocated()
+        fn()
+        torch.cuda.synchronize()
+        return {'peak_allocated_bytes': int(torch.cuda.max_memory_allocated()), 'allocated_before_bytes': int(base)}
+
+    for f in (step, step_p):
+        timed_windows(f, args.warmup, 0, 0)
+    win, win_p = [], []
+    for _ in range(args.repeats):                           # the two paths alternate
+        win += timed_windows(step, 0, 1, args.evals)
+        win_p += timed_windows(step_p, 0, 1, args.evals)
+    mem, mem_p = peak_of(step), peak_of(step_p)
     vals = [float(v) for v in losses]
-    assert all(v == v and abs(v) != float('inf') for v in vals), vals
-    med = statistics.median(win)
+    vals_p = [float(v) for v in losses_p]
+    assert all(v == v and abs(v) != float('inf') for v in vals + vals_p), (vals, vals_p)
+    med, med_p = statistics.median(win), statistics.median(win_p)
+    planned_train = {
+        'steps': {'steps_per_s': 1.0 / med_p, 'ms_per_step': med_p * 1e3, 'ms_min': min(win_p) * 1e3, 'ms_max': max(win_p) * 1e3,
+                  'windows': len(win_p), 'steps_per_window': args.evals, 'first_loss': vals_p[0], 'last_loss': vals_p[-1]},
+        'operator_path_steps_per_s': 1.0 / med, 'planned_over_operator': med / med_p,
+        'planned_workspace_bytes': int(lib().csd_unet_train_workspace_bytes(model_p._h, B, 0.1)),
+        'planned_step_memory': mem_p, 'operator_path_step_memory': mem,
+        'backward_direct': bool(getattr(model_p, '_last_backward_direct', False))}
     lv = [((12, 12, 8), 32), ((6, 6, 4), 64)] if args.small else [((96, 96, 16), 64), ((24, 24, 4), 128)]
     return {'device': torch.cuda.get_device_name(0), 'model': 'ddpm3D_paired', 'precision': 'fp16x3', 'batch': B, 'volume': list(vol), 'nf': nf,
             'ch_mult': list(ch_mult), 'num_res_blocks': nrb, 'small': bool(args.small), 'dropout': 0.1,
             'steps': {'steps_per_s': 1.0 / med, 'ms_per_step': med * 1e3, 'ms_min': min(win) * 1e3, 'ms_max': max(win) * 1e3, 'windows': len(win),
                       'steps_per_window': args.evals, 'first_loss': vals[0], 'last_loss': vals[-1]},
+            'planned_train': planned_train,
             'wgrad': [wgrad_bench(B, v, C, args.warmup, args.repeats, dev) for v, C in lv], 'torch': torch.__version__}
 
 
